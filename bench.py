@@ -4,6 +4,12 @@
     python bench.py [--gpus N] [--steps K] [--warmup W]        any N: for N > 1 this process starts its own N ranks (one child process
                                                                per GPU; see launch_ranks) and relays rank 0's JSON line
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (the same ranks started by torchrun)
+    python bench.py ... --dump-outputs DIR                     also writes what the last timed step computed as DIR/<name>.npy
+    python bench.py ... --full                                 the whole record (see below)
+
+A plain run sets up, warms up, times exactly K steps in one window, and prints the headline record. Everything else is behind
+--full: three timed windows (median reported), the CPU-oracle parity probe and baseline, the event-timed roofline leg, the
+sustained leg, the inference leg, and for data-parallel runs the proof of ranks and the communication leg.
 
 One step = the reference's inner-loop body (openset_imagenet/train.py:125-139): zero_grad, forward, loss, backward
 (+ bucketed RCCL gradient all-reduce when N > 1), optimizer step — on a synthetic batch that is already resident in HBM.
@@ -494,12 +500,39 @@ def rccl_channels(path):
     return info
 
 
+DUMP_SAMPLE = 1 << 20     # parameters (and gradients) drawn for --dump-outputs: at most 4 MiB per array in float32
+
+
+def dump_outputs(path, model, last):
+    """--dump-outputs: what a caller of the timed step receives from its last execution, as float32 DIR/<name>.npy — the loss, the
+    logits and features, the BatchNorm running statistics, and one fixed, seeded sample of the updated parameters and of their
+    gradients (the whole network is ~94 MB). Returns the names written."""
+    import numpy as np
+    j, logits, feats = last
+    params = list(model.parameters())
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+    flat_g = torch.cat([(torch.zeros_like(p) if p.grad is None else p.grad.detach()).reshape(-1) for p in params])
+    idx = torch.from_numpy(np.unique(np.random.default_rng(0).integers(0, flat_p.numel(), DUMP_SAMPLE))).to(flat_p.device)
+    stats = [b.detach().reshape(-1) for n, b in model.named_buffers() if n.endswith(("running_mean", "running_var"))]
+    arrays = {"loss": j.detach().reshape(1), "logits": logits.detach(), "features": feats.detach(), "bn_running_stats": torch.cat(stats),
+              "params_sample": flat_p[idx], "grads_sample": flat_g[idx]}
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps per window")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--windows", type=int, default=3, help="timed windows of --steps steps each; the median window is reported")
+    ap.add_argument("--full", action="store_true", help="the whole record: three timed windows, CPU-oracle parity and baseline, roofline, "
+                    "sustained and inference legs, proof of ranks and communication leg (data parallel); off: the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (loss, logits, features, "
+                    "BatchNorm running statistics, a fixed sample of the updated parameters and of the gradients) as DIR/<name>.npy")
+    ap.add_argument("--windows", type=int, default=None, help="timed windows of --steps steps each; the median window is reported. "
+                    "Default 1, and 3 with --full")
     ap.add_argument("--workload", default="p2", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="override the per-GPU batch (invalidates the headline config)")
     ap.add_argument("--cpus-per-gpu", type=int, default=int(os.environ.get("OSI_CPUS_PER_GPU", "16")),
@@ -509,17 +542,22 @@ def main():
     ap.add_argument("--force-dp", action="store_true", help="dev: with one rank, still run the data-parallel step (staged backward + "
                     "RCCL bucket all-reduce on a world-1 communicator) to price the N>1 code path on a one-GPU box")
     ap.add_argument("--sustained-steps", type=int, default=None,
-                    help="further steps AFTER the timed windows (never part of `value`), reported as `sustained` in 50-step windows; 0 = off. "
-                         "Default 600 (OSI_BENCH_SUSTAINED), and 0 for dev runs (--no-profile or --windows 1: A/B and counter passes)")
-    ap.add_argument("--eval-steps", type=int, default=None, help="inference leg after everything else (never part of `value`): eval-mode forwards "
-                    "timed per mode; 0 = off. Default 20, and 0 for dev runs (--no-profile or --windows 1)")
+                    help="--full: further steps AFTER the timed windows (never part of `value`), reported as `sustained` in 50-step windows; "
+                         "0 = off. Default 600 (OSI_BENCH_SUSTAINED), and 0 for dev runs (--no-profile or --windows 1: A/B and counter passes)")
+    ap.add_argument("--eval-steps", type=int, default=None, help="--full: inference leg after everything else (never part of `value`): eval-mode "
+                    "forwards timed per mode; 0 = off. Default 20, and 0 for dev runs (--no-profile or --windows 1)")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="N > 1 self-launch: seconds before the ranks are terminated")
     ap.add_argument("--bind", default="auto", choices=("auto", "near", "even", "none"), help="N > 1 self-launch: CPU binding of the ranks")
     args = ap.parse_args()
+    if not args.full and (args.sustained_steps or args.eval_steps):
+        ap.error("--sustained-steps and --eval-steps size legs of --full")
+    if args.windows is None:
+        args.windows = 3 if args.full else 1
+    dev_run = not args.full or args.no_profile or args.windows == 1
     if args.sustained_steps is None:
-        args.sustained_steps = 0 if (args.no_profile or args.windows == 1) else int(os.environ.get("OSI_BENCH_SUSTAINED", "600"))
+        args.sustained_steps = 0 if dev_run else int(os.environ.get("OSI_BENCH_SUSTAINED", "600"))
     if args.eval_steps is None:
-        args.eval_steps = 0 if (args.no_profile or args.windows == 1) else 20
+        args.eval_steps = 0 if dev_run else 20
     if args.windows < 1 or args.steps < 1 or args.warmup < 0 or args.cpus_per_gpu < 1 or args.sustained_steps < 0:
         ap.error("--windows, --steps and --cpus-per-gpu must be >= 1, --warmup and --sustained-steps >= 0")
 
@@ -622,25 +660,25 @@ def main():
     def step():
         model.train()
         opt.zero_grad()
-        logits, _ = net(images)
+        logits, feats = net(images)
         j = loss_fn(logits, labels)
         j.backward()
         opt.step()
-        return j
+        return j, logits, feats
 
     def fence():
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
 
-    rccl = rccl_proof(model, net, backend, world, local, dev) if use_dp else None
-    parity = parity_probe(model, C, dev) if (world == 1 and not args.no_cpu_baseline) else None
+    rccl = rccl_proof(model, net, backend, world, local, dev) if (use_dp and args.full) else None
+    parity = parity_probe(model, C, dev) if (world == 1 and args.full and not args.no_cpu_baseline) else None
     for _ in range(args.warmup):
         step()
     handle = model._net(B, 224, 224).h
-    # Three back-to-back windows of EXACTLY --steps steps, each bracketed by barrier + synchronize on both sides and reduced with
-    # MAX over the ranks; the MEDIAN window is the reported one (`value`, `ms_per_step`), all three are listed. One 0.7 s window
-    # moves by +-1.5 % between identical runs; the median of three resolves ~1 % levers with the same `steps` per window.
+    # --windows back-to-back windows (one, or three with --full) of EXACTLY --steps steps, each bracketed by barrier + synchronize on
+    # both sides and reduced with MAX over the ranks; the MEDIAN window is the reported one (`value`, `ms_per_step`), all are listed.
+    # One 0.7 s window moves by +-1.5 % between identical runs; the median of three resolves ~1 % levers with the same `steps` per window.
     windows, own_windows = [], []
     for _ in range(args.windows):
         fence()
@@ -657,7 +695,9 @@ def main():
             w = float(t)
         windows.append(w)
     elapsed = sorted(windows)[len(windows) // 2]
-    loss_value = float(last.detach())
+    loss_value = float(last[0].detach())
+    # what the last timed step computed, written before any leg of --full runs further steps
+    dumped = dump_outputs(args.dump_outputs, model, last) if (args.dump_outputs and rank == 0) else None
     # Sustained leg (never part of `value`): the timed region above is a ~2 s burst; this is the same step for --sustained-steps more
     # steps, one host synchronisation per 50-step window, so that clock / thermal drift shows as a series instead of hiding in a burst.
     sustained = None
@@ -685,7 +725,7 @@ def main():
                      "first_vs_last_window": round(series[0] / series[-1], 4),
                      "window_ms_per_step": [round(v, 3) for v in series],
                      "how": "50-step windows run back to back after the timed region, one synchronize per window (MAX over ranks per window)"}
-    if use_dp:     # communication leg: the same step with every bucket's collective bracketed by events (outside the timed windows)
+    if use_dp and args.full:     # communication leg: the same step with every bucket's collective bracketed by events (outside the timed windows)
         net.sync.timing(True)
         for _ in range(max(1, min(args.steps, 5))):
             step()
@@ -728,7 +768,7 @@ def main():
     # stream. The instrumented mode keeps every kernel on that one stream (weight gradients are NOT moved to the side stream),
     # so each class's duration is its own; the headline `value` above comes from the un-instrumented, overlapped steps.
     prof = None
-    psteps = 0 if args.no_profile else max(1, min(args.steps, 5))
+    psteps = 0 if (args.no_profile or not args.full) else max(1, min(args.steps, 5))
     if psteps:
         N.check(N.lib().osi_resnet50_profile(handle, 1))
         for _ in range(psteps):
@@ -801,7 +841,8 @@ def main():
             "value": round(ips, 2), "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_step, 3), "windows_ms_per_step": [round(w / args.steps * 1e3, 3) for w in windows],
             "timing": f"median of {len(windows)} back-to-back windows of {args.steps} steps each (barrier + synchronize around every window, "
-                      "MAX over ranks per window)", "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+                      "MAX over ranks per window)" if len(windows) > 1 else f"one window of {args.steps} steps (barrier + synchronize around "
+                      "it, MAX over ranks)", "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic (device-resident U[0,1) images, random-init weights seed 42)",
             "config": {"workload": wl["name"], "workload_key": args.workload, "classes": C, "batch_per_gpu": B, "global_batch": B * world, "image": "3x224x224",
                        "loss": wl["loss"], "optimizer": "adam lr=1e-3", "parallelism": f"dp{world}"},
@@ -859,7 +900,9 @@ def main():
         if rccl is not None:
             rccl["launcher"] = {"self_launched": os.environ.get("OSI_BENCH_LAUNCHED") == "1", "cpu_binding": os.environ.get("OSI_BENCH_BIND_POLICY")}
             out["rccl"] = rccl
-        if world == 1 and not args.no_cpu_baseline:
+        if dumped is not None:
+            out["outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "of": "the last timed step"}
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(C, wl["p_neg"], gpus_used=world, cpus_per_gpu=args.cpus_per_gpu)
             out["parity"] = parity
         sys.stdout.flush()

@@ -135,3 +135,10 @@ def test_near_binding_deals_a_locality_domain_out_among_its_ranks(monkeypatch):
     monkeypatch.setattr(b, "_cpus_near_gpu", lambda r: dom[r % 2])
     monkeypatch.setenv("HIP_VISIBLE_DEVICES", "1,0")          # a mask may have reordered the devices: sysfs order is not HIP's
     assert b.plan_rank_cpus(2, "auto")[1] == "even"
+
+
+def test_legs_of_full_are_refused_in_a_plain_run():
+    """The sustained and inference legs belong to --full: a plain run asked for them stops at argument parsing (before any GPU call)."""
+    for leg in ("--sustained-steps", "--eval-steps"):
+        r = subprocess.run([sys.executable, BENCH, leg, "5"], env=_clean_env(), capture_output=True, text=True, timeout=300)
+        assert r.returncode == 2 and "legs of --full" in r.stderr and not r.stdout.strip()

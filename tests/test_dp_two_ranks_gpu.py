@@ -81,7 +81,7 @@ def test_bench_two_rank_rehearsal_reports_the_proof_of_ranks(cuda):
     environment), rehearsed on the one GPU of the test box with gloo carrying the collectives (OSI_BENCH_BACKEND=gloo; under RCCL
     two ranks on one device make bench.py exit with an error). The JSON line carries the three timed windows with their median as
     `value`, and the `rccl` object a SCALE record needs to prove that N processes on N devices took part."""
-    out = _run_bench(["--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu-baseline", "--no-profile"], {"OSI_BENCH_BACKEND": "gloo"}, 2)
+    out = _run_bench(["--full", "--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu-baseline", "--no-profile"], {"OSI_BENCH_BACKEND": "gloo"}, 2)
     assert out["n_gpus"] == 2 and out["steps"] == 2 and out["config"]["global_batch"] == 16 and out["config"]["parallelism"] == "dp2"
     w = out["windows_ms_per_step"]
     assert len(w) == 3 and sorted(w)[1] == out["ms_per_step"]
@@ -108,7 +108,7 @@ def test_bench_self_launch_two_ranks(cuda):
     """The plain command: `python bench.py --gpus 2` with NO rank variables in the environment starts its own two ranks as child
     processes (free rendezvous port, per-rank CPU share), relays rank 0's one JSON line and returns 0. Same gloo rehearsal on the one
     GPU of the test box; the record says it was self-launched and how the ranks were bound."""
-    out = _run_bench(["--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu-baseline", "--no-profile"], {"OSI_BENCH_BACKEND": "gloo"}, 2,
+    out = _run_bench(["--full", "--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu-baseline", "--no-profile"], {"OSI_BENCH_BACKEND": "gloo"}, 2,
                      self_launch=True)
     assert out["n_gpus"] == 2 and out["config"]["global_batch"] == 16 and out["config"]["parallelism"] == "dp2"
     r = out["rccl"]
@@ -145,7 +145,7 @@ def test_bench_self_launch_failing_rank(cuda):
 @pytest.mark.timeout(900)
 def test_bench_sustained_leg(cuda):
     """After the timed windows (never part of `value`) the record carries a sustained leg in 50-step windows."""
-    out = _run_bench(["--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu-baseline", "--no-profile", "--sustained-steps", "100"], {}, 1)
+    out = _run_bench(["--full", "--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu-baseline", "--no-profile", "--sustained-steps", "100"], {}, 1)
     s = out["sustained"]
     assert s["steps"] == 100 and len(s["window_ms_per_step"]) == 2 and s["ms_per_step_p50"] <= s["ms_per_step_p95"]
     assert s["images_per_sec"] == pytest.approx(8 * 100 / s["seconds"], rel=1e-3) and s["vs_value"] > 0
@@ -156,7 +156,7 @@ def test_bench_sustained_leg(cuda):
 def test_bench_force_dp_world1_runs_the_rccl_path(cuda):
     """N = 1 with --force-dp: a world-1 RCCL communicator, the staged backward and one all_reduce per bucket, each bracketed by HIP
     events in the communication leg."""
-    out = _run_bench(["--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu-baseline", "--no-profile", "--force-dp"], {}, 1)
+    out = _run_bench(["--full", "--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu-baseline", "--no-profile", "--force-dp"], {}, 1)
     r = out["rccl"]
     assert r["world"] == 1 and r["backend"] == "nccl" and r["distinct_devices"] == 1 and r["nccl_version"]
     assert len(r["per_bucket_comm_ms"]) == 4 and all(v >= 0 for v in r["per_bucket_comm_ms"])
@@ -172,7 +172,7 @@ def test_bench_force_dp_world1_runs_the_rccl_path(cuda):
 def test_bench_dp_reserved_cus_reaches_the_launch_plan(cuda):
     """OSI_DP_RESERVED_CUS (the wave slots left to RCCL's resident channel workgroups) travels environment -> osi_set_tuning ->
     plan_tail_split's CU count, and the record says which plan was in effect."""
-    out = _run_bench(["--steps", "1", "--warmup", "1", "--windows", "1", "--batch", "8", "--no-cpu-baseline", "--no-profile", "--force-dp"],
+    out = _run_bench(["--full", "--steps", "1", "--warmup", "1", "--windows", "1", "--batch", "8", "--no-cpu-baseline", "--no-profile", "--force-dp"],
                      {"OSI_DP_RESERVED_CUS": "8"}, 1)
     lp = out["rccl"]["launch_plan"]
     assert lp["dp_reserved_cus"] == 8 and lp["tail_plan_cus_in_effect"] == 248
@@ -183,7 +183,7 @@ def test_bench_record_says_what_its_roofline_measures_and_carries_the_inference_
     """`roofline.frac` is the EFFECTIVE rate (the direct convolution's FLOPs); `issued_frac` the matrix pipe's own
     (Winograd layers issue 4/9 of their multiplies); the committed counter summary is cited with its provenance and withheld when it
     belongs to another workload / batch; the `eval` object compares the inference forms with the training topology (never part of `value`)."""
-    out = _run_bench(["--steps", "2", "--warmup", "1", "--windows", "1", "--batch", "8", "--no-cpu-baseline", "--eval-steps", "2"], {}, 1)
+    out = _run_bench(["--full", "--steps", "2", "--warmup", "1", "--windows", "1", "--batch", "8", "--no-cpu-baseline", "--eval-steps", "2"], {}, 1)
     r = out["roofline"]
     assert r["bound"] == "mfma" and r["peak"] == 157.3 and 0 < r["issued_frac"] < r["frac"]
     # B = 8: 24.287 GFLOP per image of direct convolution; the 13 Winograd layers issue 16 products per 2x2 tile instead of 36
@@ -199,3 +199,27 @@ def test_bench_record_says_what_its_roofline_measures_and_carries_the_inference_
     assert e["fused"]["serialized"]["launch_groups"] < e["training_topology"]["serialized"]["launch_groups"]
     assert e["speedup"] == pytest.approx(e["training_topology"]["ms_per_batch"] / e["fused"]["ms_per_batch"], rel=1e-2)
     assert out["value"] == pytest.approx(8 / (out["ms_per_step"] * 1e-3), rel=1e-2), "`value` comes from the timed windows alone"
+
+
+@pytest.mark.timeout(900)
+def test_bench_plain_run_times_its_steps_and_dumps_what_they_computed(cuda, tmp_path):
+    """A plain run (no --full) times exactly --steps steps in one window and carries none of the legs of --full; --dump-outputs writes
+    the last timed step's outputs as float32 .npy files (< 64 MB in all), and two runs with the same arguments write the same arrays."""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"out{run}"
+        out = _run_bench(["--steps", "3", "--warmup", "1", "--batch", "8", "--dump-outputs", str(d)], {}, 1)
+        assert out["steps"] == 3 and len(out["windows_ms_per_step"]) == 1 and out["windows_ms_per_step"][0] == out["ms_per_step"]
+        assert out["value"] == pytest.approx(8 / (out["ms_per_step"] * 1e-3), rel=1e-2)
+        assert not {"roofline", "eval", "sustained", "cpu_baseline", "parity", "rccl"} & set(out)
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(out)
+        names = sorted(p.name for p in d.iterdir())
+        assert names == sorted(n + ".npy" for n in out["outputs"]["arrays"])
+        assert sum(p.stat().st_size for p in d.iterdir()) < 64 * 2**20
+        arrays = {n: np.load(d / n) for n in names}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert arrays["logits.npy"].shape == (8, 30) and arrays["loss.npy"][0] == pytest.approx(out["final_loss"], abs=1e-5)
+        dumps.append(arrays)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), f"{n}: two runs with the same arguments computed different outputs"

@@ -35,7 +35,7 @@ def test_state_dict_is_the_reference_layout(model):
     assert abs(std - (2.0 / (64 * 9)) ** 0.5) < 0.1 * std                        # kaiming-normal, fan_out
 
 
-def test_load_reference_format_state_dict_and_arena_sharing(model):
+def test_load_reference_format_state_dict_and_arena_sharing(model, tmp_path):
     ref = R.init_state(12, 12, generator=torch.Generator().manual_seed(3))
     model.load_state_dict(ref)
     for k, v in model.state_dict().items():
@@ -48,12 +48,12 @@ def test_load_reference_format_state_dict_and_arena_sharing(model):
     assert float(p[0, 0, 0, 0]) == 42.0
     # DDP-prefixed checkpoints load too (reference train.py:79-87)
     pref = {"module." + k: v for k, v in ref.items()}
-    torch.save({"epoch": 3, "model_state_dict": pref, "opt_state_dict": {}, "best_score": 0.5}, "/tmp/_osi_ddp.pth")
+    torch.save({"epoch": 3, "model_state_dict": pref, "opt_state_dict": {}, "best_score": 0.5}, tmp_path / "ddp.pth")
     m2 = oi.ResNet50(12, 12, False)
-    assert load_checkpoint(m2, "/tmp/_osi_ddp.pth") == (3, 0.5)
+    assert load_checkpoint(m2, tmp_path / "ddp.pth") == (3, 0.5)
     assert torch.equal(m2.state_dict()["logits.weight"], ref["logits.weight"])
     with pytest.raises(Exception):
-        load_checkpoint(m2, "/tmp/does_not_exist.pth")
+        load_checkpoint(m2, tmp_path / "does_not_exist.pth")
 
 
 def test_checkpoint_round_trip_and_optimizer_state(model, tmp_path):

@@ -5,6 +5,6 @@
 for r in $(seq 1 ${1:-2}); do
 for cfg in plain staged handoff dp; do
   case $cfg in plain) e="X=1"; a="";; staged) e="OSI_BENCH_SKIP_COLLECTIVE=2"; a="--force-dp";; handoff) e="OSI_BENCH_SKIP_COLLECTIVE=1"; a="--force-dp";; dp) e="X=1"; a="--force-dp";; esac
-  env $e python bench.py --no-cpu-baseline --no-profile $a 2>/dev/null | python -c "
+  env $e python bench.py --full --no-cpu-baseline --no-profile $a 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$cfg', 'ms/step', d['ms_per_step'], d['windows_ms_per_step'])"
 done; done

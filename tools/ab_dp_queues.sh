@@ -9,6 +9,6 @@ for cfg in plain "handoff hi" "handoff normal" "handoff hi q8" "dp hi" "dp norma
   case $1 in plain) a="";; handoff) e="OSI_BENCH_SKIP_COLLECTIVE=1";; esac
   [ "$2" = normal ] && e="$e OSI_DP_COMM_PRIO=0"
   [ "$3" = q8 ] && e="$e GPU_MAX_HW_QUEUES=8"
-  env $e python bench.py --no-cpu-baseline --no-profile $a 2>/dev/null | python -c "
+  env $e python bench.py --full --no-cpu-baseline --no-profile $a 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$cfg', 'ms/step', d['ms_per_step'], d['windows_ms_per_step'])"
 done; done

@@ -8,7 +8,7 @@ L=openset-imagenet_amd/csrc/libosi_hip.so
 cp $L /tmp/libosi_hip_keep.so && cp openset-imagenet_amd/csrc/libosi_hip_diag.so $L || exit 1
 trap 'cp /tmp/libosi_hip_keep.so '$L EXIT
 for r in 1 2 3; do for B in 64 128; do for cfg in "OSI_DBG_SKIP=0" "OSI_DBG_SKIP=8"; do
-  env OSI_DEV=1 OSI_HIP_LIB=$PWD/$L $cfg python bench.py --batch $B --no-cpu-baseline --no-profile 2>/dev/null | python -c "
+  env OSI_DEV=1 OSI_HIP_LIB=$PWD/$L $cfg python bench.py --full --batch $B --no-cpu-baseline --no-profile 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('B=$B $cfg', 'ms/step', d['ms_per_step'], d['windows_ms_per_step'], 'img/s', d['value'])"
 done; done; done

@@ -4,7 +4,7 @@
 ROOT=$(pwd); TAG=${1:-r05}; OUT=$ROOT/gpurun_out/step_trace_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-OSI_NO_OVERLAP=1 rocprofv3 --kernel-trace -d "$OUT" -o t --output-format csv -- python3 "$ROOT/bench.py" --steps 2 --warmup 2 --no-cpu-baseline --sustained-steps 0 > "$OUT/bench.json" 2> "$OUT/err.txt"
+OSI_NO_OVERLAP=1 rocprofv3 --kernel-trace -d "$OUT" -o t --output-format csv -- python3 "$ROOT/bench.py" --full --steps 2 --warmup 2 --no-cpu-baseline --sustained-steps 0 > "$OUT/bench.json" 2> "$OUT/err.txt"
 python3 - "$OUT" "$ROOT/gpurun_out/${TAG}_step_trace.txt" <<'PY'
 import csv, sys, glob, re
 f = glob.glob(sys.argv[1] + "/**/t_kernel_trace.csv", recursive=True)[0]
