@@ -225,6 +225,12 @@ int osi_stem_wgrad_fused(const osi_conv_desc* d, const float* gpool, const void*
                          const float* gamma, const float* mean, const float* invstd, const float* dgamma, const float* dbeta,
                          float* dw_krsc3, void* ws, size_t ws_bytes, osi_stream_t stream);
 int osi_stem_grad_unpack(const float* g_packed, float* g_krsc3, int Cout, osi_stream_t stream);
+/* ABI 8. Input gradient of the stem conv (7x7 / stride 2 / pad 3, 3 input channels) for an image batch [B][3][H][W]:
+ *   dx[b][c][h][w] = sum_k sum_(r,s) dy[b][(h+3-r)/2][(w+3-s)/2][k] * w_krsc3[k][r][s][c]   (taps with h+3-r, w+3-s even, inside dy)
+ * dy = the stem conv's output gradient, NHWC [B][Hs][Ws][64] with Hs = (H-1)/2 + 1, Ws = (W-1)/2 + 1 (16-byte aligned); w_krsc3 =
+ * conv1's weight in the arena layout [64][7][7][3]; dx_nchw = fp32 [B][3][H][W], every element written (no pre-zeroing), no atomics
+ * (two calls give equal bits). H, W >= 32 (any size osi_resnet50_create takes, odd ones included); OSI_ERR_ARG before any launch. */
+int osi_stem_dgrad(const float* dy, const float* w_krsc3, float* dx_nchw, int B, int H, int W, osi_stream_t stream);
 
 /* ---- BatchNorm2d in training mode + ReLU + residual (torchvision Bottleneck under model.py:37; train() at train.py:125) --- */
 size_t osi_bn_workspace(int M, int C);
@@ -400,6 +406,16 @@ int osi_resnet50_forward(osi_resnet50_t net, const float* params, float* buffers
 /* runs backward stages [stage_lo, stage_hi) given dJ/dlogits and (optionally, may be NULL) dJ/dfeatures */
 int osi_resnet50_backward(osi_resnet50_t net, const float* params, float* grads, void* workspace, const float* dlogits,
                           const float* dfeatures, int stage_lo, int stage_hi, osi_stream_t stream);
+
+/* ABI 8. osi_resnet50_backward plus: dimage != NULL -> the last stage also writes dJ/dimage, [B][3][H][W] fp32 NCHW (the stem tail then
+ * materialises the stem's output gradient: bn1 backward into a scratch buffer, the stem weight gradient from it, osi_stem_dgrad);
+ * param_grads == 0 -> no parameter gradient is computed or written (grads may be NULL): no weight-gradient launch, no fc / logits
+ * dw / db, nothing on the side stream; the BatchNorm reductions dY needs still run (into workspace). dimage / param_grads are fixed by
+ * the call that runs stage 0; a later stage of the same backward with other values -> OSI_ERR_STATE. param_grads == 0 with
+ * dimage == NULL, or param_grads == 1 with grads == NULL -> OSI_ERR_ARG. osi_resnet50_backward(...) = _ex(..., NULL, 1, ...). */
+int osi_resnet50_backward_ex(osi_resnet50_t net, const float* params, float* grads, void* workspace, const float* dlogits,
+                             const float* dfeatures, float* dimage, int param_grads, int stage_lo, int stage_hi,
+                             osi_stream_t stream);
 
 /* Data-parallel hand-off (ABI 5). With option "stage_join" = 0 a staged osi_resnet50_backward call (stage_hi < stages) does NOT make
  * `stream` wait for the side stream's weight gradients (the last stage always does); instead the caller makes its COMMUNICATION stream

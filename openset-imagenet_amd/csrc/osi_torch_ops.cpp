@@ -3,6 +3,7 @@
 //
 //   torch.ops.osi.resnet50_forward    model.py:28-39   (logits, features = model(images))
 //   torch.ops.osi.resnet50_backward   train.py:138     (j.backward() through the network, stage range for the DP bucket schedule)
+//   torch.ops.osi.resnet50_backward_ex  the same, plus dJ/dimage and the input-only backward (adversarial samples, attribution)
 //   torch.ops.osi.resnet50_grads_ready  config/train.yaml:18,35-39 (hand a finished stage's gradients to the communication stream)
 //   torch.ops.osi.loss_fwd_bwd        losses.py:16-29, train.py:343-347 (the three losses + objectosphere term, value and gradient)
 //   torch.ops.osi.adam_step / sgd_step    train.py:139, 356-359
@@ -112,6 +113,37 @@ void resnet50_backward(int64_t net, const Tensor& params, Tensor grads, Tensor w
        "osi_resnet50_backward");
 }
 
+// ABI 8: the same backward that can also write dJ/dimage (NCHW fp32 [B][3][H][W] of the executor's geometry) and/or skip every
+// parameter gradient (param_grads = false: `grads` is not touched and may be an empty tensor)
+void resnet50_backward_ex(int64_t net, const Tensor& params, Tensor grads, Tensor workspace, const Tensor& dlogits,
+                          const std::optional<Tensor>& dfeatures, const std::optional<Tensor>& dimage, bool param_grads,
+                          int64_t stage_lo, int64_t stage_hi) {
+    need(params, at::kFloat, "params"); need(workspace, at::kByte, "workspace");
+    need(dlogits, at::kFloat, "dlogits", NATURAL);
+    if (dfeatures.has_value() && dfeatures->defined()) need(*dfeatures, at::kFloat, "dfeatures", NATURAL);
+    if (param_grads) {
+        need(grads, at::kFloat, "grads");
+        TORCH_CHECK(grads.numel() == params.numel(), "osi::resnet50_backward_ex: gradient arena size mismatch");
+    }
+    const bool want_dx = dimage.has_value() && dimage->defined();
+    TORCH_CHECK(want_dx || param_grads, "osi::resnet50_backward_ex: neither dimage nor parameter gradients requested");
+    float* dx = nullptr;
+    if (want_dx) {
+        need(*dimage, at::kFloat, "dimage", NATURAL);
+        TORCH_CHECK(dimage->device() == params.device(), "osi::resnet50_backward_ex: dimage lives on another device than params");
+        int B = 0, H = 0, W = 0;
+        ok(osi_resnet50_geometry(handle(net), &B, &H, &W), "osi_resnet50_geometry");
+        TORCH_CHECK(dimage->dim() == 4 && dimage->size(0) == B && dimage->size(1) == 3 && dimage->size(2) == H && dimage->size(3) == W,
+                    "osi::resnet50_backward_ex: dimage must be [", B, ", 3, ", H, ", ", W, "] (NCHW), got ", dimage->sizes());
+        dx = dimage->data_ptr<float>();
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(params.device());
+    ok(osi_resnet50_backward_ex(handle(net), params.data_ptr<float>(), param_grads ? grads.data_ptr<float>() : nullptr, workspace.data_ptr(),
+                                dlogits.data_ptr<float>(), fptr(dfeatures), dx, param_grads ? 1 : 0, (int)stage_lo, (int)stage_hi,
+                                stream_of(params)),
+       "osi_resnet50_backward_ex");
+}
+
 // Data parallel: the stream `waiter` (a raw hipStream_t handle: torch.cuda.Stream.cuda_stream of the communication stream) waits for the
 // gradients of the backward stages enqueued so far on the CURRENT stream and on the executor's side stream; the current stream waits for nothing
 void resnet50_grads_ready(int64_t net, const Tensor& grads, int64_t waiter) {
@@ -202,6 +234,8 @@ TORCH_LIBRARY(osi, m) {
           "int fc_dim, int out_features, bool training) -> (Tensor, Tensor)");
     m.def("resnet50_backward(int net, Tensor params, Tensor(a!) grads, Tensor(b!) workspace, Tensor dlogits, Tensor? dfeatures, "
           "int stage_lo, int stage_hi) -> ()");
+    m.def("resnet50_backward_ex(int net, Tensor params, Tensor(a!) grads, Tensor(b!) workspace, Tensor dlogits, Tensor? dfeatures, "
+          "Tensor(c!)? dimage, bool param_grads, int stage_lo, int stage_hi) -> ()");
     m.def("resnet50_grads_ready(int net, Tensor grads, int waiter_stream) -> ()");
     m.def("loss_fwd_bwd(int mode, Tensor logits, Tensor target, float unk_weight, int ignore_index, Tensor? class_weights, "
           "Tensor? features, float xi, float alpha, bool need_grad) -> (Tensor, Tensor, Tensor)");
@@ -217,6 +251,7 @@ TORCH_LIBRARY(osi, m) {
 TORCH_LIBRARY_IMPL(osi, CUDA, m) {
     m.impl("resnet50_forward", &resnet50_forward);
     m.impl("resnet50_backward", &resnet50_backward);
+    m.impl("resnet50_backward_ex", &resnet50_backward_ex);
     m.impl("resnet50_grads_ready", &resnet50_grads_ready);
     m.impl("loss_fwd_bwd", &loss_fwd_bwd);
     m.impl("adam_step", &adam_step);

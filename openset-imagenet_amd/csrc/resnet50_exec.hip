@@ -32,6 +32,7 @@ struct BN {
     size_t g_off, b_off;    // param arena
     size_t rm_off, rv_off;  // buffer arena
     size_t mean, invstd, scale, shift;  // workspace (floats)
+    size_t dsink;           // workspace: [2][C] dgamma / dbeta of a backward that writes no parameter gradient
 };
 struct Conv {
     osi_conv_desc d;
@@ -179,6 +180,12 @@ struct osi_resnet50 {
                                      // kernels never co-run, only HBM-bound work overlaps them. A/B against the default co-running schedule.
     struct PendingW { bool on = false; int ci = 0, gi = 0, in_bn = -1; const float* conv_in = nullptr; float* grads = nullptr; float* ws = nullptr; } pend;
     bool w_inflight = false;
+    // request of the backward in flight (osi_resnet50_backward_ex), fixed by the call that runs stage 0: bw_dimage != NULL -> the stem
+    // tail materialises dY and its input gradient writes dJ/dimage; bw_pg = 0 -> input-only (no weight gradient, nothing into grads)
+    float* bw_dimage = nullptr;
+    bool bw_pg = true;
+    float* dgam(float* grads, float* ws, const BN& b) const { return bw_pg ? grads + b.g_off : ws + b.dsink; }
+    float* dbet(float* grads, float* ws, const BN& b) const { return bw_pg ? grads + b.b_off : ws + b.dsink + b.C; }
 #ifdef OSI_DIAG                       // `make -C csrc diag` (libosi_hip_diag.so, tools only): the product library has no such switch
     int dbg_fwd_count = 0;           // training forwards so far (dbg_skip bit 3)
     int dbg_skip = 0;                // option "dbg_skip" (TIMING EXPERIMENTS ONLY, results are wrong): bit 0 = the BatchNorm-backward apply passes
@@ -360,6 +367,7 @@ int osi_resnet50_create(osi_resnet50_t* out, int B, int H, int W, int fc_dim, in
     n->dg_ws_bytes = dgws; n->dg_ws = n->ws_alloc(dgws / 4 + 4);
     n->scratch_floats = maxact;
     for (int i = 0; i < osi_resnet50::NSCR; ++i) n->scratch[i] = n->ws_alloc(maxact);
+    for (auto& b : n->bns) b.dsink = n->ws_alloc(2 * (size_t)b.C);
     *out = n;
     return OSI_OK;
 }
@@ -786,6 +794,7 @@ static int before_dgrad(osi_resnet50* n, hipStream_t st) {
 }
 
 static int wgrad(osi_resnet50* n, int ci, float* grads, float* ws, int gi, const float* conv_in, hipStream_t st, int in_bn = -1) {
+    if (!n->bw_pg) return OSI_OK;      // input-only backward: no weight gradient of any kind
     const bool async = n->async_wgrad();
     if (!(async && n->stagger)) return wgrad_launch(n, ci, grads, ws, gi, conv_in, st, in_bn, async);
     OSI_TRY(flush_wgrad(n, st));       // two weight gradients with no input gradient between them: the older one goes now
@@ -810,7 +819,7 @@ static int bn_conv_wgrad(osi_resnet50* n, int ci, const float* params, float* gr
     BN& b = n->bns[c.bn];
     float* g = ws + n->scratch[gi];
     OSI_TRY(osi_bn_backward_relu_mask(g, ws + c.mask, ws + c.y, ws + b.mean, ws + b.invstd, params + b.g_off, g, gmasked,
-                                      grads + b.g_off, grads + b.b_off, b.M, b.C, ws + n->bn_ws, n->bn_ws_bytes, st));
+                                      n->dgam(grads, ws, b), n->dbet(grads, ws, b), b.M, b.C, ws + n->bn_ws, n->bn_ws_bytes, st));
     OSI_TRY(n->mark(OSI_PROF_BN_BWD, st));
     return wgrad(n, ci, grads, ws, gi, conv_in, st);
 }
@@ -824,11 +833,11 @@ static int bn_bwd_fused(osi_resnet50* n, int ci, const float* params, float* gra
     const float* psum_g = ws + n->dg_ws;
     const float* psum_gx = psum_g + (size_t)(1 + which) * n->fused_P * b.C;
     if (n->dbg_skip & 1) {   // timing experiment: reductions only, the consumers read whatever the dy buffer holds
-        OSI_TRY(osi_bn_backward_reduce(psum_g, psum_gx, n->fused_P, grads + b.g_off, grads + b.b_off, b.M, b.C, ws + n->bn_ws, n->bn_ws_bytes, st));
+        OSI_TRY(osi_bn_backward_reduce(psum_g, psum_gx, n->fused_P, n->dgam(grads, ws, b), n->dbet(grads, ws, b), b.M, b.C, ws + n->bn_ws, n->bn_ws_bytes, st));
         return n->mark(OSI_PROF_BN_BWD, st);
     }
     OSI_TRY(osi_bn_backward_fused(ws + n->scratch[gi], ws + c.y, ws + b.mean, ws + b.invstd, params + b.g_off, psum_g, psum_gx,
-                                  n->fused_P, ws + n->scratch[dyi], grads + b.g_off, grads + b.b_off, b.M, b.C, ws + n->bn_ws,
+                                  n->fused_P, ws + n->scratch[dyi], n->dgam(grads, ws, b), n->dbet(grads, ws, b), b.M, b.C, ws + n->bn_ws,
                                   n->bn_ws_bytes, st));
     OSI_TRY(n->mark(OSI_PROF_BN_BWD, st));
     return OSI_OK;
@@ -911,7 +920,7 @@ static int block_backward(osi_resnet50* n, int bi, const float* params, float* g
             int t1 = n->take(st);
             if (t1 < 0) return t1;
             OSI_TRY(osi_bn_backward_relu_mask(S(go), ws + c3.mask, ws + cd.y, ws + bd.mean, ws + bd.invstd, params + bd.g_off,
-                                              S(t1), nullptr, grads + bd.g_off, grads + bd.b_off, bd.M, bd.C, ws + n->bn_ws,
+                                              S(t1), nullptr, n->dgam(grads, ws, bd), n->dbet(grads, ws, bd), bd.M, bd.C, ws + n->bn_ws,
                                               n->bn_ws_bytes, st));
             OSI_TRY(n->mark(OSI_PROF_BN_BWD, st));
             OSI_TRY(wgrad(n, k.ds, grads, ws, t1, x, st));
@@ -920,7 +929,7 @@ static int block_backward(osi_resnet50* n, int bi, const float* params, float* g
         }
         BN& b3 = n->bns[c3.bn];
         OSI_TRY(osi_bn_backward_relu_mask(S(go), ws + c3.mask, ws + c3.y, ws + b3.mean, ws + b3.invstd, params + b3.g_off, S(go),
-                                          has_ds ? nullptr : S(dxbase), grads + b3.g_off, grads + b3.b_off, b3.M, b3.C,
+                                          has_ds ? nullptr : S(dxbase), n->dgam(grads, ws, b3), n->dbet(grads, ws, b3), b3.M, b3.C,
                                           ws + n->bn_ws, n->bn_ws_bytes, st));
         OSI_TRY(n->mark(OSI_PROF_BN_BWD, st));
         d3 = go;
@@ -954,7 +963,8 @@ static int block_backward(osi_resnet50* n, int bi, const float* params, float* g
         // stem needs no reduction pass over its 112 x 112 tensor (pool mode of osi_conv_dgrad_fused)
         Conv& c0 = n->convs[0];
         n->stem_stats_P = 0;
-        if (n->stem_fused && n->stem_pool_stats && n->stem_ws_bytes > 0) {
+        // (not when this backward also writes dJ/dimage: the stem tail then materialises dY and reduces bn1 itself)
+        if (n->stem_fused && n->stem_pool_stats && n->stem_ws_bytes > 0 && !n->bw_dimage) {
             BN& b0 = n->bns[c0.bn];
             osi_dgrad_fusion f{};
             f.y0 = ws + c0.y; f.mean0 = ws + b0.mean; f.invstd0 = ws + b0.invstd;
@@ -978,9 +988,24 @@ static int block_backward(osi_resnet50* n, int bi, const float* params, float* g
 
 int osi_resnet50_backward(osi_resnet50_t n, const float* params, float* grads, void* workspace, const float* dlogits,
                           const float* dfeatures, int stage_lo, int stage_hi, osi_stream_t stream) {
-    OSI_REQUIRE(n && params && grads && workspace);
+    return osi_resnet50_backward_ex(n, params, grads, workspace, dlogits, dfeatures, nullptr, 1, stage_lo, stage_hi, stream);
+}
+
+int osi_resnet50_backward_ex(osi_resnet50_t n, const float* params, float* grads, void* workspace, const float* dlogits,
+                             const float* dfeatures, float* dimage, int param_grads, int stage_lo, int stage_hi, osi_stream_t stream) {
+    OSI_REQUIRE(n && params && workspace);
+    OSI_REQUIRE(param_grads == 0 || param_grads == 1);
+    OSI_REQUIRE(!param_grads || grads);
+    OSI_REQUIRE(param_grads || dimage);                 // a backward that produces nothing is a caller error
+    OSI_REQUIRE(((uintptr_t)dimage & 3) == 0);
     OSI_REQUIRE(stage_lo >= 0 && stage_lo < stage_hi && stage_hi <= n->n_stages);
     if (!n->fwd_done || stage_lo != n->next_stage || !n->plan_unchanged()) return OSI_ERR_STATE;
+    if (stage_lo == 0) {                                // the request is fixed by the call that runs stage 0 (block 0's dgrad form depends on it)
+        n->bw_dimage = dimage;
+        n->bw_pg = param_grads != 0;
+    } else if (n->bw_dimage != dimage || n->bw_pg != (param_grads != 0)) {
+        return OSI_ERR_STATE;
+    }
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
     auto S = [&](int i) { return ws + n->scratch[i]; };
@@ -1000,10 +1025,12 @@ int osi_resnet50_backward(osi_resnet50_t n, const float* params, float* grads, v
                     return OSI_ERR_LAUNCH;
                 acc = 1;
             }
-            float* dlb = n->t_lg_b >= 0 ? grads + n->tensors[n->t_lg_b].off : nullptr;
-            OSI_TRY(osi_linear_bwd(dlogits, ws + n->feat, params + lw.off, dfeat, acc, grads + lw.off, dlb, n->B, n->F, n->O, st));
-            OSI_TRY(osi_linear_bwd(dfeat, ws + n->pooled, params + fw.off, ws + n->dpooled, 0, grads + fw.off, grads + fb.off, n->B,
-                                   2048, n->F, st));
+            const bool pg = n->bw_pg;
+            float* dlb = pg && n->t_lg_b >= 0 ? grads + n->tensors[n->t_lg_b].off : nullptr;
+            OSI_TRY(osi_linear_bwd(dlogits, ws + n->feat, params + lw.off, dfeat, acc, pg ? grads + lw.off : nullptr, dlb, n->B, n->F,
+                                   n->O, st));
+            OSI_TRY(osi_linear_bwd(dfeat, ws + n->pooled, params + fw.off, ws + n->dpooled, 0, pg ? grads + fw.off : nullptr,
+                                   pg ? grads + fb.off : nullptr, n->B, 2048, n->F, st));
             int g = n->take(st);
             if (g < 0) return g;
             OSI_TRY(osi_avgpool_bwd(ws + n->dpooled, S(g), n->B, n->Hf * n->Wf, 2048, st));
@@ -1024,7 +1051,22 @@ int osi_resnet50_backward(osi_resnet50_t n, const float* params, float* grads, v
             if (t < 0) return t;
             BN& b0 = n->bns[c0.bn];
             const float* x4c = n->x4_cur ? n->x4_cur : ws + n->x4;
-            if (n->stem_fused && n->stem_ws_bytes > 0) {      // its own slab, sized at create: never the side stream's wg_ws
+            if (n->bw_dimage) {
+                // dJ/dimage wanted: the stem's dY must exist in memory. The materialising branch of stem_fused = 0 (max-pool scatter + ReLU
+                // gate + bn1 backward into a scratch buffer), its weight gradient from that dY unless input-only, then the stem's input
+                // gradient straight into the caller's NCHW tensor (osi_stem_dgrad)
+                OSI_TRY(osi_bn_relu_maxpool_bwd(S(go), ws + n->pool_idx, ws + c0.y, ws + b0.mean, ws + b0.invstd, params + b0.g_off, S(t),
+                                                n->dgam(grads, ws, b0), n->dbet(grads, ws, b0), n->B, n->Hs, n->Ws, 64, ws + n->bn_ws,
+                                                n->bn_ws_bytes, st));
+                OSI_TRY(n->mark(OSI_PROF_BN_BWD, st));
+                n->give(go);
+                OSI_TRY(wgrad(n, 0, grads, ws, t, x4c, st));
+                OSI_TRY(before_dgrad(n, st));
+                OSI_TRY(osi_stem_dgrad(S(t), params + c0.w_off, n->bw_dimage, n->B, n->H, n->W, st));
+                OSI_TRY(n->mark(OSI_PROF_CONV_DGRAD, st));
+                OSI_TRY(flush_wgrad(n, st));
+                n->give(t);
+            } else if (n->stem_fused && n->stem_ws_bytes > 0) {      // its own slab, sized at create: never the side stream's wg_ws
                 // reductions of bn1's backward (dgamma, dbeta) on the main stream, then the weight gradient with the max-pool scatter,
                 // ReLU gate and BatchNorm backward applied inside its operand loader: the 112x112x64 gradient is never written
                 n->give(t);

@@ -84,6 +84,7 @@ _SIGS = {
     "osi_stem_wgrad_fused_workspace": (c_size_t, [_PD]),
     "osi_stem_wgrad_fused": (c_int, [_PD, P, P, P, P, P, P, P, P, P, P, P, c_size_t, P]),
     "osi_stem_grad_unpack": (c_int, [P, P, c_int, P]),
+    "osi_stem_dgrad": (c_int, [P, P, P, c_int, c_int, c_int, P]),
     "osi_bn_workspace": (c_size_t, [c_int, c_int]),
     "osi_bn_train_stats": (c_int, [P, c_int, c_int, P, P, c_float, c_float, P, P, P, P, P, P, P, c_size_t, P]),
     "osi_bn_eval_coeffs": (c_int, [P, P, P, P, c_float, c_int, P, P, P]),
@@ -142,6 +143,7 @@ _SIGS = {
     "osi_resnet50_debug_gate": (c_int, [c_void_p, P, c_int, P, P, P]),
     "osi_resnet50_forward": (c_int, [c_void_p, P, P, P, P, P, P, P, c_int, P]),
     "osi_resnet50_backward": (c_int, [c_void_p, P, P, P, P, P, c_int, c_int, P]),
+    "osi_resnet50_backward_ex": (c_int, [c_void_p, P, P, P, P, P, P, c_int, c_int, c_int, P]),
 }
 
 _lib = None

@@ -55,7 +55,8 @@ class _LossValue(torch.Tensor):
     dJ/dlogits (and dJ/dfeatures) — already computed by the loss kernel — go straight to the network's backward instead of
     through autograd's seed gradient (a ones_like fill) and a `dlogits * 1` multiply: two elementwise launches fewer between the
     forward and the backward pass. Every other use (gradient=, inputs=, retain_graph, create_graph, or a loss that was combined
-    with other terms and therefore is a new tensor) takes the ordinary autograd route, which gives the same gradients.
+    with other terms and therefore is a new tensor, an image batch that requires grad, every parameter frozen) takes the ordinary
+    autograd route, which gives the same gradients.
 
     Divergence from `torch.Tensor.backward`, by design: the direct route does not run autograd, so it is taken only when nothing could
     observe the difference — logits / features carry no tensor hooks and do not retain their gradient (otherwise: the autograd route) —
@@ -69,7 +70,11 @@ class _LossValue(torch.Tensor):
         direct = self.__dict__.pop("_osi_direct", None)
         if direct is not None:
             watched = any(t is not None and (t.retains_grad or bool(getattr(t, "_backward_hooks", None))) for t in direct[2])
-            if watched:
+            # the direct route is the plain parameter-gradient step only: an image that requires grad (dJ/dimage goes to x.grad, or
+            # further back through whatever produced x) or frozen parameters (input-only backward) take the autograd route, where
+            # the network's node sees its needs_input_grad
+            image_grad, param_grad = direct[0].needs_input_grad[:2]
+            if watched or image_grad or not param_grad:
                 direct = None
         if direct is None or gradient is not None or retain_graph or create_graph or inputs is not None:
             return super().backward(gradient, retain_graph, create_graph, inputs)

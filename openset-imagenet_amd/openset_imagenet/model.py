@@ -100,7 +100,9 @@ class _Net:
 
 
 class _BackboneFn(torch.autograd.Function):
-    """Autograd node standing for the whole network: parameter gradients are written straight into the gradient arena."""
+    """Autograd node standing for the whole network: parameter gradients are written straight into the gradient arena; the
+    gradient w.r.t. an NCHW `image` that requires grad is returned as that input's gradient. `anchor` stands for the parameters:
+    a detached anchor (no parameter requires grad) makes the backward input-only (no parameter gradient is computed)."""
 
     @staticmethod
     def forward(ctx, image, anchor, model, flip):
@@ -115,8 +117,9 @@ class _BackboneFn(torch.autograd.Function):
         if ctx.serial != ctx.model._fwd_serial:
             raise RuntimeError("backward() of a forward pass that is no longer the model's latest one: the executor keeps the "
                                "activations of ONE forward (the reference loop is forward, loss, backward, step — train.py:132-139)")
-        ctx.model._run_backward(dlogits, dfeatures)
-        return None, None, None, None
+        want_dx, want_params = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dimage = ctx.model._run_backward(dlogits, dfeatures, want_image=want_dx, param_grads=want_params)
+        return dimage, None, None, None
 
 
 class ResNet50(nn.Module):
@@ -319,29 +322,40 @@ class ResNet50(nn.Module):
         self._last = (net, image if (want_grad or bound) else None)   # keeps a bound batch alive until the next forward
         return logits, features
 
-    def _run_backward(self, dlogits, dfeatures):
+    def _run_backward(self, dlogits, dfeatures, want_image=False, param_grads=True):
+        """Backward of the latest forward. want_image: also return dJ/dimage (NCHW fp32, the forward's batch geometry);
+        param_grads = False: input-only backward (no parameter gradient is computed, the gradient arena is not touched)."""
         net, _ = self._last
+        B, H, W = net_shape(self, net)
         if dlogits is None:
-            dlogits = torch.zeros(net_shape(self, net)[0], self._O, device=self._flat_params.device)
+            dlogits = torch.zeros(B, self._O, device=self._flat_params.device)
         dlogits = dlogits.contiguous().float()
         dfeatures = None if dfeatures is None else dfeatures.contiguous().float()
+        dimage = torch.empty(B, 3, H, W, device=self._flat_params.device) if want_image else None
         sync = self._grad_sync
-        bwd = N.ops().resnet50_backward
+        if dimage is None and param_grads:
+            bwd = N.ops().resnet50_backward
+        else:             # ABI 8: dJ/dimage written by the last stage, and/or no parameter gradient
+            ex = N.ops().resnet50_backward_ex
+            bwd = lambda *a: ex(*a[:6], dimage, bool(param_grads), *a[6:])
+        grads = self._flat_grads if param_grads else self._flat_grads[:0]
         if sync is None:  # single GPU: all stages in one call (one side-stream join at the end)
-            bwd(net.h.value, self._flat_params, self._flat_grads, self._ws, dlogits, dfeatures, 0, self._n_stages)
+            bwd(net.h.value, self._flat_params, grads, self._ws, dlogits, dfeatures, 0, self._n_stages)
         else:             # data parallel: stage by stage, each finished slice of the gradient arena goes to the all-reduce
             if not net.staged:   # staged calls no longer join the weight-gradient side stream into the compute stream (only the last does)
                 N.check(N.lib().osi_resnet50_set_option(net.h, b"stage_join", 0), "osi_resnet50_set_option(stage_join)")
                 net.staged = True
-            grads = self._flat_grads
             handoff = lambda comm: N.ops().resnet50_grads_ready(net.h.value, grads, comm.cuda_stream)
             for s in range(self._n_stages):
                 bwd(net.h.value, self._flat_params, grads, self._ws, dlogits, dfeatures, s, s + 1)
-                lo, hi = self._stage_ranges[s]
-                sync.bucket_ready(grads, lo, hi, handoff)
+                if param_grads:   # input-only: no parameter gradient to average, nothing goes to the all-reduce
+                    lo, hi = self._stage_ranges[s]
+                    sync.bucket_ready(grads, lo, hi, handoff)
             sync.finish()
-        self._grads_fresh = True
-        self.bind_gradients()
+        if param_grads:
+            self._grads_fresh = True
+            self.bind_gradients()
+        return dimage
 
     def forward(self, image, flip=None):
         """Forward pass: returns (logits, deep features) like the reference (model.py:28-39).
@@ -351,8 +365,16 @@ class ResNet50(nn.Module):
         layout staging then happen in one pass on the GPU and the host link carries a quarter of the bytes), or an fp32
         [B,H,W,4] batch already staged in the executor's layout by pipeline.DevicePrefetcher (read in place)."""
         self._check_image(image)
-        if torch.is_grad_enabled() and self.training and self._plist[0].requires_grad:
-            return _BackboneFn.apply(image, self._anchor, self, flip)
+        if torch.is_grad_enabled() and self.training:
+            image_grad = image.requires_grad
+            if image_grad and self._is_nhwc4(image):
+                raise ValueError("only NCHW fp32 [B, 3, H, W] image batches are differentiable; an NHWC4 batch "
+                                 "(pipeline.DevicePrefetcher's layout) cannot require grad")
+            param_grad = self._plist[0].requires_grad or any(p.requires_grad for p in self._plist)
+            if param_grad or image_grad:
+                # no parameter requires grad: a detached anchor, so the backward runs input-only
+                anchor = self._anchor if param_grad else self._anchor.detach()
+                return _BackboneFn.apply(image, anchor, self, flip)
         return self._run_forward(image, False, flip)
 
 
