@@ -424,17 +424,15 @@ int osi_resnet50_backward_ex(osi_resnet50_t net, const float* params, float* gra
  * for nothing and goes on with the next stage while the collective runs (reference intent: config/train.yaml:18,35-39). */
 int osi_resnet50_grads_ready(osi_resnet50_t net, osi_stream_t main_stream, osi_stream_t waiter_stream);
 
-/* Weight gradients on a low-priority side stream, overlapped with dgrad / BatchNorm backward (default on; joined back into
- * `stream` at the end of every backward call unless "stage_join" = 0). enable = 0 serialises everything on the caller's stream. */
-int osi_resnet50_set_overlap(osi_resnet50_t net, int enable);
-/* Per-executor switches: "overlap" (= osi_resnet50_set_overlap), "fwd_fork" (projection shortcut of the forward pass on the side
- * stream, default 1), "fwd_recompute" (conv1 of a bottleneck recomputes the previous identity-shortcut block output in its loader and
- * that block's output pass runs beside it on the side stream; default 0: measured no faster), "side_priority_normal" (side stream at default instead of lowest priority; only before the first training
- * call, else OSI_ERR_STATE), "stage_join" (default 1; see osi_resnet50_grads_ready), "stagger", "stem_fused", "stem_pool_stats", "ds_sparse",
- * "stem_wgrad_main" (A/B switches of the backward schedule), "eval_fused" (default 1: a forward with training = 0 runs
- * the inference forms — every BatchNorm + shortcut + ReLU in its convolution's epilogue, no pre-BN tensor, no block-output pass, no
- * bitmask, one coefficient launch for all 53 BatchNorms; 0 = the training topology on running statistics, kept for A/B; same bits).
- * Unknown name -> OSI_ERR_ARG. */
+/* Per-executor switches: "overlap" (default 1: weight gradients on a low-priority side stream, overlapped with dgrad / BatchNorm
+ * backward and joined back into `stream` at the end of every backward call unless "stage_join" = 0; 0 serialises everything on the
+ * caller's stream), "fwd_fork" (projection shortcut of the forward pass on the side stream, default 1), "side_priority_normal" (side
+ * stream at default instead of lowest priority; only before the first training call, else OSI_ERR_STATE), "stage_join" (default 1; see
+ * osi_resnet50_grads_ready), "eval_fused" (default 1: a forward with training = 0 runs the inference forms — every BatchNorm +
+ * shortcut + ReLU in its convolution's epilogue, no pre-BN tensor, no block-output pass, no bitmask, one coefficient launch for all 53
+ * BatchNorms; 0 = the training topology on running statistics, kept for A/B: bit-identical when both run the same launch plans (knob
+ * "tail_split" off), fp32-rounding-level differences otherwise).
+ * Unknown name -> OSI_ERR_ARG; so are the settled A/B switches retired with ABI 9. */
 int osi_resnet50_set_option(osi_resnet50_t net, const char* name, int value);
 
 /* Optional HIP-event instrumentation of the executor (bench.py's roofline leg): one event after every op on the launch

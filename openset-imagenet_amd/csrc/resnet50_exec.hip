@@ -163,42 +163,23 @@ struct osi_resnet50 {
     void* staged_ws = nullptr;   // workspace whose input buffer was filled by osi_resnet50_stage_input_u8 (consumed by one forward)
     bool overlap = true;
     bool fwd_fork = true;            // projection shortcut of the forward pass on the side stream
-    bool fwd_recompute = false;      // identity-shortcut block outputs recomputed by the next conv1, their pass moved off the critical
-                                     // path. Built, bit-exact, and measured: NO gain (35.48 vs 35.45 ms) — conv1 with the second operand
-                                     // stream is 5-27 % slower, which eats the hidden pass. Off by default; kept for A/B.
     bool side_prio_normal = false;   // side stream at default instead of lowest priority (read when the stream is created)
     const float* x4_ext = nullptr;   // external NHWC4 input bound by osi_resnet50_bind_input_nhwc4 (consumed by one forward)
     const float* x4_cur = nullptr;   // input of the step in flight (forward sets it, the stem weight gradient reads it)
-    bool stem_pool_stats = true;     // option "stem_pool_stats": bn1's backward reductions come out of layer1.0.conv1's dgrad epilogue
-    bool ds_sparse = true;           // option "ds_sparse": stride-2 shortcut gradients write / are read at the even-even pixels only
-    bool stem_wgrad_main = true;     // option "stem_wgrad_main": the fused stem weight gradient runs on the main stream (own workspace)
-    int stem_stats_P = 0;            // > 0: bn1's backward partial sums wait in dg_ws (left by the pool-mode epilogue of layer1.0.conv1's dgrad)
-    bool stem_fused = true;          // option "stem_fused": conv1's weight gradient builds dY in its operand loader (osi_stem_wgrad_fused)
-                                     // behind the BatchNorm reductions: no 112x112x64 gradient tensor, no apply pass (step -0.15 ms)
-    bool stagger = false;            // option "stagger": a weight gradient starts when the input gradient of the SAME layer has finished
-                                     // (beside the next BatchNorm-backward kernels) and the next input gradient waits for it: matrix-bound
-                                     // kernels never co-run, only HBM-bound work overlaps them. A/B against the default co-running schedule.
-    struct PendingW { bool on = false; int ci = 0, gi = 0, in_bn = -1; const float* conv_in = nullptr; float* grads = nullptr; float* ws = nullptr; } pend;
-    bool w_inflight = false;
+    int stem_stats_P = 0;            // row tiles of bn1's backward partial sums in dg_ws (left by the pool-mode epilogue of layer1.0.conv1's dgrad)
     // request of the backward in flight (osi_resnet50_backward_ex), fixed by the call that runs stage 0: bw_dimage != NULL -> the stem
     // tail materialises dY and its input gradient writes dJ/dimage; bw_pg = 0 -> input-only (no weight gradient, nothing into grads)
     float* bw_dimage = nullptr;
     bool bw_pg = true;
     float* dgam(float* grads, float* ws, const BN& b) const { return bw_pg ? grads + b.g_off : ws + b.dsink; }
     float* dbet(float* grads, float* ws, const BN& b) const { return bw_pg ? grads + b.b_off : ws + b.dsink + b.C; }
-#ifdef OSI_DIAG                       // `make -C csrc diag` (libosi_hip_diag.so, tools only): the product library has no such switch
-    int dbg_fwd_count = 0;           // training forwards so far (dbg_skip bit 3)
-    int dbg_skip = 0;                // option "dbg_skip" (TIMING EXPERIMENTS ONLY, results are wrong): bit 0 = the BatchNorm-backward apply passes
-                                     // are not launched (their reductions still are), bit 1 = the block-output passes of the forward are
-                                     // not launched, bit 2 = with "fwd_recompute" the deferred block-output pass is not launched either — upper bounds for what folding
-                                     // those passes into their consumers could buy; bit 3 = the forward's BatchNorm finalize launches are not
-                                     // launched (round 6: the ceiling of merging them)
-#else
-    static constexpr int dbg_skip = 0;
-    static constexpr int dbg_fwd_count = 0;
-#endif
+    // The stem tail's form, decided by what the backward can observe. Block 0's last input gradient and the tail both ask here, so they
+    // cannot disagree: the fused form (bn1's reductions out of that input gradient's pool-mode epilogue, dY built inside
+    // osi_stem_wgrad_fused's loader) unless dJ/dimage needs dY in memory or the geometry / knobs leave the fused form no workspace.
+    bool stem_tail_fused() const { return !bw_dimage && stem_ws_bytes > 0; }
     bool eval_fused = true;          // option "eval_fused": a forward with training = 0 runs the inference forms (forward_eval_fused); 0 = the
-                                     // training topology on running statistics (A/B, same bits)
+                                     // training topology on running statistics (A/B: the same bits when both run the same launch plans,
+                                     // i.e. tail_split off; fp32-rounding-level differences otherwise)
     bool stage_join = true;          // option "stage_join": a staged backward call (stage_hi < stages) ends by joining the side stream into
                                      // the caller's stream. 0 (data parallel): only the LAST stage joins; the caller hands each finished
                                      // stage to its communication stream with osi_resnet50_grads_ready, and the compute stream runs on
@@ -213,8 +194,7 @@ struct osi_resnet50 {
                a.dp_reserved_cus == b.dp_reserved_cus && a.fwd_wino == b.fwd_wino && a.dgrad_wino == b.dgrad_wino && a.wgrad_wino == b.wgrad_wino;
     }
     hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_wdone = nullptr, ev_rmain = nullptr, ev_rside = nullptr, ev_wt = nullptr;
-    bool wt_aside = true;            // option "wino_weights_aside": the Winograd weight transforms of a training forward run on the side stream (A/B: 0 = main)
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_rmain = nullptr, ev_rside = nullptr, ev_wt = nullptr;
     bool wt_pending = false;         // the Winograd weight transforms of this forward run on the side stream: the first consumer waits for ev_wt
     hipEvent_t buf_ev[NSCR] = {};
     bool buf_pending[NSCR] = {};
@@ -227,7 +207,6 @@ struct osi_resnet50 {
         if (hipStreamCreateWithPriority(&side, hipStreamNonBlocking, prio) != hipSuccess) return OSI_ERR_LAUNCH;
         if (hipEventCreateWithFlags(&ev_fork, EV_FLAGS) != hipSuccess) return OSI_ERR_LAUNCH;
         if (hipEventCreateWithFlags(&ev_join, EV_FLAGS) != hipSuccess) return OSI_ERR_LAUNCH;
-        if (hipEventCreateWithFlags(&ev_wdone, EV_FLAGS) != hipSuccess) return OSI_ERR_LAUNCH;
         if (hipEventCreateWithFlags(&ev_wt, EV_FLAGS) != hipSuccess) return OSI_ERR_LAUNCH;
         for (int i = 0; i < NSCR; ++i)
             if (hipEventCreateWithFlags(&buf_ev[i], EV_FLAGS) != hipSuccess) return OSI_ERR_LAUNCH;
@@ -247,6 +226,19 @@ struct osi_resnet50 {
         return i;
     }
     void give(int i) { free_list.push_back(i); }
+    // the side stream continues from everything enqueued on `st` so far
+    int fork_side(hipStream_t st) {
+        if (hipEventRecord(ev_fork, st) != hipSuccess) return OSI_ERR_LAUNCH;
+        if (hipStreamWaitEvent(side, ev_fork, 0) != hipSuccess) return OSI_ERR_LAUNCH;
+        return OSI_OK;
+    }
+    // the first consumer of the Winograd-transformed weights on `st` waits for the side stream's transforms
+    int wait_weight_transforms(hipStream_t st) {
+        if (!wt_pending) return OSI_OK;
+        if (hipStreamWaitEvent(st, ev_wt, 0) != hipSuccess) return OSI_ERR_LAUNCH;
+        wt_pending = false;
+        return OSI_OK;
+    }
     int join_side(hipStream_t st) {
         if (!side_dirty) return OSI_OK;
         if (hipEventRecord(ev_join, side) != hipSuccess) return OSI_ERR_LAUNCH;
@@ -259,7 +251,7 @@ struct osi_resnet50 {
         for (hipEvent_t e : prof_ev) (void)hipEventDestroy(e);
         if (side) {
             (void)hipStreamSynchronize(side);
-            (void)hipEventDestroy(ev_fork); (void)hipEventDestroy(ev_join); (void)hipEventDestroy(ev_wdone); (void)hipEventDestroy(ev_wt);
+            (void)hipEventDestroy(ev_fork); (void)hipEventDestroy(ev_join); (void)hipEventDestroy(ev_wt);
             for (int i = 0; i < NSCR; ++i) (void)hipEventDestroy(buf_ev[i]);
             (void)hipStreamDestroy(side);
         }
@@ -359,7 +351,7 @@ int osi_resnet50_create(osi_resnet50_t* out, int B, int H, int W, int fc_dim, in
     n->bn_ws_bytes = bnws; n->bn_ws = n->ws_alloc(bnws / 4 + 4); n->bn_ws2 = n->ws_alloc(bnws / 4 + 4);
     n->wg_ws_bytes = wgws; n->wg_ws = n->ws_alloc(wgws / 4 + 4);
     // the fused stem weight gradient has its own slab: it may run on the main stream while the side stream still owns wg_ws
-    // (0 bytes = a geometry / knob setting the fused form does not take: the executor then never calls it — see stem_fused_ok)
+    // (0 bytes = a geometry / knob setting the fused form does not take: the executor then never calls it — see stem_tail_fused)
     n->stem_ws_bytes = osi_stem_wgrad_fused_workspace(&n->convs[0].d);
     n->stem_ws = n->stem_ws_bytes ? n->ws_alloc(n->stem_ws_bytes / 4 + 4) : n->wg_ws;
     n->plan_knobs = g_osi_tuning;
@@ -457,37 +449,27 @@ int osi_resnet50_profile_read(osi_resnet50_t n, double* ms, int* count) {
 
 // conv ci + its BatchNorm statistics. in_bn >= 0: the conv's input is the PRE-BN output of the layer whose BatchNorm is `in_bn`;
 // that BatchNorm + ReLU is applied inside the conv's operand loader (osi_conv_fwd_act) — the activation never exists in HBM.
-// in_res != NULL (with in_bn): x is conv3's pre-BN output of the previous bottleneck and in_res its identity shortcut — the whole block
-// output relu(bn3(x) + in_res) is recomputed in the loader (osi_conv_fwd_act2).
 static int conv_bn_fwd(osi_resnet50* n, int ci, const float* params, float* buffers, float* ws, const float* x, const float* w,
-                       int training, hipStream_t st, size_t bn_ws_off, int in_bn = -1, const float* in_res = nullptr) {
+                       int training, hipStream_t st, size_t bn_ws_off, int in_bn = -1) {
     Conv& c = n->convs[ci];
     BN& b = n->bns[c.bn];
     const float* isc = in_bn >= 0 ? ws + n->bns[in_bn].scale : nullptr;
     const float* ish = in_bn >= 0 ? ws + n->bns[in_bn].shift : nullptr;
     // 3x3 / stride 1 (conv2 of a bottleneck without a stride): Winograd F(2x2,3x3), 2.25x fewer multiplies (csrc/conv_wino.hip); main stream only
-    const bool wino = n->plan_knobs.fwd_wino && isc && !in_res && (n->side == nullptr || st != n->side) && c.u_fw != (size_t)-1;
-    if (wino && n->wt_pending) {      // the transformed weights come from the side stream
-        if (hipStreamWaitEvent(st, n->ev_wt, 0) != hipSuccess) return OSI_ERR_LAUNCH;
-        n->wt_pending = false;
-    }
+    const bool wino = n->plan_knobs.fwd_wino && isc && (n->side == nullptr || st != n->side) && c.u_fw != (size_t)-1;
+    if (wino) OSI_TRY(n->wait_weight_transforms(st));
     if (training) {
         // batch statistics come out of the conv epilogue (per row tile), only a tiny per-channel merge follows
         int P = 0, rows = 0;
-        if (isc && in_res) OSI_TRY(osi_conv_fwd_act2(&c.d, x, isc, ish, in_res, w, ws + c.y, OSI_TILE_AUTO, ws + bn_ws_off, n->bn_ws_bytes, &P, &rows, st));
-        else if (isc && wino) OSI_TRY(osi_conv_fwd_wino_pre(&c.d, x, isc, ish, ws + c.u_fw, ws + c.y, ws + n->wino_ws, n->wino_ws_bytes, ws + bn_ws_off, n->bn_ws_bytes, &P, &rows, st));
+        if (isc && wino) OSI_TRY(osi_conv_fwd_wino_pre(&c.d, x, isc, ish, ws + c.u_fw, ws + c.y, ws + n->wino_ws, n->wino_ws_bytes, ws + bn_ws_off, n->bn_ws_bytes, &P, &rows, st));
         else if (isc) OSI_TRY(osi_conv_fwd_act(&c.d, x, isc, ish, w, ws + c.y, OSI_TILE_AUTO, ws + bn_ws_off, n->bn_ws_bytes, &P, &rows, st));
         else OSI_TRY(osi_conv_fwd_bnstats(&c.d, x, w, ws + c.y, OSI_TILE_AUTO, ws + bn_ws_off, n->bn_ws_bytes, &P, &rows, st));
         OSI_TRY(n->mark(OSI_PROF_CONV_FWD, st));
-        // (bit 3, diagnostic build only: no finalize launches from the 4th training forward on — the coefficients of the third step stay
-        // in the workspace, so the data, and with it the clock the chip holds, stay realistic: the ceiling of merging / folding these launches)
-        if (!((n->dbg_skip & 8) && n->dbg_fwd_count > 3))
         OSI_TRY(osi_bn_finalize_stats(ws + bn_ws_off, n->bn_ws_bytes, P, rows, b.M, b.C, params + b.g_off, params + b.b_off, 1e-5f, 0.1f,
                                       buffers + b.rm_off, buffers + b.rv_off, ws + b.mean, ws + b.invstd, ws + b.scale,
                                       ws + b.shift, st));
     } else {
-        if (isc && in_res) OSI_TRY(osi_conv_fwd_act2(&c.d, x, isc, ish, in_res, w, ws + c.y, OSI_TILE_AUTO, nullptr, 0, nullptr, nullptr, st));
-        else if (isc && wino) OSI_TRY(osi_conv_fwd_wino_pre(&c.d, x, isc, ish, ws + c.u_fw, ws + c.y, ws + n->wino_ws, n->wino_ws_bytes, nullptr, 0, nullptr, nullptr, st));
+        if (isc && wino) OSI_TRY(osi_conv_fwd_wino_pre(&c.d, x, isc, ish, ws + c.u_fw, ws + c.y, ws + n->wino_ws, n->wino_ws_bytes, nullptr, 0, nullptr, nullptr, st));
         else if (isc) OSI_TRY(osi_conv_fwd_act(&c.d, x, isc, ish, w, ws + c.y, OSI_TILE_AUTO, nullptr, 0, nullptr, nullptr, st));
         else OSI_TRY(osi_conv_fwd(&c.d, x, w, ws + c.y, OSI_TILE_AUTO, st));
         OSI_TRY(n->mark(OSI_PROF_CONV_FWD, st));
@@ -536,7 +518,8 @@ static int head_fwd(osi_resnet50* n, const float* params, float* ws, float* logi
 // (osi_conv_fwd_epilogue / osi_conv_fwd_wino_epilogue_pre). No pre-BN tensor, no block-output pass, no ReLU bitmask, no fused-loader
 // activation on the consumer side (every consumer reads a finished activation with its plain loader): 53 + 16 + 53 launches fewer, the 16
 // HBM-bound block-output passes and the loader-side activation arithmetic gone. Values: the same fmas on the same accumulators as the
-// training topology on running statistics (option eval_fused = 0) — bit-identical outputs.
+// training topology on running statistics (option eval_fused = 0) — bit-identical outputs when both run the same launch plans
+// (tail_split off); where the plans differ, the two differ at fp32-rounding level.
 // Buffers: conv1 / conv2 / shortcut activations live where the training forward keeps those layers' pre-BN tensors, the block outputs
 // where it keeps them; the workspace then holds no backward state (fwd_done and any_fwd are cleared).
 static int forward_eval_fused(osi_resnet50* n, const float* params, const float* buffers, float* ws, const float* x4, float* logits,
@@ -570,8 +553,7 @@ static int forward_eval_fused(osi_resnet50* n, const float* params, const float*
             Conv& cd = n->convs[k.ds];
             hipStream_t ds_st = st;
             if (fork) {
-                if (hipEventRecord(n->ev_fork, st) != hipSuccess) return OSI_ERR_LAUNCH;
-                if (hipStreamWaitEvent(n->side, n->ev_fork, 0) != hipSuccess) return OSI_ERR_LAUNCH;
+                OSI_TRY(n->fork_side(st));
                 ds_st = n->side;
             }
             const osi_conv_epilogue e = epi(k.ds, nullptr, 0);
@@ -587,10 +569,7 @@ static int forward_eval_fused(osi_resnet50* n, const float* params, const float*
         {
             const osi_conv_epilogue e = epi(k.c2, nullptr, 1);
             if (n->plan_knobs.fwd_wino && c2.u_fw != (size_t)-1) {     // 3x3 / stride 1: Winograd F(2x2,3x3)
-                if (n->wt_pending) {      // the transformed weights come from the side stream
-                    if (hipStreamWaitEvent(st, n->ev_wt, 0) != hipSuccess) return OSI_ERR_LAUNCH;
-                    n->wt_pending = false;
-                }
+                OSI_TRY(n->wait_weight_transforms(st));
                 OSI_TRY(osi_conv_fwd_wino_epilogue_pre(&c2.d, ws + c1.y, ws + c2.u_fw, ws + c2.y, &e, ws + n->wino_ws, n->wino_ws_bytes, st));
             } else {
                 OSI_TRY(osi_conv_fwd_epilogue(&c2.d, ws + c1.y, params + c2.w_off, ws + c2.y, &e, ws + n->bn_ws, n->bn_ws_bytes, st));
@@ -624,9 +603,6 @@ int osi_resnet50_forward(osi_resnet50_t n, const float* params, float* buffers, 
     const float* x4 = (!image && ext) ? ext : ws + n->x4;
     n->x4_cur = x4;
     n->fwd_done = false;
-#ifdef OSI_DIAG
-    if (training) ++n->dbg_fwd_count;
-#endif
     if (training && n->overlap && (!n->prof_on || n->prof_timeline)) OSI_TRY(n->ensure_side());
     OSI_TRY(n->mark(OSI_PROF_START, st));
     // Winograd weight transforms of every 3x3 stride-1 layer, both directions: the weights are the same for this forward and its backward.
@@ -635,12 +611,9 @@ int osi_resnet50_forward(osi_resnet50_t n, const float* params, float* buffers, 
     if (n->plan_knobs.fwd_wino || (training && n->plan_knobs.dgrad_wino)) {
         // (training forwards only: an inference forward has 13 transforms and nothing but the stem beside them — the fork / join costs more
         // than they do: 7.96 in line vs 8.00 ms aside per batch of 128, profiles/NOTES_r06.md)
-        const bool aside = training && n->async_wgrad() && n->wt_aside;
+        const bool aside = training && n->async_wgrad();
         hipStream_t wt = aside ? n->side : st;
-        if (aside) {
-            if (hipEventRecord(n->ev_fork, st) != hipSuccess) return OSI_ERR_LAUNCH;
-            if (hipStreamWaitEvent(n->side, n->ev_fork, 0) != hipSuccess) return OSI_ERR_LAUNCH;
-        }
+        if (aside) OSI_TRY(n->fork_side(st));
         for (auto& c : n->convs)
             if (n->plan_knobs.fwd_wino && c.u_fw != (size_t)-1)
                 OSI_TRY(osi_conv_wino_transform_weights(&c.d, params + c.w_off, 0, ws + c.u_fw, osi_conv_wino_weights_bytes(&c.d), wt));
@@ -670,51 +643,21 @@ int osi_resnet50_forward(osi_resnet50_t n, const float* params, float* buffers, 
     // bottleneck blocks. Only the block outputs (residual sums) are materialised: conv2 / conv3 read the pre-BN output of the conv
     // before them and apply its BatchNorm + ReLU in their operand loader; the projection shortcut's BatchNorm is applied inside the
     // block-output kernel. Per block: 3 (4) convs + one block-output pass instead of 3 (4) convs + 3 (4) apply passes.
-    // The block-output pass itself is HBM-bound and sits between two matrix-bound convolutions. Option "fwd_recompute" takes it off the
-    // critical path for blocks with an identity shortcut: conv1 of the next block recomputes relu(bn3(y3) + x) in its loader
-    // (osi_conv_fwd_act2) and the pass that materialises the tensor (for the next shortcut, the projection conv and the backward) runs
-    // beside it on the side stream. Default off (no measured gain, see the member's comment).
-    const int nb = (int)n->blocks.size();
-    bool deferred = false;          // the previous block's output pass has not been enqueued yet
-    for (int bi = 0; bi < nb; ++bi) {
-        Block& k = n->blocks[bi];
+    for (Block& k : n->blocks) {
         const float* x = ws + k.x_in;
-        const bool async = n->async_wgrad();
-        hipStream_t sd = async ? n->side : st;      // stream of the work that runs beside the main branch
-        bool forked = false;
-        if ((deferred || (k.ds >= 0 && n->fwd_fork)) && async) {
-            if (hipEventRecord(n->ev_fork, st) != hipSuccess) return OSI_ERR_LAUNCH;
-            if (hipStreamWaitEvent(n->side, n->ev_fork, 0) != hipSuccess) return OSI_ERR_LAUNCH;
-            forked = true;
-        }
-        const Block* pk = bi > 0 ? &n->blocks[bi - 1] : nullptr;
-        if (deferred && !(n->dbg_skip & 4)) {   // materialise the previous block's output (this block's shortcut / projection input)
-            Conv& c3p = n->convs[pk->c3];
-            BN& b3p = n->bns[c3p.bn];
-            OSI_TRY(osi_bn_apply_relu_mask(ws + c3p.y, ws + pk->x_in, ws + b3p.scale, ws + b3p.shift, ws + c3p.a, ws + c3p.mask, b3p.M,
-                                           b3p.C, sd));
-            OSI_TRY(n->mark(OSI_PROF_BN_FWD, sd));
-        }
+        const bool fork = k.ds >= 0 && n->fwd_fork && n->async_wgrad();
         if (k.ds >= 0) {            // the projection shortcut only depends on the block input: beside the main branch (own BN scratch)
             Conv& c = n->convs[k.ds];
-            hipStream_t ds_st = (n->fwd_fork || deferred) ? sd : st;   // behind a deferred pass it must follow it on that stream
-            OSI_TRY(conv_bn_fwd(n, k.ds, params, buffers, ws, x, params + c.w_off, training, ds_st, ds_st != st ? n->bn_ws2 : n->bn_ws));
+            if (fork) OSI_TRY(n->fork_side(st));
+            OSI_TRY(conv_bn_fwd(n, k.ds, params, buffers, ws, x, params + c.w_off, training, fork ? n->side : st, fork ? n->bn_ws2 : n->bn_ws));
+            if (fork && hipEventRecord(n->ev_join, n->side) != hipSuccess) return OSI_ERR_LAUNCH;
         }
-        if (forked && hipEventRecord(n->ev_join, n->side) != hipSuccess) return OSI_ERR_LAUNCH;
         Conv &c1 = n->convs[k.c1], &c2 = n->convs[k.c2], &c3 = n->convs[k.c3];
-        if (deferred) {
-            Conv& c3p = n->convs[pk->c3];
-            OSI_TRY(conv_bn_fwd(n, k.c1, params, buffers, ws, ws + c3p.y, params + c1.w_off, training, st, n->bn_ws, c3p.bn, ws + pk->x_in));
-        } else {
-            OSI_TRY(conv_bn_fwd(n, k.c1, params, buffers, ws, x, params + c1.w_off, training, st, n->bn_ws));
-        }
+        OSI_TRY(conv_bn_fwd(n, k.c1, params, buffers, ws, x, params + c1.w_off, training, st, n->bn_ws));
         OSI_TRY(conv_bn_fwd(n, k.c2, params, buffers, ws, ws + c1.y, params + c2.w_off, training, st, n->bn_ws, c1.bn));
         OSI_TRY(conv_bn_fwd(n, k.c3, params, buffers, ws, ws + c2.y, params + c3.w_off, training, st, n->bn_ws, c2.bn));
-        if (forked && hipStreamWaitEvent(st, n->ev_join, 0) != hipSuccess) return OSI_ERR_LAUNCH;
+        if (fork && hipStreamWaitEvent(st, n->ev_join, 0) != hipSuccess) return OSI_ERR_LAUNCH;
         BN& b3 = n->bns[c3.bn];
-        deferred = n->fwd_recompute && k.ds < 0 && bi + 1 < nb;
-        if (deferred) continue;     // the next iteration enqueues this block's output pass beside its conv1
-        if (n->dbg_skip & 2) continue;   // timing experiment: no block-output pass (the next block reads stale data)
         if (k.ds >= 0) {
             Conv& cd = n->convs[k.ds];
             BN& bd = n->bns[cd.bn];
@@ -744,8 +687,7 @@ static int wgrad_launch(osi_resnet50* n, int ci, float* grads, float* ws, int gi
     const float* dy = ws + n->scratch[gi];
     hipStream_t ws_st = st;
     if (async) {
-        if (hipEventRecord(n->ev_fork, st) != hipSuccess) return OSI_ERR_LAUNCH;
-        if (hipStreamWaitEvent(n->side, n->ev_fork, 0) != hipSuccess) return OSI_ERR_LAUNCH;
+        OSI_TRY(n->fork_side(st));
         ws_st = n->side;
     }
     if (ci == 0) {
@@ -774,42 +716,15 @@ static int wgrad_launch(osi_resnet50* n, int ci, float* grads, float* ws, int gi
     return OSI_OK;
 }
 
-// staggered schedule: issue the weight gradient that was held back, behind everything enqueued on `st` so far
-static int flush_wgrad(osi_resnet50* n, hipStream_t st) {
-    if (!n->pend.on) return OSI_OK;
-    osi_resnet50::PendingW p = n->pend;
-    n->pend.on = false;
-    OSI_TRY(wgrad_launch(n, p.ci, p.grads, p.ws, p.gi, p.conv_in, st, p.in_bn, true));
-    if (hipEventRecord(n->ev_wdone, n->side) != hipSuccess) return OSI_ERR_LAUNCH;
-    n->w_inflight = true;
-    return OSI_OK;
-}
-
-// staggered schedule: an input gradient may only start once the weight gradient issued before it has finished
-static int before_dgrad(osi_resnet50* n, hipStream_t st) {
-    if (!n->w_inflight) return OSI_OK;
-    if (hipStreamWaitEvent(st, n->ev_wdone, 0) != hipSuccess) return OSI_ERR_LAUNCH;
-    n->w_inflight = false;
-    return OSI_OK;
-}
-
 static int wgrad(osi_resnet50* n, int ci, float* grads, float* ws, int gi, const float* conv_in, hipStream_t st, int in_bn = -1) {
     if (!n->bw_pg) return OSI_OK;      // input-only backward: no weight gradient of any kind
-    const bool async = n->async_wgrad();
-    if (!(async && n->stagger)) return wgrad_launch(n, ci, grads, ws, gi, conv_in, st, in_bn, async);
-    OSI_TRY(flush_wgrad(n, st));       // two weight gradients with no input gradient between them: the older one goes now
-    n->pend.on = true; n->pend.ci = ci; n->pend.gi = gi; n->pend.in_bn = in_bn; n->pend.conv_in = conv_in; n->pend.grads = grads; n->pend.ws = ws;
-    // every caller issues the input gradient that flushes this launch BEFORE giving the dy buffer back (the stem, which has no input
-    // gradient, is flushed at the end of the call, before the join), so the buffer's reader event exists by the time it can be taken
-    return OSI_OK;
+    return wgrad_launch(n, ci, grads, ws, gi, conv_in, st, in_bn, n->async_wgrad());
 }
 
-// plain input gradient (no fused epilogue) with the staggered-schedule hooks
+// plain input gradient (no fused epilogue)
 static int dgrad_plain(osi_resnet50* n, const osi_conv_desc* d, const float* dy, const float* w, float* dx, int accumulate, hipStream_t st) {
-    OSI_TRY(before_dgrad(n, st));
     OSI_TRY(osi_conv_dgrad(d, dy, w, dx, accumulate, OSI_TILE_AUTO, st));
-    OSI_TRY(n->mark(OSI_PROF_CONV_DGRAD, st));
-    return flush_wgrad(n, st);
+    return n->mark(OSI_PROF_CONV_DGRAD, st);
 }
 
 // backward of conv+BN(+ReLU mask): dout (in scratch buffer gi) -> dy in place, then wgrad; returns with dy still in the buffer
@@ -832,10 +747,6 @@ static int bn_bwd_fused(osi_resnet50* n, int ci, const float* params, float* gra
     BN& b = n->bns[c.bn];
     const float* psum_g = ws + n->dg_ws;
     const float* psum_gx = psum_g + (size_t)(1 + which) * n->fused_P * b.C;
-    if (n->dbg_skip & 1) {   // timing experiment: reductions only, the consumers read whatever the dy buffer holds
-        OSI_TRY(osi_bn_backward_reduce(psum_g, psum_gx, n->fused_P, n->dgam(grads, ws, b), n->dbet(grads, ws, b), b.M, b.C, ws + n->bn_ws, n->bn_ws_bytes, st));
-        return n->mark(OSI_PROF_BN_BWD, st);
-    }
     OSI_TRY(osi_bn_backward_fused(ws + n->scratch[gi], ws + c.y, ws + b.mean, ws + b.invstd, params + b.g_off, psum_g, psum_gx,
                                   n->fused_P, ws + n->scratch[dyi], n->dgam(grads, ws, b), n->dbet(grads, ws, b), b.M, b.C, ws + n->bn_ws,
                                   n->bn_ws_bytes, st));
@@ -862,12 +773,8 @@ static int dgrad_fused(osi_resnet50* n, int ci, const float* params, float* ws, 
     f.partials = ws + n->dg_ws; f.partials_bytes = n->dg_ws_bytes;
     f.addend_stride = add_even ? 2 : 1;
     int P = 0;
-    OSI_TRY(before_dgrad(n, st));
     // the in-block 3x3 / stride 1 input gradients (gate recomputed, one consumer, no addend) take the Winograd form
-    if (n->wt_pending) {          // (forward Winograd off: nobody has waited for the side-stream weight transforms yet)
-        if (hipStreamWaitEvent(st, n->ev_wt, 0) != hipSuccess) return OSI_ERR_LAUNCH;
-        n->wt_pending = false;
-    }
+    OSI_TRY(n->wait_weight_transforms(st));   // (forward Winograd off: nobody has waited for the side-stream weight transforms yet)
     if (n->plan_knobs.dgrad_wino && f.scale0 && pd < 0 && addi < 0 && c.u_bw != (size_t)-1)
         OSI_TRY(osi_conv_dgrad_fused_wino_pre(&c.d, ws + n->scratch[dyi], ws + c.u_bw, ws + n->scratch[dxi], &f, ws + n->wino_ws,
                                               n->wino_ws_bytes, &P, st));
@@ -875,8 +782,7 @@ static int dgrad_fused(osi_resnet50* n, int ci, const float* params, float* ws, 
     OSI_TRY(osi_conv_dgrad_fused(&c.d, ws + n->scratch[dyi], params + c.w_off, ws + n->scratch[dxi],
                                  addi >= 0 ? ws + n->scratch[addi] : nullptr, &f, OSI_TILE_AUTO, &P, st));
     n->fused_P = P;
-    OSI_TRY(n->mark(OSI_PROF_CONV_DGRAD, st));
-    return flush_wgrad(n, st);
+    return n->mark(OSI_PROF_CONV_DGRAD, st);
 }
 
 // One bottleneck block of the backward pass. On entry n->cur_grad holds the gradient w.r.t. the block output: raw (stage entry
@@ -890,8 +796,8 @@ static int block_backward(osi_resnet50* n, int bi, const float* params, float* g
     const bool has_ds = k.ds >= 0;
     // A stride-2 1x1 shortcut reaches only the even-even pixels of the block input: its input gradient writes just those (a quarter
     // of the tensor, no zero fill) and conv1's input gradient, which completes the sum in place, reads the addend only there.
-    // bi == 0 keeps the dense form (pool mode); so does the wide-tile A/B switch.
-    const bool ds_sparse = has_ds && bi > 0 && n->ds_sparse && n->convs[k.ds].d.stride == 2 && n->convs[k.ds].d.R == 1;
+    // bi == 0 keeps the dense form (pool mode).
+    const bool ds_sparse = has_ds && bi > 0 && n->convs[k.ds].d.stride == 2 && n->convs[k.ds].d.R == 1;
     int go = n->cur_grad;
     int d3 = -1, dxbase = -1;
     if (n->go_fused) {
@@ -962,20 +868,17 @@ static int block_backward(osi_resnet50* n, int bi, const float* params, float* g
         // (it completes the gradient w.r.t. the pooled activation) also emits bn1's backward reductions through the arg-max bytes, so the
         // stem needs no reduction pass over its 112 x 112 tensor (pool mode of osi_conv_dgrad_fused)
         Conv& c0 = n->convs[0];
-        n->stem_stats_P = 0;
         // (not when this backward also writes dJ/dimage: the stem tail then materialises dY and reduces bn1 itself)
-        if (n->stem_fused && n->stem_pool_stats && n->stem_ws_bytes > 0 && !n->bw_dimage) {
+        if (n->stem_tail_fused()) {
             BN& b0 = n->bns[c0.bn];
             osi_dgrad_fusion f{};
             f.y0 = ws + c0.y; f.mean0 = ws + b0.mean; f.invstd0 = ws + b0.invstd;
             f.partials = ws + n->dg_ws; f.partials_bytes = n->dg_ws_bytes;
             f.pool_idx = ws + n->pool_idx; f.pool_H = n->Hs; f.pool_W = n->Ws;
             int P = 0;
-            OSI_TRY(before_dgrad(n, st));
             OSI_TRY(osi_conv_dgrad_fused(&c1.d, S(t3), params + c1.w_off, S(dxbase), S(dxbase), &f, OSI_TILE_AUTO, &P, st));
             n->stem_stats_P = P;
             OSI_TRY(n->mark(OSI_PROF_CONV_DGRAD, st));
-            OSI_TRY(flush_wgrad(n, st));
         } else {
             OSI_TRY(dgrad_plain(n, &c1.d, S(t3), params + c1.w_off, S(dxbase), 1, st));
         }
@@ -1051,61 +954,35 @@ int osi_resnet50_backward_ex(osi_resnet50_t n, const float* params, float* grads
             if (t < 0) return t;
             BN& b0 = n->bns[c0.bn];
             const float* x4c = n->x4_cur ? n->x4_cur : ws + n->x4;
-            if (n->bw_dimage) {
-                // dJ/dimage wanted: the stem's dY must exist in memory. The materialising branch of stem_fused = 0 (max-pool scatter + ReLU
-                // gate + bn1 backward into a scratch buffer), its weight gradient from that dY unless input-only, then the stem's input
-                // gradient straight into the caller's NCHW tensor (osi_stem_dgrad)
+            if (n->stem_tail_fused()) {      // its own slab, sized at create: never the side stream's wg_ws
+                // reductions of bn1's backward (dgamma, dbeta) on the main stream: they arrived with block 0's last input gradient, two tiny
+                // merge launches. Then the weight gradient with the max-pool scatter, ReLU gate and BatchNorm backward applied inside its
+                // operand loader: the 112x112x64 gradient is never written
+                n->give(t);
+                const float* psum_g = ws + n->dg_ws;
+                OSI_TRY(osi_bn_backward_reduce(psum_g, psum_g + (size_t)n->stem_stats_P * 64, n->stem_stats_P, grads + b0.g_off,
+                                               grads + b0.b_off, n->B * n->Hs * n->Ws, 64, ws + n->bn_ws, n->bn_ws_bytes, st));
+                OSI_TRY(n->mark(OSI_PROF_BN_BWD, st));
+                // the stem's weight gradient is the last kernel of the step; on the MAIN stream it runs beside the side stream's
+                // backlog (layer1's weight gradients) instead of behind it
+                OSI_TRY(osi_stem_wgrad_fused(&c0.d, S(go), ws + n->pool_idx, ws + c0.y, x4c, params + b0.g_off, ws + b0.mean, ws + b0.invstd,
+                                             grads + b0.g_off, grads + b0.b_off, grads + c0.w_off, ws + n->stem_ws, n->stem_ws_bytes, st));
+                OSI_TRY(n->mark(OSI_PROF_CONV_WGRAD, st));
+                n->give(go);
+            } else {
+                // dJ/dimage wanted, or a geometry the fused form does not take: the stem's dY is materialised (max-pool scatter + ReLU gate
+                // + bn1 backward gathered on the fly from the pooled gradient into a scratch buffer), its weight gradient comes from that
+                // dY unless input-only, then — for dJ/dimage — the stem's input gradient straight into the caller's NCHW tensor
                 OSI_TRY(osi_bn_relu_maxpool_bwd(S(go), ws + n->pool_idx, ws + c0.y, ws + b0.mean, ws + b0.invstd, params + b0.g_off, S(t),
                                                 n->dgam(grads, ws, b0), n->dbet(grads, ws, b0), n->B, n->Hs, n->Ws, 64, ws + n->bn_ws,
                                                 n->bn_ws_bytes, st));
                 OSI_TRY(n->mark(OSI_PROF_BN_BWD, st));
                 n->give(go);
                 OSI_TRY(wgrad(n, 0, grads, ws, t, x4c, st));
-                OSI_TRY(before_dgrad(n, st));
-                OSI_TRY(osi_stem_dgrad(S(t), params + c0.w_off, n->bw_dimage, n->B, n->H, n->W, st));
-                OSI_TRY(n->mark(OSI_PROF_CONV_DGRAD, st));
-                OSI_TRY(flush_wgrad(n, st));
-                n->give(t);
-            } else if (n->stem_fused && n->stem_ws_bytes > 0) {      // its own slab, sized at create: never the side stream's wg_ws
-                // reductions of bn1's backward (dgamma, dbeta) on the main stream, then the weight gradient with the max-pool scatter,
-                // ReLU gate and BatchNorm backward applied inside its operand loader: the 112x112x64 gradient is never written
-                n->give(t);
-                if (n->stem_stats_P > 0) {   // the reductions arrived with the last input gradient: two tiny merge launches
-                    const float* psum_g = ws + n->dg_ws;
-                    OSI_TRY(osi_bn_backward_reduce(psum_g, psum_g + (size_t)n->stem_stats_P * 64, n->stem_stats_P, grads + b0.g_off,
-                                                   grads + b0.b_off, n->B * n->Hs * n->Ws, 64, ws + n->bn_ws, n->bn_ws_bytes, st));
-                    n->stem_stats_P = 0;
-                } else {
-                    OSI_TRY(osi_bn_relu_maxpool_bwd(S(go), ws + n->pool_idx, ws + c0.y, ws + b0.mean, ws + b0.invstd, params + b0.g_off,
-                                                    nullptr, grads + b0.g_off, grads + b0.b_off, n->B, n->Hs, n->Ws, 64, ws + n->bn_ws,
-                                                    n->bn_ws_bytes, st));
+                if (n->bw_dimage) {
+                    OSI_TRY(osi_stem_dgrad(S(t), params + c0.w_off, n->bw_dimage, n->B, n->H, n->W, st));
+                    OSI_TRY(n->mark(OSI_PROF_CONV_DGRAD, st));
                 }
-                OSI_TRY(n->mark(OSI_PROF_BN_BWD, st));
-                // the stem's weight gradient is the last kernel of the step; on the MAIN stream it runs beside the side stream's
-                // backlog (layer1's weight gradients) instead of behind it
-                const bool async = n->async_wgrad() && !n->stem_wgrad_main;
-                hipStream_t gs = st;
-                if (async) {
-                    if (hipEventRecord(n->ev_fork, st) != hipSuccess) return OSI_ERR_LAUNCH;
-                    if (hipStreamWaitEvent(n->side, n->ev_fork, 0) != hipSuccess) return OSI_ERR_LAUNCH;
-                    gs = n->side;
-                }
-                OSI_TRY(osi_stem_wgrad_fused(&c0.d, S(go), ws + n->pool_idx, ws + c0.y, x4c, params + b0.g_off, ws + b0.mean, ws + b0.invstd,
-                                             grads + b0.g_off, grads + b0.b_off, grads + c0.w_off, ws + n->stem_ws, n->stem_ws_bytes, gs));
-                if (async) {
-                    if (hipEventRecord(n->buf_ev[go], n->side) != hipSuccess) return OSI_ERR_LAUNCH;
-                    n->buf_pending[go] = true;
-                    n->side_dirty = true;
-                }
-                OSI_TRY(n->mark(OSI_PROF_CONV_WGRAD, gs));
-                n->give(go);
-            } else {
-                // max-pool scatter + ReLU gate + bn1 backward gathered on the fly from the pooled gradient (no 112x112x64 gradient)
-                OSI_TRY(osi_bn_relu_maxpool_bwd(S(go), ws + n->pool_idx, ws + c0.y, ws + b0.mean, ws + b0.invstd, params + b0.g_off, S(t),
-                                                grads + b0.g_off, grads + b0.b_off, n->B, n->Hs, n->Ws, 64, ws + n->bn_ws, n->bn_ws_bytes, st));
-                OSI_TRY(n->mark(OSI_PROF_BN_BWD, st));
-                n->give(go);
-                OSI_TRY(wgrad(n, 0, grads, ws, t, x4c, st));
                 n->give(t);
             }
             n->cur_grad = -1;
@@ -1115,11 +992,7 @@ int osi_resnet50_backward_ex(osi_resnet50_t n, const float* params, float* grads
     }
     // Join once per call: every gradient of the stages just run is final on `st` from here on. A data-parallel caller issues
     // one stage per call (and reduces that slice next); a single-GPU caller issues all stages in one call and pays one join.
-    OSI_TRY(flush_wgrad(n, st));
-    if (n->stage_join || stage_hi == n->n_stages) {
-        n->w_inflight = false;         // the join below covers it
-        OSI_TRY(n->join_side(st));
-    }
+    if (n->stage_join || stage_hi == n->n_stages) OSI_TRY(n->join_side(st));
     return OSI_OK;
 }
 
@@ -1228,28 +1101,12 @@ int osi_resnet50_debug_gate(osi_resnet50_t n, void* workspace, int i, unsigned c
     return OSI_OK;
 }
 
-int osi_resnet50_set_overlap(osi_resnet50_t n, int enable) {
-    OSI_REQUIRE(n);
-    n->overlap = enable != 0;
-    return OSI_OK;
-}
-
 int osi_resnet50_set_option(osi_resnet50_t n, const char* name, int value) {
     OSI_REQUIRE(n && name);
     if (!strcmp(name, "overlap")) n->overlap = value != 0;
     else if (!strcmp(name, "fwd_fork")) n->fwd_fork = value != 0;
-    else if (!strcmp(name, "stagger")) n->stagger = value != 0;
-    else if (!strcmp(name, "fwd_recompute")) n->fwd_recompute = value != 0;
-    else if (!strcmp(name, "stem_fused")) n->stem_fused = value != 0;
-    else if (!strcmp(name, "stem_pool_stats")) n->stem_pool_stats = value != 0;
-    else if (!strcmp(name, "ds_sparse")) n->ds_sparse = value != 0;
-    else if (!strcmp(name, "stem_wgrad_main")) n->stem_wgrad_main = value != 0;
     else if (!strcmp(name, "stage_join")) n->stage_join = value != 0;
     else if (!strcmp(name, "eval_fused")) n->eval_fused = value != 0;
-    else if (!strcmp(name, "wino_weights_aside")) n->wt_aside = value != 0;
-#ifdef OSI_DIAG
-    else if (!strcmp(name, "dbg_skip")) n->dbg_skip = value;
-#endif
     else if (!strcmp(name, "side_priority_normal")) {
         if (n->side) return OSI_ERR_STATE;   // the side stream already exists with the other priority
         n->side_prio_normal = value != 0;

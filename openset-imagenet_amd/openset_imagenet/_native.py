@@ -133,7 +133,6 @@ _SIGS = {
     "osi_resnet50_geometry": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "osi_resnet50_stage_grad_range": (c_int, [c_void_p, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
     "osi_resnet50_grads_ready": (c_int, [c_void_p, P, P]),
-    "osi_resnet50_set_overlap": (c_int, [c_void_p, c_int]),
     "osi_resnet50_set_option": (c_int, [c_void_p, c_char_p, c_int]),
     "osi_resnet50_profile": (c_int, [c_void_p, c_int]),
     "osi_resnet50_profile_read": (c_int, [c_void_p, POINTER(ctypes.c_double), POINTER(c_int)]),
@@ -158,7 +157,7 @@ def lib():
     """The loaded shared library; raises NativeLibraryMissing when it has not been built."""
     global _lib, LIB_PATH
     if _lib is None:
-        # dev only: a diagnostic build of the same C ABI (csrc `make stamps / diag / ablate`: some of them compute WRONG results by
+        # dev only: a diagnostic build of the same C ABI (csrc `make stamps / ablate`: some of them compute WRONG results by
         # design). Honoured only together with OSI_DEV=1, announced loudly, and refused by train.worker() (DIAGNOSTIC_LIB).
         global DIAGNOSTIC_LIB
         if os.environ.get("OSI_HIP_LIB"):

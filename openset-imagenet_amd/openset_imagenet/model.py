@@ -37,15 +37,8 @@ def debug_options_from_env():
     osi_resnet50_set_option (the library itself never reads the environment). Every default is the measured optimum; nothing here
     is needed to run the product. {option name: value} for the variables that are set:
         OSI_NO_OVERLAP=1      overlap 0           weight gradients stay on the main stream (serialised backward)
-        OSI_FWD_RECOMPUTE=1   fwd_recompute 1     conv1 recomputes the previous identity-shortcut block output in its loader
         OSI_FWD_FORK=0        fwd_fork 0          projection shortcut of the forward pass on the main stream
-        OSI_STAGGER=1         stagger 1           weight gradients only beside BatchNorm-backward kernels, never beside an input gradient
         OSI_SIDE_PRIO=n       side_priority_normal 1
-        OSI_STEM_FUSED=0      stem_fused 0        conv1's weight gradient from a materialised 112x112x64 gradient (BatchNorm apply pass)
-        OSI_STEM_POOL_STATS=0 stem_pool_stats 0   bn1's backward reductions by their own pass instead of layer1.0.conv1's dgrad epilogue
-        OSI_DS_SPARSE=0       ds_sparse 0         stride-2 shortcut gradients written / read as dense tensors (zero fill included)
-        OSI_STEM_WGRAD_MAIN=0 stem_wgrad_main 0   the fused stem weight gradient queued on the side stream behind layer1's weight gradients
-        OSI_WINO_WEIGHTS_ASIDE=0 wino_weights_aside 0   the Winograd weight transforms of a training forward on the main stream (not beside the stem)
         OSI_EVAL_FUSED=0      eval_fused 0        eval-mode forwards through the training topology on running statistics (no inference forms)
     (There is no switch for round 2's fused in-block activations: the unfused executor path no longer exists; its price on one box is the
     three-way A/B of the committed round-1 / round-2 / current trees, profiles/r03_ab_rounds.txt.)"""
@@ -53,27 +46,10 @@ def debug_options_from_env():
     out = {}
     if env.get("OSI_NO_OVERLAP"):
         out["overlap"] = 0
-    if env.get("OSI_DBG_SKIP") and env.get("OSI_DEV") == "1" and N.DIAGNOSTIC_LIB:
-        # timing experiments only (wrong results): the switch exists in the diagnostic build alone (`make -C csrc diag`, -DOSI_DIAG)
-        out["dbg_skip"] = int(env["OSI_DBG_SKIP"])
-    if env.get("OSI_FWD_RECOMPUTE") == "1":
-        out["fwd_recompute"] = 1
     if env.get("OSI_FWD_FORK") == "0":
         out["fwd_fork"] = 0
-    if env.get("OSI_STAGGER") == "1":
-        out["stagger"] = 1
     if env.get("OSI_SIDE_PRIO", "")[:1] == "n":
         out["side_priority_normal"] = 1
-    if env.get("OSI_STEM_FUSED") == "0":
-        out["stem_fused"] = 0
-    if env.get("OSI_STEM_POOL_STATS") == "0":
-        out["stem_pool_stats"] = 0
-    if env.get("OSI_DS_SPARSE") == "0":
-        out["ds_sparse"] = 0
-    if env.get("OSI_WINO_WEIGHTS_ASIDE") == "0":
-        out["wino_weights_aside"] = 0
-    if env.get("OSI_STEM_WGRAD_MAIN") == "0":
-        out["stem_wgrad_main"] = 0
     if env.get("OSI_EVAL_FUSED") == "0":
         out["eval_fused"] = 0
     return out

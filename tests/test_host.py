@@ -167,6 +167,10 @@ def test_tuning_knobs_are_explicit():
         assert lib.osi_resnet50_set_option(h, b"overlap", 0) == 0 and lib.osi_resnet50_set_option(h, b"fwd_fork", 0) == 0
         assert lib.osi_resnet50_set_option(h, b"side_priority_normal", 1) == 0
         assert lib.osi_resnet50_set_option(h, b"bogus", 1) == -1
+        # the settled A/B switches are retired: their names are unknown names, whichever value a stale caller passes
+        for name in (b"fwd_recompute", b"stagger", b"stem_fused", b"stem_pool_stats", b"stem_wgrad_main", b"ds_sparse",
+                     b"wino_weights_aside", b"dbg_skip"):
+            assert lib.osi_resnet50_set_option(h, name, 0) == -1 and lib.osi_resnet50_set_option(h, name, 1) == -1, name
         assert lib.osi_resnet50_bind_input_nhwc4(h, None) == -1 and lib.osi_resnet50_bind_input_nhwc4(h, 24) == -1   # NULL / unaligned
     finally:
         lib.osi_resnet50_destroy(h)

@@ -7,7 +7,7 @@
 ROOT=$(cd "$(dirname "$0")/.." && pwd); CSRC=$ROOT/openset-imagenet_amd/csrc; BITS="2 4 6 16 31"
 if [ "$1" = build ]; then
   mkdir -p "$ROOT/.ab"
-  objs=$(ls "$CSRC"/*.o | grep -v "conv_wino.o\|stamps\|diag")
+  objs=$(ls "$CSRC"/*.o | grep -v "conv_wino.o\|stamps")
   for f in $BITS; do
     ( /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -Wno-unused-variable -fno-slp-vectorize -DOSI_FABL=$f \
         -c "$CSRC/conv_wino.hip" -o "$ROOT/.ab/conv_wino_f$f.o" \
