@@ -29,6 +29,13 @@
 //     direct kernels: P and rows_per_block feed osi_bn_finalize_stats unchanged), reduced with 4 DPP adds per value — no LDS, no barrier;
 //   EPI 1 input gradient, "in-block" fusion of osi_conv_dgrad_fused: dx = gate . acc with the gate recomputed from the producer's pre-BN
 //     tensor (fma(y0, scale0, shift0) > 0), and the per-64-pixel sums of g and g * xhat0 for the BatchNorm backward of that producer.
+//
+// Weight gradient (k_wino_wgrad, further down): the transposed algorithm with TWO waves per SIMD — eight waves per workgroup, each 32 x 32
+// block of the 64 x 64 unit shared by two waves that own 8 of the 16 positions each (128 accumulator registers instead of 256), one tile
+// of the K step per wave in the loader, accumulator halves swapped through LDS once per workgroup for dW = G^T S G. Same MFMAs, same
+// operands, same order per accumulator as the one-wave form it replaced: bit-identical, 168 -> 152 us per layer at B = 128, matrix pipe
+// busy 0.49 -> 0.55. Floor model: 64 cycles per MFMA + 2 cycles per vector instruction (alternating waves) instead of 4 (a lone wave).
+// k_wino itself still runs one wave per SIMD; the same split by the column index nu is its open next step (NOTES_r07.md section 5).
 #include "conv_common.h"
 #include <algorithm>
 #include <type_traits>
@@ -654,12 +661,17 @@ __global__ __launch_bounds__(64) void k_wino_fixup(WinoP p, int G) {
 //   S_p[cout][cin] = sum_tiles  Yt_p[cout][tile] * V_p[cin][tile],   p in 4 x 4   -> 16 GEMMs whose K axis is the TILE axis,
 // then dW[cout][.][.][cin] = G^T S G (16 -> 9 values per (cout, cin), register arithmetic in the epilogue): 16 multiplies per tile and
 // (cout, cin) pair instead of 36.
-// One workgroup = one (64 couts x 64 cins) block x one contiguous run of tiles (split-K over the tile axis: blocks x splits = the CUs);
-// every wave owns 32 x 32 of the block for all 16 positions (256 AGPRs, one wave per SIMD). K step = 8 tiles, both operands staged through
-// LDS (images [p][k-half h][channel][4 tiles]: a lane's 16-byte read = its operand of the four MFMAs of a position; 2 x 32 KiB per stage,
-// double buffered). Loader roles: wave w owns tiles {4 (w >> 1) + (w & 1), + 2} of the step for EVERY channel (lane = channel): tile
-// coordinates, image-border validity and all load offsets are SCALAR (one buffer load per pixel with the offset in an SGPR), the
-// transforms are per-lane scalar math on 2 tiles x 1 channel, 16-byte... 8-byte LDS stores.
+// One workgroup = one (64 couts x 64 cins) block x one contiguous run of tiles (split-K over the tile axis: blocks x splits = the CUs).
+// EIGHT waves, TWO per SIMD: wave (ph, wm, wn) owns the 32 x 32 block (wm, wn) for the positions 8 ph .. 8 ph + 7 only = 8 accumulator sets
+// of 16 registers = 128 (the one-wave form held all 16 positions in 256 AGPRs and had nothing to run while an LDS read, a wait or a
+// barrier was outstanding). Every accumulator still sees the MFMAs of the one-wave form, same operands, same order: the same bits.
+// K step = 8 tiles, both operands staged through LDS (images [p][k-half h][channel][4 tiles]: a lane's 16-byte read = its operand of the
+// four MFMAs of a position; 2 x 32 KiB per stage, double buffered). Loader roles: wave w owns tile w of the step for EVERY channel
+// (lane = channel): tile coordinates, image-border validity and all load offsets are SCALAR (one buffer load per pixel with the offset in
+// an SGPR), the transforms are per-lane scalar math on one tile x one channel (with two waves per SIMD a plain vector instruction issues
+// every ~2.2 cycles against 4.8 for a packed one, profiles/r06_mfma_valu_coexec.txt: packing two tiles per lane buys nothing any more),
+// 4-byte LDS stores. Epilogue: dW = G^T S G needs all 16 positions of a (cout, cin) pair, so the two waves of a block swap accumulator
+// halves through the (by then free) LDS once per workgroup and each finishes 8 of the 16 accumulator rows.
 struct WgradP {
     const float* x;      // conv input [B][H][W][Cin] (pre-activation when `sc`)
     const float* dy;     // [B][H][W][Cout]
@@ -673,223 +685,243 @@ struct WgradP {
 };
 
 template <bool XF>
-__global__ __launch_bounds__(256, 1) void k_wino_wgrad(WgradP p) {
+__global__ __launch_bounds__(512) void k_wino_wgrad(WgradP p) {
     __shared__ __attribute__((aligned(16))) float sL[2 * 2 * 16 * 2 * 64 * 4];   // [buf][operand][p][h][channel][4 tiles]: 128 KiB
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5, l31 = lane & 31;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ph = wave >> 2, wm = (wave >> 1) & 1, wn = wave & 1;      // position half, 32 x 32 block of the 64 x 64 unit
     const int item = blockIdx.x;
     const int split = item % p.S, blk = item / p.S, cb = blk % p.CBn, kb = blk / p.CBn;
-    // loader role of this WAVE: k-half h and pair of k-pairs
-    const int lh = __builtin_amdgcn_readfirstlane(wave & 1), kkp = __builtin_amdgcn_readfirstlane(wave >> 1);
+    // loader role of this WAVE: tile `wave` of the step = k-half lh of the MFMA that consumes the slot kq of the lane's 16-byte operand
+    // (tile = 4 (kq >> 1) + 2 (kq & 1) + lh: the order in which every accumulator has always summed the tiles of a step)
+    const int lh = wave & 1, kq = wave >> 1;
     const uint32_t xlane = (uint32_t)((cb * 64 + lane) * 4), dlane = (uint32_t)((kb * 64 + lane) * 4);
     const int t_first = split * p.steps * 8;
     const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, p.x_bytes);
     const __amdgpu_buffer_rsrc_t rd = make_rsrc(p.dy, p.dy_bytes);
-    f32x2 scsh = {1.f, 0.f};
-    if constexpr (XF) { scsh[0] = p.sc[cb * 64 + lane]; scsh[1] = p.sh[cb * 64 + lane]; }
+    float sc = 1.f, sh = 0.f;
+    if constexpr (XF) { sc = p.sc[cb * 64 + lane]; sh = p.sh[cb * 64 + lane]; }
     const int cin4 = p.Cin * 4, cout4 = p.Cout * 4;
 
     // Loads of a K step. Every offset is SCALAR (lane = channel): a pixel outside the image (or a tile past the end) is read at clamped
     // coordinates — always in bounds — and selected to zero afterwards by wave-uniform bits. Offsets are separable: byte offset of patch
     // pixel (i, j) = row part [i] (image base included) + column part [j]. prep_step computes the scalars of a step, issue_load<n> issues its
-    // n-th load (0..39: tile n / 20, patch pixel n % 20 or dy pixel n % 20 - 16): a burst of 40 one-dword loads per wave blocks at the
-    // texture addresser's queue (4 waves x 40 x 256 B: ~0.9 us per step, measured), spread over the positions of a step it is free.
-    // raw operands of this wave, two register sets — 0: the step being transformed, 1: the step in flight —: 2 tiles x (16 patch pixels of x,
-    // 4 pixels of dy) for the lane's channel + wave-uniform validity bits. Indexed by compile-time constants only.
-    // (one f32x2 per pixel: component = the wave's tile i2 — the two tiles of a wave go through the same arithmetic, so every add / fma of
-    // the transforms is ONE packed instruction for both: fp32 MFMAs hide no vector work, profiles/r06_mfma_valu_coexec.txt)
-    f32x2 rx_[2][16], rd_[2][4];
-    unsigned okx_[2][2], okd_[2][2];
-    uint32_t srb[2][4], scb[2][4], sdr[2][2], sdc[2][2];
+    // n-th load (0..19: patch pixel n, or dy pixel n - 16): a burst of one-dword loads blocks at the texture addresser's queue (measured on
+    // the one-wave form: ~0.9 us per step), spread over the positions of a step it is free.
+    // Raw operands of this wave's tile for the lane's channel: 16 patch pixels of x, 4 pixels of dy, wave-uniform validity bits — TWO sets
+    // that hold the steps of their parity (set s: steps s, s + 2, ...), so that a load has two steps of lead (see the K loop). Indexed by
+    // compile-time constants only.
+    float rx_[2][16], rd_[2][4];
+    unsigned okx_[2], okd_[2];
+    uint32_t srb[4], scb[4], sdr[2], sdc[2];
     auto prep_step = [&](int st, auto SETC) {
         constexpr int set = decltype(SETC)::value;
+        const int t_raw = t_first + st * 8 + wave;
+        const bool live = t_raw < p.T;
+        const uint32_t t = (uint32_t)(live ? t_raw : p.T - 1);
+        const uint32_t b = fdiv(t, p.dTHW), rem = t - b * p.dTHW.d, th = fdiv(rem, p.dTW), tw = rem - th * p.dTW.d;
+        const int y0 = 2 * (int)th - 1, x0 = 2 * (int)tw - 1;
+        unsigned rok = 0, cok = 0;
 #pragma unroll
-        for (int i2 = 0; i2 < 2; ++i2) {
-            const int tl = 4 * kkp + 2 * i2 + lh;
-            const int t_raw = __builtin_amdgcn_readfirstlane(t_first + st * 8 + tl);
-            const bool live = t_raw < p.T;
-            const uint32_t t = (uint32_t)(live ? t_raw : p.T - 1);
-            const uint32_t b = fdiv(t, p.dTHW), rem = t - b * p.dTHW.d, th = fdiv(rem, p.dTW), tw = rem - th * p.dTW.d;
-            const int y0 = 2 * (int)th - 1, x0 = 2 * (int)tw - 1;
-            unsigned rok = 0, cok = 0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int yy = y0 + i, xx = x0 + i;
-                rok |= ((unsigned)yy < (unsigned)p.H) ? (1u << i) : 0u;
-                cok |= ((unsigned)xx < (unsigned)p.W) ? (1u << i) : 0u;
-                srb[i2][i] = (uint32_t)((((int)b * p.H + min(max(yy, 0), p.H - 1)) * p.W) * cin4);
-                scb[i2][i] = (uint32_t)(min(max(xx, 0), p.W - 1) * cin4);
-            }
-            if (!live) rok = 0;
-            unsigned ok = 0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) ok |= ((rok >> i) & 1u) ? (cok << (4 * i)) : 0u;
-            okx_[set][i2] = ok;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                sdr[i2][i] = (uint32_t)(((int)b * p.H + min(y0 + 1 + i, p.H - 1)) * p.W) * (uint32_t)cout4;
-                sdc[i2][i] = (uint32_t)min(x0 + 1 + i, p.W - 1) * (uint32_t)cout4;
-            }
-            okd_[set][i2] = (((rok >> 1) & 1u) ? ((cok >> 1) & 3u) : 0u) | (((rok >> 2) & 1u) ? (((cok >> 1) & 3u) << 2) : 0u);
+        for (int i = 0; i < 4; ++i) {
+            const int yy = y0 + i, xx = x0 + i;
+            rok |= ((unsigned)yy < (unsigned)p.H) ? (1u << i) : 0u;
+            cok |= ((unsigned)xx < (unsigned)p.W) ? (1u << i) : 0u;
+            srb[i] = (uint32_t)((((int)b * p.H + min(max(yy, 0), p.H - 1)) * p.W) * cin4);
+            scb[i] = (uint32_t)(min(max(xx, 0), p.W - 1) * cin4);
         }
+        if (!live) rok = 0;
+        unsigned ok = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ok |= ((rok >> i) & 1u) ? (cok << (4 * i)) : 0u;
+        okx_[set] = ok;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            sdr[i] = (uint32_t)(((int)b * p.H + min(y0 + 1 + i, p.H - 1)) * p.W) * (uint32_t)cout4;
+            sdc[i] = (uint32_t)min(x0 + 1 + i, p.W - 1) * (uint32_t)cout4;
+        }
+        okd_[set] = (((rok >> 1) & 1u) ? ((cok >> 1) & 3u) : 0u) | (((rok >> 2) & 1u) ? (((cok >> 1) & 3u) << 2) : 0u);
     };
     auto issue_load = [&](auto NC, auto SETC) {
-        constexpr int n = decltype(NC)::value, set = decltype(SETC)::value, i2 = n / 20, k = n % 20;
-        if constexpr (k < 16)
-            rx_[set][k][i2] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, xlane, srb[i2][k / 4] + scb[i2][k % 4], 0));
+        constexpr int n = decltype(NC)::value, set = decltype(SETC)::value;
+        if constexpr (n < 16)
+            rx_[set][n] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, xlane, srb[n / 4] + scb[n % 4], 0));
         else
-            rd_[set][k - 16][i2] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rd, dlane, sdr[i2][(k - 16) / 2] + sdc[i2][(k - 16) % 2], 0));
+            rd_[set][n - 16] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rd, dlane, sdr[(n - 16) / 2] + sdc[(n - 16) % 2], 0));
     };
     auto load_step = [&](int st, auto SETC) {       // the whole step at once (prologue)
         prep_step(st, SETC);
         auto one = [&](auto NC) { issue_load(NC, SETC); };
-        for_each_const(one, std::make_integer_sequence<int, 40>{});
+        for_each_const(one, std::make_integer_sequence<int, 20>{});
     };
-    // LDS images. operand 0 = Yt (rows = couts), 1 = V (rows = cins); float index ((((buf * 2 + op) * 16 + pos) * 2 + h) * 64 + ch) * 4 + kk
+    // LDS images. operand 0 = Yt (rows = couts), 1 = V (rows = cins); float index ((((buf * 2 + op) * 16 + pos) * 2 + h) * 64 + ch) * 4 + slot
     auto img = [&](int buf, int op, int pos, int h, int ch) { return sL + ((((buf * 2 + op) * 16 + pos) * 2 + h) * 64 + ch) * 4; };
-    // activation of a tile's patch (padding / dead tiles selected to zero after it) and zeroing of dy pixels outside the image
-    auto act = [&](auto SETC) {                // both tiles: one packed fma per pixel, max and the (wave-uniform) padding select per tile
+    // the step being transformed: activation of the tile's patch (padding / a dead tile selected to zero after it) and zeroing of the dy
+    // pixels outside the image, OUT of the raw set — which is free for the loads of two steps later from here on
+    float tx[16], td[4];
+    auto act = [&](auto SETC) {
         constexpr int set = decltype(SETC)::value;
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
-            f32x2 v = rx_[set][k];
-            if constexpr (XF) {
-                // v = v * scale + shift for both tiles: scale = the LOW half of the pair scsh for both lanes, shift = its HIGH half
-                asm volatile("v_pk_fma_f32 %0, %0, %1, %1 op_sel:[0,0,1] op_sel_hi:[1,0,1]" : "+v"(v) : "v"(scsh));
-                // (asm: fmaxf on a value the compiler did not produce itself gets a canonicalising v_max in front of the real one)
-                asm volatile("v_max_f32 %0, 0, %0" : "+v"(v[0]));
-                asm volatile("v_max_f32 %0, 0, %0" : "+v"(v[1]));
-            }
-            v[0] = ((okx_[set][0] >> k) & 1u) ? v[0] : 0.f;
-            v[1] = ((okx_[set][1] >> k) & 1u) ? v[1] : 0.f;
-            rx_[set][k] = v;
+            float v = rx_[set][k];
+            // (asm: fmaxf on a value the compiler did not produce itself gets a canonicalising v_max in front of the real one)
+            if constexpr (XF) asm volatile("v_fma_f32 %0, %1, %2, %3\n\tv_max_f32 %0, 0, %0" : "=v"(v) : "v"(rx_[set][k]), "v"(sc), "v"(sh));
+            tx[k] = ((okx_[set] >> k) & 1u) ? v : 0.f;
         }
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            rd_[set][k][0] = ((okd_[set][0] >> k) & 1u) ? rd_[set][k][0] : 0.f;
-            rd_[set][k][1] = ((okd_[set][1] >> k) & 1u) ? rd_[set][k][1] : 0.f;
-        }
+        for (int k = 0; k < 4; ++k) td[k] = ((okd_[set] >> k) & 1u) ? rd_[set][k] : 0.f;
     };
-    auto col_x = [&](auto SETC) {      // B^T d: columns, both tiles
-        constexpr int set = decltype(SETC)::value;
+    auto col_x = [&]() {      // B^T d: columns
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const f32x2 d0 = rx_[set][j], d1 = rx_[set][4 + j], d2 = rx_[set][8 + j], d3 = rx_[set][12 + j];
-            rx_[set][j] = pk_sub(d0, d2); rx_[set][4 + j] = pk_add(d1, d2); rx_[set][8 + j] = pk_sub(d2, d1); rx_[set][12 + j] = pk_sub(d1, d3);
+            const float d0 = tx[j], d1 = tx[4 + j], d2 = tx[8 + j], d3 = tx[12 + j];
+            tx[j] = d0 - d2; tx[4 + j] = d1 + d2; tx[8 + j] = d2 - d1; tx[12 + j] = d1 - d3;
         }
     };
-    // (B^T d B) row i of both tiles -> V image; (A dY A^T) row i of both tiles -> Yt image. One 8-byte store per position and operand.
-    auto row_store = [&](auto SETC, int i, int buf) {
-        constexpr int set = decltype(SETC)::value;
-        const f32x2 t0 = rx_[set][i * 4], t1 = rx_[set][i * 4 + 1], t2 = rx_[set][i * 4 + 2], t3 = rx_[set][i * 4 + 3];
-        const f32x2 v[4] = {pk_sub(t0, t2), pk_add(t1, t2), pk_sub(t2, t1), pk_sub(t1, t3)};
+    // (B^T d B) row i -> V image; (A dY A^T) row i -> Yt image. One 4-byte store per position and operand.
+    auto row_store = [&](int i, int buf) {
+        const float t0 = tx[i * 4], t1 = tx[i * 4 + 1], t2 = tx[i * 4 + 2], t3 = tx[i * 4 + 3];
+        const float v[4] = {t0 - t2, t1 + t2, t2 - t1, t1 - t3};
         // A = [[1,0],[1,1],[1,-1],[0,-1]]: rows of A dY:  r0 = dy0., r1 = dy0. + dy1., r2 = dy0. - dy1., r3 = -dy1.
-        const f32x2 a = rd_[set][0], b = rd_[set][1], c = rd_[set][2], d = rd_[set][3];
-        const f32x2 e0 = i == 0 ? a : i == 1 ? pk_add(a, c) : i == 2 ? pk_sub(a, c) : pk_neg(c);
-        const f32x2 e1 = i == 0 ? b : i == 1 ? pk_add(b, d) : i == 2 ? pk_sub(b, d) : pk_neg(d);
-        const f32x2 y[4] = {e0, pk_add(e0, e1), pk_sub(e0, e1), pk_neg(e1)};
+        // (0 - v, not -v: the sums the matrix pipe forms are those of the packed form this replaces, a zero's sign included)
+        const float a = td[0], b = td[1], c = td[2], d = td[3];
+        const float e0 = i == 0 ? a : i == 1 ? a + c : i == 2 ? a - c : 0.f - c;
+        const float e1 = i == 0 ? b : i == 1 ? b + d : i == 2 ? b - d : 0.f - d;
+        const float y[4] = {e0, e0 + e1, e0 - e1, 0.f - e1};
 #pragma unroll
         for (int nu = 0; nu < 4; ++nu) {
-            *reinterpret_cast<f32x2*>(img(buf, 1, i * 4 + nu, lh, lane) + 2 * kkp) = v[nu];
-            *reinterpret_cast<f32x2*>(img(buf, 0, i * 4 + nu, lh, lane) + 2 * kkp) = y[nu];
+            img(buf, 1, i * 4 + nu, lh, lane)[kq] = v[nu];
+            img(buf, 0, i * 4 + nu, lh, lane)[kq] = y[nu];
         }
     };
 
-    f32x16 acc[16];
+    f32x16 acc[8];
 #pragma unroll
-    for (int i = 0; i < 16; ++i)
+    for (int i = 0; i < 8; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
 
-    // prologue: step 0 transformed into buffer 0, step 1 in flight. The loads run TWO steps ahead of the MFMAs (a step is 16 x 4 MFMAs =
-    // 1.7 us: one step of lead does not cover an HBM round trip when a lone wave per SIMD has nothing else to run), in two register sets.
+    // prologue: step 0 transformed into buffer 0, steps 1 and 2 in flight (past the end: a valid step re-loaded, never used)
     using S0 = std::integral_constant<int, 0>;
     using S1 = std::integral_constant<int, 1>;
+    const int last = p.steps - 1;
+    // (issue order pinned: set 1 is the OLDER of the two sets in flight when the K loop begins)
     load_step(0, S0{});
-    load_step(p.steps > 1 ? 1 : 0, S1{});
-    act(S0{}); col_x(S0{});
+    load_step(min(1, last), S1{});
+    __builtin_amdgcn_sched_barrier(0);
+    act(S0{});
+    __builtin_amdgcn_sched_barrier(0);
+    load_step(min(2, last), S0{});
+    __builtin_amdgcn_sched_barrier(0);
+    col_x();
 #pragma unroll
-    for (int i = 0; i < 4; ++i) row_store(S0{}, i, 0);
+    for (int i = 0; i < 4; ++i) row_store(i, 0);
     __syncthreads();
 
-    const int hh = lane >> 5, l31 = lane & 31;
-    // One K step st: MFMAs on LDS buffer st & 1 while the operands of step st + 1 are transformed into the other buffer (behind positions
-    // TR0..15) and the loads of step st + 2 are in flight. The loads need TWO steps of lead: a step is 16 x 4 MFMAs = 1.7 us, every byte of
-    // the 64-channel layers comes from HBM exactly once (~2 us under load), and a lone wave per SIMD has nothing else to run — with one
-    // step of lead the kernel waited 0.9 us per step (ablation: 190 -> 146 us without the loads). Two register sets that swap roles would
-    // need the loop unrolled by two (the register allocator then shuffles the 256 accumulators between the copies: 170 spills), so set 1
-    // (in flight, a full step old) is COPIED into set 0 at the top of a step — 44 moves — and re-loaded.
-    constexpr int TR0 = 10;
-    for (int st = 0; st < p.steps; ++st) {
-        const int buf = st & 1;
-        {   // set 1 holds step st + 1 (loaded a full step ago): into set 0
-#pragma unroll
-            for (int k = 0; k < 16; ++k) rx_[0][k] = rx_[1][k];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) rd_[0][k] = rd_[1][k];
-#pragma unroll
-            for (int i2 = 0; i2 < 2; ++i2) { okx_[0][i2] = okx_[1][i2]; okd_[0][i2] = okd_[1][i2]; }
-        }
-#if !(OSI_WABL & 1)
-        prep_step(st + 2 < p.steps ? st + 2 : p.steps - 1, S1{});   // past the end: a valid step re-loaded (never used): no branch around loads
-#endif
-        const float* ra = img(buf, 0, 0, hh, 32 * wm + l31);
-        const float* rb = img(buf, 1, 0, hh, 32 * wn + l31);
+    // One K step st: the wave's 8 positions x 4 MFMAs on LDS buffer st & 1 while the operands of step st + 1 are transformed into the other
+    // buffer and the loads of step st + 3 are issued. The loads need TWO steps of lead: a step is 2 x 8 x 4 MFMAs per SIMD = 1.7 us, every
+    // byte of the 64-channel layers comes from HBM exactly once (~2 us under load), and both waves of a SIMD stand at the same barrier.
+    // With 128 accumulator registers per wave instead of 256 that is what it says: two raw register sets, one per step parity. Position 0
+    // of step st moves set (st + 1) & 1 (loaded during step st - 2 .. st - 1) through the activation into the transform's own registers,
+    // positions 1..7 re-load the set for step st + 3. The loop is unrolled by two so that every set index is a constant (the one-wave form
+    // could not afford that — its allocator spilled — and copied one set into the other at the top of every step instead).
+    // Known and left: the compiler's counted waits are exact in the odd steps (vmcnt(39) .. (20)) but "everything" in the even ones
+    // (vmcnt(19) .. (0)) — the structurised control flow of the odd-step-count exit holds a path "even step, even step" on which set 1 would
+    // be the younger set. It costs nothing measurable (loads of the odd steps squeezed into positions 1..3 or 1..4: +-0.5 us per launch), and
+    // every cure tried spills: a third copy of the step behind the loop 202 VGPRs, the skipped half's loads issued anyway 99 - 125, asm loads
+    // with hand-counted waits 73 (profiles/NOTES_r07.md section 3).
+    auto step = [&](int st, auto BUFC) {
+        constexpr int buf = decltype(BUFC)::value;
+        using SET = std::integral_constant<int, 1 - buf>;        // parity of step st + 1 (and st + 3)
+        const float* ra = img(buf, 0, 8 * ph, hh, 32 * wm + l31);
+        const float* rb = img(buf, 1, 8 * ph, hh, 32 * wn + l31);
         f32x4 a0 = *reinterpret_cast<const f32x4*>(ra), b0 = *reinterpret_cast<const f32x4*>(rb);
         __builtin_amdgcn_sched_barrier(0);
         auto position = [&](auto POSC) {
-            constexpr int pos = decltype(POSC)::value;
+            constexpr int lp = decltype(POSC)::value;
             f32x4 na = a0, nb = b0;
-            if (pos < 15) {
-                na = *reinterpret_cast<const f32x4*>(ra + (pos + 1) * (2 * 64 * 4));
-                nb = *reinterpret_cast<const f32x4*>(rb + (pos + 1) * (2 * 64 * 4));
+            if (lp < 7) {
+                na = *reinterpret_cast<const f32x4*>(ra + (lp + 1) * (2 * 64 * 4));
+                nb = *reinterpret_cast<const f32x4*>(rb + (lp + 1) * (2 * 64 * 4));
             }
 #pragma unroll
-            for (int e = 0; e < 4; ++e) acc[pos] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[e], b0[e], acc[pos], 0, 0, 0);
-#if !(OSI_WABL & 1)
-            {   // this position's share of the step-after-next's 40 loads
-                constexpr int n0 = pos * 40 / 16, n1 = (pos + 1) * 40 / 16;
-                if constexpr (n1 > n0) issue_load(std::integral_constant<int, n0>{}, S1{});
-                if constexpr (n1 > n0 + 1) issue_load(std::integral_constant<int, n0 + 1>{}, S1{});
-                if constexpr (n1 > n0 + 2) issue_load(std::integral_constant<int, n0 + 2>{}, S1{});
-            }
-#endif
+            for (int e = 0; e < 4; ++e) acc[lp] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[e], b0[e], acc[lp], 0, 0, 0);
 #if !(OSI_WABL & 2)
-            if constexpr (pos == TR0) act(S0{});
-            if constexpr (pos == TR0 + 1) col_x(S0{});
-            if constexpr (pos >= 12) row_store(S0{}, pos - 12, buf ^ 1);
+            if constexpr (lp == 0) act(SET{});
+            if constexpr (lp == 1) col_x();
+            if constexpr (lp >= 2 && lp < 6) row_store(lp - 2, buf ^ 1);
+#endif
+#if !(OSI_WABL & 1)
+            if constexpr (lp == 0) prep_step(min(st + 3, last), SET{});
+            if constexpr (lp >= 1 && lp <= 7) {   // this position's share of the 20 loads of step st + 3
+                constexpr int n0 = (lp - 1) * 20 / 7, n1 = lp * 20 / 7;
+                auto one = [&](auto IC) { issue_load(std::integral_constant<int, n0 + decltype(IC)::value>{}, SET{}); };
+                for_each_const(one, std::make_integer_sequence<int, n1 - n0>{});
+            }
 #endif
             a0 = na; b0 = nb;
             __builtin_amdgcn_sched_barrier(0);
         };
-        for_each_const(position, std::make_integer_sequence<int, 16>{});
+        for_each_const(position, std::make_integer_sequence<int, 8>{});
         __syncthreads();
+    };
+    for (int st = 0; st < p.steps; st += 2) {
+        step(st, S0{});
+        if (st + 1 < p.steps) step(st + 1, S1{});
     }
 
     // ---- epilogue: dW = G^T S G per (cout, cin), written as a partial in [9][64 cout][64 cin] order (lane = cin: 128-byte runs) ---------
-    // The lane's coordinates are taken afresh here (lane id from mbcnt, wave role from the scalar copies): kept from the top of the kernel
-    // they would have to live through the K loop, whose 256 + 256 registers are all taken (two spills otherwise).
-    int lane_e;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
-    const int hh_e = lane_e >> 5, l31_e = lane_e & 31;      // (kkp = wave >> 1 = wm, lh = wave & 1 = wn: wave-uniform scalars)
-    float* out = p.slab + (size_t)item * (9 * 4096) + (32 * lh + l31_e);
+    // A (cout, cin) pair needs all 16 positions: the two waves of a 32 x 32 block swap, through the LDS the K loop's last barrier has
+    // freed, the accumulator rows the OTHER one finishes (wave ph finishes rows r = 8 ph .. 8 ph + 7 of the 16; 8 positions x 8 rows = 16
+    // stores and 16 loads of 16 bytes per lane, lane-contiguous, once per workgroup). The arithmetic below is the one-wave form's, term by
+    // term and in its order.
+    f32x4* const X = reinterpret_cast<f32x4*>(sL);       // [wave][position 0..7][row quad 0..1][lane]: 8 x 16 KiB
+    auto give = [&](auto PHC) {
+        constexpr int PH = decltype(PHC)::value;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int m = 32 * kkp + (r & 3) + 8 * (r >> 2) + 4 * hh_e;       // cout row of accumulator register r
-        float t[3][4];
+        for (int lp = 0; lp < 8; ++lp)
 #pragma unroll
-        for (int nu = 0; nu < 4; ++nu) {
-            const float s0 = acc[nu][r], s1 = acc[4 + nu][r], s2 = acc[8 + nu][r], s3 = acc[12 + nu][r];
-            t[0][nu] = s0 + 0.5f * (s1 + s2);
-            t[1][nu] = 0.5f * (s1 - s2);
-            t[2][nu] = 0.5f * (s1 + s2) + s3;
+            for (int hq = 0; hq < 2; ++hq) {
+                f32x4 v;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = acc[lp][8 * (1 - PH) + 4 * hq + e];
+                X[((wave * 8 + lp) * 2 + hq) * 64 + lane] = v;
+            }
+    };
+    if (ph == 0) give(S0{}); else give(S1{});
+    __syncthreads();
+    float* out = p.slab + (size_t)item * (9 * 4096) + (32 * wn + l31);
+    auto finish = [&](auto PHC) {
+        constexpr int PH = decltype(PHC)::value;
+        const f32x4* const Xp = X + ((wave ^ 4) * 16) * 64 + lane;
+#pragma unroll
+        for (int hq = 0; hq < 2; ++hq) {
+            f32x4 o[8];
+#pragma unroll
+            for (int lp = 0; lp < 8; ++lp) o[lp] = Xp[(lp * 2 + hq) * 64];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int r = 8 * PH + 4 * hq + e;                               // accumulator register: compile-time after unrolling
+                const int m = 32 * wm + (r & 3) + 8 * (r >> 2) + 4 * hh;        // its cout row
+                auto S = [&](int pos) { return (pos >> 3) == PH ? acc[pos & 7][r] : o[pos & 7][e]; };
+                float t[3][4];
+#pragma unroll
+                for (int nu = 0; nu < 4; ++nu) {
+                    const float s0 = S(nu), s1 = S(4 + nu), s2 = S(8 + nu), s3 = S(12 + nu);
+                    t[0][nu] = s0 + 0.5f * (s1 + s2);
+                    t[1][nu] = 0.5f * (s1 - s2);
+                    t[2][nu] = 0.5f * (s1 + s2) + s3;
+                }
+#pragma unroll
+                for (int rr = 0; rr < 3; ++rr) {
+                    out[(size_t)((rr * 3 + 0) * 64 + m) * 64] = t[rr][0] + 0.5f * (t[rr][1] + t[rr][2]);
+                    out[(size_t)((rr * 3 + 1) * 64 + m) * 64] = 0.5f * (t[rr][1] - t[rr][2]);
+                    out[(size_t)((rr * 3 + 2) * 64 + m) * 64] = 0.5f * (t[rr][1] + t[rr][2]) + t[rr][3];
+                }
+            }
         }
-#pragma unroll
-        for (int rr = 0; rr < 3; ++rr) {
-            out[(size_t)((rr * 3 + 0) * 64 + m) * 64] = t[rr][0] + 0.5f * (t[rr][1] + t[rr][2]);
-            out[(size_t)((rr * 3 + 1) * 64 + m) * 64] = 0.5f * (t[rr][1] - t[rr][2]);
-            out[(size_t)((rr * 3 + 2) * 64 + m) * 64] = 0.5f * (t[rr][1] + t[rr][2]) + t[rr][3];
-        }
-    }
+    };
+    if (ph == 0) finish(S0{}); else finish(S1{});
 }
 
 // dW[cout][r][s][cin] = sum over the S partials of a block, in a FIXED order (bitwise reproducible): SG split groups per output (a
@@ -1215,8 +1247,8 @@ int osi_conv_wgrad_wino(const osi_conv_desc* d, const float* dy, const float* x,
     p.x_bytes = (int)((size_t)d->B * d->H * d->W * d->Cin * 4);
     p.dy_bytes = (int)((size_t)d->B * d->H * d->W * d->Cout * 4);
     const dim3 grid((unsigned)((d->Cout / 64) * p.CBn * p.S)), blk(256);
-    if (in_scale) hipLaunchKernelGGL((k_wino_wgrad<true>), grid, blk, 0, st, p);
-    else hipLaunchKernelGGL((k_wino_wgrad<false>), grid, blk, 0, st, p);
+    if (in_scale) hipLaunchKernelGGL((k_wino_wgrad<true>), grid, dim3(512), 0, st, p);
+    else hipLaunchKernelGGL((k_wino_wgrad<false>), grid, dim3(512), 0, st, p);
     OSI_LAUNCH_CHECK();
     const int n = d->Cout * 9 * (d->Cin / 4);
     int SG = 1;

@@ -15,7 +15,8 @@ Derived columns (per launch, MI355X: 256 CUs x 4 SIMDs):
   serial_us     the kernel's SERIAL-PIPE floor: an fp32 matrix instruction (v_mfma_f32_32x32x2_f32: 64 pipe cycles) and an ordinary vector
                 instruction never execute together on a SIMD (co-execution counter exactly 0; tools/probes/mfma_valu_coexec.hip), so a SIMD
                 needs at least 64 cycles per matrix instruction PLUS the issue time of its vector instructions — 4 cycles each with one
-                wave per SIMD (the Winograd kernels), 2 cycles each once several waves alternate (the direct kernels) — at the clock held
+                wave per SIMD (k_wino), 2 cycles each once several waves alternate (the direct kernels; k_wino_wgrad, two waves per
+                SIMD — `python tools/wino_pmc_summary.py DIR none` prices it as a lone wave, for builds older than that) — at the clock held
   of_floor      serial_us / us
 """
 import csv
@@ -27,6 +28,7 @@ import sys
 from collections import defaultdict
 
 src = sys.argv[1]
+multi = tuple(f + "<" for f in (sys.argv[2] if len(sys.argv) > 2 else "k_wino_wgrad").split(","))      # Winograd kernels with several waves per SIMD
 fam_of = lambda n: next((f for f in ("k_wino_wgrad<", "k_wino<", "k_conv_fwd<", "k_conv_dgrad<") if f in n), None)
 short = lambda n: re.sub(r"\(.*", "", n.replace("(anonymous namespace)::", "").replace("void ", ""))
 acc = defaultdict(lambda: defaultdict(list))     # label -> counter -> values
@@ -90,7 +92,7 @@ for l in order:
            "issue": c["SQ_ACTIVE_INST_ANY"] / wc if wc and "SQ_ACTIVE_INST_ANY" in c else None,
            "valu_per_mfma": (c["SQ_INSTS_VALU"] - c["SQ_INSTS_MFMA"]) / c["SQ_INSTS_MFMA"] if c.get("SQ_INSTS_MFMA") and "SQ_INSTS_VALU" in c else None,
            "raw_per_launch": {k: round(v, 1) for k, v in sorted(c.items())}}
-    lone = kname[l].startswith("k_wino")          # one wave per SIMD: a vector instruction costs the wave's full 4-cycle issue
+    lone = kname[l].startswith("k_wino") and not kname[l].startswith(multi)          # one wave per SIMD: a vector instruction costs the wave's full 4-cycle issue
     if c.get("SQ_INSTS_MFMA") and "SQ_INSTS_VALU" in c and row["clock_GHz"]:
         cyc_simd = (64.0 * c["SQ_INSTS_MFMA"] + (4.0 if lone else 2.0) * (c["SQ_INSTS_VALU"] - c["SQ_INSTS_MFMA"])) / 1024.0
         row["serial_floor_us"] = cyc_simd / (row["clock_GHz"] * 1e3)
