@@ -231,6 +231,15 @@ int osi_stem_grad_unpack(const float* g_packed, float* g_krsc3, int Cout, osi_st
  * conv1's weight in the arena layout [64][7][7][3]; dx_nchw = fp32 [B][3][H][W], every element written (no pre-zeroing), no atomics
  * (two calls give equal bits). H, W >= 32 (any size osi_resnet50_create takes, odd ones included); OSI_ERR_ARG before any launch. */
 int osi_stem_dgrad(const float* dy, const float* w_krsc3, float* dx_nchw, int B, int H, int W, osi_stream_t stream);
+/* ABI 10. The same input gradient ending in an FGSM epilogue: dx is never written; with dx as above (the two partial sums added exactly
+ * as osi_stem_dgrad adds them)
+ *   x_adv[b][h][w][c] = min(hi, max(lo, x[b][h][w][c] + eps * sgn(dx[b][c][h][w])))   c = 0, 1, 2;   x_adv[b][h][w][3] = 0
+ * sgn = +1 / 0 / -1 (torch.sign). x_nhwc4 = the clean batch in the executor's input layout [B][H][W][4], x_adv_nhwc4 = the output batch
+ * of the same layout, every element written, one 16-byte load and one 16-byte store per pixel, deterministic. Argument rules of
+ * osi_stem_dgrad, plus: both image pointers 16-byte aligned, eps >= 0, lo <= hi, the two batches do not overlap; OSI_ERR_ARG before any
+ * launch. */
+int osi_stem_dgrad_fgsm(const float* dy, const float* w_krsc3, const float* x_nhwc4, float* x_adv_nhwc4, float eps, float lo, float hi,
+                        int B, int H, int W, osi_stream_t stream);
 
 /* ---- BatchNorm2d in training mode + ReLU + residual (torchvision Bottleneck under model.py:37; train() at train.py:125) --- */
 size_t osi_bn_workspace(int M, int C);
@@ -361,6 +370,9 @@ int osi_sgd_step(float* param, const float* grad, float* momentum_buf, size_t n,
                  float grad_scale, osi_stream_t stream);
 int osi_fill_f32(float* p, size_t n, float value, osi_stream_t stream);
 int osi_scale_f32(float* p, size_t n, float s, osi_stream_t stream);
+/* ABI 10. dst[i] += src[i] (one fp32 add per element): the sum of two gradient arenas, e.g. the clean and the adversarial backward of
+ * one training step. 16-byte aligned, distinct pointers, n % 4 == 0 (OSI_ERR_ARG otherwise). */
+int osi_grad_accumulate(float* dst, const float* src, size_t n, osi_stream_t stream);
 int osi_i64_add(long long* p, int n, long long inc, osi_stream_t stream);
 
 /* ---- whole-network executor: ResNet50.forward (model.py:28-39) and its autograd backward (train.py:138) ---------------
@@ -416,6 +428,17 @@ int osi_resnet50_backward(osi_resnet50_t net, const float* params, float* grads,
 int osi_resnet50_backward_ex(osi_resnet50_t net, const float* params, float* grads, void* workspace, const float* dlogits,
                              const float* dfeatures, float* dimage, int param_grads, int stage_lo, int stage_hi,
                              osi_stream_t stream);
+
+/* ABI 10. The full training backward (parameter gradients exactly as osi_resnet50_backward_ex(dimage != NULL, param_grads = 1) writes
+ * them: the stem tail takes the same dY-materialising branch) whose last stage, instead of dJ/dimage, writes the FGSM batch
+ *   x_adv = clamp(x + eps * sign(dJ/dimage), lo, hi)     [B][H][W][4] fp32, 4th lane zero (osi_stem_dgrad_fgsm)
+ * built from the NHWC4 input the forward read — the converted copy in the workspace, the staged uint8 batch or the batch bound with
+ * osi_resnet50_bind_input_nhwc4; the caller does not pass it. x_adv_nhwc4: 16-byte aligned, outside `workspace` and apart from the bound
+ * input (conv1's weight gradient still reads the clean batch), eps >= 0, lo <= hi: OSI_ERR_ARG otherwise. The request (pointer, eps, lo,
+ * hi) is fixed by the call that runs stage 0; a later stage with other values -> OSI_ERR_STATE. */
+int osi_resnet50_backward_adv(osi_resnet50_t net, const float* params, float* grads, void* workspace, const float* dlogits,
+                              const float* dfeatures, float* x_adv_nhwc4, float eps, float lo, float hi, int stage_lo, int stage_hi,
+                              osi_stream_t stream);
 
 /* Data-parallel hand-off (ABI 5). With option "stage_join" = 0 a staged osi_resnet50_backward call (stage_hi < stages) does NOT make
  * `stream` wait for the side stream's weight gradients (the last stage always does); instead the caller makes its COMMUNICATION stream

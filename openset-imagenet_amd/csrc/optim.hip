@@ -3,7 +3,8 @@
 // stepped at train.py:139. Arithmetic follows torch's single-tensor rules:
 //   Adam: m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
 //   SGD : buf = g (first step) | mu*buf + g ; p -= lr*buf
-// Also: arena utilities used by the loop (zero fill, int64 counter bump for num_batches_tracked, scale for DP averaging).
+// Also: arena utilities used by the loop (zero fill, int64 counter bump for num_batches_tracked, scale for DP averaging, and the
+// sum of two gradient arenas: the clean and the adversarial backward of one step, openset_imagenet/adversary.py).
 #include "osi_common.h"
 
 namespace {
@@ -46,6 +47,11 @@ __global__ __launch_bounds__(256) void k_scale(f32x4* __restrict__ p, size_t n4,
     size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t step = (size_t)gridDim.x * 256;
     for (; i < n4; i += step) p[i] = p[i] * s;
+}
+__global__ __launch_bounds__(256) void k_accumulate(f32x4* __restrict__ dst, const f32x4* __restrict__ src, size_t n4) {
+    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t step = (size_t)gridDim.x * 256;
+    for (; i < n4; i += step) dst[i] = dst[i] + src[i];
 }
 __global__ void k_i64_add(long long* p, int n, long long inc) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -91,6 +97,13 @@ int osi_fill_f32(float* p, size_t n, float value, osi_stream_t stream) {
 int osi_scale_f32(float* p, size_t n, float s, osi_stream_t stream) {
     OSI_REQUIRE(p && n > 0 && n % 4 == 0);
     hipLaunchKernelGGL(k_scale, dim3(sgrid(n / 4)), dim3(256), 0, (hipStream_t)stream, (f32x4*)p, n / 4, s);
+    OSI_LAUNCH_CHECK();
+    return OSI_OK;
+}
+int osi_grad_accumulate(float* dst, const float* src, size_t n, osi_stream_t stream) {
+    OSI_REQUIRE(dst && src && dst != src && n > 0 && n % 4 == 0);
+    OSI_REQUIRE(((uintptr_t)dst & 15) == 0 && ((uintptr_t)src & 15) == 0);
+    hipLaunchKernelGGL(k_accumulate, dim3(sgrid(n / 4)), dim3(256), 0, (hipStream_t)stream, (f32x4*)dst, (const f32x4*)src, n / 4);
     OSI_LAUNCH_CHECK();
     return OSI_OK;
 }

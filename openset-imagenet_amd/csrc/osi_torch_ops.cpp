@@ -4,6 +4,7 @@
 //   torch.ops.osi.resnet50_forward    model.py:28-39   (logits, features = model(images))
 //   torch.ops.osi.resnet50_backward   train.py:138     (j.backward() through the network, stage range for the DP bucket schedule)
 //   torch.ops.osi.resnet50_backward_ex  the same, plus dJ/dimage and the input-only backward (adversarial samples, attribution)
+//   torch.ops.osi.resnet50_backward_adv the same, the last stage writing the FGSM batch; torch.ops.osi.grad_accumulate sums two arenas
 //   torch.ops.osi.resnet50_grads_ready  config/train.yaml:18,35-39 (hand a finished stage's gradients to the communication stream)
 //   torch.ops.osi.loss_fwd_bwd        losses.py:16-29, train.py:343-347 (the three losses + objectosphere term, value and gradient)
 //   torch.ops.osi.adam_step / sgd_step    train.py:139, 356-359
@@ -144,6 +145,35 @@ void resnet50_backward_ex(int64_t net, const Tensor& params, Tensor grads, Tenso
        "osi_resnet50_backward_ex");
 }
 
+// ABI 10: the training backward whose last stage writes the FGSM batch x_adv = clamp(x + eps * sign(dJ/dimage), lo, hi) as NHWC4
+// [B, H, W, 4] from the input the forward read (adversarial negatives, openset_imagenet/adversary.py)
+void resnet50_backward_adv(int64_t net, const Tensor& params, Tensor grads, Tensor workspace, const Tensor& dlogits,
+                           const std::optional<Tensor>& dfeatures, Tensor x_adv, double eps, double lo, double hi, int64_t stage_lo,
+                           int64_t stage_hi) {
+    need(params, at::kFloat, "params"); need(grads, at::kFloat, "grads"); need(workspace, at::kByte, "workspace");
+    need(dlogits, at::kFloat, "dlogits", NATURAL); need(x_adv, at::kFloat, "x_adv");
+    if (dfeatures.has_value() && dfeatures->defined()) need(*dfeatures, at::kFloat, "dfeatures", NATURAL);
+    TORCH_CHECK(grads.numel() == params.numel(), "osi::resnet50_backward_adv: gradient arena size mismatch");
+    TORCH_CHECK(x_adv.device() == params.device(), "osi::resnet50_backward_adv: x_adv lives on another device than params");
+    int B = 0, H = 0, W = 0;
+    ok(osi_resnet50_geometry(handle(net), &B, &H, &W), "osi_resnet50_geometry");
+    TORCH_CHECK(x_adv.dim() == 4 && x_adv.size(0) == B && x_adv.size(1) == H && x_adv.size(2) == W && x_adv.size(3) == 4,
+                "osi::resnet50_backward_adv: x_adv must be [", B, ", ", H, ", ", W, ", 4] (NHWC4), got ", x_adv.sizes());
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(params.device());
+    ok(osi_resnet50_backward_adv(handle(net), params.data_ptr<float>(), grads.data_ptr<float>(), workspace.data_ptr(),
+                                 dlogits.data_ptr<float>(), fptr(dfeatures), x_adv.data_ptr<float>(), (float)eps, (float)lo, (float)hi,
+                                 (int)stage_lo, (int)stage_hi, stream_of(params)),
+       "osi_resnet50_backward_adv");
+}
+
+// dst += src over two gradient arenas of the same length
+void grad_accumulate(Tensor dst, const Tensor& src) {
+    need(dst, at::kFloat, "dst"); need(src, at::kFloat, "src");
+    TORCH_CHECK(dst.numel() == src.numel() && dst.device() == src.device(), "osi::grad_accumulate: arenas differ in size or device");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dst.device());
+    ok(osi_grad_accumulate(dst.data_ptr<float>(), src.data_ptr<float>(), (size_t)dst.numel(), stream_of(dst)), "osi_grad_accumulate");
+}
+
 // Data parallel: the stream `waiter` (a raw hipStream_t handle: torch.cuda.Stream.cuda_stream of the communication stream) waits for the
 // gradients of the backward stages enqueued so far on the CURRENT stream and on the executor's side stream; the current stream waits for nothing
 void resnet50_grads_ready(int64_t net, const Tensor& grads, int64_t waiter) {
@@ -236,6 +266,9 @@ TORCH_LIBRARY(osi, m) {
           "int stage_lo, int stage_hi) -> ()");
     m.def("resnet50_backward_ex(int net, Tensor params, Tensor(a!) grads, Tensor(b!) workspace, Tensor dlogits, Tensor? dfeatures, "
           "Tensor(c!)? dimage, bool param_grads, int stage_lo, int stage_hi) -> ()");
+    m.def("resnet50_backward_adv(int net, Tensor params, Tensor(a!) grads, Tensor(b!) workspace, Tensor dlogits, Tensor? dfeatures, "
+          "Tensor(c!) x_adv, float eps, float lo, float hi, int stage_lo, int stage_hi) -> ()");
+    m.def("grad_accumulate(Tensor(a!) dst, Tensor src) -> ()");
     m.def("resnet50_grads_ready(int net, Tensor grads, int waiter_stream) -> ()");
     m.def("loss_fwd_bwd(int mode, Tensor logits, Tensor target, float unk_weight, int ignore_index, Tensor? class_weights, "
           "Tensor? features, float xi, float alpha, bool need_grad) -> (Tensor, Tensor, Tensor)");
@@ -252,6 +285,8 @@ TORCH_LIBRARY_IMPL(osi, CUDA, m) {
     m.impl("resnet50_forward", &resnet50_forward);
     m.impl("resnet50_backward", &resnet50_backward);
     m.impl("resnet50_backward_ex", &resnet50_backward_ex);
+    m.impl("resnet50_backward_adv", &resnet50_backward_adv);
+    m.impl("grad_accumulate", &grad_accumulate);
     m.impl("resnet50_grads_ready", &resnet50_grads_ready);
     m.impl("loss_fwd_bwd", &loss_fwd_bwd);
     m.impl("adam_step", &adam_step);

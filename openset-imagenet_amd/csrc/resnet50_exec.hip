@@ -171,12 +171,17 @@ struct osi_resnet50 {
     // tail materialises dY and its input gradient writes dJ/dimage; bw_pg = 0 -> input-only (no weight gradient, nothing into grads)
     float* bw_dimage = nullptr;
     bool bw_pg = true;
+    // osi_resnet50_backward_adv: bw_adv != NULL -> the stem tail materialises dY as for dJ/dimage, and the stem's input gradient ends in
+    // the FGSM epilogue (osi_stem_dgrad_fgsm) that writes the adversarial NHWC4 batch; dJ/dimage itself is never written
+    float* bw_adv = nullptr;
+    float bw_eps = 0.f, bw_lo = 0.f, bw_hi = 0.f;
     float* dgam(float* grads, float* ws, const BN& b) const { return bw_pg ? grads + b.g_off : ws + b.dsink; }
     float* dbet(float* grads, float* ws, const BN& b) const { return bw_pg ? grads + b.b_off : ws + b.dsink + b.C; }
     // The stem tail's form, decided by what the backward can observe. Block 0's last input gradient and the tail both ask here, so they
     // cannot disagree: the fused form (bn1's reductions out of that input gradient's pool-mode epilogue, dY built inside
-    // osi_stem_wgrad_fused's loader) unless dJ/dimage needs dY in memory or the geometry / knobs leave the fused form no workspace.
-    bool stem_tail_fused() const { return !bw_dimage && stem_ws_bytes > 0; }
+    // osi_stem_wgrad_fused's loader) unless dJ/dimage (or the adversarial batch made from it) needs dY in memory or the geometry /
+    // knobs leave the fused form no workspace.
+    bool stem_tail_fused() const { return !bw_dimage && !bw_adv && stem_ws_bytes > 0; }
     bool eval_fused = true;          // option "eval_fused": a forward with training = 0 runs the inference forms (forward_eval_fused); 0 = the
                                      // training topology on running statistics (A/B: the same bits when both run the same launch plans,
                                      // i.e. tail_split off; fp32-rounding-level differences otherwise)
@@ -894,6 +899,17 @@ int osi_resnet50_backward(osi_resnet50_t n, const float* params, float* grads, v
     return osi_resnet50_backward_ex(n, params, grads, workspace, dlogits, dfeatures, nullptr, 1, stage_lo, stage_hi, stream);
 }
 
+// what a backward is asked for besides the parameter gradients (osi_resnet50_backward_ex / _adv)
+struct BwRequest {
+    float* dimage;
+    int param_grads;
+    float* x_adv;
+    float eps, lo, hi;
+};
+
+static int backward_stages(osi_resnet50_t n, const float* params, float* grads, void* workspace, const float* dlogits,
+                           const float* dfeatures, const BwRequest& rq, int stage_lo, int stage_hi, osi_stream_t stream);
+
 int osi_resnet50_backward_ex(osi_resnet50_t n, const float* params, float* grads, void* workspace, const float* dlogits,
                              const float* dfeatures, float* dimage, int param_grads, int stage_lo, int stage_hi, osi_stream_t stream) {
     OSI_REQUIRE(n && params && workspace);
@@ -901,12 +917,40 @@ int osi_resnet50_backward_ex(osi_resnet50_t n, const float* params, float* grads
     OSI_REQUIRE(!param_grads || grads);
     OSI_REQUIRE(param_grads || dimage);                 // a backward that produces nothing is a caller error
     OSI_REQUIRE(((uintptr_t)dimage & 3) == 0);
+    return backward_stages(n, params, grads, workspace, dlogits, dfeatures, BwRequest{dimage, param_grads, nullptr, 0.f, 0.f, 0.f}, stage_lo,
+                           stage_hi, stream);
+}
+
+int osi_resnet50_backward_adv(osi_resnet50_t n, const float* params, float* grads, void* workspace, const float* dlogits,
+                              const float* dfeatures, float* x_adv_nhwc4, float eps, float lo, float hi, int stage_lo, int stage_hi,
+                              osi_stream_t stream) {
+    OSI_REQUIRE(n && params && grads && workspace && x_adv_nhwc4);
+    OSI_REQUIRE(((uintptr_t)x_adv_nhwc4 & 15) == 0 && eps >= 0.f && lo <= hi);
+    // the adversarial batch may not touch the clean one (bound in place, or the copy inside the workspace) nor anything else in the
+    // workspace: conv1's weight gradient on the side stream still reads the clean batch while the FGSM epilogue writes
+    const size_t img_bytes = (size_t)n->B * n->H * n->W * 4 * sizeof(float);
+    auto apart = [&](const void* p, size_t bytes) {
+        const uintptr_t a = (uintptr_t)x_adv_nhwc4, b = (uintptr_t)p;
+        return a + img_bytes <= b || b + bytes <= a;
+    };
+    OSI_REQUIRE(apart(workspace, n->ws_floats * sizeof(float)));
+    OSI_REQUIRE(!n->x4_cur || apart(n->x4_cur, img_bytes));
+    return backward_stages(n, params, grads, workspace, dlogits, dfeatures, BwRequest{nullptr, 1, x_adv_nhwc4, eps, lo, hi}, stage_lo,
+                           stage_hi, stream);
+}
+
+static int backward_stages(osi_resnet50_t n, const float* params, float* grads, void* workspace, const float* dlogits,
+                           const float* dfeatures, const BwRequest& rq, int stage_lo, int stage_hi, osi_stream_t stream) {
+    float* const dimage = rq.dimage;
+    const int param_grads = rq.param_grads;
     OSI_REQUIRE(stage_lo >= 0 && stage_lo < stage_hi && stage_hi <= n->n_stages);
     if (!n->fwd_done || stage_lo != n->next_stage || !n->plan_unchanged()) return OSI_ERR_STATE;
     if (stage_lo == 0) {                                // the request is fixed by the call that runs stage 0 (block 0's dgrad form depends on it)
         n->bw_dimage = dimage;
         n->bw_pg = param_grads != 0;
-    } else if (n->bw_dimage != dimage || n->bw_pg != (param_grads != 0)) {
+        n->bw_adv = rq.x_adv; n->bw_eps = rq.eps; n->bw_lo = rq.lo; n->bw_hi = rq.hi;
+    } else if (n->bw_dimage != dimage || n->bw_pg != (param_grads != 0) || n->bw_adv != rq.x_adv || n->bw_eps != rq.eps ||
+               n->bw_lo != rq.lo || n->bw_hi != rq.hi) {
         return OSI_ERR_STATE;
     }
     hipStream_t st = (hipStream_t)stream;
@@ -970,7 +1014,7 @@ int osi_resnet50_backward_ex(osi_resnet50_t n, const float* params, float* grads
                 OSI_TRY(n->mark(OSI_PROF_CONV_WGRAD, st));
                 n->give(go);
             } else {
-                // dJ/dimage wanted, or a geometry the fused form does not take: the stem's dY is materialised (max-pool scatter + ReLU gate
+                // dJ/dimage (or the adversarial batch) wanted, or a geometry the fused form does not take: the stem's dY is materialised (max-pool scatter + ReLU gate
                 // + bn1 backward gathered on the fly from the pooled gradient into a scratch buffer), its weight gradient comes from that
                 // dY unless input-only, then — for dJ/dimage — the stem's input gradient straight into the caller's NCHW tensor
                 OSI_TRY(osi_bn_relu_maxpool_bwd(S(go), ws + n->pool_idx, ws + c0.y, ws + b0.mean, ws + b0.invstd, params + b0.g_off, S(t),
@@ -981,6 +1025,9 @@ int osi_resnet50_backward_ex(osi_resnet50_t n, const float* params, float* grads
                 OSI_TRY(wgrad(n, 0, grads, ws, t, x4c, st));
                 if (n->bw_dimage) {
                     OSI_TRY(osi_stem_dgrad(S(t), params + c0.w_off, n->bw_dimage, n->B, n->H, n->W, st));
+                    OSI_TRY(n->mark(OSI_PROF_CONV_DGRAD, st));
+                } else if (n->bw_adv) {     // the same input gradient, ending in the FGSM epilogue: x_adv from the batch the forward read
+                    OSI_TRY(osi_stem_dgrad_fgsm(S(t), params + c0.w_off, x4c, n->bw_adv, n->bw_eps, n->bw_lo, n->bw_hi, n->B, n->H, n->W, st));
                     OSI_TRY(n->mark(OSI_PROF_CONV_DGRAD, st));
                 }
                 n->give(t);

@@ -14,6 +14,11 @@
 //     over (even k, odd k); the two partial sums are added once at the end (fixed order: deterministic, no atomics);
 //   * every element of dx is written once, out-of-range pixels of the last tiles are masked; out-of-range dY pixels read as zero
 //     through the buffer range check.
+//
+// Second form (FGSM = true, osi_stem_dgrad_fgsm): the same K loop, another epilogue. dx is not written at all; the lane already holds
+// the three channel sums of each of its pixels, so it loads the clean pixel from the NHWC4 batch the forward read (16 bytes), moves
+// each channel by eps along the sign of its gradient, clamps and stores the adversarial pixel into an NHWC4 batch (16 bytes, 4th lane
+// zero): one vector store per pixel where the NCHW form needs three scattered 4-byte stores.
 #include "conv_common.h"
 
 using namespace osi_conv;
@@ -63,8 +68,10 @@ __device__ __forceinline__ void sg_chunk(const f32x2* __restrict__ sd, const flo
     }
 }
 
+template <bool FGSM>
 __global__ __launch_bounds__(256) void k_stem_dgrad(const float* __restrict__ dy, const float* __restrict__ w, float* __restrict__ dx,
-                                                    int H, int W, int Hs, int Ws, int tiles_x, int tiles_y, int dy_bytes) {
+                                                    int H, int W, int Hs, int Ws, int tiles_x, int tiles_y, int dy_bytes,
+                                                    const float* __restrict__ x4, float eps, float lo, float hi) {
     __shared__ __attribute__((aligned(16))) f32x2 sd[SG_LDS_F2];   // read as 16-byte vectors (ds_read_b128)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -103,6 +110,29 @@ __global__ __launch_bounds__(256) void k_stem_dgrad(const float* __restrict__ dy
     }
     const int h = h0 + ph + 2 * i;
     if (h >= H) return;
+    if constexpr (FGSM) {
+        // dx = the NHWC4 output batch here: x_adv = clamp(x + eps * sign(dJ/dx)), the gradient itself stays in registers
+        const size_t row = ((size_t)b * H + h) * W;
+        const f32x4* xin = reinterpret_cast<const f32x4*>(x4) + row;
+        f32x4* xout = reinterpret_cast<f32x4*>(dx) + row;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int x = w0 + pw + 2 * (8 * q + j);
+            if (x < W) {
+                const f32x4 p = xin[x];
+                f32x4 o;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float t = acc[j][c][0] + acc[j][c][1];                    // the sum the NCHW form stores
+                    const float sg = (float)((t > 0.f) - (t < 0.f));                // torch.sign
+                    o[c] = fminf(hi, fmaxf(lo, p[c] + eps * sg));
+                }
+                o[3] = 0.f;
+                xout[x] = o;
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         float* out = dx + (((size_t)b * 3 + c) * H + h) * W;
@@ -127,8 +157,30 @@ int osi_stem_dgrad(const float* dy, const float* w_krsc3, float* dx_nchw, int B,
     const int tiles_x = osi_cdiv(W, SG_TW), tiles_y = osi_cdiv(H, SG_TH);
     const size_t grid = (size_t)B * tiles_x * tiles_y;
     OSI_REQUIRE(grid < ((size_t)1 << 31));
-    hipLaunchKernelGGL(k_stem_dgrad, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, dy, w_krsc3, dx_nchw, H, W, Hs, Ws, tiles_x,
-                       tiles_y, (int)dy_bytes);
+    hipLaunchKernelGGL(k_stem_dgrad<false>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, dy, w_krsc3, dx_nchw, H, W, Hs, Ws,
+                       tiles_x, tiles_y, (int)dy_bytes, (const float*)nullptr, 0.f, 0.f, 0.f);
+    OSI_LAUNCH_CHECK();
+    return OSI_OK;
+}
+
+int osi_stem_dgrad_fgsm(const float* dy, const float* w_krsc3, const float* x_nhwc4, float* x_adv_nhwc4, float eps, float lo, float hi,
+                        int B, int H, int W, osi_stream_t stream) {
+    OSI_REQUIRE(dy && w_krsc3 && x_nhwc4 && x_adv_nhwc4 && B > 0 && H >= 32 && W >= 32);
+    OSI_REQUIRE(((uintptr_t)dy & 15) == 0 && ((uintptr_t)w_krsc3 & 3) == 0);
+    OSI_REQUIRE(((uintptr_t)x_nhwc4 & 15) == 0 && ((uintptr_t)x_adv_nhwc4 & 15) == 0);
+    OSI_REQUIRE(eps >= 0.f && lo <= hi);              // (a NaN fails both comparisons)
+    const int Hs = (H - 1) / 2 + 1, Ws = (W - 1) / 2 + 1;
+    const size_t dy_bytes = (size_t)B * Hs * Ws * 64 * sizeof(float);
+    OSI_REQUIRE(dy_bytes < ((size_t)1 << 31));
+    // the two batches may not overlap: a workgroup reads clean pixels other workgroups may already have replaced
+    const size_t img_bytes = (size_t)B * H * W * 4 * sizeof(float);
+    const uintptr_t xa = (uintptr_t)x_nhwc4, xb = (uintptr_t)x_adv_nhwc4;
+    OSI_REQUIRE(xa + img_bytes <= xb || xb + img_bytes <= xa);
+    const int tiles_x = osi_cdiv(W, SG_TW), tiles_y = osi_cdiv(H, SG_TH);
+    const size_t grid = (size_t)B * tiles_x * tiles_y;
+    OSI_REQUIRE(grid < ((size_t)1 << 31));
+    hipLaunchKernelGGL(k_stem_dgrad<true>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, dy, w_krsc3, x_adv_nhwc4, H, W, Hs, Ws,
+                       tiles_x, tiles_y, (int)dy_bytes, x_nhwc4, eps, lo, hi);
     OSI_LAUNCH_CHECK();
     return OSI_OK;
 }

@@ -85,6 +85,7 @@ _SIGS = {
     "osi_stem_wgrad_fused": (c_int, [_PD, P, P, P, P, P, P, P, P, P, P, P, c_size_t, P]),
     "osi_stem_grad_unpack": (c_int, [P, P, c_int, P]),
     "osi_stem_dgrad": (c_int, [P, P, P, c_int, c_int, c_int, P]),
+    "osi_stem_dgrad_fgsm": (c_int, [P, P, P, P, c_float, c_float, c_float, c_int, c_int, c_int, P]),
     "osi_bn_workspace": (c_size_t, [c_int, c_int]),
     "osi_bn_train_stats": (c_int, [P, c_int, c_int, P, P, c_float, c_float, P, P, P, P, P, P, P, c_size_t, P]),
     "osi_bn_eval_coeffs": (c_int, [P, P, P, P, c_float, c_int, P, P, P]),
@@ -119,6 +120,7 @@ _SIGS = {
     "osi_sgd_step": (c_int, [P, P, P, c_size_t, c_float, c_float, c_int, c_float, P]),
     "osi_fill_f32": (c_int, [P, c_size_t, c_float, P]),
     "osi_scale_f32": (c_int, [P, c_size_t, c_float, P]),
+    "osi_grad_accumulate": (c_int, [P, P, c_size_t, P]),
     "osi_i64_add": (c_int, [P, c_int, c_longlong, P]),
     "osi_resnet50_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_int]),
     "osi_resnet50_destroy": (None, [c_void_p]),
@@ -143,6 +145,7 @@ _SIGS = {
     "osi_resnet50_forward": (c_int, [c_void_p, P, P, P, P, P, P, P, c_int, P]),
     "osi_resnet50_backward": (c_int, [c_void_p, P, P, P, P, P, c_int, c_int, P]),
     "osi_resnet50_backward_ex": (c_int, [c_void_p, P, P, P, P, P, P, c_int, c_int, c_int, P]),
+    "osi_resnet50_backward_adv": (c_int, [c_void_p, P, P, P, P, P, P, c_float, c_float, c_float, c_int, c_int, P]),
 }
 
 _lib = None

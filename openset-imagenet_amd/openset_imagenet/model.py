@@ -157,6 +157,10 @@ class ResNet50(nn.Module):
         self._grad_sync = None   # set by dp.DistributedDataParallel
         self._fwd_serial = 0     # number of forward passes run; a backward must belong to the latest one
         self._grads_fresh = False  # a backward has filled the gradient arena since the last optimizer.zero_grad()
+        self._bw_request = None    # next_backward(): (epsilon or None, lo, hi, accumulate) for the one backward that follows
+        self._adv_valid = False    # the latest backward wrote adversarial_batch()
+        self._adv = {}             # (B, H, W) -> the model-owned NHWC4 buffer the FGSM epilogue writes
+        self._flat_grads2 = None   # second gradient arena of an accumulating backward
         self.reset_parameters()
 
     # ------------------------------------------------------------------------------------------------------
@@ -219,6 +223,7 @@ class ResNet50(nn.Module):
                 src = getattr(self, arena)
                 node._buffers[bname] = src[off] if arena == "_nbt" else src[off:off + c]
         self._ws = None
+        self._adv, self._flat_grads2 = {}, None
         return self
 
     # ---- arena access for the optimizer / DP layers -------------------------------------------------------
@@ -249,6 +254,28 @@ class ResNet50(nn.Module):
             self._ws = None
             self._ws = torch.empty(net.ws_bytes, dtype=torch.uint8, device=dev)
         return net
+
+    def next_backward(self, fgsm=None, lo=0.0, hi=1.0, accumulate=False):
+        """Request for the ONE backward that follows (whatever route it takes: a fused loss's plain backward(), autograd):
+          fgsm = epsilon   its last stage also writes the adversarial batch clamp(x + epsilon * sign(dJ/dx), lo, hi) from the input the
+                           forward read (NCHW, NHWC4 or uint8-staged alike) into a model-owned NHWC4 buffer: adversarial_batch();
+                           dJ/dimage itself is never written (osi_resnet50_backward_adv);
+          accumulate       its parameter gradients go into a second arena that is then added into the first (osi_grad_accumulate), so
+                           p.grad holds the sum of this backward and the one before it, as autograd's accumulation would leave it."""
+        if fgsm is not None and not float(fgsm) >= 0.0:
+            raise ValueError("next_backward: fgsm (epsilon) must be >= 0")
+        if not float(lo) <= float(hi):
+            raise ValueError("next_backward: lo <= hi")
+        self._bw_request = (None if fgsm is None else float(fgsm), float(lo), float(hi), bool(accumulate))
+
+    def adversarial_batch(self):
+        """The NHWC4 batch [B, H, W, 4] written by the latest backward that ran under next_backward(fgsm=...). Model-owned and
+        overwritten by the next such backward of the same geometry; feed it to the model as it is."""
+        last = getattr(self, "_last", None)
+        x_adv = self._adv.get(net_shape(self, last[0])) if last is not None else None
+        if x_adv is None or not self._adv_valid:
+            raise RuntimeError("adversarial_batch(): the latest backward did not run under next_backward(fgsm=...)")
+        return x_adv
 
     def mark_gradients_ready(self):
         """Tell the fused optimizers that the gradient arena was filled by hand (tests, custom loops) rather than by backward()."""
@@ -309,12 +336,33 @@ class ResNet50(nn.Module):
         dfeatures = None if dfeatures is None else dfeatures.contiguous().float()
         dimage = torch.empty(B, 3, H, W, device=self._flat_params.device) if want_image else None
         sync = self._grad_sync
-        if dimage is None and param_grads:
+        request, self._bw_request = self._bw_request, None
+        eps, clamp_lo, clamp_hi, accumulate = request if request is not None else (None, 0.0, 1.0, False)
+        self._adv_valid = False
+        if (eps is not None or accumulate) and not param_grads:
+            raise RuntimeError("next_backward(): the requested backward computes parameter gradients, but every parameter is frozen")
+        if eps is not None and want_image:
+            raise ValueError("next_backward(fgsm=...) builds the adversarial batch inside the backward: the image batch must not require "
+                             "grad as well (dJ/dimage is not written on that path)")
+        if accumulate and not self._grads_fresh:
+            raise RuntimeError("next_backward(accumulate=True): no backward has filled the gradient arena since zero_grad()")
+        dev = self._flat_params.device
+        if accumulate and (self._flat_grads2 is None or self._flat_grads2.device != dev):
+            self._flat_grads2 = torch.zeros_like(self._flat_grads)   # zeros: the alignment gaps between tensors are never written
+        if eps is not None:
+            x_adv = self._adv.get((B, H, W))
+            if x_adv is None or x_adv.device != dev:
+                x_adv = self._adv[(B, H, W)] = torch.empty(B, H, W, 4, device=dev)
+            adv = N.ops().resnet50_backward_adv
+            bwd = lambda *a: adv(*a[:6], x_adv, eps, clamp_lo, clamp_hi, *a[6:])
+        elif dimage is None and param_grads:
             bwd = N.ops().resnet50_backward
         else:             # ABI 8: dJ/dimage written by the last stage, and/or no parameter gradient
             ex = N.ops().resnet50_backward_ex
             bwd = lambda *a: ex(*a[:6], dimage, bool(param_grads), *a[6:])
         grads = self._flat_grads if param_grads else self._flat_grads[:0]
+        if accumulate:    # into the second arena (under data parallel its buckets are averaged on their own), added into the first below
+            grads = self._flat_grads2
         if sync is None:  # single GPU: all stages in one call (one side-stream join at the end)
             bwd(net.h.value, self._flat_params, grads, self._ws, dlogits, dfeatures, 0, self._n_stages)
         else:             # data parallel: stage by stage, each finished slice of the gradient arena goes to the all-reduce
@@ -328,6 +376,9 @@ class ResNet50(nn.Module):
                     lo, hi = self._stage_ranges[s]
                     sync.bucket_ready(grads, lo, hi, handoff)
             sync.finish()
+        if accumulate:
+            N.ops().grad_accumulate(self._flat_grads, grads)
+        self._adv_valid = eps is not None
         if param_grads:
             self._grads_fresh = True
             self.bind_gradients()

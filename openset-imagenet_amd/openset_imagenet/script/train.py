@@ -1,6 +1,7 @@
 """train_imagenet.py — command line of the reference (openset_imagenet/script/train.py:8-63): `configuration protocol
 [-o DIR] [-g [IDX]] [--nice N]`. One fix over the reference: `-g 0` / bare `-g` selects GPU 0 (the reference tests `if args.gpu:`,
-which is false for index 0, script/train.py:58). `--synthetic N` (new) trains on N synthetic samples instead of the protocol CSVs.
+which is false for index 0, script/train.py:58). `--synthetic N` (new) trains on N synthetic samples instead of the protocol CSVs;
+`--adversary WHO` (new) turns on adversarial negatives (openset_imagenet/adversary.py) over the configuration's `adv` block.
 
 Data parallel: started under `python -m torch.distributed.run` (RANK / WORLD_SIZE / LOCAL_RANK in the environment) every rank
 simply runs worker(); with `dist.distributed: on` in the configuration (config/train.yaml, the reference's unused `dist:` block)
@@ -24,6 +25,8 @@ def get_args(command_line_options=None):
     p.add_argument("--gpu", "-g", type=int, nargs="?", default=None, const=0, help="GPU index (bare -g = 0)")
     p.add_argument("--nice", type=int, default=20, help="Select Priority Level")
     p.add_argument("--synthetic", type=int, default=0, help="train on this many synthetic samples instead of the protocol CSV files")
+    p.add_argument("--adversary", choices=("no_adv", "fgsm", "gaussian", "uniform"), default=None,
+                   help="adversarial negatives per step (overrides adv.who of the configuration; strength from its adv block)")
     args = p.parse_args(command_line_options)
     os.nice(args.nice)
     return args
@@ -82,6 +85,10 @@ def main(command_line_options=None):
     config.output_directory = args.output_directory
     if args.synthetic:
         config.data.synthetic = args.synthetic
+    if args.adversary is not None:
+        if getattr(config, "adv", None) is None:
+            config.adv = util.NameSpace({})
+        config.adv.who = args.adversary
     return _train.worker(config)
 
 

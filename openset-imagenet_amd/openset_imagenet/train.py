@@ -19,6 +19,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
+from . import adversary as _adversary
 from . import dp as _dp
 from . import losses as _losses
 from . import optim as _optim
@@ -95,21 +96,39 @@ def build_optimizer(cfg, model):
     return _optim.Adam(_unwrap(model), lr=cfg.opt.lr)
 
 
-def train(model, data_loader, optimizer, loss_fn, trackers, cfg):
-    """One epoch of training (reference train.py:104-139)."""
+def train(model, data_loader, optimizer, loss_fn, trackers, cfg, epsilon=None):
+    """One epoch of training (reference train.py:104-139).
+
+    With `cfg.adv.who` in {fgsm, gaussian, uniform} (new; absent block or `no_adv`: the loop below is the reference's) every step
+    trains on the batch AND on negatives generated from it (adversary.py): clean forward / loss j / backward, negatives, second
+    training-mode forward / loss j_adv on the negative label / backward adding to the clean gradients, one optimizer.step().
+    `epsilon` overrides cfg.adv.epsilon (worker() passes the scheduled value); trackers["j_adv"] receives j_adv like trackers["j"]."""
+    plan = _adversary.Plan(cfg, epsilon) if _adversary.who_of(cfg) != "no_adv" else None
+    if plan is not None:
+        trackers.setdefault("j_adv", _losses.AverageMeter())
     for metric in trackers.values():
         metric.reset()
     if not cfg.parallel:
         import tqdm
         data_loader = tqdm.tqdm(data_loader)
     wants_features = isinstance(loss_fn, _losses.ObjectosphereLoss)
-    pending, counts = [], []
+    pending, counts, pending_adv = [], [], []
     from .pipeline import device_batch
+    if plan is not None:
+        net = _unwrap(model) if isinstance(_unwrap(model), ResNet50) else None
+        loss = (lambda lg, ft, y: loss_fn(lg, y, ft)) if wants_features else (lambda lg, ft, y: loss_fn(lg, y))
     for batch in data_loader:
         model.train()  # batch-norm uses and collects batch statistics
         optimizer.zero_grad()
         images, labels = device_batch(batch)   # device(images), device(labels) of train.py:128-129; canvas batches are staged
         batch_len = labels.shape[0]
+        if plan is not None:
+            j, j_adv = _adversary.two_pass_step(model, net, images, labels, loss, plan)
+            pending.append(j)
+            pending_adv.append(j_adv)
+            counts.append(batch_len)
+            optimizer.step()
+            continue
         logits, features = model(images)
         j = loss_fn(logits, labels, features) if wants_features else loss_fn(logits, labels)
         pending.append(j.detach())
@@ -119,6 +138,9 @@ def train(model, data_loader, optimizer, loss_fn, trackers, cfg):
     if pending:
         for value, n in zip(torch.stack(pending).cpu().tolist(), counts):
             trackers["j"].update(value, n)
+    if pending_adv:
+        for value, n in zip(torch.stack(pending_adv).cpu().tolist(), counts):
+            trackers["j_adv"].update(value, n)
 
 
 class ShardedEvalBatches(torch.utils.data.Sampler):
@@ -419,6 +441,13 @@ def _worker_body(cfg, log, out_dir, rank, world, distributed):
     _last_worker_state.clear()
     _last_worker_state.update(model=model, optimizer=opt, rank=rank, world=world, checkpoints_written=0, sharded_validation=shard_val)
     t_metrics = {"j": _losses.AverageMeter()}
+    # adversarial negatives (new block `adv`, adversary.py): refused with a loss that has no target for them, before the first epoch
+    adv_on = _adversary.who_of(cfg) != "no_adv"
+    if adv_on:
+        _adversary.Plan(cfg)
+        t_metrics["j_adv"] = _losses.AverageMeter()
+        if _adversary.who_of(cfg) != "fgsm" and getattr(cfg.adv, "generator", None) is None:   # the noise stream: seeded per rank
+            cfg.adv.generator = torch.Generator(device=tools.get_device()).manual_seed(cfg.seed + rank)
     v_metrics = {"j": _losses.AverageMeter(), "conf_kn": _losses.AverageMeter(), "conf_unk": _losses.AverageMeter()}
     _last_worker_state.update(v_metrics=v_metrics, val_loader=val_loader, loss_fn=loss_fn, n_classes=n_classes)
     early = _losses.EarlyStopping(patience=cfg.patience) if cfg.patience > 0 else None
@@ -432,7 +461,7 @@ def _worker_body(cfg, log, out_dir, rank, world, distributed):
         t0 = time.time()
         if sampler is not None:
             sampler.set_epoch(epoch)
-        train(net, train_loader, opt, loss_fn, t_metrics, cfg)
+        train(net, train_loader, opt, loss_fn, t_metrics, cfg, epsilon=_adversary.scheduled_epsilon(cfg.adv, epoch) if adv_on else None)
         t1 = time.time()
         stop, failure = False, None
         curr_score = None
