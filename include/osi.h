@@ -368,6 +368,39 @@ int osi_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
                   double beta2, double eps, long long step, float grad_scale, osi_stream_t stream);
 int osi_sgd_step(float* param, const float* grad, float* momentum_buf, size_t n, float lr, float momentum, int first_step,
                  float grad_scale, osi_stream_t stream);
+/* ABI 11. The same steps with parameter groups: ONE launch over the arena, every 16-byte unit (4 floats) updated under the options of
+ * the segment it lies in. A segment is a run [begin4, end4) of units with a group index; segments are sorted by begin4, do not overlap,
+ * are not empty, end at or before n/4 and need not cover the arena: units outside every segment are neither read nor written, in the
+ * parameter arena or any state arena. segments and groups are HOST pointers, read during the call (they travel in the kernel
+ * arguments) and not needed afterwards. Arithmetic is torch's single-tensor path (torch.optim.Adam / AdamW / SGD); the scalars are
+ * prepared in double as osi_adam_step does, and a group with default options (weight_decay 0, not decoupled, no amsgrad, no nesterov,
+ * dampening 0, no maximize) gives the bits of osi_adam_step / osi_sgd_step. OSI_ERR_ARG before any launch on: a null pointer
+ * (max_exp_avg_sq may be NULL unless a group has amsgrad), n % 4 != 0 or n/4 > 2^32 - 512, n_segments outside 1..OSI_OPT_MAX_SEGMENTS,
+ * n_groups outside 1..OSI_OPT_MAX_GROUPS, a malformed segment table, a group index out of range, step < 1, nesterov with
+ * momentum <= 0 or dampening != 0. */
+#define OSI_OPT_MAX_SEGMENTS 192
+#define OSI_OPT_MAX_GROUPS 16
+typedef struct {
+    unsigned int begin4, end4; /* in units of 4 floats */
+    int group;
+} osi_opt_segment;
+typedef struct {
+    double lr, beta1, beta2, eps, weight_decay;
+    long long step;     /* step count of this group's parameters AFTER this step (>= 1) */
+    int decoupled;      /* 1: AdamW, p *= 1 - lr*weight_decay; 0: L2, g += weight_decay*p */
+    int amsgrad, maximize;
+} osi_adam_group;
+typedef struct {
+    double lr, momentum, dampening, weight_decay;
+    int nesterov;
+    int first_step;     /* 1: the momentum buffer is initialised with the gradient (torch's first step) */
+    int maximize;
+} osi_sgd_group;
+int osi_adam_step_groups(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, size_t n,
+                         const osi_opt_segment* segments, int n_segments, const osi_adam_group* groups, int n_groups,
+                         float grad_scale, osi_stream_t stream);
+int osi_sgd_step_groups(float* param, const float* grad, float* momentum_buf, size_t n, const osi_opt_segment* segments,
+                        int n_segments, const osi_sgd_group* groups, int n_groups, float grad_scale, osi_stream_t stream);
 int osi_fill_f32(float* p, size_t n, float value, osi_stream_t stream);
 int osi_scale_f32(float* p, size_t n, float s, osi_stream_t stream);
 /* ABI 10. dst[i] += src[i] (one fp32 add per element): the sum of two gradient arenas, e.g. the clean and the adversarial backward of

@@ -7,6 +7,8 @@
 // sum of two gradient arenas: the clean and the adversarial backward of one step, openset_imagenet/adversary.py).
 #include "osi_common.h"
 
+#include <cstring>
+
 namespace {
 
 __global__ __launch_bounds__(256) void k_adam(f32x4* __restrict__ p, const f32x4* __restrict__ g, f32x4* __restrict__ m, f32x4* __restrict__ v,
@@ -38,6 +40,149 @@ __global__ __launch_bounds__(256) void k_sgd(f32x4* __restrict__ p, const f32x4*
     }
 }
 
+// Per-group scalars of the grouped kernels, prepared on the host in double (osi_*_step_groups).
+enum : uint32_t { OPT_DECOUPLED = 1, OPT_AMSGRAD = 2, OPT_MAXIMIZE = 4, OPT_NESTEROV = 8, OPT_FIRST = 16, OPT_MOMENTUM = 32 };
+struct AdamScal {
+    float step_size, sqrt_bc2, b2, omb1, omb2, eps, wd, decay_mul;   // lr/bc1, sqrt(bc2), beta2, 1-beta1, 1-beta2, eps, wd, 1-lr*wd
+    uint32_t flags;
+};
+struct SgdScal {
+    float lr, mu, omd, wd;   // omd = 1 - dampening
+    uint32_t flags;
+};
+
+__device__ __forceinline__ f32x4 splat4(float s) { return f32x4{s, s, s, s}; }
+__device__ __forceinline__ f32x4 fma4(f32x4 a, f32x4 b, f32x4 c) { return __builtin_elementwise_fma(a, b, c); }
+
+// The per-element rules of the grouped kernels. The contractions are spelled out as the compiler forms them in k_adam / k_sgd above
+// (whose bodies stay as they are: routing them through these functions changed their register allocation and schedule), so a group
+// with default options (no flags besides OPT_MOMENTUM / OPT_FIRST, wd 0, omd 1) gives the bits of the plain kernel:
+//   k_adam: d = fma(g, gscale, -m); m = fma(d, 1-b1, m); v = fma(v, b2, ((g*gscale)^2)*(1-b2)); p = fma(-step_size, m/den, p)
+//   k_sgd : b = fma(mu, buf, g*gscale); p = fma(-lr, b, p)
+// g is the raw gradient; vmax is read and written only under OPT_AMSGRAD.
+__device__ __forceinline__ void adam_update(f32x4& pp, f32x4 g, f32x4& mm, f32x4& vv, f32x4& vmax, const AdamScal& s, float gscale) {
+    f32x4 gg = g * gscale;
+    f32x4 d = fma4(g, splat4(gscale), -mm);      // (g*gscale - m) in one rounding
+    const bool l2 = s.wd != 0.f && !(s.flags & OPT_DECOUPLED);
+    if (s.flags & OPT_MAXIMIZE) gg = -gg;
+    if (s.flags & OPT_DECOUPLED) pp = pp * s.decay_mul;     // torch AdamW: param.mul_(1 - lr*wd)
+    if (l2) gg = fma4(splat4(s.wd), pp, gg);                // torch Adam: grad.add(param, alpha=wd)
+    if (l2 || (s.flags & OPT_MAXIMIZE)) d = gg - mm;
+    mm = fma4(d, splat4(s.omb1), mm);                       // torch: exp_avg.lerp_(grad, 1-beta1)
+    vv = fma4(vv, splat4(s.b2), gg * gg * s.omb2);          // torch: exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2)
+    f32x4 vd = vv;
+    if (s.flags & OPT_AMSGRAD) {                            // torch: max_exp_avg_sq = max(max_exp_avg_sq, exp_avg_sq)
+        vmax.x = fmaxf(vmax.x, vv.x); vmax.y = fmaxf(vmax.y, vv.y); vmax.z = fmaxf(vmax.z, vv.z); vmax.w = fmaxf(vmax.w, vv.w);
+        vd = vmax;
+    }
+    f32x4 den;
+    den.x = sqrtf(vd.x) / s.sqrt_bc2 + s.eps; den.y = sqrtf(vd.y) / s.sqrt_bc2 + s.eps;
+    den.z = sqrtf(vd.z) / s.sqrt_bc2 + s.eps; den.w = sqrtf(vd.w) / s.sqrt_bc2 + s.eps;
+    pp = fma4(-(mm / den), splat4(s.step_size), pp);         // torch: param.addcdiv_(exp_avg, denom, value=-step_size)
+}
+
+// b: the momentum buffer, read by the caller unless OPT_FIRST, written back under OPT_MOMENTUM.
+__device__ __forceinline__ void sgd_update(f32x4& pp, f32x4 g, f32x4& b, const SgdScal& s, float gscale) {
+    f32x4 gg = g * gscale;
+    if (s.flags & OPT_MAXIMIZE) gg = -gg;
+    if (s.wd != 0.f) gg = fma4(splat4(s.wd), pp, gg);
+    if (s.flags & OPT_MOMENTUM) {
+        b = (s.flags & OPT_FIRST) ? gg : fma4(splat4(s.mu), b, gg * s.omd);
+        gg = (s.flags & OPT_NESTEROV) ? fma4(splat4(s.mu), b, gg) : b;
+    }
+    pp = fma4(-gg, splat4(s.lr), pp);
+}
+
+// ---- grouped forms: one launch over the arena, every 16-byte unit under the rule of the segment it lies in -------------------
+// The host cuts the arena into contiguous chunks of whole 256-unit tiles, one per workgroup, so a thread's unit index only grows and
+// its segment index only advances. The tables arrive by value in the kernel arguments and are staged in LDS once per workgroup
+// (so that the divergent lookups below index LDS, not the argument struct); a thread keeps its current segment's bounds and
+// its group's scalars in registers and touches LDS again only when it crosses a segment end.
+struct SegTable {
+    uint32_t begin[OSI_OPT_MAX_SEGMENTS], end[OSI_OPT_MAX_SEGMENTS];
+    uint8_t group[OSI_OPT_MAX_SEGMENTS];
+    int n;
+};
+struct AdamGroups { AdamScal g[OSI_OPT_MAX_GROUPS]; };
+struct SgdGroups { SgdScal g[OSI_OPT_MAX_GROUPS]; };
+
+template <class Scal, class Groups>
+struct SegWalker {
+    uint32_t* s_begin; uint32_t* s_end; uint32_t* s_group; Scal* s_scal;
+    int nseg, st;
+    uint32_t cb, ce;   // bounds of segment st; both ~0u past the last one
+    Scal sc;
+
+    __device__ __forceinline__ void stage(const SegTable& tab, const Groups& grp) {
+        const int t = threadIdx.x;
+        if (t < OSI_OPT_MAX_SEGMENTS) { s_begin[t] = tab.begin[t]; s_end[t] = tab.end[t]; s_group[t] = tab.group[t]; }
+        constexpr int words = (int)(sizeof(Groups) / 4);
+        static_assert(words <= 256, "group table is staged by one pass of the workgroup");
+        if (t < words) ((uint32_t*)s_scal)[t] = ((const uint32_t*)&grp)[t];
+        __syncthreads();
+        nseg = tab.n;
+    }
+    __device__ __forceinline__ void load() {
+        if (st < nseg) { cb = s_begin[st]; ce = s_end[st]; sc = s_scal[s_group[st]]; }
+        else cb = ce = ~0u;
+    }
+    // first segment that ends after unit i
+    __device__ __forceinline__ void seek(uint32_t i) {
+        int a = 0, b = nseg;
+        while (a < b) { const int mid = (a + b) >> 1; if (s_end[mid] <= i) a = mid + 1; else b = mid; }
+        st = a;
+        load();
+    }
+    // i only grows between calls; true when unit i lies in a segment (sc then holds its group)
+    __device__ __forceinline__ bool covers(uint32_t i) {
+        if (i >= ce) { do ++st; while (st < nseg && s_end[st] <= i); load(); }
+        return i >= cb;
+    }
+};
+
+__global__ __launch_bounds__(256) void k_adam_groups(f32x4* __restrict__ p, const f32x4* __restrict__ g, f32x4* __restrict__ m,
+                                                    f32x4* __restrict__ v, f32x4* __restrict__ vmax, uint32_t n4, uint32_t chunk4,
+                                                    float gscale, SegTable tab, AdamGroups grp) {
+    __shared__ uint32_t s_begin[OSI_OPT_MAX_SEGMENTS], s_end[OSI_OPT_MAX_SEGMENTS], s_group[OSI_OPT_MAX_SEGMENTS];
+    __shared__ AdamScal s_scal[OSI_OPT_MAX_GROUPS];
+    SegWalker<AdamScal, AdamGroups> w{s_begin, s_end, s_group, s_scal};
+    w.stage(tab, grp);
+    const uint32_t lo = blockIdx.x * chunk4;                       // lo < n4 <= 2^32 - 512 (fill_seg_table), so i += 256 cannot wrap
+    const uint32_t hi = n4 - lo < chunk4 ? n4 : lo + chunk4;
+    uint32_t i = lo + threadIdx.x;
+    w.seek(i);
+    for (; i < hi && w.st < w.nseg; i += 256) {
+        if (!w.covers(i)) continue;
+        const AdamScal& s = w.sc;
+        f32x4 mm = m[i], vv = v[i], pp = p[i], vm = {};
+        if (s.flags & OPT_AMSGRAD) vm = vmax[i];
+        adam_update(pp, g[i], mm, vv, vm, s, gscale);
+        m[i] = mm; v[i] = vv; p[i] = pp;
+        if (s.flags & OPT_AMSGRAD) vmax[i] = vm;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_sgd_groups(f32x4* __restrict__ p, const f32x4* __restrict__ g, f32x4* __restrict__ buf,
+                                                   uint32_t n4, uint32_t chunk4, float gscale, SegTable tab, SgdGroups grp) {
+    __shared__ uint32_t s_begin[OSI_OPT_MAX_SEGMENTS], s_end[OSI_OPT_MAX_SEGMENTS], s_group[OSI_OPT_MAX_SEGMENTS];
+    __shared__ SgdScal s_scal[OSI_OPT_MAX_GROUPS];
+    SegWalker<SgdScal, SgdGroups> w{s_begin, s_end, s_group, s_scal};
+    w.stage(tab, grp);
+    const uint32_t lo = blockIdx.x * chunk4;
+    const uint32_t hi = n4 - lo < chunk4 ? n4 : lo + chunk4;
+    uint32_t i = lo + threadIdx.x;
+    w.seek(i);
+    for (; i < hi && w.st < w.nseg; i += 256) {
+        if (!w.covers(i)) continue;
+        const SgdScal& s = w.sc;
+        f32x4 b = {}, pp = p[i];
+        if ((s.flags & (OPT_MOMENTUM | OPT_FIRST)) == OPT_MOMENTUM) b = buf[i];   // a momentum-free group never touches the buffer arena
+        sgd_update(pp, g[i], b, s, gscale);
+        if (s.flags & OPT_MOMENTUM) buf[i] = b;
+        p[i] = pp;
+    }
+}
+
 __global__ __launch_bounds__(256) void k_fill(f32x4* __restrict__ p, size_t n4, float val) {
     size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t step = (size_t)gridDim.x * 256;
@@ -63,6 +208,30 @@ static int sgrid(size_t n4) {
     return (int)(g > 2048 ? 2048 : (g ? g : 1));
 }
 
+// Validates the caller's segment table against the arena (n floats) and packs it for the kernel arguments; false = malformed.
+static bool fill_seg_table(SegTable& tab, const osi_opt_segment* seg, int n_segments, int n_groups, size_t n) {
+    if (!seg || n == 0 || n % 4 != 0 || n / 4 > 0xFFFFFFFFull - 511) return false;   // unit indices are 32 bits; room for one stride past the end
+    if (n_segments < 1 || n_segments > OSI_OPT_MAX_SEGMENTS || n_groups < 1 || n_groups > OSI_OPT_MAX_GROUPS) return false;
+    memset(&tab, 0, sizeof tab);
+    uint32_t prev_end = 0;
+    for (int i = 0; i < n_segments; ++i) {
+        if (seg[i].begin4 < prev_end || seg[i].end4 <= seg[i].begin4 || seg[i].end4 > n / 4) return false;
+        if (seg[i].group < 0 || seg[i].group >= n_groups) return false;
+        tab.begin[i] = seg[i].begin4; tab.end[i] = seg[i].end4; tab.group[i] = (uint8_t)seg[i].group;
+        prev_end = seg[i].end4;
+    }
+    tab.n = n_segments;
+    return true;
+}
+
+// One contiguous chunk of whole 256-unit tiles per workgroup, at most 2048 workgroups (the plain kernels' grid).
+static int chunk_grid(size_t n4, uint32_t& chunk4) {
+    const size_t tiles = (n4 + 255) / 256;
+    const size_t per = (tiles + 2047) / 2048;
+    chunk4 = (uint32_t)(per * 256);
+    return (int)((tiles + per - 1) / per);
+}
+
 }  // namespace
 
 extern "C" {
@@ -84,6 +253,53 @@ int osi_sgd_step(float* param, const float* grad, float* momentum_buf, size_t n,
     OSI_REQUIRE(param && grad && momentum_buf && n > 0 && n % 4 == 0);
     hipLaunchKernelGGL(k_sgd, dim3(sgrid(n / 4)), dim3(256), 0, (hipStream_t)stream, (f32x4*)param, (const f32x4*)grad,
                        (f32x4*)momentum_buf, n / 4, lr, momentum, first_step, grad_scale);
+    OSI_LAUNCH_CHECK();
+    return OSI_OK;
+}
+
+int osi_adam_step_groups(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, size_t n,
+                         const osi_opt_segment* segments, int n_segments, const osi_adam_group* groups, int n_groups,
+                         float grad_scale, osi_stream_t stream) {
+    OSI_REQUIRE(param && grad && exp_avg && exp_avg_sq && groups);
+    SegTable tab;
+    OSI_REQUIRE(fill_seg_table(tab, segments, n_segments, n_groups, n));
+    AdamGroups gs;
+    memset(&gs, 0, sizeof gs);
+    for (int i = 0; i < n_groups; ++i) {
+        const osi_adam_group& u = groups[i];
+        OSI_REQUIRE(u.step >= 1 && (!u.amsgrad || max_exp_avg_sq));
+        const double bc1 = 1.0 - pow(u.beta1, (double)u.step);
+        const double bc2 = 1.0 - pow(u.beta2, (double)u.step);
+        gs.g[i] = AdamScal{(float)(u.lr / bc1), (float)sqrt(bc2), (float)u.beta2, (float)(1.0 - u.beta1), (float)(1.0 - u.beta2),
+                           (float)u.eps, (float)u.weight_decay, (float)(1.0 - u.lr * u.weight_decay),
+                           (u.decoupled ? OPT_DECOUPLED : 0u) | (u.amsgrad ? OPT_AMSGRAD : 0u) | (u.maximize ? OPT_MAXIMIZE : 0u)};
+    }
+    uint32_t chunk4;
+    const int grid = chunk_grid(n / 4, chunk4);
+    hipLaunchKernelGGL(k_adam_groups, dim3(grid), dim3(256), 0, (hipStream_t)stream, (f32x4*)param, (const f32x4*)grad,
+                       (f32x4*)exp_avg, (f32x4*)exp_avg_sq, (f32x4*)max_exp_avg_sq, (uint32_t)(n / 4), chunk4, grad_scale, tab, gs);
+    OSI_LAUNCH_CHECK();
+    return OSI_OK;
+}
+
+int osi_sgd_step_groups(float* param, const float* grad, float* momentum_buf, size_t n, const osi_opt_segment* segments,
+                        int n_segments, const osi_sgd_group* groups, int n_groups, float grad_scale, osi_stream_t stream) {
+    OSI_REQUIRE(param && grad && momentum_buf && groups);
+    SegTable tab;
+    OSI_REQUIRE(fill_seg_table(tab, segments, n_segments, n_groups, n));
+    SgdGroups gs;
+    memset(&gs, 0, sizeof gs);
+    for (int i = 0; i < n_groups; ++i) {
+        const osi_sgd_group& u = groups[i];
+        OSI_REQUIRE(!u.nesterov || (u.momentum > 0.0 && u.dampening == 0.0));
+        gs.g[i] = SgdScal{(float)u.lr, (float)u.momentum, (float)(1.0 - u.dampening), (float)u.weight_decay,
+                          (u.nesterov ? OPT_NESTEROV : 0u) | (u.maximize ? OPT_MAXIMIZE : 0u) |
+                              (u.momentum != 0.0 ? OPT_MOMENTUM | (u.first_step ? OPT_FIRST : 0u) : 0u)};
+    }
+    uint32_t chunk4;
+    const int grid = chunk_grid(n / 4, chunk4);
+    hipLaunchKernelGGL(k_sgd_groups, dim3(grid), dim3(256), 0, (hipStream_t)stream, (f32x4*)param, (const f32x4*)grad,
+                       (f32x4*)momentum_buf, (uint32_t)(n / 4), chunk4, grad_scale, tab, gs);
     OSI_LAUNCH_CHECK();
     return OSI_OK;
 }

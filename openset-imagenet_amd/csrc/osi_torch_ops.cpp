@@ -7,7 +7,7 @@
 //   torch.ops.osi.resnet50_backward_adv the same, the last stage writing the FGSM batch; torch.ops.osi.grad_accumulate sums two arenas
 //   torch.ops.osi.resnet50_grads_ready  config/train.yaml:18,35-39 (hand a finished stage's gradients to the communication stream)
 //   torch.ops.osi.loss_fwd_bwd        losses.py:16-29, train.py:343-347 (the three losses + objectosphere term, value and gradient)
-//   torch.ops.osi.adam_step / sgd_step    train.py:139, 356-359
+//   torch.ops.osi.adam_step / sgd_step    train.py:139, 356-359; adam_step_groups / sgd_step_groups: the same with parameter groups
 //   torch.ops.osi.stage_canvas        train.py:259-263 after decode + resize (crop, flip, ToTensor, NHWC4)
 //   torch.ops.osi.softmax / confidence_accumulate    train.py:177, metrics.py:8-42
 //
@@ -24,6 +24,7 @@
 #include <optional>
 #include <string>
 #include <tuple>
+#include <vector>
 
 #include "../../include/osi.h"
 
@@ -225,6 +226,60 @@ void sgd_step(Tensor params, const Tensor& grads, Tensor momentum_buffer, double
                     (float)lr, (float)momentum, first ? 1 : 0, (float)grad_scale, stream_of(params)), "osi_sgd_step");
 }
 
+// segments: flat (begin4, end4, group) triples; the group tables are flat rows of doubles in the field order of osi_adam_group /
+// osi_sgd_group. Everything else is validated by the C ABI.
+std::vector<osi_opt_segment> opt_segments(c10::ArrayRef<int64_t> segments) {
+    TORCH_CHECK(segments.size() % 3 == 0, "segments: flat (begin4, end4, group) triples");
+    std::vector<osi_opt_segment> seg(segments.size() / 3);
+    for (size_t i = 0; i < seg.size(); ++i) {
+        for (int j = 0; j < 2; ++j)
+            TORCH_CHECK(segments[3 * i + j] >= 0 && segments[3 * i + j] <= 0xFFFFFFFFll, "segment bounds out of range");
+        TORCH_CHECK(segments[3 * i + 2] >= 0 && segments[3 * i + 2] < OSI_OPT_MAX_GROUPS, "segment group index out of range");
+        seg[i] = osi_opt_segment{(unsigned)segments[3 * i], (unsigned)segments[3 * i + 1], (int)segments[3 * i + 2]};
+    }
+    return seg;
+}
+
+void adam_step_groups(Tensor params, const Tensor& grads, Tensor exp_avg, Tensor exp_avg_sq, const std::optional<Tensor>& max_exp_avg_sq,
+                      c10::ArrayRef<int64_t> segments, c10::ArrayRef<double> groups, double grad_scale) {
+    need(params, at::kFloat, "params"); need(grads, at::kFloat, "grads"); need(exp_avg, at::kFloat, "exp_avg"); need(exp_avg_sq, at::kFloat, "exp_avg_sq");
+    TORCH_CHECK(grads.numel() == params.numel() && exp_avg.numel() == params.numel() && exp_avg_sq.numel() == params.numel());
+    float* vmax = nullptr;
+    if (max_exp_avg_sq.has_value() && max_exp_avg_sq->defined()) {
+        need(*max_exp_avg_sq, at::kFloat, "max_exp_avg_sq");
+        TORCH_CHECK(max_exp_avg_sq->numel() == params.numel());
+        vmax = max_exp_avg_sq->data_ptr<float>();
+    }
+    TORCH_CHECK(groups.size() % 9 == 0, "groups: rows of (lr, beta1, beta2, eps, weight_decay, step, decoupled, amsgrad, maximize)");
+    const std::vector<osi_opt_segment> seg = opt_segments(segments);
+    std::vector<osi_adam_group> gs(groups.size() / 9);
+    for (size_t i = 0; i < gs.size(); ++i) {
+        const double* r = &groups[9 * i];
+        gs[i] = osi_adam_group{r[0], r[1], r[2], r[3], r[4], (long long)r[5], r[6] != 0.0, r[7] != 0.0, r[8] != 0.0};
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(params.device());
+    ok(osi_adam_step_groups(params.data_ptr<float>(), grads.data_ptr<float>(), exp_avg.data_ptr<float>(), exp_avg_sq.data_ptr<float>(), vmax,
+                            (size_t)params.numel(), seg.data(), (int)seg.size(), gs.data(), (int)gs.size(), (float)grad_scale,
+                            stream_of(params)), "osi_adam_step_groups");
+}
+
+void sgd_step_groups(Tensor params, const Tensor& grads, Tensor momentum_buffer, c10::ArrayRef<int64_t> segments,
+                     c10::ArrayRef<double> groups, double grad_scale) {
+    need(params, at::kFloat, "params"); need(grads, at::kFloat, "grads"); need(momentum_buffer, at::kFloat, "momentum_buffer");
+    TORCH_CHECK(grads.numel() == params.numel() && momentum_buffer.numel() == params.numel());
+    TORCH_CHECK(groups.size() % 7 == 0, "groups: rows of (lr, momentum, dampening, weight_decay, nesterov, first_step, maximize)");
+    const std::vector<osi_opt_segment> seg = opt_segments(segments);
+    std::vector<osi_sgd_group> gs(groups.size() / 7);
+    for (size_t i = 0; i < gs.size(); ++i) {
+        const double* r = &groups[7 * i];
+        gs[i] = osi_sgd_group{r[0], r[1], r[2], r[3], r[4] != 0.0, r[5] != 0.0, r[6] != 0.0};
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(params.device());
+    ok(osi_sgd_step_groups(params.data_ptr<float>(), grads.data_ptr<float>(), momentum_buffer.data_ptr<float>(), (size_t)params.numel(),
+                           seg.data(), (int)seg.size(), gs.data(), (int)gs.size(), (float)grad_scale, stream_of(params)),
+       "osi_sgd_step_groups");
+}
+
 Tensor stage_canvas(const Tensor& canvas, const std::optional<Tensor>& crop_xy, const std::optional<Tensor>& flip, int64_t H, int64_t W) {
     need(canvas, at::kByte, "canvas");
     TORCH_CHECK(canvas.dim() == 4 && canvas.size(3) == 3, "canvas must be uint8 [B,Hc,Wc,3]");
@@ -275,6 +330,9 @@ TORCH_LIBRARY(osi, m) {
     m.def("adam_step(Tensor(a!) params, Tensor grads, Tensor(b!) exp_avg, Tensor(c!) exp_avg_sq, float lr, float beta1, float beta2, "
           "float eps, int step, float grad_scale) -> ()");
     m.def("sgd_step(Tensor(a!) params, Tensor grads, Tensor(b!) momentum_buffer, float lr, float momentum, bool first, float grad_scale) -> ()");
+    m.def("adam_step_groups(Tensor(a!) params, Tensor grads, Tensor(b!) exp_avg, Tensor(c!) exp_avg_sq, Tensor(d!)? max_exp_avg_sq, "
+          "int[] segments, float[] groups, float grad_scale) -> ()");
+    m.def("sgd_step_groups(Tensor(a!) params, Tensor grads, Tensor(b!) momentum_buffer, int[] segments, float[] groups, float grad_scale) -> ()");
     m.def("stage_canvas(Tensor canvas, Tensor? crop_xy, Tensor? flip, int H, int W) -> Tensor");   // crop corners are read-only (clamped in registers)
     m.def("softmax(Tensor logits) -> Tensor");
     m.def("confidence_accumulate(Tensor logits, Tensor target, float offset, int unknown_class, int last_valid_class, Tensor(a!) acc4) -> ()");
@@ -291,6 +349,8 @@ TORCH_LIBRARY_IMPL(osi, CUDA, m) {
     m.impl("loss_fwd_bwd", &loss_fwd_bwd);
     m.impl("adam_step", &adam_step);
     m.impl("sgd_step", &sgd_step);
+    m.impl("adam_step_groups", &adam_step_groups);
+    m.impl("sgd_step_groups", &sgd_step_groups);
     m.impl("stage_canvas", &stage_canvas);
     m.impl("softmax", &softmax);
     m.impl("confidence_accumulate", &confidence_accumulate);

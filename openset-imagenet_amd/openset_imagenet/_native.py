@@ -39,6 +39,25 @@ class BnEvalLayer(Structure):
                 ("shift", c_void_p), ("C", c_int)]
 
 
+class OptSegment(Structure):
+    """osi_opt_segment: the 16-byte units [begin4, end4) of the arena belong to kernel group `group`"""
+    _fields_ = [("begin4", ctypes.c_uint), ("end4", ctypes.c_uint), ("group", c_int)]
+
+
+class AdamGroup(Structure):
+    """osi_adam_group"""
+    _fields_ = [("lr", c_double), ("beta1", c_double), ("beta2", c_double), ("eps", c_double), ("weight_decay", c_double),
+                ("step", c_longlong), ("decoupled", c_int), ("amsgrad", c_int), ("maximize", c_int)]
+
+
+class SgdGroup(Structure):
+    """osi_sgd_group"""
+    _fields_ = [("lr", c_double), ("momentum", c_double), ("dampening", c_double), ("weight_decay", c_double),
+                ("nesterov", c_int), ("first_step", c_int), ("maximize", c_int)]
+
+
+OPT_MAX_SEGMENTS, OPT_MAX_GROUPS = 192, 16
+
 P = c_void_p
 _PD = POINTER(ConvDesc)
 
@@ -118,6 +137,8 @@ _SIGS = {
     "osi_oscr_f64": (c_int, [P, P, c_int, c_int, c_longlong, P, c_size_t, P, P, P, P, P]),
     "osi_adam_step": (c_int, [P, P, P, P, c_size_t, c_double, c_double, c_double, c_double, c_longlong, c_float, P]),
     "osi_sgd_step": (c_int, [P, P, P, c_size_t, c_float, c_float, c_int, c_float, P]),
+    "osi_adam_step_groups": (c_int, [P, P, P, P, P, c_size_t, POINTER(OptSegment), c_int, POINTER(AdamGroup), c_int, c_float, P]),
+    "osi_sgd_step_groups": (c_int, [P, P, P, c_size_t, POINTER(OptSegment), c_int, POINTER(SgdGroup), c_int, c_float, P]),
     "osi_fill_f32": (c_int, [P, c_size_t, c_float, P]),
     "osi_scale_f32": (c_int, [P, c_size_t, c_float, P]),
     "osi_grad_accumulate": (c_int, [P, P, c_size_t, P]),

@@ -238,9 +238,12 @@ class ResNet50(nn.Module):
         return list(self._stage_ranges)
 
     def bind_gradients(self):
-        """Point every parameter's .grad at its slice of the gradient arena."""
+        """Point every parameter's .grad at its slice of the gradient arena; a parameter that does not require grad keeps
+        .grad = None, as under autograd (the optimizers skip it)."""
         for (name, off, numel, shape), p in zip(self._pinfo, self._plist):
-            if p.grad is None or p.grad.data_ptr() != self._flat_grads.data_ptr() + 4 * off:
+            if not p.requires_grad:
+                p.grad = None
+            elif p.grad is None or p.grad.data_ptr() != self._flat_grads.data_ptr() + 4 * off:
                 p.grad = self._view(self._flat_grads, off, numel, shape)
 
     # ---- execution -------------------------------------------------------------------------------------------

@@ -90,10 +90,43 @@ def build_loss(cfg, n_classes, class_weights=None):
 
 
 def build_optimizer(cfg, model):
-    """Adam(lr) or SGD(lr, momentum=0.9) over the model's arena (train.py:356-359)."""
-    if cfg.opt.type == "sgd":
-        return _optim.SGD(_unwrap(model), lr=cfg.opt.lr, momentum=0.9)
-    return _optim.Adam(_unwrap(model), lr=cfg.opt.lr)
+    """Adam(lr) or SGD(lr, momentum=0.9) over the model's arena (train.py:356-359). Optional keys under `opt:` (this build's
+    addition; with all of them absent the optimizer is the reference's): type adamw, weight_decay, nesterov, amsgrad,
+    no_decay: norm_bias (BatchNorm weights / biases and linear biases in a weight_decay = 0 group, optim.split_decay) and
+    train_only: [name prefixes] (the optimizer is built over those parameters only; requires_grad is not changed)."""
+    opt = cfg.opt
+    get = lambda key: getattr(opt, key, None)
+    net = _unwrap(model)
+    kind = opt.type if opt.type in ("sgd", "adamw") else "adam"   # as in the reference, anything but sgd is Adam
+    extra = {}
+    if get("weight_decay") is not None:
+        extra["weight_decay"] = float(opt.weight_decay)
+    if get("amsgrad") is not None:
+        if kind == "sgd" and opt.amsgrad:
+            raise ValueError("opt.amsgrad belongs to adam / adamw, not to opt.type sgd")
+        if kind != "sgd":
+            extra["amsgrad"] = bool(opt.amsgrad)
+    if get("nesterov") is not None:
+        if kind != "sgd" and opt.nesterov:
+            raise ValueError(f"opt.nesterov belongs to sgd, not to opt.type {opt.type}")
+        if kind == "sgd":
+            extra["nesterov"] = bool(opt.nesterov)
+    params = net
+    prefixes = get("train_only")
+    if prefixes:
+        prefixes = [prefixes] if isinstance(prefixes, str) else list(prefixes)
+        params = [p for n, p in net.named_parameters() if any(n == q or n.startswith(q + ".") for q in prefixes)]
+        if not params:
+            raise ValueError(f"opt.train_only: no parameter name starts with any of {prefixes}")
+    if get("no_decay"):
+        chosen = None if params is net else {id(p) for p in params}
+        wd = extra.pop("weight_decay", 1e-2 if kind == "adamw" else 0.0)
+        params = [dict(g, params=[p for p in g["params"] if chosen is None or id(p) in chosen])
+                  for g in _optim.split_decay(net, wd, opt.no_decay)]
+        params = [g for g in params if g["params"]]
+    if kind == "sgd":
+        return _optim.SGD(params, lr=opt.lr, momentum=0.9, **extra)
+    return (_optim.AdamW if kind == "adamw" else _optim.Adam)(params, lr=opt.lr, **extra)
 
 
 def train(model, data_loader, optimizer, loss_fn, trackers, cfg, epsilon=None):
