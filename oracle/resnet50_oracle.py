@@ -71,15 +71,42 @@ def init_state(fc_layer_dim, out_features, logit_bias=False, dtype=torch.float32
     return ordered
 
 
-def randomize_bn(sd, generator=None):
+SIGNED_BETA_STD = 0.7
+
+
+def signed_bn_affine(gamma, beta):
+    """The "signed" BatchNorm state: channel c takes class c % 7 of
+        0     gamma as drawn (U[0.5, 1.5]), beta as drawn         control
+        1, 6  -gamma, beta as drawn                               negative scale
+        2     gamma 0, beta +0.7                                  constant positive activation: the ReLU gate open everywhere
+        3     gamma 0, beta 0                                     activation exactly 0: gate closed (0 > 0 is false)
+        4     gamma -0.05, beta +1                                negative scale, gate open for every element
+        5     gamma +0.05, beta -1                                gate closed for every element
+    so every f32x4 lane group and every 16-channel MFMA group mixes classes. Classes 4 / 5 saturate the gate with a small |gamma|
+    (|0.05 * xhat| < 1 for any normalised value below 20 sigma) without raising the tensor's maximum. Returns new tensors."""
+    cls = torch.arange(gamma.numel()) % 7
+    gamma, beta = gamma.clone(), beta.clone()
+    neg = (cls == 1) | (cls == 6)
+    gamma[neg] = -gamma[neg]
+    for k, (ga, be) in {2: (0.0, 0.7), 3: (0.0, 0.0), 4: (-0.05, 1.0), 5: (0.05, -1.0)}.items():
+        gamma[cls == k], beta[cls == k] = ga, be
+    return gamma, beta
+
+
+def randomize_bn(sd, generator=None, kind="positive"):
     """Replace the trivial BatchNorm initialisation (gamma 1, beta 0, running 0/1) by seeded random values so that parity
-    checks exercise the affine part and the eval-mode (running statistics) path. In place; returns sd."""
+    checks exercise the affine part and the eval-mode (running statistics) path. kind = "positive": gamma in [0.5, 1.5];
+    kind = "signed": the per-channel classes of signed_bn_affine (negative, zero and saturated scales) on every layer, running
+    statistics as for "positive". In place; returns sd."""
+    assert kind in ("positive", "signed"), kind
     for k in list(sd):
         if k.endswith("running_mean"):
             pre = k[:-len("running_mean")]
             c = sd[k].numel()
-            sd[pre + "weight"] = (0.5 + torch.rand(c, generator=generator)).to(sd[k].dtype)
-            sd[pre + "bias"] = (0.2 * torch.randn(c, generator=generator)).to(sd[k].dtype)
+            gamma, noise = 0.5 + torch.rand(c, generator=generator), torch.randn(c, generator=generator)
+            gamma, beta = (gamma, 0.2 * noise) if kind == "positive" else signed_bn_affine(gamma, SIGNED_BETA_STD * noise)
+            sd[pre + "weight"] = gamma.to(sd[k].dtype)
+            sd[pre + "bias"] = beta.to(sd[k].dtype)
             sd[pre + "running_mean"] = (0.1 * torch.randn(c, generator=generator)).to(sd[k].dtype)
             sd[pre + "running_var"] = (0.5 + torch.rand(c, generator=generator)).to(sd[k].dtype)
     return sd

@@ -58,6 +58,78 @@ def conv_wgrad(dy_nhwc, x_nhwc, k, stride, pad):
     return dw if stem else dw.view(Cout, k, k, Cin)
 
 
+def bn_classes(C):
+    """Class (c % 7) of every channel of the "signed" BatchNorm state, see bn_state()."""
+    return torch.arange(C) % 7
+
+
+def dead_channels(C):
+    """bool [C]: the channels a "signed" case makes identically zero before BatchNorm (c % 13 == 5): batch variance exactly 0."""
+    return torch.arange(C) % 13 == 5
+
+
+def bn_state(C, generator, kind="positive", beta_std=1.0):
+    """(gamma, beta), fp32 on the CPU, drawn from `generator`.
+    "positive": gamma = U[0, 1) + 0.5, beta = N(0, 1) * beta_std, the draws the GPU tests made before this helper existed (same
+    numbers from the same seeds).
+    "signed": the per-channel classes of oracle.resnet50_oracle.signed_bn_affine (control, negative, zero, saturated open, saturated
+    closed; beta of the drawn classes is N(0, 0.7^2)); the generator advances exactly as for "positive". Fails when C cannot hold all
+    seven classes and one dead channel (dead_channels), so that no case passes vacuously."""
+    from oracle import resnet50_oracle as R
+    assert kind in ("positive", "signed"), kind
+    dev = generator.device            # a test's generator may live on the GPU: drawn there, as that test always did, returned on the CPU
+    gamma, noise = (torch.rand(C, generator=generator, device=dev) + 0.5).cpu(), torch.randn(C, generator=generator, device=dev).cpu()
+    if kind == "positive":
+        return gamma, noise * beta_std
+    assert len(set(bn_classes(C).tolist())) == 7 and bool(dead_channels(C).any()), f"C = {C} cannot hold the seven classes + a dead channel"
+    return R.signed_bn_affine(gamma, noise * R.SIGNED_BETA_STD)
+
+
+def saturating(x):
+    """Where a test hands gamma / beta of the signed state to a loader as scale / shift: classes 4 and 5 (|scale| 0.05, |shift| 1) hold
+    the gate open / closed for EVERY element only while 0.05 |x| < 1. Returns x."""
+    assert 0.05 * float(x.abs().max()) < 1.0
+    return x
+
+
+def assert_signed_gates(gate, C, what=""):
+    """gate: bool [..., C] (ReLU decisions, mask bits, "maximum > 0" bits) of a signed state WITHOUT a shortcut addend, saturation
+    checked by the caller: classes 3 (activation exactly 0) and 5 all off, classes 2 and 4 all on."""
+    cls = bn_classes(C)
+    g = gate.reshape(-1, C).cpu()
+    assert not bool(g[:, (cls == 3) | (cls == 5)].any()), f"{what}: a gate bit is on in a class-3 / class-5 channel"
+    assert bool(g[:, (cls == 2) | (cls == 4)].all()), f"{what}: a gate bit is off in a class-2 / class-4 channel"
+
+
+NET_B, NET_HW, NET_C = 4, 64, 10      # geometry of the whole-network cases on the BatchNorm states below
+NET_SEED = {"signed": 41, "zero_init_residual": 43}
+
+
+def network_case(which):
+    """(state_dict, image, labels) of the whole-network BatchNorm-state cases (tests/test_gate_pinned_gpu.py; their CPU anchors in
+    tests/test_oracle.py run the same numbers).
+    "signed": every BatchNorm layer on the signed state, and the filters o % 13 == 5 of conv1 / conv2 of the first block of each stage
+    zeroed (pre-BN channel identically 0, batch variance exactly 0).
+    "zero_init_residual": the positive state with every bn3.weight = 0 (torchvision's zero_init_residual=True)."""
+    from oracle import resnet50_oracle as R
+    gen = torch.Generator().manual_seed(NET_SEED[which])
+    sd = R.init_state(NET_C, NET_C, False, generator=gen)
+    if which == "signed":
+        R.randomize_bn(sd, generator=gen, kind="signed")
+        for s in range(1, 5):
+            for conv in ("conv1", "conv2"):
+                w = sd[f"resnet_base.layer{s}.0.{conv}.weight"]
+                w[dead_channels(w.shape[0])] = 0
+    else:
+        R.randomize_bn(sd, generator=gen)
+        for k in sd:
+            if k.endswith("bn3.weight"):
+                sd[k] = torch.zeros_like(sd[k])
+    x = torch.rand(NET_B, 3, NET_HW, NET_HW, generator=gen)
+    y = torch.randint(-1, NET_C, (NET_B,), generator=gen)
+    return sd, x, y
+
+
 def hip_gates(model):
     """The ReLU / arg-max decisions of the model's latest forward, in the structure oracle.resnet50_oracle.forward(gates=...)
     takes: {"relu": [49 bool tensors, NCHW], "pool_idx": int64 [B,64,Hp,Wp]} (CPU tensors). Read through the debug entry points of

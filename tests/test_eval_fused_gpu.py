@@ -62,6 +62,28 @@ FORMS = [
 
 @pytest.mark.parametrize("B,H,Cin,Cout,k,stride,shortcut,relu,tail", FORMS)
 def test_conv_epilogue_equals_conv_then_bn_apply(cuda, B, H, Cin, Cout, k, stride, shortcut, relu, tail):
+    _epilogue_case(cuda, B, H, Cin, Cout, k, stride, shortcut, relu, tail, "positive")
+
+
+@pytest.mark.parametrize("relu", [True, False])
+@pytest.mark.parametrize("shortcut", [False, True])
+@pytest.mark.parametrize("B,H,Cin,Cout,k", [(5, 9, 64, 192, 1), (8, 28, 128, 128, 3)])      # the smallest 1x1 and 3x3 shapes of FORMS
+def test_conv_epilogue_signed_state(cuda, B, H, Cin, Cout, k, shortcut, relu):
+    """The same on negative / zero / saturated scales, with zeroed filters (output = [relu](shift [+ shortcut]) exactly)."""
+    _epilogue_case(cuda, B, H, Cin, Cout, k, 1, shortcut, relu, False, "signed")
+
+
+def _signed_epilogue_checks(T, out, conv64, sh, res, relu, Cout):
+    dead, cls = T.dead_channels(Cout), T.bn_classes(Cout)
+    want = sh[dead].expand(out.shape[0], -1) + (res[:, dead] if res is not None else 0)
+    assert torch.equal(out[:, dead], torch.relu(want) if relu else want), "zeroed filter: the output is shift (+ shortcut)"
+    if relu and res is None:
+        T.saturating(conv64)
+        T.assert_signed_gates(out > 0, Cout, "epilogue output")
+        assert float(out[:, (cls == 3) | (cls == 5)].abs().max()) == 0
+
+
+def _epilogue_case(cuda, B, H, Cin, Cout, k, stride, shortcut, relu, tail, kind):
     import osi_testlib as T
     from openset_imagenet import _native as N
     L = N.lib()
@@ -73,6 +95,9 @@ def test_conv_epilogue_equals_conv_then_bn_apply(cuda, B, H, Cin, Cout, k, strid
     w = torch.randn(Cout, k, k, Cin, device=cuda, generator=g) / math.sqrt(Cin * k * k)
     sc = torch.rand(Cout, device=cuda, generator=g) + 0.5
     sh = torch.randn(Cout, device=cuda, generator=g) * 0.3
+    if kind == "signed":
+        w[T.dead_channels(Cout)] = 0
+        sc, sh = (t.to(cuda) for t in T.bn_state(Cout, g, kind))
     res = torch.randn(M, Cout, device=cuda, generator=g) if shortcut else None
     nb = L.osi_conv_fwd_epilogue_workspace(ctypes.byref(d)) if tail else 0
     if tail:
@@ -99,6 +124,8 @@ def test_conv_epilogue_equals_conv_then_bn_apply(cuda, B, H, Cin, Cout, k, strid
     assert err <= bound, f"{err:.3e} > {bound:.3e}"
     if relu:
         assert float(out.min()) >= 0.0
+    if kind == "signed":
+        _signed_epilogue_checks(T, out, conv64, sh, res, relu, Cout)
 
 
 def test_conv_epilogue_argument_checks(cuda):
@@ -123,6 +150,15 @@ def test_conv_epilogue_argument_checks(cuda):
 @pytest.mark.parametrize("B,H,C,Cout", [(128, 56, 64, 64), (128, 28, 128, 128), (128, 14, 256, 256), (128, 7, 512, 512),      # the network's four
                                         (16, 14, 128, 64), (6, 7, 64, 128)])                                                   # stream-K pieces; tiles over the border
 def test_winograd_epilogue_equals_winograd_then_bn_apply(cuda, B, H, C, Cout):
+    _wino_epilogue_case(cuda, B, H, C, Cout, "positive")
+
+
+def test_winograd_epilogue_signed_state(cuda):
+    """The same on the signed scales with zeroed filters, at the smallest Winograd-eligible shape above."""
+    _wino_epilogue_case(cuda, 6, 7, 64, 128, "signed")
+
+
+def _wino_epilogue_case(cuda, B, H, C, Cout, kind):
     import osi_testlib as T
     from openset_imagenet import _native as N
     L = N.lib()
@@ -134,6 +170,9 @@ def test_winograd_epilogue_equals_winograd_then_bn_apply(cuda, B, H, C, Cout):
     w = torch.randn(Cout, 3, 3, C, device=cuda, generator=g) / math.sqrt(C * 9)
     sc = torch.rand(Cout, device=cuda, generator=g) + 0.5
     sh = torch.randn(Cout, device=cuda, generator=g) * 0.3
+    if kind == "signed":
+        w[T.dead_channels(Cout)] = 0
+        sc, sh = (t.to(cuda) for t in T.bn_state(Cout, g, kind))
     ub, sb = L.osi_conv_wino_weights_bytes(ctypes.byref(d)), L.osi_conv_wino_slab_bytes()
     u = torch.empty(ub, dtype=torch.uint8, device=cuda); slab = torch.empty(sb, dtype=torch.uint8, device=cuda)
     N.check(L.osi_conv_wino_transform_weights(ctypes.byref(d), N.ptr(w), 0, N.ptr(u), ub, T.S()))
@@ -147,6 +186,9 @@ def test_winograd_epilogue_equals_winograd_then_bn_apply(cuda, B, H, C, Cout):
         want = torch.full((M, Cout), float("nan"), device=cuda)
         N.check(L.osi_bn_apply(N.ptr(y), None, N.ptr(sc), N.ptr(sh), N.ptr(want), M, Cout, relu, T.S()))
         assert torch.equal(out, want), f"relu={relu}: max diff {float((out - want).abs().max()):.3e}"
+        if kind == "signed":
+            c64 = F.conv2d(T.nchw(_cpu64(x)), T.oihw(_cpu64(w)), None, 1, 1).permute(0, 2, 3, 1).reshape(M, Cout)
+            _signed_epilogue_checks(T, out, c64, sh, None, relu, Cout)
     conv64 = F.conv2d(T.nchw(_cpu64(x)), T.oihw(_cpu64(w)), None, 1, 1).permute(0, 2, 3, 1).reshape(M, Cout)
     ref = conv64 * _cpu64(sc) + _cpu64(sh)
     bound = _bound(C * 9, conv64) * float(sc.max()) + 4e-7 * float(ref.abs().max())

@@ -15,11 +15,19 @@ SHAPES = [(64, 64, 1, 1, 14, 3), (64, 128, 3, 1, 9, 3), (128, 64, 3, 2, 9, 2), (
           (128, 256, 1, 2, 8, 3)]
 
 
-def _case(cuda, Cin, Cout, k, stride, H, B):
+SIGNED_SHAPES = SHAPES[:3]       # the select-free 1x1 loader, the 3x3 row-window loader, stride 2
+
+
+def _case(cuda, Cin, Cout, k, stride, H, B, kind="positive"):
+    """kind = "signed": scale / shift = gamma / beta of the signed BatchNorm state (negative, zero, saturated), and the producer's
+    zero-variance channels identically 0."""
+    import osi_testlib as T
     g = torch.Generator().manual_seed(Cin * 7 + Cout + k + H)
-    x = (torch.randn(B, H, H, Cin, generator=g) * 1.5).to(cuda)
-    sc = (torch.rand(Cin, generator=g) + 0.5).to(cuda)
-    sh = (torch.randn(Cin, generator=g) * 0.7).to(cuda)
+    x = torch.randn(B, H, H, Cin, generator=g) * 1.5
+    if kind == "signed":
+        T.saturating(x)[..., T.dead_channels(Cin)] = 0
+    x = x.to(cuda)
+    sc, sh = (t.to(cuda) for t in T.bn_state(Cin, g, kind, beta_std=0.7))
     w = (torch.randn(Cout, k, k, Cin, generator=g) / (Cin * k * k) ** 0.5).to(cuda)
     act64 = torch.relu(x.double() * sc.double() + sh.double())          # [B,H,W,Cin]
     return x, sc, sh, w, act64
@@ -28,13 +36,22 @@ def _case(cuda, Cin, Cout, k, stride, H, B):
 @pytest.mark.parametrize("Cin,Cout,k,stride,H,B", SHAPES)
 @pytest.mark.parametrize("tile", [0, 5, 6])
 def test_conv_fwd_with_fused_input_activation(cuda, Cin, Cout, k, stride, H, B, tile):
-    import osi_testlib as T
-    from openset_imagenet import _native as N
     if tile == 6 and Cout % 128:
         pytest.skip("64x128 tile needs Cout % 128 == 0")
+    _fwd_act_case(cuda, Cin, Cout, k, stride, H, B, tile, "positive")
+
+
+@pytest.mark.parametrize("Cin,Cout,k,stride,H,B,tile", [s + (t,) for s in SIGNED_SHAPES for t in (0, 5, 6) if t != 6 or s[1] % 128 == 0])
+def test_conv_fwd_with_fused_input_activation_signed_state(cuda, Cin, Cout, k, stride, H, B, tile):
+    _fwd_act_case(cuda, Cin, Cout, k, stride, H, B, tile, "signed")
+
+
+def _fwd_act_case(cuda, Cin, Cout, k, stride, H, B, tile, kind):
+    import osi_testlib as T
+    from openset_imagenet import _native as N
     L = N.lib()
     pad = 1 if k == 3 else 0
-    x, sc, sh, w, act64 = _case(cuda, Cin, Cout, k, stride, H, B)
+    x, sc, sh, w, act64 = _case(cuda, Cin, Cout, k, stride, H, B, kind)
     d = N.ConvDesc.make(B, H, H, Cin, Cout, k, stride, pad)
     y = torch.full((B, d.Ho, d.Wo, Cout), float("nan"), device=cuda)
     pb = L.osi_conv_fwd_bnstats_workspace(ctypes.byref(d))
@@ -66,11 +83,21 @@ def test_conv_fwd_with_fused_input_activation(cuda, Cin, Cout, k, stride, H, B, 
 
 @pytest.mark.parametrize("Cin,Cout,k,stride,H,B", SHAPES + [(128, 128, 3, 1, 28, 8), (256, 256, 1, 1, 14, 16)])
 def test_conv_wgrad_with_fused_input_activation(cuda, Cin, Cout, k, stride, H, B):
+    _wgrad_act_case(cuda, Cin, Cout, k, stride, H, B, "positive")
+
+
+@pytest.mark.parametrize("Cin,Cout,k,stride,H,B", SIGNED_SHAPES)
+def test_conv_wgrad_with_fused_input_activation_signed_state(cuda, Cin, Cout, k, stride, H, B):
+    """... and the weight gradient towards an input channel whose activation is 0 everywhere (classes 3 and 5) is exactly 0."""
+    _wgrad_act_case(cuda, Cin, Cout, k, stride, H, B, "signed")
+
+
+def _wgrad_act_case(cuda, Cin, Cout, k, stride, H, B, kind):
     import osi_testlib as T
     from openset_imagenet import _native as N
     L = N.lib()
     pad = 1 if k == 3 else 0
-    x, sc, sh, w, act64 = _case(cuda, Cin, Cout, k, stride, H, B)
+    x, sc, sh, w, act64 = _case(cuda, Cin, Cout, k, stride, H, B, kind)
     d = N.ConvDesc.make(B, H, H, Cin, Cout, k, stride, pad)
     g = torch.Generator().manual_seed(5)
     dy = torch.randn(B, d.Ho, d.Wo, Cout, generator=g).to(cuda)
@@ -88,6 +115,10 @@ def test_conv_wgrad_with_fused_input_activation(cuda, Cin, Cout, k, stride, H, B
     assert torch.equal(dw, dw2)
     act32 = torch.relu(torch.addcmul(sh, x, sc)).contiguous()
     assert float((T.conv_wgrad(dy, act32, k, stride, pad) - dw).abs().max()) <= 2e-5 * float(ref.abs().max())
+    if kind == "signed":
+        cls = T.bn_classes(Cin)
+        assert float(act64[..., (cls == 3) | (cls == 5)].abs().max()) == 0 and float(act64[..., (cls == 2) | (cls == 4)].min()) > 0
+        assert float(dw[..., (cls == 3) | (cls == 5)].abs().max()) == 0
 
 
 class _Fusion(ctypes.Structure):
@@ -101,6 +132,17 @@ class _Fusion(ctypes.Structure):
 def test_dgrad_gate_from_pre_bn_tensor_equals_bitmask(cuda, Cin, Cout, k, stride, H, B):
     """The fused dgrad epilogue with the ReLU gate recomputed as y0 * scale0 + shift0 > 0 gives exactly the bits of the stored
     bitmask route (osi_bn_apply_relu_mask evaluates the same fma): masked gradient and BatchNorm partials identical."""
+    _dgrad_gate_case(cuda, Cin, Cout, k, stride, H, B, "positive")
+
+
+@pytest.mark.parametrize("Cin,Cout,k,stride,H,B", [(64, 64, 1, 1, 14, 3), (128, 64, 3, 1, 9, 3)])
+def test_dgrad_gate_from_pre_bn_tensor_equals_bitmask_signed_state(cuda, Cin, Cout, k, stride, H, B):
+    """The same on the signed BatchNorm state with zero-variance channels: still bit for bit, and the saturated classes' gates are
+    all on / all off."""
+    _dgrad_gate_case(cuda, Cin, Cout, k, stride, H, B, "signed")
+
+
+def _dgrad_gate_case(cuda, Cin, Cout, k, stride, H, B, kind):
     import osi_testlib as T
     from openset_imagenet import _native as N
     L = N.lib()
@@ -112,7 +154,9 @@ def test_dgrad_gate_from_pre_bn_tensor_equals_bitmask(cuda, Cin, Cout, k, stride
     w = (torch.randn(Cout, k, k, Cin, generator=g) / (Cout * k * k) ** 0.5).to(cuda)
     y0 = (torch.randn(M, Cin, generator=g) * 2 + 0.3).to(cuda)
     y0.view(-1)[::97] = 0.0                                               # exact zeros: gate must be off exactly where relu' is 0
-    ga, be = (torch.rand(Cin, generator=g) + 0.5).to(cuda), torch.randn(Cin, generator=g).to(cuda)
+    if kind == "signed":
+        y0[:, T.dead_channels(Cin)] = 0
+    ga, be = (t.to(cuda) for t in T.bn_state(Cin, g, kind))
     wsb = max(L.osi_bn_workspace(M, Cin), L.osi_bn_backward_workspace(M, Cin))
     ws = torch.empty(wsb, dtype=torch.uint8, device=cuda)
     st = [torch.empty(Cin, device=cuda) for _ in range(4)]                # mean, invstd, scale, shift
@@ -135,6 +179,10 @@ def test_dgrad_gate_from_pre_bn_tensor_equals_bitmask(cuda, Cin, Cout, k, stride
         return res
 
     gate = (out > 0).view(B, H, H, Cin)
+    if kind == "signed":
+        T.saturating((y0 - st[0]) * st[1])
+        T.assert_signed_gates(gate, Cin, "gate")
+        assert float(st[0][T.dead_channels(Cin)].abs().max()) == 0
     N.check(L.osi_set_tuning(b"dgrad_w3", 0))      # both routes on the same kernel form (same K order): bit for bit
     try:
         res = both_routes()
@@ -177,14 +225,26 @@ def test_conv1_recomputes_the_previous_block_output(cuda, Cin, Cout, H, B, tile)
     """osi_conv_fwd_act2: the A operand relu(x * scale + shift + res) — a whole identity-shortcut block output — recomputed in the
     loader gives exactly the bits of the plain convolution on the tensor osi_bn_apply_relu_mask materialises (same fma, add, max; same
     tile and K order), and its BatchNorm partials are those of the plain fused form."""
+    _act2_case(cuda, Cin, Cout, H, B, tile, "positive")
+
+
+def test_conv1_recomputes_the_previous_block_output_signed_state(cuda):
+    """The same, called directly at the smallest 1x1 shape, with the signed BatchNorm state as scale / shift and zero-variance channels."""
+    _act2_case(cuda, 64, 64, 14, 3, 0, "signed")
+
+
+def _act2_case(cuda, Cin, Cout, H, B, tile, kind):
     import osi_testlib as T
     from openset_imagenet import _native as N
     L = N.lib()
     g = torch.Generator().manual_seed(Cin + H)
     M = B * H * H
-    y3 = (torch.randn(B, H, H, Cin, generator=g) * 1.3).to(cuda)
+    y3 = torch.randn(B, H, H, Cin, generator=g) * 1.3
+    if kind == "signed":
+        T.saturating(y3)[..., T.dead_channels(Cin)] = 0
+    y3 = y3.to(cuda)
     res = torch.relu(torch.randn(B, H, H, Cin, generator=g)).to(cuda)
-    sc, sh = (torch.rand(Cin, generator=g) + 0.5).to(cuda), (torch.randn(Cin, generator=g) * 0.5).to(cuda)
+    sc, sh = (t.to(cuda) for t in T.bn_state(Cin, g, kind, beta_std=0.5))
     w = (torch.randn(Cout, 1, 1, Cin, generator=g) / Cin ** 0.5).to(cuda)
     d = N.ConvDesc.make(B, H, H, Cin, Cout, 1, 1, 0)
     out = torch.empty(M, Cin, device=cuda)

@@ -152,3 +152,106 @@ def test_gates_read_back_are_the_decisions_the_forward_took(cuda):
     # every gate has the oracle's shape
     for g, r in zip(gates["relu"], rec["relu"]):
         assert g.shape == r.shape
+
+
+# ---- the whole network on BatchNorm states training reaches and checkpoints carry: negative / zero / saturated gamma, zero-variance
+# channels, zero_init_residual. The bars are GRAD_TOL / LOGIT_TOL: the CPU anchors of these very cases (same numbers,
+# tests/test_oracle.py::test_gate_pinned_anchor_on_bn_states) put torch-CPU fp32 under pinned decisions at 3.6e-5 max ("signed") and
+# 3.6e-6 max ("zero_init_residual"), both below a third of 5e-4 — the headroom the bar has over its original anchor.
+def _train_step_under_the_hip_gates(cuda, which):
+    from openset_imagenet import ResNet50, EntropicOpensetLoss
+    from oracle import resnet50_oracle as R, losses_oracle as L
+    import osi_testlib as T
+    sd, x, y = T.network_case(which)
+    C = T.NET_C
+    model = ResNet50(C, C, False)
+    model.load_state_dict(sd)
+    model = model.to(cuda).train()
+    logits, _ = model(x.to(cuda))
+    j = EntropicOpensetLoss(C, 1.0)(logits, y.to(cuda))
+    j.backward()
+    torch.cuda.synchronize()
+    gates = T.hip_gates(model)
+    ref_fn = lambda lg, t, f: L.entropic_openset_loss(lg, t, 1.0)
+    sd64 = lambda: {k: (v.double() if v.is_floating_point() else v.clone()) for k, v in sd.items()}
+    free = {}
+    r_free = R.forward_backward(sd64(), x.double(), y, ref_fn, record_gates=free)
+    r_pin = R.forward_backward(sd64(), x.double(), y, ref_fn, gates=gates)
+    flips, pool_flips, total = R.gate_disagreements(gates, free)
+    print(f"{which}: {flips} of {total} ReLU decisions and {pool_flips} arg-max positions differ from the free fp64 run")
+    assert flips <= 2e-5 * total + 20 and pool_flips <= 2e-5 * gates["pool_idx"].numel() + 5
+    assert float((logits.detach().cpu().double() - r_pin[0]).abs().max()) <= LOGIT_TOL
+    assert float((logits.detach().cpu().double() - r_free[0]).abs().max()) <= LOGIT_TOL
+    assert abs(float(j) - float(r_pin[2])) <= 1e-5 * max(1.0, abs(float(r_pin[2])))
+    named = dict(model.named_parameters())
+    errs, zeros = {}, []
+    for k in R.param_keys(sd):
+        g, ref = named[k].grad.detach().cpu(), r_pin[3][k]
+        assert g.shape == ref.shape and torch.isfinite(g).all(), k
+        if float(ref.abs().max()) == 0:           # an identically zero gradient has no relative measure: it must be reproduced exactly
+            assert float(g.abs().max()) == 0, f"grad {k}: the fp64 oracle's gradient is identically 0, the GPU's is not"
+            zeros.append(k)
+        else:
+            errs[k] = _rel(g, ref)
+    worst = max(errs, key=errs.get)
+    print(f"{which}: gradient rel-L2 vs fp64 under the HIP gates: median {np.median(list(errs.values())):.2e} max {errs[worst]:.2e} ({worst}); "
+          f"{len(zeros)} identically zero tensors")
+    assert len(errs) + len(zeros) == 162
+    for k, e in errs.items():
+        assert e <= GRAD_TOL, f"grad {k}: rel-L2 {e:.2e} > {GRAD_TOL:.0e} under pinned gates"
+    assert np.median(list(errs.values())) <= 1.5e-4
+    return sd, gates, zeros
+
+
+def test_signed_network_gradients_under_the_hip_gates(cuda):
+    """(a) Every BatchNorm on the signed state + zeroed filters in conv1 / conv2 of the first block of each stage, training mode:
+    logits, loss, all 162 gradients, flip counts — the assertions of test_all_gradients_vs_fp64_oracle_under_the_hip_gates. And the
+    decisions the backward consumes show the saturated classes: bn1 / bn2 gates (no shortcut) of classes 3 and 5 all off, of 2 and 4
+    all on; the stem's "maximum > 0" gate likewise."""
+    import osi_testlib as T
+    sd, gates, zeros = _train_step_under_the_hip_gates(cuda, "signed")
+    assert not zeros
+    checked = 0
+    for i, g in enumerate(gates["relu"]):
+        if i % 3 != 0 or i == 0:                  # 0: stem (after the pool), then per block bn1, bn2, block output (has a shortcut)
+            T.assert_signed_gates(g.permute(0, 2, 3, 1), g.shape[1], f"gate {i}")
+            checked += 1
+    assert checked == 33
+
+
+def test_zero_init_residual_network_gradients_under_the_hip_gates(cuda):
+    """(b) Every bn3.weight = 0 (torchvision's zero_init_residual=True), everything else on the positive state: wherever the fp64
+    oracle's gradient is identically 0 — every conv3.weight, and conv1 / conv2 / bn1 / bn2 of every block — the GPU's is identically 0;
+    every other tensor goes by the relative-L2 bar."""
+    sd, _, zeros = _train_step_under_the_hip_gates(cuda, "zero_init_residual")
+    want = {k for k in sd if any(k.endswith(s) for s in ("conv1.weight", "conv2.weight", "conv3.weight", "bn1.weight", "bn1.bias",
+                                                          "bn2.weight", "bn2.bias")) and "layer" in k}
+    assert set(zeros) == want and len(want) == 16 * 7
+
+
+def test_signed_network_eval_forward(cuda):
+    """(c) model.eval() on the signed state with randomised running statistics: logits and features of the inference forward validate()
+    takes (BatchNorm in the convolutions' epilogues) and of the training topology on running statistics (executor option eval_fused = 0)
+    against the oracle's eval forward in fp64."""
+    from openset_imagenet import ResNet50, _native as N
+    from oracle import resnet50_oracle as R
+    import osi_testlib as T
+    sd, x, _ = T.network_case("signed")
+    model = ResNet50(T.NET_C, T.NET_C, False)
+    model.load_state_dict(sd)
+    model = model.to(cuda).eval()
+    xd = x.to(cuda)
+    with torch.no_grad():
+        rl, rf = R.forward({k: (v.double() if v.is_floating_point() else v.clone()) for k, v in sd.items()}, x.double(), training=False)
+    net = model._net(T.NET_B, T.NET_HW, T.NET_HW)
+    try:
+        for fused in (1, 0):
+            N.check(N.lib().osi_resnet50_set_option(net.h, b"eval_fused", fused))
+            with torch.no_grad():
+                lg, ft = model(xd)
+            torch.cuda.synchronize()
+            e_l, e_f = float((lg.cpu().double() - rl).abs().max()), float((ft.cpu().double() - rf).abs().max())
+            print(f"eval_fused {fused}: max|logit - oracle| {e_l:.2e} (|logit| <= {float(rl.abs().max()):.2f}), features {e_f:.2e}")
+            assert e_l <= LOGIT_TOL and e_f <= LOGIT_TOL
+    finally:
+        N.check(N.lib().osi_resnet50_set_option(net.h, b"eval_fused", 1))

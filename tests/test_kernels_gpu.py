@@ -112,15 +112,37 @@ def test_stem(cuda, B, H):
     _check_vs64(T.oihw(gk), dw32, dw64, "stem wgrad")
 
 
+def _fp32_ulps(a, b):
+    """distance of two fp32 tensors of one sign in units in the last place"""
+    return (a.cpu().contiguous().view(torch.int32).long() - b.cpu().contiguous().view(torch.int32).long()).abs()
+
+
+INVSTD_OF_ZERO_VARIANCE = 1.0 / torch.sqrt(torch.tensor(1e-5, dtype=torch.float32))     # 1 / sqrt(0 + eps) evaluated in fp32
+
+
 @pytest.mark.parametrize("B,C,H", [(4, 64, 14), (3, 256, 7), (2, 2048, 3), (5, 12, 6), (2, 64, 56)])
 @pytest.mark.parametrize("relu,res", [(True, False), (True, True), (False, False)])
 def test_batchnorm(cuda, B, C, H, relu, res):
+    _batchnorm_case(cuda, B, C, H, relu, res, "positive")
+
+
+@pytest.mark.parametrize("B,C,H", [(5, 12, 6), (3, 256, 7)])
+@pytest.mark.parametrize("relu,res", [(True, False), (True, True), (False, False)])
+def test_batchnorm_signed_state(cuda, B, C, H, relu, res):
+    """test_batchnorm (same reference, same bounds) on negative / zero / saturated scales and zero-variance channels, plus what follows
+    from the arithmetic exactly: see the end of _batchnorm_case."""
+    _batchnorm_case(cuda, B, C, H, relu, res, "signed")
+
+
+def _batchnorm_case(cuda, B, C, H, relu, res, kind):
     import osi_testlib as T
     from openset_imagenet import _native as N
     L = N.lib()
     g = torch.Generator().manual_seed(C + H)
     y = torch.randn(B, C, H, H, generator=g) * 2 + torch.randn(1, C, 1, 1, generator=g) * 5   # non-zero means
-    gamma, beta = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g)
+    gamma, beta = T.bn_state(C, g, kind)
+    if kind == "signed":
+        y[:, T.dead_channels(C)] = 0
     rm0, rv0 = torch.randn(C, generator=g), torch.rand(C, generator=g) + 0.5
     resid = torch.randn(B, C, H, H, generator=g) if res else None
     dout = torch.randn(B, C, H, H, generator=g)
@@ -168,6 +190,25 @@ def test_batchnorm(cuda, B, C, H, relu, res):
     N.check(L.osi_bn_backward(N.ptr(dog), N.ptr(out) if relu else None, N.ptr(yg), N.ptr(mean), N.ptr(invstd), N.ptr(ga), N.ptr(dog),
                               None, N.ptr(dg), N.ptr(db), M, C, N.ptr(ws), wsb, T.S()))
     assert torch.equal(dog, dy)
+    if kind != "signed":
+        return
+    # exact consequences of the signed state (NHWC tensors: channel = last dimension)
+    cls, dead = T.bn_classes(C), T.dead_channels(C)
+    assert torch.isfinite(dy).all() and torch.isfinite(dg).all() and torch.isfinite(db).all()
+    assert float(dy[..., gamma == 0].abs().max()) == 0, "gamma = 0: the input gradient is exactly 0"
+    assert float(mean[dead].abs().max()) == 0, "zero channel: mean exactly 0"
+    assert int(_fp32_ulps(invstd[dead], INVSTD_OF_ZERO_VARIANCE.expand(int(dead.sum()))).max()) <= 1, "zero channel: invstd = 1 / sqrt(eps)"
+    want = beta[dead].view(1, 1, 1, -1).expand(B, H, H, -1)
+    if res:
+        want = want + T.nhwc(resid)[..., dead]
+    assert torch.equal(out[..., dead].cpu(), torch.relu(want) if relu else want), "zero channel: the output is beta (+ shortcut)"
+    if relu and not res:
+        y64 = y.double()
+        T.saturating((y64 - y64.mean(dim=(0, 2, 3), keepdim=True)) / y64.std(dim=(0, 2, 3), unbiased=False, keepdim=True).clamp_min(1e-3))
+        T.assert_signed_gates(out > 0, C, "bn out")
+        shut = (cls == 3) | (cls == 5)
+        assert float(out[..., shut].abs().max()) == 0 and float(gm[..., shut].abs().max()) == 0
+        assert float(dg[shut].abs().max()) == 0 and float(db[shut].abs().max()) == 0
 
 
 def test_bn_eval_coeffs(cuda):
@@ -184,6 +225,40 @@ def test_bn_eval_coeffs(cuda):
     xg = T.nhwc(x).to(cuda)
     out = torch.empty_like(xg)
     N.check(N.lib().osi_bn_apply(N.ptr(xg), None, N.ptr(sc), N.ptr(sh), N.ptr(out), 50, C, 0, T.S()))
+    assert torch.allclose(T.nchw(out).cpu(), ref, atol=2e-6, rtol=1e-5)
+
+
+@pytest.mark.parametrize("C", [12, 256])
+def test_bn_eval_coeffs_signed_state(cuda, C):
+    """osi_bn_eval_coeffs and osi_bn_eval_coeffs_multi on signed gamma with running_var exactly 0 in the dead channels (scale =
+    gamma / sqrt(eps)): against fp64 (the relative 1e-6 of test_eval_coefficients_of_all_layers_in_one_launch), the applied output
+    against torch's eval-mode batch_norm (the bound of test_bn_eval_coeffs), one launch == per-layer launches bit for bit."""
+    from openset_imagenet import _native as N
+    import osi_testlib as T
+    L = N.lib()
+    g = torch.Generator().manual_seed(C)
+    rm, rv = torch.randn(C, generator=g), torch.rand(C, generator=g) + .1
+    ga, be = T.bn_state(C, g, "signed")
+    dead = T.dead_channels(C)
+    rv[dead] = 0
+    x = torch.randn(2, C, 5, 5, generator=g)
+    ref = F.batch_norm(x, rm, rv, ga, be, False, 0.1, 1e-5)
+    sc, sh, sc2, sh2 = (torch.full((C,), float("nan"), device=cuda) for _ in range(4))
+    rmg, rvg, gag, beg = rm.to(cuda), rv.to(cuda), ga.to(cuda), be.to(cuda)
+    N.check(L.osi_bn_eval_coeffs(N.ptr(rmg), N.ptr(rvg), N.ptr(gag), N.ptr(beg), 1e-5, C, N.ptr(sc), N.ptr(sh), T.S()))
+    layers = (N.BnEvalLayer * 1)()
+    layers[0] = N.BnEvalLayer(rmg.data_ptr(), rvg.data_ptr(), gag.data_ptr(), beg.data_ptr(), sc2.data_ptr(), sh2.data_ptr(), C)
+    N.check(L.osi_bn_eval_coeffs_multi(layers, 1, 1e-5, T.S()), "osi_bn_eval_coeffs_multi")
+    assert torch.equal(sc, sc2) and torch.equal(sh, sh2)
+    want = ga.double() / torch.sqrt(rv.double() + 1e-5)
+    assert bool(((sc.cpu().double() - want).abs() <= 1e-6 * want.abs()).all())
+    assert float(sc[ga == 0].abs().max()) == 0 and torch.equal(sh[ga == 0].cpu(), be[ga == 0])
+    live = dead & (ga != 0)
+    # 1 ulp of 1 / sqrt(eps), then one rounding of the product
+    assert int(_fp32_ulps(sc[live], ga[live] * INVSTD_OF_ZERO_VARIANCE).max()) <= 2
+    xg = T.nhwc(x).to(cuda)
+    out = torch.empty_like(xg)
+    N.check(L.osi_bn_apply(N.ptr(xg), None, N.ptr(sc), N.ptr(sh), N.ptr(out), 50, C, 0, T.S()))
     assert torch.allclose(T.nchw(out).cpu(), ref, atol=2e-6, rtol=1e-5)
 
 
@@ -345,14 +420,29 @@ def test_adam_sgd_vs_torch(cuda, n):
 @pytest.mark.parametrize("B,C,H,res", [(3, 64, 14, False), (2, 256, 7, True), (5, 12, 6, True), (2, 2048, 3, False)])
 def test_batchnorm_relu_bitmask_forms(cuda, B, C, H, res):
     """The bitmask forms (forward writes 1 bit/element, backward consumes it) give the same bits as the activation-mask forms."""
+    _bitmask_forms_case(cuda, B, C, H, res, "positive")
+
+
+@pytest.mark.parametrize("B,C,H,res", [(5, 12, 6, True), (2, 256, 7, True), (5, 12, 6, False)])
+def test_batchnorm_relu_bitmask_forms_signed_state(cuda, B, C, H, res):
+    """The same on negative / zero / saturated scales and zero-variance channels; with a shortcut also osi_bn_apply_relu_mask2 (the
+    shortcut's own BatchNorm, a second signed draw, applied on the fly) against the materialised shortcut, bit for bit."""
+    _bitmask_forms_case(cuda, B, C, H, res, "signed")
+
+
+def _bitmask_forms_case(cuda, B, C, H, res, kind):
     import osi_testlib as T
     from openset_imagenet import _native as N
     L = N.lib()
     g = torch.Generator().manual_seed(C * 3 + H)
     M = B * H * H
-    y = (torch.randn(M, C, generator=g)).to(cuda)
+    y = torch.randn(M, C, generator=g)
+    if kind == "signed":
+        y[:, T.dead_channels(C)] = 0
+    y = y.to(cuda)
     resid = torch.randn(M, C, generator=g).to(cuda) if res else None
-    ga, be = (torch.rand(C, generator=g) + 0.5).to(cuda), torch.randn(C, generator=g).to(cuda)
+    gamma, beta = T.bn_state(C, g, kind)
+    ga, be = gamma.to(cuda), beta.to(cuda)
     dout = torch.randn(M, C, generator=g).to(cuda)
     mean, invstd, scale, shift = (torch.empty(C, device=cuda) for _ in range(4))
     wsb = max(L.osi_bn_workspace(M, C), L.osi_bn_backward_workspace(M, C))
@@ -386,6 +476,36 @@ def test_batchnorm_relu_bitmask_forms(cuda, B, C, H, res):
         store += [dy, gm, dg, db]
     for a, b in zip(res_a, res_b):
         assert torch.equal(a, b)
+    if kind != "signed":
+        return
+    cls, dead = T.bn_classes(C), T.dead_channels(C)
+    assert float(mean[dead].abs().max()) == 0
+    assert int(_fp32_ulps(invstd[dead], INVSTD_OF_ZERO_VARIANCE.expand(int(dead.sum()))).max()) <= 1
+    for dy, gm, dg, db in (res_a, res_b):
+        assert torch.isfinite(dy).all() and torch.isfinite(dg).all() and torch.isfinite(db).all()
+        assert float(dy[:, gamma == 0].abs().max()) == 0, "gamma = 0: the input gradient is exactly 0"
+    want = be[dead].expand(M, -1) + (resid[:, dead] if res else 0)
+    assert torch.equal(out2[:, dead], torch.relu(want)), "zero channel: the output is relu(beta (+ shortcut))"
+    if not res:
+        T.saturating((y - mean) * invstd)
+        T.assert_signed_gates(torch.from_numpy(bits).view(M, C), C, "mask bits")
+        shut = (cls == 3) | (cls == 5)
+        for dy, gm, dg, db in (res_a, res_b):
+            assert float(out2[:, shut].abs().max()) == 0 and float(gm[:, shut].abs().max()) == 0
+            assert float(dg[shut].abs().max()) == 0 and float(db[shut].abs().max()) == 0
+        return
+    # the shortcut's own BatchNorm on the fly, its scale / shift a second signed draw
+    rsc, rsh = (t.to(cuda) for t in T.bn_state(C, g, "signed"))
+    xd = torch.empty(M, C, device=cuda)
+    N.check(L.osi_bn_apply(N.ptr(resid), None, N.ptr(rsc), N.ptr(rsh), N.ptr(xd), M, C, 0, T.S()))
+    o1, m1 = torch.empty(M, C, device=cuda), torch.zeros(mb, dtype=torch.uint8, device=cuda)
+    o2, m2 = torch.empty(M, C, device=cuda), torch.zeros(mb, dtype=torch.uint8, device=cuda)
+    N.check(L.osi_bn_apply_relu_mask(N.ptr(y), N.ptr(xd), N.ptr(scale), N.ptr(shift), N.ptr(o1), N.ptr(m1), M, C, T.S()))
+    N.check(L.osi_bn_apply_relu_mask2(N.ptr(y), N.ptr(scale), N.ptr(shift), N.ptr(resid), N.ptr(rsc), N.ptr(rsh), N.ptr(o2), N.ptr(m2), M, C, T.S()))
+    assert torch.equal(o1, o2) and torch.equal(m1, m2)
+    ref = torch.relu(y.double() * scale.double() + shift.double() + resid.double() * rsc.double() + rsh.double())
+    assert float((o2.double() - ref).abs().max()) <= 1e-5       # the bound of test_block_output_with_fused_shortcut_batchnorm
+    assert float(o2[:, cls == 3].abs().max()) == 0              # class 3 in both draws: relu(0 + 0)
 
 
 @pytest.mark.parametrize("Cin,Cout,k,stride,H,B", [(64, 64, 1, 1, 14, 3), (128, 128, 3, 2, 9, 3), (256, 512, 1, 1, 7, 5), (64, 256, 3, 1, 12, 2),
@@ -394,6 +514,17 @@ def test_batchnorm_relu_bitmask_forms(cuda, B, C, H, res):
 def test_conv_epilogue_batchnorm_statistics(cuda, Cin, Cout, k, stride, H, B):
     """BN statistics emitted by the conv-forward epilogue + osi_bn_finalize_stats == statistics of the conv output (fp64),
     for every tile shape (ragged last row tile included), and the conv output itself is unchanged."""
+    _conv_bnstats_case(cuda, Cin, Cout, k, stride, H, B, "positive")
+
+
+@pytest.mark.parametrize("Cin,Cout,k,stride,H,B", [(64, 64, 1, 1, 14, 3), (64, 256, 3, 1, 12, 2)])
+def test_conv_epilogue_batchnorm_statistics_signed_state(cuda, Cin, Cout, k, stride, H, B):
+    """The same with zeroed filters (the kernel itself produces channels of variance exactly 0) and signed gamma: in those channels
+    mean = 0, invstd = 1 / sqrt(eps), shift = beta exactly, in every tile and finalisation form."""
+    _conv_bnstats_case(cuda, Cin, Cout, k, stride, H, B, "signed")
+
+
+def _conv_bnstats_case(cuda, Cin, Cout, k, stride, H, B, kind):
     import osi_testlib as T
     from openset_imagenet import _native as N
     L = N.lib()
@@ -401,12 +532,16 @@ def test_conv_epilogue_batchnorm_statistics(cuda, Cin, Cout, k, stride, H, B):
     g = torch.Generator().manual_seed(Cin + Cout + H)
     x = torch.randn(B, Cin, H, H, generator=g) + 0.3
     w = torch.randn(Cout, Cin, k, k, generator=g) / (Cin * k * k) ** 0.5
+    dead = T.dead_channels(Cout)
+    if kind == "signed":
+        w[dead] = 0
     y64 = F.conv2d(x.double(), w.double(), None, stride, pad)
     mean64 = y64.mean(dim=(0, 2, 3)); var64 = y64.var(dim=(0, 2, 3), unbiased=False)
     xg, wg = T.nhwc(x).to(cuda), T.krsc(w).to(cuda)
     d = N.ConvDesc.make(B, H, H, Cin, Cout, k, stride, pad)
     M = B * d.Ho * d.Wo
-    ga, be = (torch.rand(Cout, generator=g) + 0.5).to(cuda), torch.randn(Cout, generator=g).to(cuda)
+    gamma, beta = T.bn_state(Cout, g, kind)
+    ga, be = gamma.to(cuda), beta.to(cuda)
     nb = L.osi_conv_fwd_bnstats_workspace(ctypes.byref(d))
     for tile in [0, 4, 5, 2] + ([1, 3, 6] if Cout % 128 == 0 else []):
         ps = torch.full((nb // 4,), float("nan"), device=cuda)
@@ -443,6 +578,11 @@ def test_conv_epilogue_batchnorm_statistics(cuda, Cin, Cout, k, stride, H, B):
             assert float(((invstd.cpu().double() - inv64) / inv64).abs().max()) <= 2e-5, f"{form} invstd"
             assert torch.allclose(rv.cpu().double(), 0.9 + 0.1 * var64 * M / (M - 1), rtol=2e-5), form
             assert torch.allclose(scale, ga * invstd) and torch.allclose(shift, be - mean * scale, atol=1e-6), form
+            if kind == "signed":
+                assert float(y[..., dead].abs().max()) == 0 and float(mean[dead].abs().max()) == 0, form
+                assert int(_fp32_ulps(invstd[dead], INVSTD_OF_ZERO_VARIANCE.expand(int(dead.sum()))).max()) <= 1, form
+                assert torch.equal(shift[dead], be[dead]) and float(scale[gamma == 0].abs().max()) == 0, form
+                assert torch.isfinite(scale).all() and torch.isfinite(shift).all() and torch.isfinite(rv).all(), form
 
 
 class _Fusion(ctypes.Structure):
@@ -520,6 +660,15 @@ def test_sparse_shortcut_gradient_and_even_pixel_addend(cuda, H, B, two, tail):
 def test_dgrad_fused_epilogue_vs_unfused(cuda, Cin, Cout, k, stride, H, B, two):
     """dgrad with the fused epilogue (addend + ReLU bitmask + BatchNorm reductions) followed by osi_bn_backward_fused equals
     plain dgrad + osi_bn_backward_relu_mask on the same data: masked gradient bit for bit, BN outputs to fp32 summation noise."""
+    _dgrad_fused_case(cuda, Cin, Cout, k, stride, H, B, two, "positive")
+
+
+def test_dgrad_fused_epilogue_vs_unfused_signed_state(cuda):
+    """The same on the signed BatchNorm state with zero-variance channels in the previous layer's pre-BN tensor."""
+    _dgrad_fused_case(cuda, 64, 64, 1, 1, 14, 3, False, "signed")
+
+
+def _dgrad_fused_case(cuda, Cin, Cout, k, stride, H, B, two, kind):
     import osi_testlib as T
     from openset_imagenet import _native as N
     L = N.lib()
@@ -532,8 +681,13 @@ def test_dgrad_fused_epilogue_vs_unfused(cuda, Cin, Cout, k, stride, H, B, two):
     addend = torch.randn(B, H, H, Cin, generator=g).to(cuda)
     # the "previous layer": y0 (and y1) pre-BN tensors, their batch statistics, the ReLU bitmask of their BN output
     ys = [(torch.randn(M, Cin, generator=g) * 2 + 1).to(cuda) for _ in range(2 if two else 1)]
-    ga = [(torch.rand(Cin, generator=g) + 0.5).to(cuda) for _ in ys]
-    be = [torch.randn(Cin, generator=g).to(cuda) for _ in ys]
+    if kind == "positive":
+        ga = [(torch.rand(Cin, generator=g) + 0.5).to(cuda) for _ in ys]
+        be = [torch.randn(Cin, generator=g).to(cuda) for _ in ys]
+    else:
+        for yv in ys:
+            yv[:, T.dead_channels(Cin)] = 0
+        ga, be = (list(t) for t in zip(*[[v.to(cuda) for v in T.bn_state(Cin, g, kind)] for _ in ys]))
     wsb = max(L.osi_bn_workspace(M, Cin), L.osi_bn_backward_workspace(M, Cin))
     ws = torch.empty(wsb, dtype=torch.uint8, device=cuda)
     stats = []
@@ -588,6 +742,17 @@ def test_dgrad_fused_epilogue_vs_unfused(cuda, Cin, Cout, k, stride, H, B, two):
             assert float((dyo - rdy).abs().max()) <= 2e-5 * scale, f"dy consumer {j} wide_p {wide_p}"
             assert float((dg - rdg).abs().max()) <= 2e-5 * (float(rdg.abs().max()) + 1e-30), f"dgamma consumer {j} wide_p {wide_p}"
             assert float((db - rdb).abs().max()) <= 2e-5 * (float(rdb.abs().max()) + 1e-30), f"dbeta consumer {j} wide_p {wide_p}"
+            if kind == "signed":
+                assert torch.isfinite(dyo).all() and torch.isfinite(dg).all() and torch.isfinite(db).all()
+                assert float(dyo[:, gv == 0].abs().max()) == 0 and float(rdy[:, gv == 0].abs().max()) == 0, "gamma = 0: dy exactly 0"
+                if j == 0:       # consumer 0's BatchNorm made the mask: no shortcut, so the saturated classes hold for every element
+                    cls = T.bn_classes(Cin)
+                    shut = ((cls == 3) | (cls == 5)).to(cuda)
+                    T.saturating((yv - st[0]) * st[1])
+                    T.assert_signed_gates(out > 0, Cin, "previous layer's activation")
+                    assert float(gbuf.view(M, Cin)[:, shut].abs().max()) == 0
+                    assert float(dg[shut].abs().max()) == 0 and float(db[shut].abs().max()) == 0
+                    assert float(st[0][T.dead_channels(Cin)].abs().max()) == 0
 
 
 @pytest.mark.parametrize("P,C", [(392, 256), (1568, 128), (6272, 64), (98, 512)])

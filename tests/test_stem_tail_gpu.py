@@ -9,6 +9,24 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("B,H,W,C", [(3, 16, 16, 64), (2, 17, 23, 64), (4, 9, 9, 8), (1, 112, 112, 64)])
 def test_bn_relu_maxpool_fused_equals_composition(cuda, B, H, W, C):
+    _fused_tail_case(cuda, B, H, W, C, "positive")
+
+
+def test_bn_relu_maxpool_fused_equals_composition_signed_state(cuda):
+    """The same bits on negative / zero / saturated scales (a negative scale turns the window's maximum into the raw tensor's minimum)
+    and zero-variance channels; the "maximum > 0" bit of the saturated classes is off / on in every index byte."""
+    _fused_tail_case(cuda, 3, 16, 16, 64, "signed")
+
+
+def _signed_stem_bits(T, bit, pooled, C):
+    """bit: bool [..., C], the "maximum > 0" bit of every arg-max byte; pooled: the pooled activation (or None)"""
+    cls = T.bn_classes(C)
+    T.assert_signed_gates(bit, C, "maximum > 0 bit")
+    if pooled is not None:
+        assert float(pooled[..., (cls == 3) | (cls == 5)].abs().max()) == 0 and float(pooled[..., (cls == 2) | (cls == 4)].min()) > 0
+
+
+def _fused_tail_case(cuda, B, H, W, C, kind):
     import osi_testlib as T
     from openset_imagenet import _native as N
     L = N.lib()
@@ -16,7 +34,9 @@ def test_bn_relu_maxpool_fused_equals_composition(cuda, B, H, W, C):
     M = B * H * W
     y = (torch.randn(B, H, W, C, generator=g) * 2 + 0.3).to(cuda)
     y[0, :4, :4] = -5.0                       # a window whose maximum is not positive: the ReLU gate must block its gradient
-    gamma, beta = (torch.rand(C, generator=g) + 0.5).to(cuda), torch.randn(C, generator=g).to(cuda)
+    if kind == "signed":
+        y[..., T.dead_channels(C)] = 0
+    gamma, beta = (t.to(cuda) for t in T.bn_state(C, g, kind))
     wsb = max(L.osi_bn_workspace(M, C), L.osi_bn_backward_workspace(M, C))
     ws = torch.empty(wsb, dtype=torch.uint8, device=cuda)
     mean, invstd, scale, shift = (torch.empty(C, device=cuda) for _ in range(4))
@@ -50,6 +70,14 @@ def test_bn_relu_maxpool_fused_equals_composition(cuda, B, H, W, C):
                                       N.ptr(db), B, H, W, C, N.ptr(ws), wsb, T.S()))
     assert torch.equal(db, db_ref) and torch.equal(dg, dg_ref)
     assert torch.equal(dy, dy_ref)
+    if kind == "signed":
+        cls, dead = T.bn_classes(C), T.dead_channels(C)
+        T.saturating((y - mean) * invstd)
+        _signed_stem_bits(T, (idx >> 7).bool().view(B, Ho, Wo, C), p, C)
+        assert float(mean[dead].abs().max()) == 0 and torch.equal(p[..., dead], torch.relu(beta[dead]).expand(B, Ho, Wo, -1))
+        shut = (cls == 3) | (cls == 5)
+        assert torch.isfinite(dy).all() and torch.isfinite(dg).all() and torch.isfinite(db).all()
+        assert float(dg[shut].abs().max()) == 0 and float(db[shut].abs().max()) == 0 and float(dy[..., gamma == 0].abs().max()) == 0
 
 
 @pytest.mark.parametrize("B,H,W", [(2, 64, 64), (3, 96, 128), (2, 224, 224), (5, 32, 96)])
@@ -153,6 +181,15 @@ def test_stem_weight_gradient_with_fused_tail(cuda, B, H, W):
     (osi_stem_wgrad_fused) against (a) the fp64 evaluation of the same mathematics on the SAME decisions (max-pool scatter through
     the stored arg-max bytes, BatchNorm backward, conv2d_weight), and (b) the route it replaces (osi_bn_relu_maxpool_bwd writing the
     112x112x64 gradient + osi_stem_wgrad_direct reading it back)."""
+    _stem_wgrad_fused_case(cuda, B, H, W, "positive")
+
+
+def test_stem_weight_gradient_with_fused_tail_signed_state(cuda):
+    """The same on the signed bn1 state, with zeroed conv1 filters (zero-variance channels produced by the convolution itself)."""
+    _stem_wgrad_fused_case(cuda, 2, 64, 64, "signed")
+
+
+def _stem_wgrad_fused_case(cuda, B, H, W, kind):
     import ctypes
     import torch.nn.functional as F
     import osi_testlib as T
@@ -161,6 +198,8 @@ def test_stem_weight_gradient_with_fused_tail(cuda, B, H, W):
     g = torch.Generator().manual_seed(31 * B + H)
     x = (torch.rand(B, 3, H, W, generator=g) * 0.4 + torch.tensor([0.1, 0.3, 0.6]).view(1, 3, 1, 1))
     w = torch.randn(64, 3, 7, 7, generator=g) * 0.05
+    if kind == "signed":
+        w[T.dead_channels(64)] = 0
     d = N.ConvDesc.make(B, H, W, 4, 64, 7, 2, 3)
     Ho, Wo = d.Ho, d.Wo
     Hp, Wp = (Ho + 2 - 3) // 2 + 1, (Wo + 2 - 3) // 2 + 1
@@ -168,7 +207,7 @@ def test_stem_weight_gradient_with_fused_tail(cuda, B, H, W):
     x4 = torch.zeros(B, H, W, 4, device=cuda)
     x4[..., :3] = x.permute(0, 2, 3, 1).to(cuda)
     y = T.nhwc(F.conv2d(x, w, None, 2, 3)).to(cuda).contiguous()                      # [B,Ho,Wo,64]
-    gamma, beta = (torch.rand(64, generator=g) + 0.5).to(cuda), (torch.randn(64, generator=g) * 0.3).to(cuda)
+    gamma, beta = (t.to(cuda) for t in T.bn_state(64, g, kind, beta_std=0.3))
     yv = y.view(M, 64)
     mean = yv.mean(0)
     invstd = 1 / torch.sqrt(yv.var(0, unbiased=False) + 1e-5)
@@ -206,6 +245,10 @@ def test_stem_weight_gradient_with_fused_tail(cuda, B, H, W):
     # ---- fp64 evaluation of the same mathematics on the same decisions
     ib = idx.view(B, Hp, Wp, 16).cpu().numpy().view("uint8").reshape(B, Hp, Wp, 64)        # one byte per channel
     ib = torch.from_numpy(ib.astype("int64"))
+    if kind == "signed":
+        T.saturating((y - mean) * invstd)
+        _signed_stem_bits(T, ib >= 128, pooled, 64)
+        assert float(mean[T.dead_channels(64)].abs().max()) == 0 and torch.isfinite(fused[0]).all() and torch.isfinite(dg).all()
     gp = gpool.cpu().double()
     g64 = torch.zeros(B, Ho, Wo, 64, dtype=torch.float64)
     gate = (ib >= 128)
@@ -236,6 +279,15 @@ def test_pool_mode_dgrad_emits_the_stem_batchnorm_reductions(cuda, B, Hs, Ws, Co
     """Pool mode of osi_conv_dgrad_fused (the input gradient of layer1.0.conv1, whose input is the stem's max-pooled activation): dx is
     the plain input gradient + addend, and the per-row-tile partials finished by osi_bn_backward_reduce are bn1's dgamma / dbeta —
     equal (to fp32 summation noise) to the reductions osi_bn_relu_maxpool_bwd computes by scanning the 112 x 112 tensor."""
+    _pool_mode_case(cuda, B, Hs, Ws, Cout, "positive")
+
+
+def test_pool_mode_dgrad_emits_the_stem_batchnorm_reductions_signed_state(cuda):
+    """The same on the signed bn1 state with zero-variance channels: the always-closed channels' dgamma / dbeta are exactly 0."""
+    _pool_mode_case(cuda, 2, 16, 16, 64, "signed")
+
+
+def _pool_mode_case(cuda, B, Hs, Ws, Cout, kind):
     import ctypes
     import osi_testlib as T
     from openset_imagenet import _native as N
@@ -251,7 +303,9 @@ def test_pool_mode_dgrad_emits_the_stem_batchnorm_reductions(cuda, B, Hs, Ws, Co
     Hp, Wp = (Hs + 2 - 3) // 2 + 1, (Ws + 2 - 3) // 2 + 1
     Ms = B * Hs * Ws
     y = (torch.randn(B, Hs, Ws, C, generator=g) * 1.5 + 0.2).to(cuda)
-    gamma, beta = (torch.rand(C, generator=g) + 0.5).to(cuda), (torch.randn(C, generator=g) * 0.3).to(cuda)
+    if kind == "signed":
+        y[..., T.dead_channels(C)] = 0
+    gamma, beta = (t.to(cuda) for t in T.bn_state(C, g, kind, beta_std=0.3))
     mean = y.view(Ms, C).mean(0)
     invstd = 1 / torch.sqrt(y.view(Ms, C).var(0, unbiased=False) + 1e-5)
     scale, shift = gamma * invstd, beta - mean * gamma * invstd
@@ -292,3 +346,9 @@ def test_pool_mode_dgrad_emits_the_stem_batchnorm_reductions(cuda, B, Hs, Ws, Co
     sc = float(dg64.abs().max()) + float(db64.abs().max())
     assert float((dg.cpu().double() - dg64).abs().max()) <= 2e-5 * sc and float((db.cpu().double() - db64).abs().max()) <= 2e-5 * sc
     assert float((dg0.cpu().double() - dg64).abs().max()) <= 2e-5 * sc and float((db0.cpu().double() - db64).abs().max()) <= 2e-5 * sc
+    if kind == "signed":
+        T.saturating((y - mean) * invstd)
+        _signed_stem_bits(T, gate, pooled, C)
+        shut = (T.bn_classes(C) == 3) | (T.bn_classes(C) == 5)
+        for t in (dg, db, dg0, db0):
+            assert torch.isfinite(t).all() and float(t[shut].abs().max()) == 0

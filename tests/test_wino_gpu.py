@@ -38,7 +38,14 @@ def _both_directions_cut():
 NETWORK = [(64, 56), (128, 28), (256, 14), (512, 7)]
 
 
-def _fwd(cuda, B, H, W, Cin, Cout, act, seed):
+def _signed_input(T, x, Cin, g, cuda):
+    """scale / shift of the fused input activation = gamma / beta of the signed BatchNorm state; the producer's zero-variance channels
+    of x identically 0 (in place)"""
+    T.saturating(x)[..., T.dead_channels(Cin)] = 0
+    return (t.to(cuda) for t in T.bn_state(Cin, g, "signed"))
+
+
+def _fwd(cuda, B, H, W, Cin, Cout, act, seed, kind="positive"):
     import osi_testlib as T
     from openset_imagenet import _native as N
     L = N.lib()
@@ -51,7 +58,9 @@ def _fwd(cuda, B, H, W, Cin, Cout, act, seed):
     sc = sh = None
     if act:
         sc, sh = torch.rand(Cin, device=cuda, generator=g) + 0.5, torch.randn(Cin, device=cuda, generator=g) * 0.5
-        a64 = torch.relu(a64 * _cpu64(sc) + _cpu64(sh))
+        if kind == "signed":
+            sc, sh = _signed_input(T, x, Cin, g, cuda)
+        a64 = torch.relu(_cpu64(x) * _cpu64(sc) + _cpu64(sh))
     ref = F.conv2d(T.nchw(a64), T.oihw(_cpu64(w)), None, 1, 1).permute(0, 2, 3, 1).contiguous()
     wb = L.osi_conv_wino_workspace(ctypes.byref(d))
     assert wb >= 16 * Cin * Cout * 4
@@ -92,7 +101,7 @@ def test_forward_ragged_and_odd_geometries(cuda, B, H, W, Cin, Cout, act):
     _fwd(cuda, B, H, W, Cin, Cout, act, 1)
 
 
-def _dgrad(cuda, B, H, W, Cin, Cout, seed, partials=True):
+def _dgrad(cuda, B, H, W, Cin, Cout, seed, partials=True, kind="positive"):
     import osi_testlib as T
     from openset_imagenet import _native as N
     L = N.lib()
@@ -109,6 +118,14 @@ def _dgrad(cuda, B, H, W, Cin, Cout, seed, partials=True):
     pre = torch.randn(M, Cin, device=cuda, generator=g)
     pre = torch.where(pre >= 0, pre.clamp_min(1e-3), pre.clamp_max(-1e-3))
     y0 = ((pre.double() - sh.double()) / sc.double()).float()
+    if kind == "signed":   # a zero scale has no inverse: y0 is drawn, and moved where its pre-activation would sit within 1e-3 of zero
+        y0 = torch.randn(M, Cin, device=cuda, generator=g) * 1.5
+        sc, sh = _signed_input(T, y0, Cin, g, cuda)
+        near = ((y0.double() * sc.double() + sh.double()).abs() < 1e-3) & (sc != 0)
+        y0 = torch.where(near, ((2e-3 - sh.double()) / sc.double()).float().expand_as(y0), y0)
+        pre = y0.double() * sc.double() + sh.double()
+        assert bool(((pre.abs() >= 1e-3) | (pre == 0)).all())
+        T.assert_signed_gates(pre > 0, Cin, "gate")
     gate = _cpu64(pre > 0).view(B, H, W, Cin)
     mean0, inv0 = _col_stats(y0)
     tiles = B * ((H + 1) // 2) * ((W + 1) // 2)
@@ -150,6 +167,15 @@ def test_input_gradient_network_shapes_at_the_benchmarked_batch(cuda, C, H):
 def test_input_gradient_ragged_and_odd_geometries(cuda, B, H, W, Cin, Cout):
     a = _dgrad(cuda, B, H, W, Cin, Cout, 2)
     b = _dgrad(cuda, B, H, W, Cin, Cout, 2, partials=False)
+    assert torch.equal(a, b), "the sums are optional and do not change dx"
+
+
+def test_forward_and_input_gradient_signed_state(cuda):
+    """osi_conv_fwd_wino with in_scale / in_shift and osi_conv_dgrad_fused_wino (gate recomputed, partials) on negative / zero /
+    saturated scales and zero-variance producer channels: the smallest eligible shape of each list above, same references and bounds."""
+    _fwd(cuda, 6, 7, 7, 64, 128, True, 1, kind="signed")
+    a = _dgrad(cuda, 5, 10, 6, 64, 48, 2, kind="signed")
+    b = _dgrad(cuda, 5, 10, 6, 64, 48, 2, partials=False, kind="signed")
     assert torch.equal(a, b), "the sums are optional and do not change dx"
 
 
@@ -209,7 +235,7 @@ def test_executor_takes_the_winograd_forms(cuda):
     assert not torch.equal(outs[1][0], outs[0][0]), "the two executors run different conv2 kernels"
 
 
-def _wgrad(cuda, B, H, W, Cin, Cout, act, seed):
+def _wgrad(cuda, B, H, W, Cin, Cout, act, seed, kind="positive"):
     import osi_testlib as T
     from openset_imagenet import _native as N
     L = N.lib()
@@ -223,7 +249,9 @@ def _wgrad(cuda, B, H, W, Cin, Cout, act, seed):
     sc = sh = None
     if act:
         sc, sh = torch.rand(Cin, device=cuda, generator=g) + 0.5, torch.randn(Cin, device=cuda, generator=g) * 0.5
-        a64 = torch.relu(a64 * _cpu64(sc) + _cpu64(sh))
+        if kind == "signed":
+            sc, sh = _signed_input(T, x, Cin, g, cuda)
+        a64 = torch.relu(_cpu64(x) * _cpu64(sc) + _cpu64(sh))
     ws = torch.empty(nb, dtype=torch.uint8, device=cuda)
     dw = torch.full((Cout, 3, 3, Cin), float("nan"), device=cuda)
     N.check(L.osi_conv_wgrad_wino(ctypes.byref(d), N.ptr(dy), N.ptr(x), N.ptr(sc) if act else None, N.ptr(sh) if act else None, N.ptr(dw), N.ptr(ws), nb,
@@ -236,7 +264,22 @@ def _wgrad(cuda, B, H, W, Cin, Cout, act, seed):
     N.check(L.osi_conv_wgrad_wino(ctypes.byref(d), N.ptr(dy), N.ptr(x), N.ptr(sc) if act else None, N.ptr(sh) if act else None, N.ptr(dw2), N.ptr(ws), nb,
                                   T.S()))
     assert torch.equal(dw, dw2), "split-K over the tile axis with a fixed-order reduce: bitwise reproducible"
+    if kind == "signed":
+        _signed_wgrad_zeros(T, a64, ref, Cin)
     return err
+
+
+def _signed_wgrad_zeros(T, a64, ref, Cin):
+    """classes 3 and 5: the activation is 0 everywhere, and so is the fp64 weight gradient towards those input channels. The Winograd
+    form sums transformed tiles (B^T a B of an all-zero tile is exactly 0), so nothing else is asserted of the kernel here than the bound."""
+    shut = (T.bn_classes(Cin) == 3) | (T.bn_classes(Cin) == 5)
+    assert float(a64[..., shut].abs().max()) == 0 and float(ref[..., shut].abs().max()) == 0
+    assert float(a64[..., (T.bn_classes(Cin) == 2) | (T.bn_classes(Cin) == 4)].min()) > 0
+
+
+def test_weight_gradient_signed_state(cuda):
+    """osi_conv_wgrad_wino with in_scale / in_shift on the signed state: the smallest eligible shape of the list below."""
+    _wgrad(cuda, 6, 7, 7, 64, 128, True, 1, kind="signed")
 
 
 @pytest.mark.parametrize("C,H", NETWORK)

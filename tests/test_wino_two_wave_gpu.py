@@ -13,12 +13,12 @@ import pytest
 import torch
 
 from test_production_shapes_gpu import _bound, _cpu64, _gen
-from test_wino_gpu import _both_directions_cut, _dgrad, _fwd  # noqa: F401  (the fixture: input-gradient pieces + fix-up stay covered)
+from test_wino_gpu import _both_directions_cut, _dgrad, _fwd, _signed_input, _signed_wgrad_zeros  # noqa: F401  (the fixture: input-gradient pieces + fix-up stay covered)
 
 pytestmark = pytest.mark.gpu
 
 
-def _wgrad_blocks(cuda, B, H, W, Cin, Cout, act, seed):
+def _wgrad_blocks(cuda, B, H, W, Cin, Cout, act, seed, kind="positive"):
     import osi_testlib as T
     from openset_imagenet import _native as N
     L = N.lib()
@@ -32,7 +32,9 @@ def _wgrad_blocks(cuda, B, H, W, Cin, Cout, act, seed):
     sc = sh = None
     if act:
         sc, sh = torch.rand(Cin, device=cuda, generator=g) + 0.5, torch.randn(Cin, device=cuda, generator=g) * 0.5
-        a64 = torch.relu(a64 * _cpu64(sc) + _cpu64(sh))
+        if kind == "signed":
+            sc, sh = _signed_input(T, x, Cin, g, cuda)
+        a64 = torch.relu(_cpu64(x) * _cpu64(sc) + _cpu64(sh))
     ws = torch.full((nb // 4,), float("nan"), device=cuda)
     outs = []
     for _ in range(2):
@@ -55,6 +57,18 @@ def _wgrad_blocks(cuda, B, H, W, Cin, Cout, act, seed):
     print(f"wgrad {(B, H, W, Cin, Cout, act)}: max err {max(worst):.3e} = {max(worst) / bound:.3f} of the bound")
     assert bool(torch.isfinite(outs[0]).all())
     assert torch.equal(outs[0], outs[1]), "the same call twice: equal bits"
+    if kind == "signed":
+        _signed_wgrad_zeros(T, a64, ref, Cin)
+
+
+def test_non_square_signed_state(cuda):
+    """The non-square 13 x 9 geometry on the signed BatchNorm state (negative / zero / saturated scales, zero-variance producer
+    channels): the weight gradient per tap and block at (3, 13, 9, 64, 64), the widest the Winograd weight gradient takes at that
+    geometry here (it needs Cout % 64 == 0), and the in-block input gradient at (3, 13, 9, 64, 96)."""
+    _wgrad_blocks(cuda, 3, 13, 9, 64, 64, True, 0, kind="signed")
+    a = _dgrad(cuda, 3, 13, 9, 64, 96, 3, kind="signed")
+    b = _dgrad(cuda, 3, 13, 9, 64, 96, 3, kind="signed")
+    assert torch.equal(a, b), "the same call twice: equal bits"
 
 
 @pytest.mark.parametrize("B,H,W,Cin,Cout,act", [
