@@ -188,6 +188,16 @@ typedef struct {
 size_t osi_conv_dgrad_fused_workspace(const osi_conv_desc* d);
 int osi_conv_dgrad_fused(const osi_conv_desc* d, const float* dy, const float* w, float* dx, const float* addend,
                          const osi_dgrad_fusion* f, int tile, int* P, osi_stream_t stream);
+/* ABI 12, frozen BatchNorm statistics. The in-block form of osi_conv_dgrad_fused (f->scale0 / shift0 / y0 set: gate recomputed as
+ * fma(y0, scale0, shift0) > 0; relu_mask, y1, pool_idx NULL, no addend: OSI_ERR_ARG otherwise) for a producer BatchNorm that ran on
+ * FIXED statistics: g = gate . conv2d_input_grad(dy, w), and the store is the producer's BatchNorm backward itself,
+ *   dx = scale0[c] * g        (dy0 = gamma * invstd * g: with constant mean / variance no mean(g) or mean(g * xhat) term exists),
+ * so no BatchNorm-backward apply pass follows. f->partials set: the per-row-tile column sums of the UNSCALED g and of g * xhat0
+ * (xhat0 from mean0 / invstd0) as partials[2][*P][Cin], to be finished by osi_bn_backward_reduce into dbeta / dgamma; partials = NULL:
+ * nothing but dx is written (input-only backward; P may be NULL). tile: OSI_TILE_AUTO or OSI_TILE_64x64_S1 — the 64x64 single-buffered
+ * tile in all its forms (stride-2 parity classes, 3x3 row windows, K-split tail + fix-up when the partials' workspace has room). */
+int osi_conv_dgrad_fused_frozen(const osi_conv_desc* d, const float* dy, const float* w, float* dx, const osi_dgrad_fusion* f, int tile,
+                                int* P, osi_stream_t stream);
 int osi_conv_dgrad_fused_wino(const osi_conv_desc* d, const float* dy, const float* w, float* dx, const osi_dgrad_fusion* f, void* ws,
                               size_t ws_bytes, int* P, osi_stream_t stream);
 int osi_conv_dgrad_fused_wino_pre(const osi_conv_desc* d, const float* dy, const float* u, float* dx, const osi_dgrad_fusion* f, void* slab,
@@ -263,6 +273,16 @@ typedef struct {
     int C;
 } osi_bn_eval_layer;
 int osi_bn_eval_coeffs_multi(const osi_bn_eval_layer* layers, int n, float eps, osi_stream_t stream);
+/* ABI 12. Frozen statistics for a differentiable forward: scale / shift with the bits of osi_bn_eval_coeffs, plus mean = running_mean and
+ * invstd = 1 / sqrt(running_var + eps) where the backward kernels read them; up to OSI_BN_FROZEN_MAX layers in one launch. The running
+ * statistics are only read. */
+#define OSI_BN_FROZEN_MAX 54
+typedef struct {
+    const float *running_mean, *running_var, *gamma, *beta;
+    float *scale, *shift, *mean, *invstd;
+    int C;
+} osi_bn_frozen_layer;
+int osi_bn_frozen_coeffs_multi(const osi_bn_frozen_layer* layers, int n, float eps, osi_stream_t stream);
 /* out = [relu](y*scale + shift [+ residual]) */
 int osi_bn_apply(const float* y, const float* residual, const float* scale, const float* shift, float* out, int M, int C,
                  int relu, osi_stream_t stream);
@@ -293,6 +313,21 @@ int osi_bn_backward_relu_mask(const float* dout, const void* relu_mask, const fl
 int osi_bn_backward_fused(const float* g, const float* y, const float* mean, const float* invstd, const float* gamma,
                           const float* psum_g, const float* psum_gx, int P, float* dy, float* dgamma, float* dbeta, int M, int C,
                           void* ws, size_t ws_bytes, osi_stream_t stream);
+
+/* ABI 12. BatchNorm backward on FROZEN statistics (mean / invstd are constants of the graph): with g = dout gated by relu_mask (NULL:
+ * dout is already gated, e.g. by a dgrad epilogue), every consumer k < n (n = 1 or 2: bn3 and the projection shortcut's BatchNorm read
+ * the same gated gradient) gets dy_k = scale_k[c] * g in ONE pass that does not read y. dgamma_k / dbeta_k non-NULL (both or neither):
+ * dbeta = sum g, dgamma = sum g * xhat_k first (y, mean, invstd needed; ws >= osi_bn_backward_workspace(M, C)); NULL: no reduction is
+ * launched (the sums may also arrive as dgrad-epilogue partials: osi_bn_backward_reduce). gmasked (optional) receives g. consumers[0].dy
+ * may alias dout. */
+typedef struct {
+    const float *y, *mean, *invstd;   /* pre-BN tensor and frozen statistics: read only for dgamma */
+    const float* scale;               /* gamma * invstd [C] */
+    float* dy;
+    float *dgamma, *dbeta;            /* NULL: no parameter gradient */
+} osi_bn_frozen_consumer;
+int osi_bn_backward_frozen(const float* dout, const void* relu_mask, const osi_bn_frozen_consumer* consumers, int n, float* gmasked, int M,
+                           int C, void* ws, size_t ws_bytes, osi_stream_t stream);
 
 /* ---- pooling / layout (ResNet.maxpool, ResNet.avgpool, flatten; image batch of train.py:128) --- */
 int osi_nchw3_to_nhwc4(const float* x_nchw, float* y_nhwc4, int B, int H, int W, osi_stream_t stream);
@@ -325,6 +360,11 @@ int osi_bn_relu_maxpool_fwd(const float* y, const float* scale, const float* shi
 int osi_bn_relu_maxpool_bwd(const float* gpool, const void* idx, const float* y, const float* mean, const float* invstd,
                             const float* gamma, float* dy, float* dgamma, float* dbeta, int B, int H, int W, int C, void* ws,
                             size_t ws_bytes, osi_stream_t stream);
+/* ABI 12. The stem tail's backward on frozen statistics: dy = scale * (pool-scattered, bit-7-gated gpool); dgamma / dbeta (both or
+ * neither; NULL: no reduction launched) = sum g * xhat / sum g. */
+int osi_bn_relu_maxpool_bwd_frozen(const float* gpool, const void* idx, const float* y, const float* mean, const float* invstd,
+                                   const float* scale, float* dy, float* dgamma, float* dbeta, int B, int H, int W, int C, void* ws,
+                                   size_t ws_bytes, osi_stream_t stream);
 int osi_avgpool_fwd(const float* x, float* y, int B, int HW, int C, osi_stream_t stream);
 int osi_avgpool_bwd(const float* dy, float* dx, int B, int HW, int C, osi_stream_t stream);
 
@@ -448,6 +488,16 @@ int osi_resnet50_bind_input_nhwc4(osi_resnet50_t net, const float* x_nhwc4);
  * osi_resnet50_bind_input_nhwc4). training != 0: batch statistics + running-stat update. */
 int osi_resnet50_forward(osi_resnet50_t net, const float* params, float* buffers, long long* nbt, const float* image,
                          void* workspace, float* logits, float* features, int training, osi_stream_t stream);
+/* ABI 12. Differentiable forward on FROZEN BatchNorm statistics (eval-mode gradients, fine-tuning with frozen statistics): the training
+ * topology (pre-BN tensors, block-output bitmasks, arg-max bytes) on the running statistics, all 53 coefficient sets from one launch
+ * (osi_bn_frozen_coeffs_multi). buffers are only read; num_batches_tracked is not an argument. Outputs: the bits of
+ * osi_resnet50_forward(training = 0) under option eval_fused = 0. The backward that follows (osi_resnet50_backward / _ex / _adv, any
+ * stage split) runs the frozen dataflow: dy = scale * g in the in-block input-gradient epilogues (osi_conv_dgrad_fused_frozen, the 3x3
+ * stride-1 layers included: no Winograd form), osi_bn_backward_frozen at block outputs, osi_bn_relu_maxpool_bwd_frozen + the
+ * materialised stem tail; param_grads = 0 launches no reduction at all. A later osi_resnet50_forward of any kind replaces this state
+ * (a backward after an inference forward: OSI_ERR_STATE). */
+int osi_resnet50_forward_frozen(osi_resnet50_t net, const float* params, const float* buffers, const float* image, void* workspace,
+                                float* logits, float* features, osi_stream_t stream);
 /* runs backward stages [stage_lo, stage_hi) given dJ/dlogits and (optionally, may be NULL) dJ/dfeatures */
 int osi_resnet50_backward(osi_resnet50_t net, const float* params, float* grads, void* workspace, const float* dlogits,
                           const float* dfeatures, int stage_lo, int stage_hi, osi_stream_t stream);

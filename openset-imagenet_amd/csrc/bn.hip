@@ -303,6 +303,19 @@ __global__ void k_bn_eval_coeffs_multi(BnEvalTable t, float eps) {
     L.scale[c] = sc; L.shift[c] = L.beta[c] - L.running_mean[c] * sc;
 }
 
+// frozen statistics (osi_bn_frozen_coeffs_multi): the coefficients of k_bn_eval_coeffs_multi — the same expressions, so the same bits —
+// plus what the backward kernels read from the workspace: mean = running_mean, invstd = 1 / sqrt(running_var + eps)
+struct BnFrozenTable { osi_bn_frozen_layer l[OSI_BN_FROZEN_MAX]; };
+__global__ void k_bn_frozen_coeffs_multi(BnFrozenTable t, float eps) {
+    const osi_bn_frozen_layer& L = t.l[blockIdx.y];
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= L.C) return;
+    const float is = 1.0f / sqrtf(L.running_var[c] + eps);
+    const float sc = L.gamma[c] * is;                                          // the expression of k_bn_eval_coeffs
+    L.scale[c] = sc; L.shift[c] = L.beta[c] - L.running_mean[c] * sc;
+    L.mean[c] = L.running_mean[c]; L.invstd[c] = is;
+}
+
 // ---- apply: out = [relu]( y*scale + shift [+ res] ) ---------------------------------------------------
 // ReLU bitmask: bit (i & 63) of word [(i >> 6) * 4 + c] = (component c of float4 #i is > 0 after BN(+res)). One bit per
 // element (1/32 of the tensor) lets both BatchNorm-backward passes skip re-reading the activation just to rebuild the mask.
@@ -550,6 +563,25 @@ __global__ __launch_bounds__(NT) void k_bn_bwd_apply(const f32x4* dA /* may alia
     }
 }
 
+// Frozen statistics: mean and variance are constants of the backward, so dy = scale * g (scale = gamma * invstd) — y is not read, and
+// nothing waits for a reduction. One pass serves one or two consumers of the same gated gradient (bn3 and the projection shortcut's
+// BatchNorm) and can emit g itself for an identity shortcut. dy0 may alias dA (every lane reads its element before it writes it).
+template <int MODE, bool EMITG, bool TWO>
+__global__ __launch_bounds__(NT) void k_bn_frozen_apply(const f32x4* dA, const void* __restrict__ msk, const f32x4* __restrict__ scale0,
+                                                       const f32x4* __restrict__ scale1, f32x4* dy0, f32x4* __restrict__ dy1,
+                                                       f32x4* __restrict__ gout, size_t n4, int c4n, PoolSrc ps) {
+    const size_t nq = (n4 + NT - 1) / NT;
+    for (size_t q = blockIdx.x; q < nq; q += gridDim.x) {
+        const size_t i = ((OSI_BN_REVERSE & 2) ? nq - 1 - q : q) * NT + threadIdx.x;
+        if (i >= n4) continue;
+        const int c4 = (int)(i % (size_t)c4n);
+        const f32x4 gv = MODE == 3 ? pool_gather(dA, ps, (uint32_t)(i / (size_t)c4n), c4, c4n) : masked<MODE>(__builtin_nontemporal_load(dA + i), msk, i);
+        if (EMITG) gout[i] = gv;
+        if (TWO) dy1[i] = gv * scale1[c4];
+        dy0[i] = gv * scale0[c4];
+    }
+}
+
 static int rows_per_block(int M, int C, int& P) {
     // ~256 KiB of activations per workgroup, at most 1024 workgroups
     long rows = (256l * 1024) / ((long)C * 4);
@@ -656,6 +688,21 @@ int osi_bn_eval_coeffs_multi(const osi_bn_eval_layer* layers, int n, float eps, 
         if (L.C > cmax) cmax = L.C;
     }
     hipLaunchKernelGGL(k_bn_eval_coeffs_multi, dim3(osi_cdiv(cmax, 256), n), dim3(256), 0, (hipStream_t)stream, t, eps);
+    OSI_LAUNCH_CHECK();
+    return OSI_OK;
+}
+
+int osi_bn_frozen_coeffs_multi(const osi_bn_frozen_layer* layers, int n, float eps, osi_stream_t stream) {
+    OSI_REQUIRE(layers && n > 0 && n <= OSI_BN_FROZEN_MAX);
+    BnFrozenTable t{};
+    int cmax = 0;
+    for (int i = 0; i < n; ++i) {
+        const osi_bn_frozen_layer& L = layers[i];
+        OSI_REQUIRE(L.running_mean && L.running_var && L.gamma && L.beta && L.scale && L.shift && L.mean && L.invstd && L.C > 0);
+        t.l[i] = L;
+        if (L.C > cmax) cmax = L.C;
+    }
+    hipLaunchKernelGGL(k_bn_frozen_coeffs_multi, dim3(osi_cdiv(cmax, 256), n), dim3(256), 0, (hipStream_t)stream, t, eps);
     OSI_LAUNCH_CHECK();
     return OSI_OK;
 }
@@ -798,6 +845,71 @@ int osi_bn_backward_reduce(const float* psum_g, const float* psum_gx, int P, flo
     float* c2 = c1 + C;
     if (int e = bwd_reduce_partials(psum_g, psum_gx, P, M, C, gb, gg, S, Pc, dgamma, dbeta, c1, c2, st)) return e;
     return OSI_OK;
+}
+
+// mode 0: dout is used as it is (already gated by a dgrad epilogue), 2: gated by the bitmask, 3: gathered through the stem's max-pool
+static int bn_frozen_impl(const float* dout, const void* msk, int mode, const osi_bn_frozen_consumer* cs, int n, float* gmasked, int M, int C,
+                          void* ws, size_t ws_bytes, hipStream_t st, PoolSrc ps = PoolSrc{}) {
+    OSI_REQUIRE(dout && cs && (n == 1 || n == 2) && M > 0 && C > 0 && C % 4 == 0);
+    OSI_REQUIRE(mode != 3 || (n == 1 && !gmasked));
+    for (int k = 0; k < n; ++k) {
+        OSI_REQUIRE(cs[k].scale && cs[k].dy && (cs[k].dgamma == nullptr) == (cs[k].dbeta == nullptr));
+        if (cs[k].dgamma) {
+            int P;
+            rows_per_block(M, C, P);
+            OSI_REQUIRE(cs[k].y && cs[k].mean && cs[k].invstd && ws && ws_bytes >= ((size_t)2 * P * C + 2 * (size_t)C) * sizeof(float));
+        }
+    }
+    OSI_REQUIRE(n == 1 || (cs[1].dy != cs[0].dy && cs[1].dy != dout));
+    // dgamma = sum g * xhat (xhat from the frozen statistics), dbeta = sum g: the reduction kernels of the training form, before the
+    // apply pass (dy0 may overwrite dout). Only when a parameter gradient is asked for.
+    for (int k = 0; k < n; ++k) {
+        if (!cs[k].dgamma) continue;
+        int P;
+        const int rpb = rows_per_block(M, C, P);
+        float* pdb = (float*)ws;
+        float* pdg = pdb + (size_t)P * C;
+        float* c1 = pdg + (size_t)P * C;
+        if (mode == 3) hipLaunchKernelGGL(k_bn_bwd_partial<3>, dim3(P), dim3(NT), 0, st, dout, msk, cs[k].y, cs[k].mean, cs[k].invstd, M, C, rpb, pdb, pdg, ps);
+        else if (mode == 2) hipLaunchKernelGGL(k_bn_bwd_partial<2>, dim3(P), dim3(NT), 0, st, dout, msk, cs[k].y, cs[k].mean, cs[k].invstd, M, C, rpb, pdb, pdg, ps);
+        else hipLaunchKernelGGL(k_bn_bwd_partial<0>, dim3(P), dim3(NT), 0, st, dout, msk, cs[k].y, cs[k].mean, cs[k].invstd, M, C, rpb, pdb, pdg, ps);
+        OSI_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_bn_bwd_final, dim3(osi_cdiv(C, NT / 64)), dim3(NT), 0, st, pdb, pdg, P, M, C, cs[k].dgamma, cs[k].dbeta, c1, c1 + C);
+        OSI_LAUNCH_CHECK();
+    }
+    const size_t n4 = (size_t)M * C / 4;
+    const int grid = stream_grid(n4, true), c4n = C / 4;
+    auto D = (const f32x4*)dout; auto S0 = (const f32x4*)cs[0].scale; auto S1 = (const f32x4*)(n == 2 ? cs[1].scale : nullptr);
+    auto DY0 = (f32x4*)cs[0].dy; auto DY1 = (f32x4*)(n == 2 ? cs[1].dy : nullptr); auto GO = (f32x4*)gmasked;
+#define OSI_FRZ_APPLY(MODE_, EMIT_, TWO_) hipLaunchKernelGGL((k_bn_frozen_apply<MODE_, EMIT_, TWO_>), dim3(grid), dim3(NT), 0, st, D, msk, S0, S1, DY0, DY1, GO, n4, c4n, ps)
+    if (mode == 3) OSI_FRZ_APPLY(3, false, false);
+    else if (mode == 2) {
+        if (n == 2) { if (gmasked) OSI_FRZ_APPLY(2, true, true); else OSI_FRZ_APPLY(2, false, true); }
+        else { if (gmasked) OSI_FRZ_APPLY(2, true, false); else OSI_FRZ_APPLY(2, false, false); }
+    } else {
+        if (n == 2) { if (gmasked) OSI_FRZ_APPLY(0, true, true); else OSI_FRZ_APPLY(0, false, true); }
+        else { if (gmasked) OSI_FRZ_APPLY(0, true, false); else OSI_FRZ_APPLY(0, false, false); }
+    }
+#undef OSI_FRZ_APPLY
+    OSI_LAUNCH_CHECK();
+    return OSI_OK;
+}
+
+int osi_bn_backward_frozen(const float* dout, const void* relu_mask, const osi_bn_frozen_consumer* consumers, int n, float* gmasked, int M,
+                           int C, void* ws, size_t ws_bytes, osi_stream_t stream) {
+    return bn_frozen_impl(dout, relu_mask, relu_mask ? 2 : 0, consumers, n, gmasked, M, C, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int osi_bn_relu_maxpool_bwd_frozen(const float* gpool, const void* idx, const float* y, const float* mean, const float* invstd,
+                                   const float* scale, float* dy, float* dgamma, float* dbeta, int B, int H, int W, int C, void* ws,
+                                   size_t ws_bytes, osi_stream_t stream) {
+    OSI_REQUIRE(idx && B > 0 && H > 0 && W > 0 && (long)B * H * W < (1l << 31));
+    PoolSrc ps;
+    ps.idx = (const uint32_t*)idx;
+    ps.dW = make_fastdiv((uint32_t)W); ps.dH = make_fastdiv((uint32_t)H);
+    ps.H = H; ps.W = W; ps.Ho = (H + 2 - 3) / 2 + 1; ps.Wo = (W + 2 - 3) / 2 + 1;
+    const osi_bn_frozen_consumer c{y, mean, invstd, scale, dy, dgamma, dbeta};
+    return bn_frozen_impl(gpool, nullptr, 3, &c, 1, nullptr, B * H * W, C, ws, ws_bytes, (hipStream_t)stream, ps);
 }
 
 int osi_bn_relu_maxpool_bwd(const float* gpool, const void* idx, const float* y, const float* mean, const float* invstd,

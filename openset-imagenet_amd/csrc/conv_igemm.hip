@@ -647,12 +647,15 @@ __global__ __launch_bounds__(256, XF ? (WM * WN == 1 ? 8 : 5) : (NST == 1 ? (WM 
 // FUSED: 0 = addend only; 1 = every fusion the ABI allows (tests, pool mode); 2 = "in-block" (the gate recomputed from y0 and / or
 // the sums over y0; no addend, bitmask or second consumer: all four rows' loads in flight); 3 = "block input" (addend, bitmask,
 // sums over y0 and y1; no recomputed gate). 2 and 3 are what the executor issues; they exist so that each fits 64 registers.
+// 4 = "in-block, frozen statistics" (osi_conv_dgrad_fused_frozen): flavour 2 whose STORE is scale0[c] * g — with fixed statistics the
+// producer's BatchNorm backward is dy0 = (gamma * invstd) * g, and that factor is the gate's scale, already in registers; the sums stay
+// over the unscaled g (dbeta, dgamma). Its own instantiation: the multiply never enters a training launch.
 template <int FUSED, bool POOL, typename RD>
 __device__ __forceinline__ void dgrad_epilogue64(const ConvP& p, float* smem, int cls, int mt, int m0, int n0, int Mc, int st, int ph,
                                                  int pw, const FastDiv& dHW, const FastDiv& dW, RD rd) {
     constexpr int BN = 64;
-    constexpr bool USE_ADD = FUSED != 2, USE_BITS = FUSED == 1 || FUSED == 3, USE_Y1 = FUSED == 1 || FUSED == 3;
-    constexpr bool USE_GATE = FUSED == 1 || FUSED == 2;
+    constexpr bool USE_ADD = FUSED != 2 && FUSED != 4, USE_BITS = FUSED == 1 || FUSED == 3, USE_Y1 = FUSED == 1 || FUSED == 3;
+    constexpr bool USE_GATE = FUSED == 1 || FUSED == 2 || FUSED == 4;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c4 = tid & 15, rg = tid >> 4;
     const int col = n0 + c4 * 4;
@@ -687,7 +690,7 @@ __device__ __forceinline__ void dgrad_epilogue64(const ConvP& p, float* smem, in
         offb[k] = valid ? (pix * p.Cin + col) * 4u : OOB;
     }
     const __amdgpu_buffer_rsrc_t r_y0 = make_rsrc(p.ey0, (has_sum || has_gate) ? FULL : 0);
-    if constexpr (FUSED == 2) {
+    if constexpr (FUSED == 2 || FUSED == 4) {
         // in-block: one optional tensor, so all four rows go out together
         f32x4 y0v[4];
 #pragma unroll
@@ -702,6 +705,7 @@ __device__ __forceinline__ void dgrad_epilogue64(const ConvP& p, float* smem, in
             }
             sg += v;
             s0 += (v * (y0v[k] - mu0)) * is0;
+            if constexpr (FUSED == 4) v *= gsc;     // frozen statistics: the store is the producer's dy0 = scale0 * g
             bst4(r_out, v, offb[k], 0);
         }
     } else {
@@ -2449,7 +2453,7 @@ static int dgrad_rows(int tile) {
     return (tile == OSI_TILE_128x128 || tile == OSI_TILE_128x64 || tile == OSI_TILE_128x128_S1 || tile == OSI_TILE_128x64_S1) ? 128 : 64;
 }
 static int conv_dgrad_impl(const osi_conv_desc* d, const float* dy, const float* w, float* dx, const float* addend,
-                           const osi_dgrad_fusion* f, int tile, int* P, osi_stream_t stream, bool sparse = false);
+                           const osi_dgrad_fusion* f, int tile, int* P, osi_stream_t stream, bool sparse = false, bool frozen = false);
 
 int osi_conv_dgrad(const osi_conv_desc* d, const float* dy, const float* w, float* dx, int accumulate, int tile,
                    osi_stream_t stream) {
@@ -2480,8 +2484,19 @@ int osi_conv_dgrad_fused(const osi_conv_desc* d, const float* dy, const float* w
     return conv_dgrad_impl(d, dy, w, dx, addend, f, tile, P, stream);
 }
 
+// In-block input gradient under frozen BatchNorm statistics (flavour 4 of dgrad_epilogue64): the in-block fusion only — gate recomputed
+// from y0, one consumer, no addend / bitmask / pool mode — on the 64x64 single-buffered tile in each of its forms (plain, stride-2
+// parity classes, 3x3 row windows, K-split tail + fix-up). *P is written only when partials are asked for.
+int osi_conv_dgrad_fused_frozen(const osi_conv_desc* d, const float* dy, const float* w, float* dx, const osi_dgrad_fusion* f, int tile,
+                                int* P, osi_stream_t stream) {
+    OSI_REQUIRE(f && f->scale0 && f->shift0 && f->y0 && !f->relu_mask && !f->y1 && !f->pool_idx && f->addend_stride <= 1);
+    OSI_REQUIRE(!f->partials || P);
+    OSI_REQUIRE(tile == OSI_TILE_AUTO || tile == OSI_TILE_64x64_S1);
+    return conv_dgrad_impl(d, dy, w, dx, nullptr, f, OSI_TILE_64x64_S1, P, stream, false, true);
+}
+
 static int conv_dgrad_impl(const osi_conv_desc* d, const float* dy, const float* w, float* dx, const float* addend,
-                           const osi_dgrad_fusion* f, int tile, int* P, osi_stream_t stream, bool sparse) {
+                           const osi_dgrad_fusion* f, int tile, int* P, osi_stream_t stream, bool sparse, bool frozen) {
     OSI_REQUIRE(desc_ok(d) && dy && w && dx);
     OSI_REQUIRE(!is_stem(d));  // the image needs no gradient (train.py:128-139: input is a leaf without grad)
     OSI_REQUIRE(d->Cout % BK == 0 && d->Cin % 64 == 0 && d->stride <= 2);
@@ -2527,11 +2542,13 @@ static int conv_dgrad_impl(const osi_conv_desc* d, const float* dy, const float*
             {
                 float* slab = f->partials + dgrad_partial_floats(d);
                 const int fl = dgrad_flavour(p);
+                if (frozen) return dgrad_w3(d) ? launch_dgrad_split<4, true>(p, tp, slab, st) : launch_dgrad_split<4>(p, tp, slab, st);
                 if (fl == 2 && dgrad_w3(d)) return launch_dgrad_split<2, true>(p, tp, slab, st);
                 return fl == 2 ? launch_dgrad_split<2>(p, tp, slab, st) : fl == 3 ? launch_dgrad_split<3>(p, tp, slab, st) : launch_dgrad_split<1>(p, tp, slab, st);
             }
         }
     }
+    if (frozen) return dgrad_w3(d) ? launch_dgrad_impl<1, 1, 1, 4, false, true>(p, st) : launch_dgrad_impl<1, 1, 1, 4>(p, st);
     // the executor's in-block 3x3 stride-1 input gradients on the row-window form
     if (tile == OSI_TILE_64x64_S1 && dgrad_w3(d) && (p.ebits || p.esum || p.escale0) && !p.epool && dgrad_flavour(p) == 2)
         return launch_dgrad_impl<1, 1, 1, 2, false, true>(p, st);

@@ -2,6 +2,7 @@
 // ("surfaced through PyTorch-ROCm custom ops") for the arithmetic the reference runs at openset_imagenet/train.py:132-139:
 //
 //   torch.ops.osi.resnet50_forward    model.py:28-39   (logits, features = model(images))
+//   torch.ops.osi.resnet50_forward_frozen  the same on frozen BatchNorm statistics, differentiable (eval-mode gradients, freeze_bn())
 //   torch.ops.osi.resnet50_backward   train.py:138     (j.backward() through the network, stage range for the DP bucket schedule)
 //   torch.ops.osi.resnet50_backward_ex  the same, plus dJ/dimage and the input-only backward (adversarial samples, attribution)
 //   torch.ops.osi.resnet50_backward_adv the same, the last stage writing the FGSM batch; torch.ops.osi.grad_accumulate sums two arenas
@@ -60,10 +61,12 @@ osi_resnet50_t handle(int64_t h) {
 const float* fptr(const std::optional<Tensor>& t) { return t.has_value() && t->defined() ? t->data_ptr<float>() : nullptr; }
 
 // image: fp32 NCHW [B,3,H,W] (the reference's batch), fp32 NHWC4 [B,H,W,4] (bound in place) or uint8 [B,H,W,3] (+ flip flags)
-std::tuple<Tensor, Tensor> resnet50_forward(int64_t net, const Tensor& params, Tensor buffers, Tensor nbt, const Tensor& image,
-                                            const std::optional<Tensor>& flip, Tensor workspace, int64_t fc_dim, int64_t out_features,
-                                            bool training) {
-    need(params, at::kFloat, "params"); need(buffers, at::kFloat, "buffers"); need(nbt, at::kLong, "num_batches_tracked");
+// nbt == nullptr: the frozen-statistics forward (osi_resnet50_forward_frozen: buffers read-only, no num_batches_tracked)
+std::tuple<Tensor, Tensor> forward_common(int64_t net, const Tensor& params, const Tensor& buffers, const Tensor* nbt_p, const Tensor& image,
+                                          const std::optional<Tensor>& flip, Tensor workspace, int64_t fc_dim, int64_t out_features,
+                                          bool training) {
+    need(params, at::kFloat, "params"); need(buffers, at::kFloat, "buffers");
+    if (nbt_p) need(*nbt_p, at::kLong, "num_batches_tracked");
     need(workspace, at::kByte, "workspace");
     TORCH_CHECK(image.dim() == 4, "osi::resnet50_forward: image must be 4-D");
     c10::hip::HIPGuardMasqueradingAsCUDA guard(params.device());
@@ -71,7 +74,7 @@ std::tuple<Tensor, Tensor> resnet50_forward(int64_t net, const Tensor& params, T
     TORCH_CHECK((size_t)workspace.numel() >= osi_resnet50_workspace_bytes(h), "osi::resnet50_forward: workspace too small");
     TORCH_CHECK((size_t)params.numel() == osi_resnet50_param_floats(h), "osi::resnet50_forward: parameter arena size mismatch");
     TORCH_CHECK((size_t)buffers.numel() == osi_resnet50_buffer_floats(h), "osi::resnet50_forward: buffer arena size mismatch");
-    TORCH_CHECK(nbt.numel() == osi_resnet50_num_bn(h), "osi::resnet50_forward: num_batches_tracked size mismatch");
+    TORCH_CHECK(!nbt_p || nbt_p->numel() == osi_resnet50_num_bn(h), "osi::resnet50_forward: num_batches_tracked size mismatch");
     osi_stream_t st = stream_of(params);
     const int64_t B = image.size(0);
     {   // the executor was created for ONE geometry: a batch of another shape would read / write outside its workspace
@@ -97,10 +100,29 @@ std::tuple<Tensor, Tensor> resnet50_forward(int64_t net, const Tensor& params, T
     }
     Tensor logits = at::empty({B, out_features}, params.options());
     Tensor features = at::empty({B, fc_dim}, params.options());
-    ok(osi_resnet50_forward(h, params.data_ptr<float>(), buffers.data_ptr<float>(), (long long*)nbt.data_ptr<int64_t>(), img,
-                            workspace.data_ptr(), logits.data_ptr<float>(), features.data_ptr<float>(), training ? 1 : 0, st),
-       "osi_resnet50_forward");
+    if (nbt_p)
+        ok(osi_resnet50_forward(h, params.data_ptr<float>(), buffers.data_ptr<float>(), (long long*)nbt_p->data_ptr<int64_t>(), img,
+                                workspace.data_ptr(), logits.data_ptr<float>(), features.data_ptr<float>(), training ? 1 : 0, st),
+           "osi_resnet50_forward");
+    else
+        ok(osi_resnet50_forward_frozen(h, params.data_ptr<float>(), buffers.data_ptr<float>(), img, workspace.data_ptr(),
+                                       logits.data_ptr<float>(), features.data_ptr<float>(), st),
+           "osi_resnet50_forward_frozen");
     return {logits, features};
+}
+
+std::tuple<Tensor, Tensor> resnet50_forward(int64_t net, const Tensor& params, Tensor buffers, Tensor nbt, const Tensor& image,
+                                            const std::optional<Tensor>& flip, Tensor workspace, int64_t fc_dim, int64_t out_features,
+                                            bool training) {
+    return forward_common(net, params, buffers, &nbt, image, flip, workspace, fc_dim, out_features, training);
+}
+
+// ABI 12: the differentiable forward on frozen BatchNorm statistics (eval-mode gradients, freeze_bn()); the running statistics are read,
+// never written, and the backward ops that follow run the frozen dataflow
+std::tuple<Tensor, Tensor> resnet50_forward_frozen(int64_t net, const Tensor& params, const Tensor& buffers, const Tensor& image,
+                                                   const std::optional<Tensor>& flip, Tensor workspace, int64_t fc_dim,
+                                                   int64_t out_features) {
+    return forward_common(net, params, buffers, nullptr, image, flip, workspace, fc_dim, out_features, false);
 }
 
 void resnet50_backward(int64_t net, const Tensor& params, Tensor grads, Tensor workspace, const Tensor& dlogits,
@@ -317,6 +339,8 @@ void confidence_accumulate(const Tensor& logits, const Tensor& target, double of
 TORCH_LIBRARY(osi, m) {
     m.def("resnet50_forward(int net, Tensor params, Tensor(a!) buffers, Tensor(b!) nbt, Tensor image, Tensor? flip, Tensor(c!) workspace, "
           "int fc_dim, int out_features, bool training) -> (Tensor, Tensor)");
+    m.def("resnet50_forward_frozen(int net, Tensor params, Tensor buffers, Tensor image, Tensor? flip, Tensor(a!) workspace, "
+          "int fc_dim, int out_features) -> (Tensor, Tensor)");
     m.def("resnet50_backward(int net, Tensor params, Tensor(a!) grads, Tensor(b!) workspace, Tensor dlogits, Tensor? dfeatures, "
           "int stage_lo, int stage_hi) -> ()");
     m.def("resnet50_backward_ex(int net, Tensor params, Tensor(a!) grads, Tensor(b!) workspace, Tensor dlogits, Tensor? dfeatures, "
@@ -341,6 +365,7 @@ TORCH_LIBRARY(osi, m) {
 // The ops are MI355X-only: registered for the HIP device key (spelled CUDA in PyTorch-ROCm); a CPU tensor finds no kernel and raises.
 TORCH_LIBRARY_IMPL(osi, CUDA, m) {
     m.impl("resnet50_forward", &resnet50_forward);
+    m.impl("resnet50_forward_frozen", &resnet50_forward_frozen);
     m.impl("resnet50_backward", &resnet50_backward);
     m.impl("resnet50_backward_ex", &resnet50_backward_ex);
     m.impl("resnet50_backward_adv", &resnet50_backward_adv);

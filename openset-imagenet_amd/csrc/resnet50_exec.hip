@@ -181,7 +181,10 @@ struct osi_resnet50 {
     // cannot disagree: the fused form (bn1's reductions out of that input gradient's pool-mode epilogue, dY built inside
     // osi_stem_wgrad_fused's loader) unless dJ/dimage (or the adversarial batch made from it) needs dY in memory or the geometry /
     // knobs leave the fused form no workspace.
-    bool stem_tail_fused() const { return !bw_dimage && !bw_adv && stem_ws_bytes > 0; }
+    bool stem_tail_fused() const { return !frozen && !bw_dimage && !bw_adv && stem_ws_bytes > 0; }
+    // osi_resnet50_forward_frozen ran last: every BatchNorm's mean / invstd slots hold the running statistics and the backward that follows
+    // takes the frozen dataflow (dy = scale * g; the fused stem tail and the Winograd input gradients are training-only)
+    bool frozen = false;
     bool eval_fused = true;          // option "eval_fused": a forward with training = 0 runs the inference forms (forward_eval_fused); 0 = the
                                      // training topology on running statistics (A/B: the same bits when both run the same launch plans,
                                      // i.e. tail_split off; fp32-rounding-level differences otherwise)
@@ -463,7 +466,7 @@ static int conv_bn_fwd(osi_resnet50* n, int ci, const float* params, float* buff
     // 3x3 / stride 1 (conv2 of a bottleneck without a stride): Winograd F(2x2,3x3), 2.25x fewer multiplies (csrc/conv_wino.hip); main stream only
     const bool wino = n->plan_knobs.fwd_wino && isc && (n->side == nullptr || st != n->side) && c.u_fw != (size_t)-1;
     if (wino) OSI_TRY(n->wait_weight_transforms(st));
-    if (training) {
+    if (training == 1) {
         // batch statistics come out of the conv epilogue (per row tile), only a tiny per-channel merge follows
         int P = 0, rows = 0;
         if (isc && wino) OSI_TRY(osi_conv_fwd_wino_pre(&c.d, x, isc, ish, ws + c.u_fw, ws + c.y, ws + n->wino_ws, n->wino_ws_bytes, ws + bn_ws_off, n->bn_ws_bytes, &P, &rows, st));
@@ -478,6 +481,7 @@ static int conv_bn_fwd(osi_resnet50* n, int ci, const float* params, float* buff
         else if (isc) OSI_TRY(osi_conv_fwd_act(&c.d, x, isc, ish, w, ws + c.y, OSI_TILE_AUTO, nullptr, 0, nullptr, nullptr, st));
         else OSI_TRY(osi_conv_fwd(&c.d, x, w, ws + c.y, OSI_TILE_AUTO, st));
         OSI_TRY(n->mark(OSI_PROF_CONV_FWD, st));
+        if (training != 2)   // (2 = frozen forward: one launch wrote every layer's coefficients up front)
         OSI_TRY(osi_bn_eval_coeffs(buffers + b.rm_off, buffers + b.rv_off, params + b.g_off, params + b.b_off, 1e-5f, b.C,
                                    ws + b.scale, ws + b.shift, st));
     }
@@ -594,10 +598,27 @@ static int forward_eval_fused(osi_resnet50* n, const float* params, const float*
     return OSI_OK;
 }
 
+static int forward_impl(osi_resnet50_t n, const float* params, float* buffers, long long* nbt, const float* image,
+                        void* workspace, float* logits, float* features, int training, osi_stream_t stream);
+
 int osi_resnet50_forward(osi_resnet50_t n, const float* params, float* buffers, long long* nbt, const float* image,
                          void* workspace, float* logits, float* features, int training, osi_stream_t stream) {
     OSI_REQUIRE(n && params && buffers && workspace && logits && features);
     OSI_REQUIRE(!training || nbt);
+    return forward_impl(n, params, buffers, nbt, image, workspace, logits, features, training ? 1 : 0, stream);
+}
+
+// The training topology on the running statistics, differentiable: `buffers` are only read (mode 2 of forward_impl never passes them to a
+// kernel that writes), num_batches_tracked is not touched, and the backward that follows runs the frozen dataflow.
+int osi_resnet50_forward_frozen(osi_resnet50_t n, const float* params, const float* buffers, const float* image, void* workspace,
+                                float* logits, float* features, osi_stream_t stream) {
+    OSI_REQUIRE(n && params && buffers && workspace && logits && features);
+    return forward_impl(n, params, const_cast<float*>(buffers), nullptr, image, workspace, logits, features, 2, stream);
+}
+
+// training: 0 = inference, 1 = batch statistics + running-statistics update, 2 = frozen (running statistics, backward state kept)
+static int forward_impl(osi_resnet50_t n, const float* params, float* buffers, long long* nbt, const float* image,
+                        void* workspace, float* logits, float* features, int training, osi_stream_t stream) {
     if (!n->plan_unchanged()) return OSI_ERR_STATE;   // a plan-relevant knob changed after create: the workspace no longer fits the plans
     const float* ext = n->x4_ext;
     n->x4_ext = nullptr;
@@ -608,22 +629,23 @@ int osi_resnet50_forward(osi_resnet50_t n, const float* params, float* buffers, 
     const float* x4 = (!image && ext) ? ext : ws + n->x4;
     n->x4_cur = x4;
     n->fwd_done = false;
+    n->frozen = false;
     if (training && n->overlap && (!n->prof_on || n->prof_timeline)) OSI_TRY(n->ensure_side());
     OSI_TRY(n->mark(OSI_PROF_START, st));
     // Winograd weight transforms of every 3x3 stride-1 layer, both directions: the weights are the same for this forward and its backward.
     // On the side stream beside the stem (26 launches of 4 - 16 us that used to sit in front of their convolutions); the first Winograd
     // convolution waits for them.
-    if (n->plan_knobs.fwd_wino || (training && n->plan_knobs.dgrad_wino)) {
+    if (n->plan_knobs.fwd_wino || (training == 1 && n->plan_knobs.dgrad_wino)) {
         // (training forwards only: an inference forward has 13 transforms and nothing but the stem beside them — the fork / join costs more
         // than they do: 7.96 in line vs 8.00 ms aside per batch of 128, profiles/NOTES_r06.md)
-        const bool aside = training && n->async_wgrad();
+        const bool aside = training == 1 && n->async_wgrad();
         hipStream_t wt = aside ? n->side : st;
         if (aside) OSI_TRY(n->fork_side(st));
         for (auto& c : n->convs)
             if (n->plan_knobs.fwd_wino && c.u_fw != (size_t)-1)
                 OSI_TRY(osi_conv_wino_transform_weights(&c.d, params + c.w_off, 0, ws + c.u_fw, osi_conv_wino_weights_bytes(&c.d), wt));
         OSI_TRY(n->mark(OSI_PROF_CONV_FWD, wt));
-        if (training && n->plan_knobs.dgrad_wino) {
+        if (training == 1 && n->plan_knobs.dgrad_wino) {   // (a frozen backward has no Winograd input gradient)
             for (auto& c : n->convs)
                 if (c.u_bw != (size_t)-1)
                     OSI_TRY(osi_conv_wino_transform_weights(&c.d, params + c.w_off, 1, ws + c.u_bw, osi_conv_wino_weights_bytes(&c.d), wt));
@@ -640,6 +662,18 @@ int osi_resnet50_forward(osi_resnet50_t n, const float* params, float* buffers, 
     OSI_TRY(osi_stem_weight_pack(params + c0.w_off, ws + n->wpack, 64, st));
     OSI_TRY(n->mark(OSI_PROF_OTHER, st));
     if (!training && n->eval_fused) return forward_eval_fused(n, params, buffers, ws, x4, logits, features, st);
+    if (training == 2) {      // frozen: every BatchNorm's scale / shift (forward) and mean / invstd (backward) from ONE launch
+        osi_bn_frozen_layer tab[OSI_BN_FROZEN_MAX];
+        const int nb = (int)n->bns.size();
+        if (nb > OSI_BN_FROZEN_MAX) return OSI_ERR_STATE;
+        for (int j = 0; j < nb; ++j) {
+            const BN& b = n->bns[j];
+            tab[j] = osi_bn_frozen_layer{buffers + b.rm_off, buffers + b.rv_off, params + b.g_off, params + b.b_off, ws + b.scale, ws + b.shift,
+                                         ws + b.mean, ws + b.invstd, b.C};
+        }
+        OSI_TRY(osi_bn_frozen_coeffs_multi(tab, nb, 1e-5f, st));
+        OSI_TRY(n->mark(OSI_PROF_BN_FWD, st));
+    }
     OSI_TRY(conv_bn_fwd(n, 0, params, buffers, ws, x4, ws + n->wpack, training, st, n->bn_ws));
     BN& b0 = n->bns[c0.bn];
     // bn1 + relu + maxpool in one pass: the 112x112x64 post-ReLU tensor is never materialised
@@ -676,7 +710,8 @@ int osi_resnet50_forward(osi_resnet50_t n, const float* params, float* buffers, 
     OSI_TRY(head_fwd(n, params, ws, logits, features, st));
     n->any_fwd = true;
     if (training) {
-        OSI_TRY(osi_i64_add(nbt, (int)n->bns.size(), 1, st));
+        if (training == 1) OSI_TRY(osi_i64_add(nbt, (int)n->bns.size(), 1, st));
+        n->frozen = training == 2;
         n->fwd_done = true;
         n->next_stage = 0;
     }
@@ -759,6 +794,56 @@ static int bn_bwd_fused(osi_resnet50* n, int ci, const float* params, float* gra
     return OSI_OK;
 }
 
+// Frozen statistics. Finish the dgamma / dbeta of conv `ci`'s BatchNorm from the row-tile partials a dgrad epilogue left in dg_ws (column
+// `which` as in bn_bwd_fused). Nothing is launched in an input-only backward.
+static int bn_reduce_frozen(osi_resnet50* n, int ci, float* grads, float* ws, int which, hipStream_t st) {
+    if (!n->bw_pg) return OSI_OK;
+    BN& b = n->bns[n->convs[ci].bn];
+    const float* psum_g = ws + n->dg_ws;
+    const float* psum_gx = psum_g + (size_t)(1 + which) * n->fused_P * b.C;
+    OSI_TRY(osi_bn_backward_reduce(psum_g, psum_gx, n->fused_P, grads + b.g_off, grads + b.b_off, b.M, b.C, ws + n->bn_ws, n->bn_ws_bytes, st));
+    return n->mark(OSI_PROF_BN_BWD, st);
+}
+// Frozen statistics. BatchNorm backward of conv `ci` (and `cj` >= 0, the projection shortcut: same gated gradient) from buffer gi:
+// dy = scale * g into buffer dyi (dyj). masked: the gradient is raw and the block-output bitmask of conv `ci` gates it here, the
+// reductions run here too; otherwise they arrive through bn_reduce_frozen. gmasked >= 0: buffer that receives g (identity shortcut).
+static int bn_bwd_frozen(osi_resnet50* n, int ci, int cj, float* grads, float* ws, int gi, int dyi, int dyj, int gmasked, bool masked,
+                         hipStream_t st) {
+    osi_bn_frozen_consumer cs[2];
+    const int idx[2] = {ci, cj}, out[2] = {dyi, dyj};
+    const int nc = cj >= 0 ? 2 : 1;
+    for (int k = 0; k < nc; ++k) {
+        Conv& c = n->convs[idx[k]];
+        BN& b = n->bns[c.bn];
+        const bool red = masked && n->bw_pg;
+        cs[k] = osi_bn_frozen_consumer{ws + c.y, ws + b.mean, ws + b.invstd, ws + b.scale, ws + n->scratch[out[k]],
+                                       red ? grads + b.g_off : nullptr, red ? grads + b.b_off : nullptr};
+    }
+    Conv& c = n->convs[ci];
+    BN& b = n->bns[c.bn];
+    OSI_TRY(osi_bn_backward_frozen(ws + n->scratch[gi], masked ? ws + c.mask : nullptr, cs, nc, gmasked >= 0 ? ws + n->scratch[gmasked] : nullptr,
+                                   b.M, b.C, ws + n->bn_ws, n->bn_ws_bytes, st));
+    return n->mark(OSI_PROF_BN_BWD, st);
+}
+// Frozen statistics. Input gradient of conv `ci` (dy in buffer dyi) into buffer dxi, ending in the BatchNorm backward of the in-block
+// producer `pc`: dxi = scale * gate * dgrad (osi_conv_dgrad_fused_frozen), the producer's dgamma / dbeta merged from the epilogue's partials.
+// The partials are emitted in an input-only backward as well (and dropped): the launch plan — a K-split tail needs their workspace — and
+// with it every bit of dJ/dimage stays the one of the backward with parameter gradients.
+static int dgrad_frozen(osi_resnet50* n, int ci, const float* params, float* grads, float* ws, int dyi, int dxi, int pc, hipStream_t st) {
+    Conv& c = n->convs[ci];
+    Conv& p0 = n->convs[pc];
+    BN& b0 = n->bns[p0.bn];
+    osi_dgrad_fusion f{};
+    f.scale0 = ws + b0.scale; f.shift0 = ws + b0.shift;
+    f.y0 = ws + p0.y; f.mean0 = ws + b0.mean; f.invstd0 = ws + b0.invstd;
+    f.partials = ws + n->dg_ws; f.partials_bytes = n->dg_ws_bytes;
+    int P = 0;
+    OSI_TRY(osi_conv_dgrad_fused_frozen(&c.d, ws + n->scratch[dyi], params + c.w_off, ws + n->scratch[dxi], &f, OSI_TILE_AUTO, &P, st));
+    n->fused_P = P;
+    OSI_TRY(n->mark(OSI_PROF_CONV_DGRAD, st));
+    return bn_reduce_frozen(n, pc, grads, ws, 0, st);
+}
+
 // dgrad of conv `ci` (dy in buffer dyi) into buffer dxi, adding buffer addi (-1: none), with the epilogue fused for the layer
 // that produced this conv's input: its ReLU bitmask and the BatchNorm reductions of conv `pc` (and `pd`, the downsample twin).
 static int dgrad_fused(osi_resnet50* n, int ci, const float* params, float* ws, int dyi, int dxi, int addi, int pc, int pd,
@@ -805,7 +890,32 @@ static int block_backward(osi_resnet50* n, int bi, const float* params, float* g
     const bool ds_sparse = has_ds && bi > 0 && n->convs[k.ds].d.stride == 2 && n->convs[k.ds].d.R == 1;
     int go = n->cur_grad;
     int d3 = -1, dxbase = -1;
-    if (n->go_fused) {
+    if (n->frozen) {
+        // Frozen statistics: one pass turns the (gated) block-output gradient into dy of bn3 and of the shortcut's BatchNorm
+        int t1 = -1;
+        if (has_ds) { t1 = n->take(st); if (t1 < 0) return t1; }
+        if (n->go_fused) {          // already gated, reductions in dg_ws
+            OSI_TRY(bn_reduce_frozen(n, k.c3, grads, ws, 0, st));
+            if (has_ds) OSI_TRY(bn_reduce_frozen(n, k.ds, grads, ws, 1, st));
+            d3 = n->take(st);
+            if (d3 < 0) return d3;
+            OSI_TRY(bn_bwd_frozen(n, k.c3, k.ds, grads, ws, go, d3, t1, -1, false, st));
+            if (has_ds) n->give(go);
+            else dxbase = go;       // identity skip: the gated gradient itself continues to the block input
+        } else {                    // stage entry: raw gradient, gated by the stored bitmask here
+            if (!has_ds) { dxbase = n->take(st); if (dxbase < 0) return dxbase; }
+            OSI_TRY(bn_bwd_frozen(n, k.c3, k.ds, grads, ws, go, go, t1, has_ds ? -1 : dxbase, true, st));
+            d3 = go;
+        }
+        if (has_ds) {
+            Conv& cd = n->convs[k.ds];
+            OSI_TRY(wgrad(n, k.ds, grads, ws, t1, x, st));
+            dxbase = n->take(st);
+            if (dxbase < 0) return dxbase;
+            OSI_TRY(dgrad_plain(n, &cd.d, S(t1), params + cd.w_off, S(dxbase), ds_sparse ? 2 : 0, st));
+            n->give(t1);
+        }
+    } else if (n->go_fused) {
         if (has_ds) {
             Conv& cd = n->convs[k.ds];
             int t1 = n->take(st);
@@ -849,15 +959,17 @@ static int block_backward(osi_resnet50* n, int bi, const float* params, float* g
     OSI_TRY(wgrad(n, k.c3, grads, ws, d3, ws + c2.y, st, c2.bn));
     int t2 = n->take(st);
     if (t2 < 0) return t2;
-    OSI_TRY(dgrad_fused(n, k.c3, params, ws, d3, t2, -1, k.c2, -1, st));
+    if (n->frozen) OSI_TRY(dgrad_frozen(n, k.c3, params, grads, ws, d3, t2, k.c2, st));
+    else OSI_TRY(dgrad_fused(n, k.c3, params, ws, d3, t2, -1, k.c2, -1, st));
     n->give(d3);
-    OSI_TRY(bn_bwd_fused(n, k.c2, params, grads, ws, t2, t2, 0, st));
+    if (!n->frozen) OSI_TRY(bn_bwd_fused(n, k.c2, params, grads, ws, t2, t2, 0, st));
     OSI_TRY(wgrad(n, k.c2, grads, ws, t2, ws + c1.y, st, c1.bn));
     int t3 = n->take(st);
     if (t3 < 0) return t3;
-    OSI_TRY(dgrad_fused(n, k.c2, params, ws, t2, t3, -1, k.c1, -1, st));
+    if (n->frozen) OSI_TRY(dgrad_frozen(n, k.c2, params, grads, ws, t2, t3, k.c1, st));
+    else OSI_TRY(dgrad_fused(n, k.c2, params, ws, t2, t3, -1, k.c1, -1, st));
     n->give(t2);
-    OSI_TRY(bn_bwd_fused(n, k.c1, params, grads, ws, t3, t3, 0, st));
+    if (!n->frozen) OSI_TRY(bn_bwd_fused(n, k.c1, params, grads, ws, t3, t3, 0, st));
     OSI_TRY(wgrad(n, k.c1, grads, ws, t3, x, st));
     if (bi > 0) {
         // the block input is the previous block's output: fuse that block's final ReLU mask and its bn3 (+ downsample BN) reductions
@@ -1017,6 +1129,11 @@ static int backward_stages(osi_resnet50_t n, const float* params, float* grads, 
                 // dJ/dimage (or the adversarial batch) wanted, or a geometry the fused form does not take: the stem's dY is materialised (max-pool scatter + ReLU gate
                 // + bn1 backward gathered on the fly from the pooled gradient into a scratch buffer), its weight gradient comes from that
                 // dY unless input-only, then — for dJ/dimage — the stem's input gradient straight into the caller's NCHW tensor
+                if (n->frozen)   // frozen statistics: dY = scale * (scattered, gated gradient); reductions only for the parameter gradients
+                    OSI_TRY(osi_bn_relu_maxpool_bwd_frozen(S(go), ws + n->pool_idx, ws + c0.y, ws + b0.mean, ws + b0.invstd, ws + b0.scale, S(t),
+                                                           n->bw_pg ? grads + b0.g_off : nullptr, n->bw_pg ? grads + b0.b_off : nullptr, n->B,
+                                                           n->Hs, n->Ws, 64, ws + n->bn_ws, n->bn_ws_bytes, st));
+                else
                 OSI_TRY(osi_bn_relu_maxpool_bwd(S(go), ws + n->pool_idx, ws + c0.y, ws + b0.mean, ws + b0.invstd, params + b0.g_off, S(t),
                                                 n->dgam(grads, ws, b0), n->dbet(grads, ws, b0), n->B, n->Hs, n->Ws, 64, ws + n->bn_ws,
                                                 n->bn_ws_bytes, st));

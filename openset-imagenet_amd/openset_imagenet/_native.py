@@ -39,6 +39,18 @@ class BnEvalLayer(Structure):
                 ("shift", c_void_p), ("C", c_int)]
 
 
+class BnFrozenLayer(Structure):
+    """osi_bn_frozen_layer"""
+    _fields_ = [("running_mean", c_void_p), ("running_var", c_void_p), ("gamma", c_void_p), ("beta", c_void_p), ("scale", c_void_p),
+                ("shift", c_void_p), ("mean", c_void_p), ("invstd", c_void_p), ("C", c_int)]
+
+
+class BnFrozenConsumer(Structure):
+    """osi_bn_frozen_consumer"""
+    _fields_ = [("y", c_void_p), ("mean", c_void_p), ("invstd", c_void_p), ("scale", c_void_p), ("dy", c_void_p), ("dgamma", c_void_p),
+                ("dbeta", c_void_p)]
+
+
 class OptSegment(Structure):
     """osi_opt_segment: the 16-byte units [begin4, end4) of the arena belong to kernel group `group`"""
     _fields_ = [("begin4", ctypes.c_uint), ("end4", ctypes.c_uint), ("group", c_int)]
@@ -164,6 +176,11 @@ _SIGS = {
     "osi_resnet50_debug_gate_shape": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "osi_resnet50_debug_gate": (c_int, [c_void_p, P, c_int, P, P, P]),
     "osi_resnet50_forward": (c_int, [c_void_p, P, P, P, P, P, P, P, c_int, P]),
+    "osi_bn_frozen_coeffs_multi": (c_int, [POINTER(BnFrozenLayer), c_int, c_float, P]),
+    "osi_conv_dgrad_fused_frozen": (c_int, [_PD, P, P, P, P, c_int, POINTER(c_int), P]),
+    "osi_bn_backward_frozen": (c_int, [P, P, POINTER(BnFrozenConsumer), c_int, P, c_int, c_int, P, c_size_t, P]),
+    "osi_bn_relu_maxpool_bwd_frozen": (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, c_size_t, P]),
+    "osi_resnet50_forward_frozen": (c_int, [c_void_p, P, P, P, P, P, P, P]),
     "osi_resnet50_backward": (c_int, [c_void_p, P, P, P, P, P, c_int, c_int, P]),
     "osi_resnet50_backward_ex": (c_int, [c_void_p, P, P, P, P, P, P, c_int, c_int, c_int, P]),
     "osi_resnet50_backward_adv": (c_int, [c_void_p, P, P, P, P, P, P, c_float, c_float, c_float, c_int, c_int, P]),

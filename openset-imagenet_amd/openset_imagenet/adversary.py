@@ -21,7 +21,9 @@ does with two training-mode forwards. j and j_adv are each a mean over their own
   scheduled_epsilon(adv_cfg, epoch)                     max(min_epsilon, epsilon * mu ** (epoch // decay));  decay = 0: constant
 
 Out of scope: "filter" mode (perturbing only the correctly classified known samples changes the batch size per step, and with it the
-executor's geometry), multi-step attacks, adversaries in validate().
+executor's geometry), multi-step attacks, adversaries in validate() — no longer for want of a gradient: in eval mode
+`model.next_backward(fgsm=eps)` BEFORE the forward makes it differentiable on the running statistics and its backward ends in the same
+FGSM epilogue (`adversarial_batch()`), the statistics untouched; wiring that into validate() is not done here.
 """
 import torch
 

@@ -81,10 +81,10 @@ class _BackboneFn(torch.autograd.Function):
     a detached anchor (no parameter requires grad) makes the backward input-only (no parameter gradient is computed)."""
 
     @staticmethod
-    def forward(ctx, image, anchor, model, flip):
+    def forward(ctx, image, anchor, model, flip, frozen=False):
         ctx.model = model
         ctx.set_materialize_grads(False)
-        out = model._run_forward(image, True, flip)
+        out = model._run_forward(image, True, flip, frozen)
         ctx.serial = model._fwd_serial
         return out
 
@@ -95,7 +95,7 @@ class _BackboneFn(torch.autograd.Function):
                                "activations of ONE forward (the reference loop is forward, loss, backward, step — train.py:132-139)")
         want_dx, want_params = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         dimage = ctx.model._run_backward(dlogits, dfeatures, want_image=want_dx, param_grads=want_params)
-        return dimage, None, None, None
+        return dimage, None, None, None, None
 
 
 class ResNet50(nn.Module):
@@ -161,6 +161,8 @@ class ResNet50(nn.Module):
         self._adv_valid = False    # the latest backward wrote adversarial_batch()
         self._adv = {}             # (B, H, W) -> the model-owned NHWC4 buffer the FGSM epilogue writes
         self._flat_grads2 = None   # second gradient arena of an accumulating backward
+        self._bn_frozen = False    # freeze_bn(): BatchNorm on the running statistics (read-only) while the model is differentiated
+        self._eval_plain = False   # the latest forward was an eval-mode inference forward run with grad enabled (no graph)
         self.reset_parameters()
 
     # ------------------------------------------------------------------------------------------------------
@@ -258,13 +260,33 @@ class ResNet50(nn.Module):
             self._ws = torch.empty(net.ws_bytes, dtype=torch.uint8, device=dev)
         return net
 
+    def freeze_bn(self, mode=True):
+        """Freeze (mode=True) or release the BatchNorm statistics of the WHOLE model; returns self. Frozen: every differentiable forward
+        normalises with the running statistics and neither updates them nor num_batches_tracked (fine-tuning on small batches keeps the
+        checkpoint's statistics), and its backward is the frozen form dy = gamma * invstd * g. `model.training` keeps its meaning;
+        in eval mode the statistics are frozen anyway (see forward)."""
+        self._bn_frozen = bool(mode)
+        return self
+
+    @property
+    def bn_frozen(self):
+        """True after freeze_bn() (read-only; eval mode differentiates on the running statistics without it)."""
+        return self._bn_frozen
+
     def next_backward(self, fgsm=None, lo=0.0, hi=1.0, accumulate=False):
         """Request for the ONE backward that follows (whatever route it takes: a fused loss's plain backward(), autograd):
           fgsm = epsilon   its last stage also writes the adversarial batch clamp(x + epsilon * sign(dJ/dx), lo, hi) from the input the
                            forward read (NCHW, NHWC4 or uint8-staged alike) into a model-owned NHWC4 buffer: adversarial_batch();
                            dJ/dimage itself is never written (osi_resnet50_backward_adv);
           accumulate       its parameter gradients go into a second arena that is then added into the first (osi_grad_accumulate), so
-                           p.grad holds the sum of this backward and the one before it, as autograd's accumulation would leave it."""
+                           p.grad holds the sum of this backward and the one before it, as autograd's accumulation would leave it.
+        In eval mode (without freeze_bn()) the request has to PRECEDE the forward: it is what makes that forward differentiable (a plain
+        eval-mode forward builds no graph). A request that arrives after such a forward raises; run plain eval-mode forwards under
+        torch.no_grad(), as validate() does, when requests for later forwards follow them."""
+        if (fgsm is not None or accumulate) and self._eval_plain and not self.training and not self._bn_frozen:
+            raise RuntimeError("next_backward(): the latest forward was an eval-mode inference forward, which keeps nothing to differentiate; "
+                               "in eval mode call next_backward(...) BEFORE the forward it belongs to (or freeze_bn() / requires_grad_ on "
+                               "the image), and run plain eval-mode forwards under torch.no_grad()")
         if fgsm is not None and not float(fgsm) >= 0.0:
             raise ValueError("next_backward: fgsm (epsilon) must be >= 0")
         if not float(lo) <= float(hi):
@@ -305,7 +327,7 @@ class ResNet50(nn.Module):
         if image.dtype not in (torch.float32, torch.uint8):
             raise TypeError("image batch must be float32 [B,3,H,W] (reference: ToTensor(), train.py:259-263) or uint8 [B,H,W,3]")
 
-    def _run_forward(self, image, want_grad, flip=None):
+    def _run_forward(self, image, want_grad, flip=None, frozen=False):
         image = image.contiguous()
         staged = image.dtype == torch.uint8
         bound = not staged and self._is_nhwc4(image)
@@ -322,8 +344,13 @@ class ResNet50(nn.Module):
             raise ValueError("flip flags are only meaningful with a uint8 [B,H,W,3] batch")
         # one custom op = the whole network on the current HIP stream: uint8 batches are staged, NHWC4 batches bound in place
         # (conv1 forward now, conv1 weight gradient at the end of this step's backward), NCHW batches converted on the way in
-        logits, features = N.ops().resnet50_forward(net.h.value, self._flat_params, self._flat_buffers, self._nbt, image, flip,
-                                                    self._ws, self._F, self._O, bool(self.training))
+        if frozen:   # the training topology on the running statistics (read-only), differentiable: osi_resnet50_forward_frozen
+            logits, features = N.ops().resnet50_forward_frozen(net.h.value, self._flat_params, self._flat_buffers, image, flip, self._ws,
+                                                               self._F, self._O)
+        else:
+            logits, features = N.ops().resnet50_forward(net.h.value, self._flat_params, self._flat_buffers, self._nbt, image, flip,
+                                                        self._ws, self._F, self._O, bool(self.training and not self._bn_frozen))
+        self._eval_plain = not frozen and not self.training and torch.is_grad_enabled()
         self._fwd_serial += 1
         self._last = (net, image if (want_grad or bound) else None)   # keeps a bound batch alive until the next forward
         return logits, features
@@ -393,9 +420,16 @@ class ResNet50(nn.Module):
         `image` is the reference's fp32 [B,3,H,W] batch in [0,1], or — the device-side input pipeline — a uint8 [B,H,W,3] batch
         of decoded, cropped RGB rows with optional per-image horizontal-flip flags (ToTensor(), RandomHorizontalFlip and the
         layout staging then happen in one pass on the GPU and the host link carries a quarter of the bytes), or an fp32
-        [B,H,W,4] batch already staged in the executor's layout by pipeline.DevicePrefetcher (read in place)."""
+        [B,H,W,4] batch already staged in the executor's layout by pipeline.DevicePrefetcher (read in place).
+
+        With grad enabled: in training mode the forward is differentiable on batch statistics (which it updates) — unless freeze_bn()
+        is on: then, and in eval mode whenever something asks for a gradient (freeze_bn(), an image that requires grad, a pending
+        next_backward(...) request), it is differentiable on the running statistics, which it leaves untouched (the frozen route).
+        Every other eval-mode forward is the inference forward without a graph."""
         self._check_image(image)
-        if torch.is_grad_enabled() and self.training:
+        frozen = self._bn_frozen or not self.training
+        differentiable = self.training or self._bn_frozen or image.requires_grad or self._bw_request is not None
+        if torch.is_grad_enabled() and differentiable:
             image_grad = image.requires_grad
             if image_grad and self._is_nhwc4(image):
                 raise ValueError("only NCHW fp32 [B, 3, H, W] image batches are differentiable; an NHWC4 batch "
@@ -404,7 +438,7 @@ class ResNet50(nn.Module):
             if param_grad or image_grad:
                 # no parameter requires grad: a detached anchor, so the backward runs input-only
                 anchor = self._anchor if param_grad else self._anchor.detach()
-                return _BackboneFn.apply(image, anchor, self, flip)
+                return _BackboneFn.apply(image, anchor, self, flip, frozen)
         return self._run_forward(image, False, flip)
 
 

@@ -341,6 +341,16 @@ def dist_env():
 _last_worker_state = {}   # introspection for tests: the objects of the most recent worker() call in this process
 
 
+def _freeze_bn_of(cfg):
+    """The optional top-level key `freeze_bn` (on / off, true / false; absent = off)."""
+    value = getattr(cfg, "freeze_bn", False)
+    if isinstance(value, str):
+        if value.lower() not in ("on", "off", "true", "false", "yes", "no"):
+            raise ValueError(f"freeze_bn: expected on / off, got {value!r}")
+        return value.lower() in ("on", "true", "yes")
+    return bool(value)
+
+
 def worker(cfg):
     """Creates datasets, model, loss, optimizer, runs the epoch loop with checkpoints — the reference's worker()
     (train.py:237-482) reduced to what drives the hot path. Same cfg keys (config/train.yaml), same checkpoint files
@@ -470,6 +480,10 @@ def _worker_body(cfg, log, out_dir, rank, world, distributed):
         else:
             start_epoch, best_score = load_checkpoint(model, cfg.checkpoint, opt, scheduler)
         log.info(f"Loaded {cfg.checkpoint} at epoch {start_epoch}")
+    # top-level `freeze_bn: on` (absent = off): BatchNorm on the running statistics, read-only, while the weights train (model.freeze_bn)
+    if _freeze_bn_of(cfg):
+        model.freeze_bn()
+        log.info("BatchNorm statistics frozen (freeze_bn: on)")
     net = _dp.DistributedDataParallel(model) if distributed else model   # broadcasts rank 0's parameters and BN buffers
     _last_worker_state.clear()
     _last_worker_state.update(model=model, optimizer=opt, rank=rank, world=world, checkpoints_written=0, sharded_validation=shard_val)
