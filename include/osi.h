@@ -530,6 +530,35 @@ int osi_resnet50_backward_adv(osi_resnet50_t net, const float* params, float* gr
  * for nothing and goes on with the next stage while the collective runs (reference intent: config/train.yaml:18,35-39). */
 int osi_resnet50_grads_ready(osi_resnet50_t net, osi_stream_t main_stream, osi_stream_t waiter_stream);
 
+/* ABI 13. Fine-tuning a suffix. The network is 18 UNITS in forward order: 0 = the stem (conv1, bn1), 1 .. 16 = the bottlenecks
+ * layer1.0 .. layer4.2 (three convolutions, three BatchNorms, plus the downsample pair on block 0 of a layer), 17 = the head (fc,
+ * logits). tensor_unit / bn_unit: the unit of parameter tensor i / BatchNorm j, -1 on a bad index.
+ * osi_resnet50_set_trainable(net, unit_mask, eval_prefix_units): bit u of unit_mask = unit u has a parameter somebody trains; c = the
+ * lowest set bit is the CUT, the units below it the frozen prefix. Default (0x3FFFF, 0): every launch of every entry point as before.
+ *   backward without an image gradient (osi_resnet50_backward; _ex with dimage = NULL, param_grads = 1): runs from the head down to
+ *     unit c and launches nothing more. The gradient w.r.t. unit c's input is not computed: block c leaves out conv1's input gradient
+ *     (the one fused with the previous block's gate and reductions) and the downsample's input gradient; c = 1 leaves out block 0's
+ *     pool-mode input gradient and the whole stem tail; c = 17 leaves out fc's dx and osi_avgpool_bwd. Unit c's own BatchNorm
+ *     reductions arrive as ever (in-unit input-gradient epilogues; the block above, or the stage-entry BatchNorm backward). A stage
+ *     wholly below the cut is accepted in order, launches nothing, advances and joins; the last stage ends the backward.
+ *   every backward (plain, _ex with dimage, _adv): a frozen unit (bit clear) gets no conv / fc / logits weight-gradient launch and
+ *     its slices of `grads` are not written; under frozen statistics its parameter-only BatchNorm reductions are left out, under batch
+ *     statistics the reductions dx needs still run (into workspace). With dimage / x_adv the input gradients run to full depth.
+ *   forward with eval_prefix_units = p > 0 (osi_resnet50_forward(training = 1), osi_resnet50_forward_frozen; training = 0 ignores
+ *     p): units 0 .. p-1 run the inference forms on the running statistics (coefficients from one osi_bn_eval_coeffs_multi launch over
+ *     their BatchNorms), keep no backward state, update neither running statistics nor num_batches_tracked; units p .. 17 run the
+ *     requested topology (running-statistics update and num_batches_tracked + 1, or osi_bn_frozen_coeffs_multi, over their BatchNorms
+ *     only). After such a forward a backward with dimage / x_adv returns OSI_ERR_STATE and launches nothing, and
+ *     osi_resnet50_debug_gate returns OSI_ERR_STATE for the gates of units below p.
+ * The setting takes effect at the next forward and holds for it and its backward: a call between a differentiable forward and the last
+ * stage of its backward returns OSI_ERR_STATE (option "forget_forward" gives such a forward up). OSI_ERR_ARG: unit_mask == 0 (that is
+ * param_grads = 0), a bit at or above 18, eval_prefix_units < 0 or > c. */
+int osi_resnet50_num_units(osi_resnet50_t net);                 /* 18 */
+int osi_resnet50_tensor_unit(osi_resnet50_t net, int i);
+int osi_resnet50_bn_unit(osi_resnet50_t net, int j);
+int osi_resnet50_set_trainable(osi_resnet50_t net, unsigned unit_mask, int eval_prefix_units);
+int osi_resnet50_get_trainable(osi_resnet50_t net, unsigned* unit_mask, int* eval_prefix_units);
+
 /* Per-executor switches: "overlap" (default 1: weight gradients on a low-priority side stream, overlapped with dgrad / BatchNorm
  * backward and joined back into `stream` at the end of every backward call unless "stage_join" = 0; 0 serialises everything on the
  * caller's stream), "fwd_fork" (projection shortcut of the forward pass on the side stream, default 1), "side_priority_normal" (side
@@ -537,7 +566,8 @@ int osi_resnet50_grads_ready(osi_resnet50_t net, osi_stream_t main_stream, osi_s
  * osi_resnet50_grads_ready), "eval_fused" (default 1: a forward with training = 0 runs the inference forms — every BatchNorm +
  * shortcut + ReLU in its convolution's epilogue, no pre-BN tensor, no block-output pass, no bitmask, one coefficient launch for all 53
  * BatchNorms; 0 = the training topology on running statistics, kept for A/B: bit-identical when both run the same launch plans (knob
- * "tail_split" off), fp32-rounding-level differences otherwise).
+ * "tail_split" off), fp32-rounding-level differences otherwise), "forget_forward" (an action, value != 0: the latest differentiable
+ * forward will get no backward; its state is given up, so osi_resnet50_set_trainable is accepted again).
  * Unknown name -> OSI_ERR_ARG; so are the settled A/B switches retired with ABI 9. */
 int osi_resnet50_set_option(osi_resnet50_t net, const char* name, int value);
 

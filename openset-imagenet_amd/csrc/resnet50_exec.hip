@@ -25,6 +25,7 @@ struct Tensor {
     std::string name;
     int ndim; int shape[4];
     size_t off, numel;  // floats in the param arena
+    int unit;           // fine-tuning unit (0 = stem, 1..16 = bottlenecks in forward order, 17 = head)
 };
 struct BN {
     std::string prefix;
@@ -33,6 +34,7 @@ struct BN {
     size_t rm_off, rv_off;  // buffer arena
     size_t mean, invstd, scale, shift;  // workspace (floats)
     size_t dsink;           // workspace: [2][C] dgamma / dbeta of a backward that writes no parameter gradient
+    int unit;
 };
 struct Conv {
     osi_conv_desc d;
@@ -42,6 +44,7 @@ struct Conv {
     size_t a;      // workspace: BN(+res)+ReLU output (SIZE_MAX for downsample: goes to scratch)
     size_t mask;   // workspace: ReLU bitmask of `a` (1 bit per element)
     size_t u_fw = (size_t)-1, u_bw = (size_t)-1;   // workspace: Winograd-transformed weights (forward / input-gradient form), 3x3 stride-1 layers only
+    int unit;
 };
 struct Block {
     int c1, c2, c3, ds;  // conv indices, ds = -1 if identity skip
@@ -120,11 +123,26 @@ struct osi_resnet50 {
         return OSI_OK;
     }
 
+    // Fine-tuning units (osi_resnet50_set_trainable). unit_mask: bit u = unit u has a trainable parameter; the units below the lowest set
+    // bit (the cut) are the frozen prefix. A backward that owes nobody an image gradient stops at the cut, and a frozen unit gets no
+    // weight gradient in any backward. eval_prefix: that many leading units run the inference forms in a differentiable forward.
+    // The setting cannot change between a differentiable forward and the end of its backward, so the backward reads it as it stands.
+    static constexpr int NUNITS = 18;
+    int cur_unit = 0;                // unit of the tensors being registered (osi_resnet50_create)
+    unsigned unit_mask = (1u << NUNITS) - 1;
+    int eval_prefix = 0;
+    int fw_prefix = 0;               // eval_prefix of the latest differentiable forward: the gates of those units do not exist
+    bool trainable(int unit) const { return (unit_mask >> unit) & 1u; }
+    int cut() const { int c = 0; while (!((unit_mask >> c) & 1u)) ++c; return c; }
+    // first unit the backward in flight computes: the cut, unless the image gradient is wanted (then full depth)
+    int bw_stop() const { return (bw_pg && !bw_dimage && !bw_adv) ? cut() : 0; }
+
     size_t add_tensor(const std::string& name, int ndim, const int* shape) {
         Tensor t; t.name = name; t.ndim = ndim; t.numel = 1;
         for (int i = 0; i < 4; ++i) t.shape[i] = i < ndim ? shape[i] : 1;
         for (int i = 0; i < ndim; ++i) t.numel *= (size_t)shape[i];
         t.off = param_floats;
+        t.unit = cur_unit;
         param_floats = up(param_floats + t.numel, 4);
         tensors.push_back(t);
         return t.off;
@@ -148,6 +166,7 @@ struct osi_resnet50 {
         b.rm_off = buffer_floats; buffer_floats += up(Cout, 4);
         b.rv_off = buffer_floats; buffer_floats += up(Cout, 4);
         b.mean = ws_alloc(Cout); b.invstd = ws_alloc(Cout); b.scale = ws_alloc(Cout); b.shift = ws_alloc(Cout);
+        b.unit = c.unit = cur_unit;
         c.bn = (int)bns.size();
         bns.push_back(b);
         size_t n = (size_t)b.M * Cout;
@@ -175,8 +194,9 @@ struct osi_resnet50 {
     // the FGSM epilogue (osi_stem_dgrad_fgsm) that writes the adversarial NHWC4 batch; dJ/dimage itself is never written
     float* bw_adv = nullptr;
     float bw_eps = 0.f, bw_lo = 0.f, bw_hi = 0.f;
-    float* dgam(float* grads, float* ws, const BN& b) const { return bw_pg ? grads + b.g_off : ws + b.dsink; }
-    float* dbet(float* grads, float* ws, const BN& b) const { return bw_pg ? grads + b.b_off : ws + b.dsink + b.C; }
+    // (a frozen unit's reductions, which the batch-statistics dx still needs, land in the sink as well)
+    float* dgam(float* grads, float* ws, const BN& b) const { return bw_pg && trainable(b.unit) ? grads + b.g_off : ws + b.dsink; }
+    float* dbet(float* grads, float* ws, const BN& b) const { return bw_pg && trainable(b.unit) ? grads + b.b_off : ws + b.dsink + b.C; }
     // The stem tail's form, decided by what the backward can observe. Block 0's last input gradient and the tail both ask here, so they
     // cannot disagree: the fused form (bn1's reductions out of that input gradient's pool-mode epilogue, dY built inside
     // osi_stem_wgrad_fused's loader) unless dJ/dimage (or the adversarial batch made from it) needs dY in memory or the geometry /
@@ -279,6 +299,7 @@ int osi_resnet50_create(osi_resnet50_t* out, int B, int H, int W, int fc_dim, in
     n->x4 = n->ws_alloc((size_t)B * H * W * 4);
     n->wpack = n->ws_alloc(64 * 224);
     n->gpack = n->ws_alloc(64 * 224);
+    n->cur_unit = 0;
     int stem = n->add_conv_bn(rb + "conv1", rb + "bn1", B, H, W, 4, 64, 7, 2, 3, false);   // its activation only exists max-pooled
     n->Hs = n->convs[stem].d.Ho; n->Ws = n->convs[stem].d.Wo;
     n->Hp = (n->Hs + 2 - 3) / 2 + 1; n->Wp = (n->Ws + 2 - 3) / 2 + 1;
@@ -294,6 +315,7 @@ int osi_resnet50_create(osi_resnet50_t* out, int B, int H, int W, int fc_dim, in
             const std::string pre = rb + "layer" + std::to_string(s + 1) + "." + std::to_string(b) + ".";
             const int st = b == 0 ? strides[s] : 1;
             Block blk{};
+            n->cur_unit = (int)n->blocks.size() + 1;
             blk.x_in = x; blk.stage = 3 - s;
             // conv1 / conv2: only the pre-BN output is kept (their activation is recomputed in the consumers' loaders)
             blk.c1 = n->add_conv_bn(pre + "conv1", pre + "bn1", B, h, w, inpl, planes[s], 1, 1, 0, false);
@@ -311,6 +333,7 @@ int osi_resnet50_create(osi_resnet50_t* out, int B, int H, int W, int fc_dim, in
     n->stage_lo[3] = 0;  // the stem belongs to the last backward stage
     n->Hf = h; n->Wf = w;
     // head
+    n->cur_unit = osi_resnet50::NUNITS - 1;
     { int shp[2] = {fc_dim, 2048}; n->t_fc_w = (int)n->tensors.size(); n->add_tensor(rb + "fc.weight", 2, shp); }
     { int shp[1] = {fc_dim}; n->t_fc_b = (int)n->tensors.size(); n->add_tensor(rb + "fc.bias", 1, shp); }
     { int shp[2] = {out_features, fc_dim}; n->t_lg_w = (int)n->tensors.size(); n->add_tensor("logits.weight", 2, shp); }
@@ -379,6 +402,25 @@ int osi_resnet50_num_bn(osi_resnet50_t net) { return net ? (int)net->bns.size() 
 size_t osi_resnet50_buffer_floats(osi_resnet50_t net) { return net ? net->buffer_floats : 0; }
 size_t osi_resnet50_workspace_bytes(osi_resnet50_t net) { return net ? net->ws_floats * sizeof(float) : 0; }
 int osi_resnet50_num_stages(osi_resnet50_t net) { return net ? net->n_stages : 0; }
+int osi_resnet50_num_units(osi_resnet50_t net) { return net ? osi_resnet50::NUNITS : 0; }
+int osi_resnet50_tensor_unit(osi_resnet50_t net, int i) { return net && i >= 0 && i < (int)net->tensors.size() ? net->tensors[i].unit : -1; }
+int osi_resnet50_bn_unit(osi_resnet50_t net, int j) { return net && j >= 0 && j < (int)net->bns.size() ? net->bns[j].unit : -1; }
+int osi_resnet50_set_trainable(osi_resnet50_t net, unsigned unit_mask, int eval_prefix_units) {
+    OSI_REQUIRE(net && unit_mask != 0 && (unit_mask >> osi_resnet50::NUNITS) == 0 && eval_prefix_units >= 0);
+    int c = 0;
+    while (!((unit_mask >> c) & 1u)) ++c;
+    OSI_REQUIRE(eval_prefix_units <= c);
+    if (net->fwd_done) return OSI_ERR_STATE;   // a backward is owed to the forward that ran under the current setting
+    net->unit_mask = unit_mask;
+    net->eval_prefix = eval_prefix_units;
+    return OSI_OK;
+}
+int osi_resnet50_get_trainable(osi_resnet50_t net, unsigned* unit_mask, int* eval_prefix_units) {
+    OSI_REQUIRE(net && unit_mask && eval_prefix_units);
+    *unit_mask = net->unit_mask;
+    *eval_prefix_units = net->eval_prefix;
+    return OSI_OK;
+}
 int osi_resnet50_geometry(osi_resnet50_t net, int* B, int* H, int* W) {
     OSI_REQUIRE(net);
     if (B) *B = net->B;
@@ -531,67 +573,75 @@ static int head_fwd(osi_resnet50* n, const float* params, float* ws, float* logi
 // (tail_split off); where the plans differ, the two differ at fp32-rounding level.
 // Buffers: conv1 / conv2 / shortcut activations live where the training forward keeps those layers' pre-BN tensors, the block outputs
 // where it keeps them; the workspace then holds no backward state (fwd_done and any_fwd are cleared).
-static int forward_eval_fused(osi_resnet50* n, const float* params, const float* buffers, float* ws, const float* x4, float* logits,
-                              float* features, hipStream_t st) {
-    {
-        osi_bn_eval_layer tab[OSI_BN_MULTI_MAX];
-        const int nb = (int)n->bns.size();
-        if (nb > OSI_BN_MULTI_MAX) return OSI_ERR_STATE;
-        for (int j = 0; j < nb; ++j) {
-            const BN& b = n->bns[j];
-            tab[j] = osi_bn_eval_layer{buffers + b.rm_off, buffers + b.rv_off, params + b.g_off, params + b.b_off, ws + b.scale, ws + b.shift, b.C};
-        }
-        OSI_TRY(osi_bn_eval_coeffs_multi(tab, nb, 1e-5f, st));
-        OSI_TRY(n->mark(OSI_PROF_BN_FWD, st));
+// The pieces of the inference forward, shared with the frozen prefix of a differentiable forward (osi_resnet50_set_trainable,
+// eval_prefix_units > 0). Coefficients of the BatchNorms of units [0, units) from ONE launch:
+static int eval_coeffs(osi_resnet50* n, const float* params, const float* buffers, float* ws, int units, hipStream_t st) {
+    osi_bn_eval_layer tab[OSI_BN_MULTI_MAX];
+    int nb = 0;
+    for (const BN& b : n->bns) {
+        if (b.unit >= units) continue;
+        if (nb == OSI_BN_MULTI_MAX) return OSI_ERR_STATE;
+        tab[nb++] = osi_bn_eval_layer{buffers + b.rm_off, buffers + b.rv_off, params + b.g_off, params + b.b_off, ws + b.scale, ws + b.shift, b.C};
     }
+    OSI_TRY(osi_bn_eval_coeffs_multi(tab, nb, 1e-5f, st));
+    return n->mark(OSI_PROF_BN_FWD, st);
+}
+static int stem_fwd_eval(osi_resnet50* n, float* ws, const float* x4, hipStream_t st) {
     Conv& c0 = n->convs[0];
     OSI_TRY(osi_conv_fwd(&c0.d, x4, ws + n->wpack, ws + c0.y, OSI_TILE_AUTO, st));
     OSI_TRY(n->mark(OSI_PROF_CONV_FWD, st));
     BN& b0 = n->bns[c0.bn];
     OSI_TRY(osi_bn_relu_maxpool_fwd(ws + c0.y, ws + b0.scale, ws + b0.shift, ws + n->a_pool, ws + n->pool_idx, n->B, n->Hs, n->Ws, 64, st));
-    OSI_TRY(n->mark(OSI_PROF_BN_FWD, st));
+    return n->mark(OSI_PROF_BN_FWD, st);
+}
+static int block_fwd_eval(osi_resnet50* n, Block& k, const float* params, float* ws, hipStream_t st) {
     auto epi = [&](int ci, const float* res, int relu) {
         const BN& b = n->bns[n->convs[ci].bn];
         return osi_conv_epilogue{ws + b.scale, ws + b.shift, res, relu};
     };
-    for (Block& k : n->blocks) {
-        const float* x = ws + k.x_in;
-        Conv &c1 = n->convs[k.c1], &c2 = n->convs[k.c2], &c3 = n->convs[k.c3];
-        const bool fork = k.ds >= 0 && n->fwd_fork && n->async_wgrad();
-        if (k.ds >= 0) {            // the projection shortcut only depends on the block input: beside the main branch where a side stream exists
-            Conv& cd = n->convs[k.ds];
-            hipStream_t ds_st = st;
-            if (fork) {
-                OSI_TRY(n->fork_side(st));
-                ds_st = n->side;
-            }
-            const osi_conv_epilogue e = epi(k.ds, nullptr, 0);
-            OSI_TRY(osi_conv_fwd_epilogue(&cd.d, x, params + cd.w_off, ws + cd.y, &e, ws + (fork ? n->bn_ws2 : n->bn_ws), n->bn_ws_bytes, ds_st));
-            OSI_TRY(n->mark(OSI_PROF_CONV_FWD, ds_st));
-            if (fork && hipEventRecord(n->ev_join, n->side) != hipSuccess) return OSI_ERR_LAUNCH;
+    const float* x = ws + k.x_in;
+    Conv &c1 = n->convs[k.c1], &c2 = n->convs[k.c2], &c3 = n->convs[k.c3];
+    const bool fork = k.ds >= 0 && n->fwd_fork && n->async_wgrad();
+    if (k.ds >= 0) {            // the projection shortcut only depends on the block input: beside the main branch where a side stream exists
+        Conv& cd = n->convs[k.ds];
+        hipStream_t ds_st = st;
+        if (fork) {
+            OSI_TRY(n->fork_side(st));
+            ds_st = n->side;
         }
-        {
-            const osi_conv_epilogue e = epi(k.c1, nullptr, 1);
-            OSI_TRY(osi_conv_fwd_epilogue(&c1.d, x, params + c1.w_off, ws + c1.y, &e, ws + n->bn_ws, n->bn_ws_bytes, st));
-            OSI_TRY(n->mark(OSI_PROF_CONV_FWD, st));
-        }
-        {
-            const osi_conv_epilogue e = epi(k.c2, nullptr, 1);
-            if (n->plan_knobs.fwd_wino && c2.u_fw != (size_t)-1) {     // 3x3 / stride 1: Winograd F(2x2,3x3)
-                OSI_TRY(n->wait_weight_transforms(st));
-                OSI_TRY(osi_conv_fwd_wino_epilogue_pre(&c2.d, ws + c1.y, ws + c2.u_fw, ws + c2.y, &e, ws + n->wino_ws, n->wino_ws_bytes, st));
-            } else {
-                OSI_TRY(osi_conv_fwd_epilogue(&c2.d, ws + c1.y, params + c2.w_off, ws + c2.y, &e, ws + n->bn_ws, n->bn_ws_bytes, st));
-            }
-            OSI_TRY(n->mark(OSI_PROF_CONV_FWD, st));
-        }
-        if (fork && hipStreamWaitEvent(st, n->ev_join, 0) != hipSuccess) return OSI_ERR_LAUNCH;
-        {
-            const osi_conv_epilogue e = epi(k.c3, k.ds >= 0 ? ws + n->convs[k.ds].y : x, 1);
-            OSI_TRY(osi_conv_fwd_epilogue(&c3.d, ws + c2.y, params + c3.w_off, ws + c3.a, &e, ws + n->bn_ws, n->bn_ws_bytes, st));
-            OSI_TRY(n->mark(OSI_PROF_CONV_FWD, st));
-        }
+        const osi_conv_epilogue e = epi(k.ds, nullptr, 0);
+        OSI_TRY(osi_conv_fwd_epilogue(&cd.d, x, params + cd.w_off, ws + cd.y, &e, ws + (fork ? n->bn_ws2 : n->bn_ws), n->bn_ws_bytes, ds_st));
+        OSI_TRY(n->mark(OSI_PROF_CONV_FWD, ds_st));
+        if (fork && hipEventRecord(n->ev_join, n->side) != hipSuccess) return OSI_ERR_LAUNCH;
     }
+    {
+        const osi_conv_epilogue e = epi(k.c1, nullptr, 1);
+        OSI_TRY(osi_conv_fwd_epilogue(&c1.d, x, params + c1.w_off, ws + c1.y, &e, ws + n->bn_ws, n->bn_ws_bytes, st));
+        OSI_TRY(n->mark(OSI_PROF_CONV_FWD, st));
+    }
+    {
+        const osi_conv_epilogue e = epi(k.c2, nullptr, 1);
+        if (n->plan_knobs.fwd_wino && c2.u_fw != (size_t)-1) {     // 3x3 / stride 1: Winograd F(2x2,3x3)
+            OSI_TRY(n->wait_weight_transforms(st));
+            OSI_TRY(osi_conv_fwd_wino_epilogue_pre(&c2.d, ws + c1.y, ws + c2.u_fw, ws + c2.y, &e, ws + n->wino_ws, n->wino_ws_bytes, st));
+        } else {
+            OSI_TRY(osi_conv_fwd_epilogue(&c2.d, ws + c1.y, params + c2.w_off, ws + c2.y, &e, ws + n->bn_ws, n->bn_ws_bytes, st));
+        }
+        OSI_TRY(n->mark(OSI_PROF_CONV_FWD, st));
+    }
+    if (fork && hipStreamWaitEvent(st, n->ev_join, 0) != hipSuccess) return OSI_ERR_LAUNCH;
+    {
+        const osi_conv_epilogue e = epi(k.c3, k.ds >= 0 ? ws + n->convs[k.ds].y : x, 1);
+        OSI_TRY(osi_conv_fwd_epilogue(&c3.d, ws + c2.y, params + c3.w_off, ws + c3.a, &e, ws + n->bn_ws, n->bn_ws_bytes, st));
+        OSI_TRY(n->mark(OSI_PROF_CONV_FWD, st));
+    }
+    return OSI_OK;
+}
+static int forward_eval_fused(osi_resnet50* n, const float* params, const float* buffers, float* ws, const float* x4, float* logits,
+                              float* features, hipStream_t st) {
+    OSI_TRY(eval_coeffs(n, params, buffers, ws, osi_resnet50::NUNITS, st));
+    OSI_TRY(stem_fwd_eval(n, ws, x4, st));
+    for (Block& k : n->blocks) OSI_TRY(block_fwd_eval(n, k, params, ws, st));
     OSI_TRY(head_fwd(n, params, ws, logits, features, st));
     n->any_fwd = false;           // no pre-BN tensors, bitmasks or arg-max decisions of a training forward remain (osi_resnet50_debug_gate)
     OSI_TRY(n->mark(OSI_PROF_OTHER, st));
@@ -630,6 +680,8 @@ static int forward_impl(osi_resnet50_t n, const float* params, float* buffers, l
     n->x4_cur = x4;
     n->fwd_done = false;
     n->frozen = false;
+    // units [0, p) of a differentiable forward run the inference forms on the running statistics (an inference forward ignores it)
+    const int p = training ? n->eval_prefix : 0;
     if (training && n->overlap && (!n->prof_on || n->prof_timeline)) OSI_TRY(n->ensure_side());
     OSI_TRY(n->mark(OSI_PROF_START, st));
     // Winograd weight transforms of every 3x3 stride-1 layer, both directions: the weights are the same for this forward and its backward.
@@ -646,10 +698,13 @@ static int forward_impl(osi_resnet50_t n, const float* params, float* buffers, l
                 OSI_TRY(osi_conv_wino_transform_weights(&c.d, params + c.w_off, 0, ws + c.u_fw, osi_conv_wino_weights_bytes(&c.d), wt));
         OSI_TRY(n->mark(OSI_PROF_CONV_FWD, wt));
         if (training == 1 && n->plan_knobs.dgrad_wino) {   // (a frozen backward has no Winograd input gradient)
+            int nt = 0;      // (no backward ever reaches the inference-form prefix)
             for (auto& c : n->convs)
-                if (c.u_bw != (size_t)-1)
+                if (c.u_bw != (size_t)-1 && c.unit >= p) {
                     OSI_TRY(osi_conv_wino_transform_weights(&c.d, params + c.w_off, 1, ws + c.u_bw, osi_conv_wino_weights_bytes(&c.d), wt));
-            OSI_TRY(n->mark(OSI_PROF_CONV_DGRAD, wt));
+                    ++nt;
+                }
+            if (nt) OSI_TRY(n->mark(OSI_PROF_CONV_DGRAD, wt));
         }
         if (aside) {
             if (hipEventRecord(n->ev_wt, n->side) != hipSuccess) return OSI_ERR_LAUNCH;
@@ -662,27 +717,38 @@ static int forward_impl(osi_resnet50_t n, const float* params, float* buffers, l
     OSI_TRY(osi_stem_weight_pack(params + c0.w_off, ws + n->wpack, 64, st));
     OSI_TRY(n->mark(OSI_PROF_OTHER, st));
     if (!training && n->eval_fused) return forward_eval_fused(n, params, buffers, ws, x4, logits, features, st);
+    if (p > 0) OSI_TRY(eval_coeffs(n, params, buffers, ws, p, st));
     if (training == 2) {      // frozen: every BatchNorm's scale / shift (forward) and mean / invstd (backward) from ONE launch
         osi_bn_frozen_layer tab[OSI_BN_FROZEN_MAX];
-        const int nb = (int)n->bns.size();
-        if (nb > OSI_BN_FROZEN_MAX) return OSI_ERR_STATE;
-        for (int j = 0; j < nb; ++j) {
-            const BN& b = n->bns[j];
-            tab[j] = osi_bn_frozen_layer{buffers + b.rm_off, buffers + b.rv_off, params + b.g_off, params + b.b_off, ws + b.scale, ws + b.shift,
-                                         ws + b.mean, ws + b.invstd, b.C};
+        int nb = 0;
+        for (const BN& b : n->bns) {
+            if (b.unit < p) continue;
+            if (nb == OSI_BN_FROZEN_MAX) return OSI_ERR_STATE;
+            tab[nb++] = osi_bn_frozen_layer{buffers + b.rm_off, buffers + b.rv_off, params + b.g_off, params + b.b_off, ws + b.scale, ws + b.shift,
+                                            ws + b.mean, ws + b.invstd, b.C};
         }
-        OSI_TRY(osi_bn_frozen_coeffs_multi(tab, nb, 1e-5f, st));
-        OSI_TRY(n->mark(OSI_PROF_BN_FWD, st));
+        if (nb) {
+            OSI_TRY(osi_bn_frozen_coeffs_multi(tab, nb, 1e-5f, st));
+            OSI_TRY(n->mark(OSI_PROF_BN_FWD, st));
+        }
     }
+    if (p > 0) {
+        OSI_TRY(stem_fwd_eval(n, ws, x4, st));
+    } else {
     OSI_TRY(conv_bn_fwd(n, 0, params, buffers, ws, x4, ws + n->wpack, training, st, n->bn_ws));
     BN& b0 = n->bns[c0.bn];
     // bn1 + relu + maxpool in one pass: the 112x112x64 post-ReLU tensor is never materialised
     OSI_TRY(osi_bn_relu_maxpool_fwd(ws + c0.y, ws + b0.scale, ws + b0.shift, ws + n->a_pool, ws + n->pool_idx, n->B, n->Hs, n->Ws, 64, st));
     OSI_TRY(n->mark(OSI_PROF_BN_FWD, st));
+    }
     // bottleneck blocks. Only the block outputs (residual sums) are materialised: conv2 / conv3 read the pre-BN output of the conv
     // before them and apply its BatchNorm + ReLU in their operand loader; the projection shortcut's BatchNorm is applied inside the
     // block-output kernel. Per block: 3 (4) convs + one block-output pass instead of 3 (4) convs + 3 (4) apply passes.
     for (Block& k : n->blocks) {
+        if (n->convs[k.c1].unit < p) {      // frozen prefix: the inference form; it leaves the finished block output where the next block reads it
+            OSI_TRY(block_fwd_eval(n, k, params, ws, st));
+            continue;
+        }
         const float* x = ws + k.x_in;
         const bool fork = k.ds >= 0 && n->fwd_fork && n->async_wgrad();
         if (k.ds >= 0) {            // the projection shortcut only depends on the block input: beside the main branch (own BN scratch)
@@ -710,7 +776,12 @@ static int forward_impl(osi_resnet50_t n, const float* params, float* buffers, l
     OSI_TRY(head_fwd(n, params, ws, logits, features, st));
     n->any_fwd = true;
     if (training) {
-        if (training == 1) OSI_TRY(osi_i64_add(nbt, (int)n->bns.size(), 1, st));
+        if (training == 1) {      // the BatchNorms that ran on batch statistics: those of units >= p, the tail of the forward-ordered table
+            int j0 = 0;
+            while (j0 < (int)n->bns.size() && n->bns[j0].unit < p) ++j0;
+            if (j0 < (int)n->bns.size()) OSI_TRY(osi_i64_add(nbt + j0, (int)n->bns.size() - j0, 1, st));
+        }
+        n->fw_prefix = p;
         n->frozen = training == 2;
         n->fwd_done = true;
         n->next_stage = 0;
@@ -758,6 +829,7 @@ static int wgrad_launch(osi_resnet50* n, int ci, float* grads, float* ws, int gi
 
 static int wgrad(osi_resnet50* n, int ci, float* grads, float* ws, int gi, const float* conv_in, hipStream_t st, int in_bn = -1) {
     if (!n->bw_pg) return OSI_OK;      // input-only backward: no weight gradient of any kind
+    if (!n->trainable(n->convs[ci].unit)) return OSI_OK;   // frozen unit: nobody reads its slice of the gradient arena
     return wgrad_launch(n, ci, grads, ws, gi, conv_in, st, in_bn, n->async_wgrad());
 }
 
@@ -799,6 +871,7 @@ static int bn_bwd_fused(osi_resnet50* n, int ci, const float* params, float* gra
 static int bn_reduce_frozen(osi_resnet50* n, int ci, float* grads, float* ws, int which, hipStream_t st) {
     if (!n->bw_pg) return OSI_OK;
     BN& b = n->bns[n->convs[ci].bn];
+    if (!n->trainable(b.unit)) return OSI_OK;    // parameter-only reduction of a frozen unit
     const float* psum_g = ws + n->dg_ws;
     const float* psum_gx = psum_g + (size_t)(1 + which) * n->fused_P * b.C;
     OSI_TRY(osi_bn_backward_reduce(psum_g, psum_gx, n->fused_P, grads + b.g_off, grads + b.b_off, b.M, b.C, ws + n->bn_ws, n->bn_ws_bytes, st));
@@ -815,7 +888,7 @@ static int bn_bwd_frozen(osi_resnet50* n, int ci, int cj, float* grads, float* w
     for (int k = 0; k < nc; ++k) {
         Conv& c = n->convs[idx[k]];
         BN& b = n->bns[c.bn];
-        const bool red = masked && n->bw_pg;
+        const bool red = masked && n->bw_pg && n->trainable(b.unit);
         cs[k] = osi_bn_frozen_consumer{ws + c.y, ws + b.mean, ws + b.invstd, ws + b.scale, ws + n->scratch[out[k]],
                                        red ? grads + b.g_off : nullptr, red ? grads + b.b_off : nullptr};
     }
@@ -878,7 +951,9 @@ static int dgrad_fused(osi_resnet50* n, int ci, const float* params, float* ws, 
 // One bottleneck block of the backward pass. On entry n->cur_grad holds the gradient w.r.t. the block output: raw (stage entry
 // from the average pool) or, when n->go_fused, already masked by the block's final ReLU with the bn3 / downsample-BN reductions
 // in dg_ws (left there by the conv1 dgrad epilogue of the block above).
-static int block_backward(osi_resnet50* n, int bi, const float* params, float* grads, float* ws, hipStream_t st) {
+// no_dx: the block is the first trainable unit of a backward that stops at the cut: nothing below reads the gradient w.r.t. its
+// input, so the two launches that produce it (the shortcut's and conv1's input gradient) are left out and the gradient chain ends here.
+static int block_backward(osi_resnet50* n, int bi, const float* params, float* grads, float* ws, hipStream_t st, bool no_dx) {
     Block& k = n->blocks[bi];
     auto S = [&](int i) { return ws + n->scratch[i]; };
     Conv &c1 = n->convs[k.c1], &c2 = n->convs[k.c2], &c3 = n->convs[k.c3];
@@ -910,9 +985,11 @@ static int block_backward(osi_resnet50* n, int bi, const float* params, float* g
         if (has_ds) {
             Conv& cd = n->convs[k.ds];
             OSI_TRY(wgrad(n, k.ds, grads, ws, t1, x, st));
-            dxbase = n->take(st);
-            if (dxbase < 0) return dxbase;
-            OSI_TRY(dgrad_plain(n, &cd.d, S(t1), params + cd.w_off, S(dxbase), ds_sparse ? 2 : 0, st));
+            if (!no_dx) {
+                dxbase = n->take(st);
+                if (dxbase < 0) return dxbase;
+                OSI_TRY(dgrad_plain(n, &cd.d, S(t1), params + cd.w_off, S(dxbase), ds_sparse ? 2 : 0, st));
+            }
             n->give(t1);
         }
     } else if (n->go_fused) {
@@ -922,9 +999,11 @@ static int block_backward(osi_resnet50* n, int bi, const float* params, float* g
             if (t1 < 0) return t1;
             OSI_TRY(bn_bwd_fused(n, k.ds, params, grads, ws, go, t1, 1, st));
             OSI_TRY(wgrad(n, k.ds, grads, ws, t1, x, st));
-            dxbase = n->take(st);
-            if (dxbase < 0) return dxbase;
-            OSI_TRY(dgrad_plain(n, &cd.d, S(t1), params + cd.w_off, S(dxbase), ds_sparse ? 2 : 0, st));
+            if (!no_dx) {
+                dxbase = n->take(st);
+                if (dxbase < 0) return dxbase;
+                OSI_TRY(dgrad_plain(n, &cd.d, S(t1), params + cd.w_off, S(dxbase), ds_sparse ? 2 : 0, st));
+            }
             n->give(t1);
         }
         d3 = n->take(st);
@@ -945,7 +1024,7 @@ static int block_backward(osi_resnet50* n, int bi, const float* params, float* g
                                               n->bn_ws_bytes, st));
             OSI_TRY(n->mark(OSI_PROF_BN_BWD, st));
             OSI_TRY(wgrad(n, k.ds, grads, ws, t1, x, st));
-            OSI_TRY(dgrad_plain(n, &cd.d, S(t1), params + cd.w_off, S(dxbase), ds_sparse ? 2 : 0, st));
+            if (!no_dx) OSI_TRY(dgrad_plain(n, &cd.d, S(t1), params + cd.w_off, S(dxbase), ds_sparse ? 2 : 0, st));
             n->give(t1);
         }
         BN& b3 = n->bns[c3.bn];
@@ -971,7 +1050,11 @@ static int block_backward(osi_resnet50* n, int bi, const float* params, float* g
     n->give(t2);
     if (!n->frozen) OSI_TRY(bn_bwd_fused(n, k.c1, params, grads, ws, t3, t3, 0, st));
     OSI_TRY(wgrad(n, k.c1, grads, ws, t3, x, st));
-    if (bi > 0) {
+    if (no_dx) {                   // the chain ends: no launch, the buffers go back
+        if (dxbase >= 0) n->give(dxbase);
+        n->cur_grad = -1;
+        n->go_fused = false;
+    } else if (bi > 0) {
         // the block input is the previous block's output: fuse that block's final ReLU mask and its bn3 (+ downsample BN) reductions
         Block& pk = n->blocks[bi - 1];
         int dxn = has_ds ? dxbase : n->take(st);   // downsample case: add in place (each lane reads then writes its own element)
@@ -1057,6 +1140,8 @@ static int backward_stages(osi_resnet50_t n, const float* params, float* grads, 
     const int param_grads = rq.param_grads;
     OSI_REQUIRE(stage_lo >= 0 && stage_lo < stage_hi && stage_hi <= n->n_stages);
     if (!n->fwd_done || stage_lo != n->next_stage || !n->plan_unchanged()) return OSI_ERR_STATE;
+    // the inference-form prefix of the forward kept no backward state: no image gradient exists behind it
+    if (n->fw_prefix > 0 && (dimage || rq.x_adv)) return OSI_ERR_STATE;
     if (stage_lo == 0) {                                // the request is fixed by the call that runs stage 0 (block 0's dgrad form depends on it)
         n->bw_dimage = dimage;
         n->bw_pg = param_grads != 0;
@@ -1070,6 +1155,9 @@ static int backward_stages(osi_resnet50_t n, const float* params, float* grads, 
     auto S = [&](int i) { return ws + n->scratch[i]; };
     if (n->overlap && (!n->prof_on || n->prof_timeline)) OSI_TRY(n->ensure_side());
     OSI_TRY(n->mark(OSI_PROF_START, st));
+    // Units below `stop` launch nothing; unit `stop` leaves out its input gradient. A stage wholly below it is still accepted in order.
+    const int stop = n->bw_stop();
+    const int head = osi_resnet50::NUNITS - 1;
 
     for (int stage = stage_lo; stage < stage_hi; ++stage) {
         if (stage == 0) {
@@ -1084,25 +1172,32 @@ static int backward_stages(osi_resnet50_t n, const float* params, float* grads, 
                     return OSI_ERR_LAUNCH;
                 acc = 1;
             }
-            const bool pg = n->bw_pg;
+            const bool pg = n->bw_pg && n->trainable(head);
             float* dlb = pg && n->t_lg_b >= 0 ? grads + n->tensors[n->t_lg_b].off : nullptr;
             OSI_TRY(osi_linear_bwd(dlogits, ws + n->feat, params + lw.off, dfeat, acc, pg ? grads + lw.off : nullptr, dlb, n->B, n->F,
                                    n->O, st));
-            OSI_TRY(osi_linear_bwd(dfeat, ws + n->pooled, params + fw.off, ws + n->dpooled, 0, pg ? grads + fw.off : nullptr,
+            const bool below = stop < head;      // somebody below the head reads the gradient w.r.t. the pooled features
+            OSI_TRY(osi_linear_bwd(dfeat, ws + n->pooled, params + fw.off, below ? ws + n->dpooled : nullptr, 0, pg ? grads + fw.off : nullptr,
                                    pg ? grads + fb.off : nullptr, n->B, 2048, n->F, st));
-            int g = n->take(st);
-            if (g < 0) return g;
-            OSI_TRY(osi_avgpool_bwd(ws + n->dpooled, S(g), n->B, n->Hf * n->Wf, 2048, st));
+            n->cur_grad = -1;
+            if (below) {
+                int g = n->take(st);
+                if (g < 0) return g;
+                OSI_TRY(osi_avgpool_bwd(ws + n->dpooled, S(g), n->B, n->Hf * n->Wf, 2048, st));
+                n->cur_grad = g;
+            }
             OSI_TRY(n->mark(OSI_PROF_OTHER, st));
-            n->cur_grad = g;
             n->go_fused = false;
         }
         for (int bi = (int)n->blocks.size() - 1; bi >= 0; --bi) {
             Block& k = n->blocks[bi];
-            if (k.stage != stage) continue;
-            OSI_TRY(block_backward(n, bi, params, grads, ws, st));
+            if (k.stage != stage || bi + 1 < stop) continue;
+            OSI_TRY(block_backward(n, bi, params, grads, ws, st, bi + 1 == stop));
         }
-        if (stage == n->n_stages - 1) {
+        if (stage == n->n_stages - 1 && stop > 0) {
+            n->cur_grad = -1;      // the stem is frozen and nobody wants the image gradient: the stem tail is not run
+            n->fwd_done = false;
+        } else if (stage == n->n_stages - 1) {
             // maxpool + stem
             Conv& c0 = n->convs[0];
             int go = n->cur_grad;
@@ -1131,7 +1226,8 @@ static int backward_stages(osi_resnet50_t n, const float* params, float* grads, 
                 // dY unless input-only, then — for dJ/dimage — the stem's input gradient straight into the caller's NCHW tensor
                 if (n->frozen)   // frozen statistics: dY = scale * (scattered, gated gradient); reductions only for the parameter gradients
                     OSI_TRY(osi_bn_relu_maxpool_bwd_frozen(S(go), ws + n->pool_idx, ws + c0.y, ws + b0.mean, ws + b0.invstd, ws + b0.scale, S(t),
-                                                           n->bw_pg ? grads + b0.g_off : nullptr, n->bw_pg ? grads + b0.b_off : nullptr, n->B,
+                                                           n->bw_pg && n->trainable(0) ? grads + b0.g_off : nullptr,
+                                                           n->bw_pg && n->trainable(0) ? grads + b0.b_off : nullptr, n->B,
                                                            n->Hs, n->Ws, 64, ws + n->bn_ws, n->bn_ws_bytes, st));
                 else
                 OSI_TRY(osi_bn_relu_maxpool_bwd(S(go), ws + n->pool_idx, ws + c0.y, ws + b0.mean, ws + b0.invstd, params + b0.g_off, S(t),
@@ -1240,6 +1336,7 @@ int osi_resnet50_debug_gate(osi_resnet50_t n, void* workspace, int i, unsigned c
     OSI_REQUIRE(n && workspace && gate_nchw && i >= 0 && i < 1 + 3 * (int)n->blocks.size());
     OSI_REQUIRE(i == 0 || !pool_argmax_nchw);
     if (!n->any_fwd) return OSI_ERR_STATE;
+    if ((i == 0 ? 0 : (i - 1) / 3 + 1) < n->fw_prefix) return OSI_ERR_STATE;   // a unit that ran the inference form stored no decision
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
     if (i == 0) {
@@ -1271,6 +1368,7 @@ int osi_resnet50_set_option(osi_resnet50_t n, const char* name, int value) {
     else if (!strcmp(name, "fwd_fork")) n->fwd_fork = value != 0;
     else if (!strcmp(name, "stage_join")) n->stage_join = value != 0;
     else if (!strcmp(name, "eval_fused")) n->eval_fused = value != 0;
+    else if (!strcmp(name, "forget_forward")) { if (value) n->fwd_done = false; }
     else if (!strcmp(name, "side_priority_normal")) {
         if (n->side) return OSI_ERR_STATE;   // the side stream already exists with the other priority
         n->side_prio_normal = value != 0;

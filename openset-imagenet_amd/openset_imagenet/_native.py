@@ -168,6 +168,11 @@ _SIGS = {
     "osi_resnet50_geometry": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "osi_resnet50_stage_grad_range": (c_int, [c_void_p, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
     "osi_resnet50_grads_ready": (c_int, [c_void_p, P, P]),
+    "osi_resnet50_num_units": (c_int, [c_void_p]),
+    "osi_resnet50_tensor_unit": (c_int, [c_void_p, c_int]),
+    "osi_resnet50_bn_unit": (c_int, [c_void_p, c_int]),
+    "osi_resnet50_set_trainable": (c_int, [c_void_p, ctypes.c_uint, c_int]),
+    "osi_resnet50_get_trainable": (c_int, [c_void_p, POINTER(ctypes.c_uint), POINTER(c_int)]),
     "osi_resnet50_set_option": (c_int, [c_void_p, c_char_p, c_int]),
     "osi_resnet50_profile": (c_int, [c_void_p, c_int]),
     "osi_resnet50_profile_read": (c_int, [c_void_p, POINTER(ctypes.c_double), POINTER(c_int)]),

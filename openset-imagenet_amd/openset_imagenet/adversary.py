@@ -113,6 +113,12 @@ class Plan:
         if not self.strength >= 0.0:
             raise ValueError("adv: epsilon / std must be >= 0")
         self.generator = getattr(adv, "generator", None)
+        from .model import freeze_below_of
+        if self.who == "fgsm" and freeze_below_of(cfg) is not None:
+            # the loop asks for the adversarial batch after the clean forward, which by then has run the frozen prefix in the inference
+            # form: there is no image gradient behind it (the noise modes need none)
+            raise ValueError("adv.who: fgsm needs the image gradient through the whole network and cannot be combined with freeze_below; "
+                             "use a noise mode (gaussian, uniform), or freeze by hand with train_only and freeze_bn")
 
     def labels(self, labels, n_logits):
         return torch.full_like(labels, negative_label(self.loss_type, n_logits))

@@ -63,6 +63,8 @@ class _Net:
         N.check(N.lib().osi_resnet50_create(ctypes.byref(self.h), B, H, W, F, O, int(bool(logit_bias))), "osi_resnet50_create")
         self.ws_bytes = N.lib().osi_resnet50_workspace_bytes(self.h)
         self.staged = False      # executor option "stage_join" = 0 has been set (data-parallel backward)
+        self.trainable = None    # (unit mask, inference-form prefix units) last handed to osi_resnet50_set_trainable; None = the default
+        self.owes_backward = False   # a differentiable forward ran and its backward has not finished
         for name, value in debug_options_from_env().items():
             N.check(N.lib().osi_resnet50_set_option(self.h, name.encode(), value), f"osi_resnet50_set_option({name})")
 
@@ -115,6 +117,8 @@ class ResNet50(nn.Module):
         object.__setattr__(self, "_flat_buffers", torch.zeros(nbuf))
         object.__setattr__(self, "_nbt", torch.zeros(nbn, dtype=torch.int64))
         object.__setattr__(self, "_anchor", torch.zeros(1, requires_grad=True))
+        self._n_units = lib.osi_resnet50_num_units(probe.h)
+        self._tunit = [lib.osi_resnet50_tensor_unit(probe.h, i) for i in range(lib.osi_resnet50_num_tensors(probe.h))]
         self._stage_ranges = []
         lo, hi = ctypes.c_size_t(), ctypes.c_size_t()
         for s in range(self._n_stages):
@@ -150,6 +154,16 @@ class ResNet50(nn.Module):
         self.logits.in_features, self.logits.out_features = self._F, self._O
         self.resnet_base.fc.in_features, self.resnet_base.fc.out_features = 2048, self._F
         self._plist = [dict(self.named_parameters())[n] for (n, _, _, _) in self._pinfo]
+        self._unit_names = {}      # unit -> "layerN.K" (bottlenecks), "fc" for the head
+        for (full, _, _, _), u in zip(self._pinfo, self._tunit):
+            parts = full.split(".")
+            if 0 < u < self._n_units - 1 and u not in self._unit_names:
+                self._unit_names[u] = parts[1] + "." + parts[2]
+        self._unit_names[self._n_units - 1] = "fc"
+        self._cut = 0              # freeze_below(): first trainable unit; 0 = nothing declared
+        self._cut_froze = set()    # indices of the parameters whose requires_grad freeze_below() itself turned off
+        self._plan_cache = {}      # requires_grad flag tuple -> (unit mask, stages that hold a trainable tensor)
+        self._prefix_fwd = False   # the latest differentiable forward ran its frozen prefix in the inference form
         for p in self._plist:
             p._osi_owner = weakref.ref(self)
         self._nets = {}
@@ -163,6 +177,7 @@ class ResNet50(nn.Module):
         self._flat_grads2 = None   # second gradient arena of an accumulating backward
         self._bn_frozen = False    # freeze_bn(): BatchNorm on the running statistics (read-only) while the model is differentiated
         self._eval_plain = False   # the latest forward was an eval-mode inference forward run with grad enabled (no graph)
+        self._fwd_prefix = 0       # units the differentiable forward being set up runs in the inference forms (forward())
         self.reset_parameters()
 
     # ------------------------------------------------------------------------------------------------------
@@ -260,6 +275,73 @@ class ResNet50(nn.Module):
             self._ws = torch.empty(net.ws_bytes, dtype=torch.uint8, device=dev)
         return net
 
+    def _unit_of(self, first_trainable):
+        """Unit index of a freeze_below() name: "layerN" (= its block 0), "layerN.K", "fc"."""
+        by_name = {v: k for k, v in self._unit_names.items()}
+        name = first_trainable
+        if isinstance(name, str) and name + ".0" in by_name:
+            name = name + ".0"
+        if not isinstance(name, str) or name not in by_name:
+            raise ValueError(f"freeze_below: {first_trainable!r} is not a cut; expected 'layer1' .. 'layer4', 'layerN.K' with an "
+                             "existing block K, 'fc', or None")
+        return by_name[name]
+
+    def freeze_below(self, first_trainable):
+        """Declare that everything before `first_trainable` is frozen ENTIRELY — weights, BatchNorm affine parameters and BatchNorm
+        statistics — which is what `.eval()` plus `requires_grad_(False)` on those sub-modules means in torch; returns self.
+        `first_trainable`: "layer1" .. "layer4" (that layer's block 0 is the first trainable unit), "layerN.K" (that block), "fc" (head
+        only), None (clears the declaration). The prefix's parameters get requires_grad_(False); parameters an earlier call froze and
+        that are no longer in the prefix get requires_grad_(True) back; no other flag is touched. While a cut is declared a
+        differentiable forward runs the prefix in the inference forms on the running statistics (no backward state, no statistics
+        update); the suffix follows the model's mode: batch statistics in train(), running statistics under freeze_bn() or eval."""
+        cut = 0 if first_trainable is None else self._unit_of(first_trainable)
+        for i, (p, u) in enumerate(zip(self._plist, self._tunit)):
+            if u < cut:
+                if p.requires_grad:
+                    p.requires_grad_(False)
+                    self._cut_froze.add(i)
+            elif i in self._cut_froze:
+                p.requires_grad_(True)
+                self._cut_froze.discard(i)
+        self._cut = cut
+        return self
+
+    @property
+    def frozen_below(self):
+        """Canonical name of the declared cut ("layerN.K" or "fc"), None when nothing is declared (read-only)."""
+        return self._unit_names[self._cut] if self._cut else None
+
+    def _trainable_plan(self):
+        """(unit mask, per backward stage: does its gradient range hold a trainable tensor) from the requires_grad flags, cached on
+        the flag tuple. The units come from the executor's table (osi_resnet50_tensor_unit), not from the names."""
+        flags = tuple(p.requires_grad for p in self._plist)
+        plan = self._plan_cache.get(flags)
+        if plan is None:
+            mask = 0
+            live = [False] * self._n_stages
+            for f, u, (_, off, _, _) in zip(flags, self._tunit, self._pinfo):
+                if f:
+                    mask |= 1 << u
+                    for s, (lo, hi) in enumerate(self._stage_ranges):
+                        if lo <= off < hi:
+                            live[s] = True
+            if len(self._plan_cache) > 64:
+                self._plan_cache.clear()
+            plan = self._plan_cache[flags] = (mask, tuple(live))
+        return plan
+
+    def _set_trainable(self, net, mask, prefix):
+        """Hand (unit mask, inference-form prefix) to the executor of this geometry when it changed."""
+        full = (1 << self._n_units) - 1
+        want = (mask or full, prefix)        # no trainable parameter at all: the backward runs input-only, the mask plays no part
+        if (net.trainable or (full, 0)) == want:
+            return
+        if net.owes_backward:   # a differentiable forward that never got its backward: give its state up, the setting may change then
+            N.check(N.lib().osi_resnet50_set_option(net.h, b"forget_forward", 1), "osi_resnet50_set_option(forget_forward)")
+            net.owes_backward = False
+        N.check(N.lib().osi_resnet50_set_trainable(net.h, want[0], want[1]), "osi_resnet50_set_trainable")
+        net.trainable = want
+
     def freeze_bn(self, mode=True):
         """Freeze (mode=True) or release the BatchNorm statistics of the WHOLE model; returns self. Frozen: every differentiable forward
         normalises with the running statistics and neither updates them nor num_batches_tracked (fine-tuning on small batches keeps the
@@ -283,6 +365,9 @@ class ResNet50(nn.Module):
         In eval mode (without freeze_bn()) the request has to PRECEDE the forward: it is what makes that forward differentiable (a plain
         eval-mode forward builds no graph). A request that arrives after such a forward raises; run plain eval-mode forwards under
         torch.no_grad(), as validate() does, when requests for later forwards follow them."""
+        if fgsm is not None and self._prefix_fwd and getattr(self, "_last", None) is not None and self._last[0].owes_backward:
+            raise RuntimeError("next_backward(fgsm=...): the latest forward ran the prefix frozen by freeze_below() in the inference form, which "
+                               "keeps nothing to differentiate; call next_backward(fgsm=...) BEFORE the forward it belongs to")
         if (fgsm is not None or accumulate) and self._eval_plain and not self.training and not self._bn_frozen:
             raise RuntimeError("next_backward(): the latest forward was an eval-mode inference forward, which keeps nothing to differentiate; "
                                "in eval mode call next_backward(...) BEFORE the forward it belongs to (or freeze_bn() / requires_grad_ on "
@@ -336,6 +421,8 @@ class ResNet50(nn.Module):
         else:
             B, _, H, W = image.shape
         net = self._net(B, H, W)
+        if want_grad:    # the executor learns which units are trainable, and how much of the frozen prefix runs the inference forms
+            self._set_trainable(net, self._trainable_plan()[0], self._fwd_prefix)
         if staged and flip is not None:   # ToTensor + horizontal flip + NHWC4 staging in one pass on the device (osi_u8hwc3_to_nhwc4)
             flip = torch.as_tensor(flip).to(device=image.device, dtype=torch.uint8).contiguous()
             if flip.numel() != B:
@@ -351,6 +438,9 @@ class ResNet50(nn.Module):
             logits, features = N.ops().resnet50_forward(net.h.value, self._flat_params, self._flat_buffers, self._nbt, image, flip,
                                                         self._ws, self._F, self._O, bool(self.training and not self._bn_frozen))
         self._eval_plain = not frozen and not self.training and torch.is_grad_enabled()
+        # (any forward replaces the executor's backward state; only a differentiable one leaves a backward owed)
+        net.owes_backward = bool(want_grad)
+        self._prefix_fwd = bool(want_grad) and self._fwd_prefix > 0
         self._fwd_serial += 1
         self._last = (net, image if (want_grad or bound) else None)   # keeps a bound batch alive until the next forward
         return logits, features
@@ -400,12 +490,15 @@ class ResNet50(nn.Module):
                 N.check(N.lib().osi_resnet50_set_option(net.h, b"stage_join", 0), "osi_resnet50_set_option(stage_join)")
                 net.staged = True
             handoff = lambda comm: N.ops().resnet50_grads_ready(net.h.value, grads, comm.cuda_stream)
+            live = self._trainable_plan()[1]
             for s in range(self._n_stages):
                 bwd(net.h.value, self._flat_params, grads, self._ws, dlogits, dfeatures, s, s + 1)
-                if param_grads:   # input-only: no parameter gradient to average, nothing goes to the all-reduce
+                # input-only: no parameter gradient to average; a stage without a trainable tensor: nobody reads its slice
+                if param_grads and live[s]:
                     lo, hi = self._stage_ranges[s]
                     sync.bucket_ready(grads, lo, hi, handoff)
             sync.finish()
+        net.owes_backward = False
         if accumulate:
             N.ops().grad_accumulate(self._flat_grads, grads)
         self._adv_valid = eps is not None
@@ -435,11 +528,35 @@ class ResNet50(nn.Module):
                 raise ValueError("only NCHW fp32 [B, 3, H, W] image batches are differentiable; an NHWC4 batch "
                                  "(pipeline.DevicePrefetcher's layout) cannot require grad")
             param_grad = self._plist[0].requires_grad or any(p.requires_grad for p in self._plist)
+            self._fwd_prefix = 0
+            if self._cut and (param_grad or image_grad):
+                for p, u, (name, _, _, _) in zip(self._plist, self._tunit, self._pinfo):
+                    if u < self._cut and p.requires_grad:
+                        raise RuntimeError(f"freeze_below({self.frozen_below!r}) is declared, but parameter {name} of the frozen prefix "
+                                           "requires grad; clear the declaration with freeze_below(None) or move the cut")
+                if image_grad or (self._bw_request is not None and self._bw_request[0] is not None):
+                    if not frozen:
+                        raise RuntimeError("image gradients through a prefix frozen by freeze_below() need freeze_bn() or eval mode: under a "
+                                           "batch-statistics suffix the prefix keeps no backward state")
+                    # frozen route: the full frozen topology, the backward runs to full depth (frozen units get no weight gradient)
+                else:
+                    self._fwd_prefix = self._cut
             if param_grad or image_grad:
                 # no parameter requires grad: a detached anchor, so the backward runs input-only
                 anchor = self._anchor if param_grad else self._anchor.detach()
                 return _BackboneFn.apply(image, anchor, self, flip, frozen)
         return self._run_forward(image, False, flip)
+
+
+def freeze_below_of(cfg):
+    """The optional top-level config key `freeze_below` (a cut name of ResNet50.freeze_below; absent, null or off = none): the name, or
+    None. The name itself is checked by ResNet50.freeze_below when it is applied."""
+    value = getattr(cfg, "freeze_below", None)
+    if value is None or value is False or (isinstance(value, str) and value.lower() in ("", "off", "none", "null", "false", "no")):
+        return None
+    if not isinstance(value, str):
+        raise ValueError(f"freeze_below: expected a cut name ('layer1' .. 'layer4', 'layerN.K', 'fc'), got {value!r}")
+    return value
 
 
 def net_shape(model, net):

@@ -351,6 +351,12 @@ def _freeze_bn_of(cfg):
     return bool(value)
 
 
+def _freeze_below_of(cfg):
+    """The optional top-level key `freeze_below` (a cut name of ResNet50.freeze_below; absent / off = none)."""
+    from .model import freeze_below_of
+    return freeze_below_of(cfg)
+
+
 def worker(cfg):
     """Creates datasets, model, loss, optimizer, runs the epoch loop with checkpoints — the reference's worker()
     (train.py:237-482) reduced to what drives the hot path. Same cfg keys (config/train.yaml), same checkpoint files
@@ -484,6 +490,12 @@ def _worker_body(cfg, log, out_dir, rank, world, distributed):
     if _freeze_bn_of(cfg):
         model.freeze_bn()
         log.info("BatchNorm statistics frozen (freeze_bn: on)")
+    # top-level `freeze_below: layer4` (absent = off): everything before that unit frozen entirely, applied to the loaded weights
+    # (model.freeze_below: the prefix runs at inference speed, the backward stops at the cut)
+    cut = _freeze_below_of(cfg)
+    if cut is not None:
+        model.freeze_below(cut)
+        log.info(f"Frozen below {model.frozen_below} (freeze_below: {cut})")
     net = _dp.DistributedDataParallel(model) if distributed else model   # broadcasts rank 0's parameters and BN buffers
     _last_worker_state.clear()
     _last_worker_state.update(model=model, optimizer=opt, rank=rank, world=world, checkpoints_written=0, sharded_validation=shard_val)
