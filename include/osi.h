@@ -314,6 +314,21 @@ int osi_bn_backward_fused(const float* g, const float* y, const float* mean, con
                           const float* psum_g, const float* psum_gx, int P, float* dy, float* dgamma, float* dbeta, int M, int C,
                           void* ws, size_t ws_bytes, osi_stream_t stream);
 
+/* ABI 14. osi_bn_backward_fused for the TWO BatchNorms that read one gated gradient (a projection block's bn3 and its shortcut's
+ * BatchNorm): g is streamed once, both sets of sums are finished in one launch (two for P beyond the one-launch limit), and every
+ * consumer's dy, dgamma and dbeta are bit for bit those of its own osi_bn_backward_fused call. psum_g [P][C] is shared (dbeta = sum g for
+ * both), psum_gx [P][C] is per consumer. consumers[0].dy may alias g; consumers[1].dy is a third buffer.
+ * ws: osi_bn_backward_fused2_workspace(C) bytes (any P). */
+typedef struct {
+    const float *y, *mean, *invstd, *gamma;   /* pre-BN tensor, batch statistics, scale parameter */
+    const float* psum_gx;                     /* [P][C] row-tile partials of sum g * xhat */
+    float* dy;
+    float *dgamma, *dbeta;
+} osi_bn_fused_consumer;
+size_t osi_bn_backward_fused2_workspace(int C);
+int osi_bn_backward_fused2(const float* g, const osi_bn_fused_consumer* consumers, const float* psum_g, int P, int M, int C, void* ws,
+                           size_t ws_bytes, osi_stream_t stream);
+
 /* ABI 12. BatchNorm backward on FROZEN statistics (mean / invstd are constants of the graph): with g = dout gated by relu_mask (NULL:
  * dout is already gated, e.g. by a dgrad epilogue), every consumer k < n (n = 1 or 2: bn3 and the projection shortcut's BatchNorm read
  * the same gated gradient) gets dy_k = scale_k[c] * g in ONE pass that does not read y. dgamma_k / dbeta_k non-NULL (both or neither):

@@ -327,28 +327,48 @@ typedef unsigned long long u64;
 #ifndef OSI_BN_REVERSE
 #define OSI_BN_REVERSE 3
 #endif
+// Channel constants of the streaming passes. A pass walks [M][C] as float4 #i = tile * NT + lane, channel group c4 = i % c4n with
+// c4n = C / 4. GEO says what that modulo is for the launch's channel count (stream_geo):
+//   1: c4n divides NT (C = 4 ... 1024 in powers of two): c4 = lane % c4n in every tile, the coefficient vectors are loop constants
+//   2: c4n = 2 * NT (C = 2048): c4 = lane or NT + lane by the parity of the TILE index (not of the loop counter: the walk may descend)
+//   0: any other channel count: c4 and the coefficients are taken per element
+// The per-element expressions are the same in all three, only where their operands come from differs: the same bits.
 // RES: 0 = none, 1 = add `res`, 2 = add res * rscale + rshift (the projection shortcut's own BatchNorm applied on the fly)
-template <int RES, bool RELU, bool BITS>
+struct FwdCoef { f32x4 sc, sh, rs, rh; };
+template <int RES>
+__device__ __forceinline__ FwdCoef fwd_coef(const f32x4* __restrict__ scale, const f32x4* __restrict__ shift,
+                                            const f32x4* __restrict__ rscale, const f32x4* __restrict__ rshift, int c4) {
+    FwdCoef k;
+    k.sc = scale[c4]; k.sh = shift[c4];
+    if (RES == 2) { k.rs = rscale[c4]; k.rh = rshift[c4]; } else { k.rs = k.sc; k.rh = k.sh; }
+    return k;
+}
+template <int RES, bool RELU, bool BITS, int GEO>
 __global__ __launch_bounds__(NT) void k_bn_apply(const f32x4* __restrict__ y, const f32x4* __restrict__ res,
                                                 const f32x4* __restrict__ scale, const f32x4* __restrict__ shift,
                                                 const f32x4* __restrict__ rscale, const f32x4* __restrict__ rshift,
                                                 f32x4* __restrict__ out, u64* __restrict__ bits, size_t n4, int c4n) {
     const size_t nq = (n4 + NT - 1) / NT;
+    const int tid = threadIdx.x;
+    FwdCoef k0 = {}, k1 = {};
+    if (GEO == 1) k0 = fwd_coef<RES>(scale, shift, rscale, rshift, tid % c4n);
+    if (GEO == 2) { k0 = fwd_coef<RES>(scale, shift, rscale, rshift, tid); k1 = fwd_coef<RES>(scale, shift, rscale, rshift, NT + tid); }
     for (size_t q = blockIdx.x; q < nq; q += gridDim.x) {
-        const size_t i = ((OSI_BN_REVERSE & 1) ? nq - 1 - q : q) * NT + threadIdx.x;
+        const size_t t = (OSI_BN_REVERSE & 1) ? nq - 1 - q : q;
+        const size_t i = t * NT + tid;
         if (i >= n4) continue;
-        int c4 = (int)(i % (size_t)c4n);
-        const f32x4 yv = __builtin_nontemporal_load(y + i), sc = scale[c4], sh = shift[c4];
+        const FwdCoef k = GEO == 1 ? k0 : GEO == 2 ? ((t & 1) ? k1 : k0) : fwd_coef<RES>(scale, shift, rscale, rshift, (int)(i % (size_t)c4n));
+        const f32x4 yv = __builtin_nontemporal_load(y + i), sc = k.sc, sh = k.sh;
         f32x4 v;   // one fma per element: the same expression the fused conv loaders and the dgrad gate evaluate
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = __builtin_fmaf(yv[e], sc[e], sh[e]);
         if (RES == 1) v += __builtin_nontemporal_load(res + i);
         if (RES == 2) {
-            const f32x4 rv = __builtin_nontemporal_load(res + i), rs = rscale[c4], rh = rshift[c4];
-            f32x4 t;
+            const f32x4 rv = __builtin_nontemporal_load(res + i), rs = k.rs, rh = k.rh;
+            f32x4 t2;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) t[e] = __builtin_fmaf(rv[e], rs[e], rh[e]);
-            v += t;
+            for (int e = 0; e < 4; ++e) t2[e] = __builtin_fmaf(rv[e], rs[e], rh[e]);
+            v += t2;
         }
         if (BITS) {
             const u64 b0 = __ballot(v.x > 0.f), b1 = __ballot(v.y > 0.f), b2 = __ballot(v.z > 0.f), b3 = __ballot(v.w > 0.f);
@@ -472,9 +492,15 @@ __global__ __launch_bounds__(NT) void k_bn_bwd_partial(const float* __restrict__
     }
 }
 
-__global__ __launch_bounds__(NT) void k_bn_bwd_final(const float* __restrict__ pdb, const float* __restrict__ pdg, int P, int M,
-                                                    int C, float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                    float* __restrict__ c1, float* __restrict__ c2) {
+// One consumer of a gated gradient in the finalising kernels (blockIdx.y = consumer; a projection block's bn3 and its shortcut's BatchNorm
+// read the same g, so their column of sum g is shared and finished once per consumer in the same order: the same bits as two launches).
+// pa / pb: the partials this consumer's kernel reads; ga / gb: the [C][S] group sums of the two-level form.
+struct BwdCons { const float *pa, *pb; float *ga, *gb, *dgamma, *dbeta, *c1, *c2; };
+struct BwdConsTable { BwdCons k[2]; };
+__global__ __launch_bounds__(NT) void k_bn_bwd_final(BwdConsTable t, bool grouped, int P, int M, int C) {
+    const BwdCons& o = t.k[blockIdx.y];
+    const float* __restrict__ pdb = grouped ? o.ga : o.pa;
+    const float* __restrict__ pdg = grouped ? o.gb : o.pb;
     const int lane = threadIdx.x & 63;
     const int c = blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
     if (c >= C) return;
@@ -482,22 +508,24 @@ __global__ __launch_bounds__(NT) void k_bn_bwd_final(const float* __restrict__ p
     for (int b = lane; b < P; b += 64) { ab += pdb[(size_t)c * P + b]; ag += pdg[(size_t)c * P + b]; }
     ab = wave_sum(ab); ag = wave_sum(ag);
     if (lane == 0) {
-        dbeta[c] = ab; dgamma[c] = ag;
-        c1[c] = ab / (float)M; c2[c] = ag / (float)M;
+        o.dbeta[c] = ab; o.dgamma[c] = ag;
+        o.c1[c] = ab / (float)M; o.c2[c] = ag / (float)M;
     }
 }
 
 // dy = gamma*invstd * ( g - c1 - xhat*c2 ) ; optionally also emits g (the masked upstream gradient) for the skip path
 // Column sums of two row-major [P][C] partial matrices over row group s (blockIdx.y) -> channel-major [C][S] for k_bn_bwd_final.
-__global__ __launch_bounds__(NT) void k_colsum2_group(const float* __restrict__ a, const float* __restrict__ b, int P, int Pc, int C,
-                                                     int S, float* __restrict__ ga, float* __restrict__ gb) {
+__global__ __launch_bounds__(NT) void k_colsum2_group(BwdConsTable t, int P, int Pc, int C, int S) {
     __shared__ float ra[16][16], rb[16][16];
+    const BwdCons& o = t.k[blockIdx.z];
+    float* __restrict__ ga = o.ga;
+    float* __restrict__ gb = o.gb;
     const int cl = threadIdx.x & 15, pl = threadIdx.x >> 4;
     const int c = min(blockIdx.x * 16 + cl, C - 1), s = blockIdx.y;
     const bool ok = blockIdx.x * 16 + cl < C;
     const int b0 = s * Pc, b1 = min(P, b0 + Pc);
-    const float* pa = a + c;
-    const float* pb = b + c;
+    const float* __restrict__ pa = o.pa + c;
+    const float* __restrict__ pb = o.pb + c;
     float xa0 = 0.f, xa1 = 0.f, xb0 = 0.f, xb1 = 0.f;
     int r = b0 + pl;
     for (; r + 48 < b1; r += 64) {     // four rows in flight per lane
@@ -517,15 +545,14 @@ __global__ __launch_bounds__(NT) void k_colsum2_group(const float* __restrict__ 
 }
 
 // Single-launch form of k_colsum2_group + k_bn_bwd_final for mid-sized P: 16 channels x 64 row lanes, four loads in flight per lane.
-__global__ __launch_bounds__(16 * WPL) void k_bn_bwd_final_wide(const float* __restrict__ a, const float* __restrict__ b, int P, int M, int C,
-                                                               float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                               float* __restrict__ c1, float* __restrict__ c2) {
+__global__ __launch_bounds__(16 * WPL) void k_bn_bwd_final_wide(BwdConsTable t, int P, int M, int C) {
     __shared__ float red[WPL][16];
+    const BwdCons& o = t.k[blockIdx.y];
     const int cl = threadIdx.x & 15, pl = threadIdx.x >> 4;
     const int c = min(blockIdx.x * 16 + cl, C - 1);
     const bool ok = blockIdx.x * 16 + cl < C;
-    const float* pa = a + c;
-    const float* pb = b + c;
+    const float* __restrict__ pa = o.pa + c;
+    const float* __restrict__ pb = o.pb + c;
     float xa0 = 0.f, xa1 = 0.f, xb0 = 0.f, xb1 = 0.f;
     int r = pl;
     for (; r + 3 * WPL < P; r += 4 * WPL) {
@@ -538,49 +565,105 @@ __global__ __launch_bounds__(16 * WPL) void k_bn_bwd_final_wide(const float* __r
     const float sa = wide_reduce(red, xa0 + xa1, pl, cl);
     const float sb = wide_reduce(red, xb0 + xb1, pl, cl);
     if (pl == 0 && ok) {
-        dbeta[c] = sa; dgamma[c] = sb;
-        c1[c] = sa / (float)M; c2[c] = sb / (float)M;
+        o.dbeta[c] = sa; o.dgamma[c] = sb;
+        o.c1[c] = sa / (float)M; o.c2[c] = sb / (float)M;
     }
 }
 
-template <int MODE, bool EMITG>
+// The channel constants of the backward apply (GEO as in k_bn_apply): gis = gamma * invstd is the same product the per-element form
+// evaluates, taken once.
+struct BwdCoef { f32x4 mu, is, c1, c2, gis; };
+__device__ __forceinline__ BwdCoef bwd_coef(const f32x4* __restrict__ mean, const f32x4* __restrict__ invstd, const f32x4* __restrict__ gamma,
+                                            const f32x4* __restrict__ c1, const f32x4* __restrict__ c2, int c4) {
+    BwdCoef k;
+    k.mu = mean[c4]; k.is = invstd[c4]; k.c1 = c1[c4]; k.c2 = c2[c4];
+    k.gis = gamma[c4] * k.is;
+    return k;
+}
+__device__ __forceinline__ f32x4 bwd_elem(f32x4 gv, f32x4 yv, const BwdCoef& k) {
+    const f32x4 xh = (yv - k.mu) * k.is;
+    return (gv - k.c1 - xh * k.c2) * k.gis;
+}
+template <int MODE, bool EMITG, int GEO>
 __global__ __launch_bounds__(NT) void k_bn_bwd_apply(const f32x4* dA /* may alias dy */, const void* __restrict__ msk,
                                                     const f32x4* __restrict__ y, const f32x4* __restrict__ mean,
                                                     const f32x4* __restrict__ invstd, const f32x4* __restrict__ gamma,
                                                     const f32x4* __restrict__ c1, const f32x4* __restrict__ c2,
                                                     f32x4* dy, f32x4* __restrict__ gout, size_t n4, int c4n, PoolSrc ps) {
     const size_t nq = (n4 + NT - 1) / NT;
+    const int tid = threadIdx.x;
+    BwdCoef k0 = {}, k1 = {};
+    if (GEO == 1) k0 = bwd_coef(mean, invstd, gamma, c1, c2, tid % c4n);
+    if (GEO == 2) { k0 = bwd_coef(mean, invstd, gamma, c1, c2, tid); k1 = bwd_coef(mean, invstd, gamma, c1, c2, NT + tid); }
     for (size_t q = blockIdx.x; q < nq; q += gridDim.x) {
-        const size_t i = ((OSI_BN_REVERSE & 2) ? nq - 1 - q : q) * NT + threadIdx.x;
+        const size_t t = (OSI_BN_REVERSE & 2) ? nq - 1 - q : q;
+        const size_t i = t * NT + tid;
         if (i >= n4) continue;
-        int c4 = (int)(i % (size_t)c4n);
+        const int c4 = GEO == 1 ? tid % c4n : GEO == 2 ? (int)(t & 1) * NT + tid : (int)(i % (size_t)c4n);
         f32x4 gv = MODE == 3 ? pool_gather(dA, ps, (uint32_t)(i / (size_t)c4n), c4, c4n) : masked<MODE>(__builtin_nontemporal_load(dA + i), msk, i);
-        f32x4 is = invstd[c4];
-        f32x4 xh = (__builtin_nontemporal_load(y + i) - mean[c4]) * is;
-        f32x4 r = (gv - c1[c4] - xh * c2[c4]) * (gamma[c4] * is);
+        const BwdCoef k = GEO == 1 ? k0 : GEO == 2 ? ((t & 1) ? k1 : k0) : bwd_coef(mean, invstd, gamma, c1, c2, c4);
+        f32x4 r = bwd_elem(gv, __builtin_nontemporal_load(y + i), k);
         if (EMITG) gout[i] = gv;
         dy[i] = r;
+    }
+}
+
+// The same pass for the two BatchNorms of a projection block (bn3 and the shortcut's): both read the same gated gradient g, which is
+// streamed once; every consumer keeps its own y, statistics and coefficients and gets the dy the single-consumer kernel would write.
+// dy0 may alias g (every lane reads its element before it writes it); dy1 is a third buffer.
+// Two consumers times two coefficient sets do not fit the 128 registers of four workgroups per CU, so GEO 2 here asks more of the launch:
+// c4n = 2 * NT AND every workgroup's tiles have one parity (an even grid, or one tile per workgroup) — one set per consumer, picked by the
+// workgroup's first tile. The launcher falls back to GEO 0 otherwise.
+struct BwdApplyCons { const f32x4 *y, *mean, *invstd, *gamma, *c1, *c2; f32x4* dy; };
+template <int GEO>
+__global__ __launch_bounds__(NT) void k_bn_bwd_apply2(const f32x4* g, BwdApplyCons a, BwdApplyCons b, size_t n4, int c4n) {
+    const size_t nq = (n4 + NT - 1) / NT;
+    const int tid = threadIdx.x;
+    const size_t tfirst = (OSI_BN_REVERSE & 2) ? nq - 1 - blockIdx.x : blockIdx.x;
+    const int ck = GEO == 1 ? tid % c4n : (int)(tfirst & 1) * NT + tid;
+    BwdCoef a0 = {}, b0 = {};
+    if (GEO != 0) { a0 = bwd_coef(a.mean, a.invstd, a.gamma, a.c1, a.c2, ck); b0 = bwd_coef(b.mean, b.invstd, b.gamma, b.c1, b.c2, ck); }
+    for (size_t q = blockIdx.x; q < nq; q += gridDim.x) {
+        const size_t t = (OSI_BN_REVERSE & 2) ? nq - 1 - q : q;
+        const size_t i = t * NT + tid;
+        if (i >= n4) continue;
+        const f32x4 gv = __builtin_nontemporal_load(g + i);
+        const f32x4 ya = __builtin_nontemporal_load(a.y + i), yb = __builtin_nontemporal_load(b.y + i);
+        const BwdCoef ka = GEO != 0 ? a0 : bwd_coef(a.mean, a.invstd, a.gamma, a.c1, a.c2, (int)(i % (size_t)c4n));
+        const BwdCoef kb = GEO != 0 ? b0 : bwd_coef(b.mean, b.invstd, b.gamma, b.c1, b.c2, (int)(i % (size_t)c4n));
+        const f32x4 ra = bwd_elem(gv, ya, ka), rb = bwd_elem(gv, yb, kb);
+        b.dy[i] = rb;
+        a.dy[i] = ra;
     }
 }
 
 // Frozen statistics: mean and variance are constants of the backward, so dy = scale * g (scale = gamma * invstd) — y is not read, and
 // nothing waits for a reduction. One pass serves one or two consumers of the same gated gradient (bn3 and the projection shortcut's
 // BatchNorm) and can emit g itself for an identity shortcut. dy0 may alias dA (every lane reads its element before it writes it).
-template <int MODE, bool EMITG, bool TWO>
+template <int MODE, bool EMITG, bool TWO, int GEO>
 __global__ __launch_bounds__(NT) void k_bn_frozen_apply(const f32x4* dA, const void* __restrict__ msk, const f32x4* __restrict__ scale0,
                                                        const f32x4* __restrict__ scale1, f32x4* dy0, f32x4* __restrict__ dy1,
                                                        f32x4* __restrict__ gout, size_t n4, int c4n, PoolSrc ps) {
     const size_t nq = (n4 + NT - 1) / NT;
+    const int tid = threadIdx.x;
+    f32x4 s00 = {}, s01 = {}, s10 = {}, s11 = {};     // scale<consumer><set>
+    if (GEO == 1) { s00 = scale0[tid % c4n]; if (TWO) s10 = scale1[tid % c4n]; }
+    if (GEO == 2) { s00 = scale0[tid]; s01 = scale0[NT + tid]; if (TWO) { s10 = scale1[tid]; s11 = scale1[NT + tid]; } }
     for (size_t q = blockIdx.x; q < nq; q += gridDim.x) {
-        const size_t i = ((OSI_BN_REVERSE & 2) ? nq - 1 - q : q) * NT + threadIdx.x;
+        const size_t t = (OSI_BN_REVERSE & 2) ? nq - 1 - q : q;
+        const size_t i = t * NT + tid;
         if (i >= n4) continue;
-        const int c4 = (int)(i % (size_t)c4n);
+        const int c4 = GEO == 1 ? tid % c4n : GEO == 2 ? (int)(t & 1) * NT + tid : (int)(i % (size_t)c4n);
         const f32x4 gv = MODE == 3 ? pool_gather(dA, ps, (uint32_t)(i / (size_t)c4n), c4, c4n) : masked<MODE>(__builtin_nontemporal_load(dA + i), msk, i);
         if (EMITG) gout[i] = gv;
-        if (TWO) dy1[i] = gv * scale1[c4];
-        dy0[i] = gv * scale0[c4];
+        if (TWO) dy1[i] = gv * (GEO == 1 ? s10 : GEO == 2 ? ((t & 1) ? s11 : s10) : scale1[c4]);
+        dy0[i] = gv * (GEO == 1 ? s00 : GEO == 2 ? ((t & 1) ? s01 : s00) : scale0[c4]);
     }
 }
+
+// which of the three forms a streaming pass takes for a channel count (see k_bn_apply)
+static int stream_geo(int c4n) { return NT % c4n == 0 ? 1 : c4n == 2 * NT ? 2 : 0; }
+#define OSI_BY_GEO(geo_, X_) do { if ((geo_) == 1) { X_(1); } else if ((geo_) == 2) { X_(2); } else { X_(0); } } while (0)
 
 static int rows_per_block(int M, int C, int& P) {
     // ~256 KiB of activations per workgroup, at most 1024 workgroups
@@ -717,7 +800,9 @@ static int bn_apply_impl(const float* y, const float* residual, const float* sca
     auto Y = (const f32x4*)y; auto R = (const f32x4*)residual; auto S = (const f32x4*)scale; auto H = (const f32x4*)shift;
     auto RS = (const f32x4*)rscale; auto RH = (const f32x4*)rshift;
     auto O = (f32x4*)out; auto B = (u64*)bits;
-#define OSI_APPLY(RES_, RELU_, BITS_) hipLaunchKernelGGL((k_bn_apply<RES_, RELU_, BITS_>), dim3(grid), dim3(NT), 0, st, Y, R, S, H, RS, RH, O, B, n4, c4n)
+    const int geo = stream_geo(c4n);
+#define OSI_APPLY_G(RES_, RELU_, BITS_, GEO_) hipLaunchKernelGGL((k_bn_apply<RES_, RELU_, BITS_, GEO_>), dim3(grid), dim3(NT), 0, st, Y, R, S, H, RS, RH, O, B, n4, c4n)
+#define OSI_APPLY(RES_, RELU_, BITS_) do { if (geo == 1) OSI_APPLY_G(RES_, RELU_, BITS_, 1); else if (geo == 2) OSI_APPLY_G(RES_, RELU_, BITS_, 2); else OSI_APPLY_G(RES_, RELU_, BITS_, 0); } while (0)
     if (rscale) OSI_APPLY(2, true, true);
     else if (bits && residual) OSI_APPLY(1, true, true);
     else if (bits) OSI_APPLY(0, true, true);
@@ -726,6 +811,7 @@ static int bn_apply_impl(const float* y, const float* residual, const float* sca
     else if (relu) OSI_APPLY(0, true, false);
     else OSI_APPLY(0, false, false);
 #undef OSI_APPLY
+#undef OSI_APPLY_G
     OSI_LAUNCH_CHECK();
     return OSI_OK;
 }
@@ -753,6 +839,12 @@ int osi_bn_apply_relu_mask2(const float* y, const float* scale, const float* shi
     return bn_apply_impl(y, res_y, scale, shift, out, relu_mask, M, C, 1, (hipStream_t)stream, res_scale, res_shift);
 }
 
+static BwdConsTable one_cons(const float* pa, const float* pb, float* ga, float* gb, float* dgamma, float* dbeta, float* c1, float* c2) {
+    BwdConsTable t{};
+    t.k[0] = BwdCons{pa, pb, ga, gb, dgamma, dbeta, c1, c2};
+    return t;
+}
+
 static int bn_backward_impl(const float* dout, const void* msk, int mode, const float* y, const float* mean, const float* invstd,
                             const float* gamma, float* dy, float* gmasked, float* dgamma, float* dbeta, int M, int C, void* ws,
                             size_t ws_bytes, hipStream_t st, PoolSrc ps = PoolSrc{}) {
@@ -771,7 +863,7 @@ static int bn_backward_impl(const float* dout, const void* msk, int mode, const 
     else if (mode == 1) hipLaunchKernelGGL(k_bn_bwd_partial<1>, dim3(P), dim3(NT), 0, st, dout, msk, y, mean, invstd, M, C, rpb, pdb, pdg, ps);
     else hipLaunchKernelGGL(k_bn_bwd_partial<0>, dim3(P), dim3(NT), 0, st, dout, msk, y, mean, invstd, M, C, rpb, pdb, pdg, ps);
     OSI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_bn_bwd_final, dim3(osi_cdiv(C, NT / 64)), dim3(NT), 0, st, pdb, pdg, P, M, C, dgamma, dbeta, c1, c2);
+    hipLaunchKernelGGL(k_bn_bwd_final, dim3(osi_cdiv(C, NT / 64)), dim3(NT), 0, st, one_cons(pdb, pdg, nullptr, nullptr, dgamma, dbeta, c1, c2), false, P, M, C);
     OSI_LAUNCH_CHECK();
     if (!dy) return OSI_OK;     // reductions only (dgamma, dbeta): the caller assembles the consumer's gradient another way
     const size_t n4 = (size_t)M * C / 4;
@@ -780,30 +872,39 @@ static int bn_backward_impl(const float* dout, const void* msk, int mode, const 
     auto MU = (const f32x4*)mean; auto IS = (const f32x4*)invstd; auto G = (const f32x4*)gamma;
     auto C1 = (const f32x4*)c1; auto C2 = (const f32x4*)c2;
     auto DY = (f32x4*)dy; auto GO = (f32x4*)gmasked;
-#define OSI_BWD_APPLY(MODE_, EMIT_) hipLaunchKernelGGL((k_bn_bwd_apply<MODE_, EMIT_>), dim3(grid), dim3(NT), 0, st, D, msk, Y, MU, IS, G, C1, C2, DY, GO, n4, c4n, ps)
-    if (mode == 3) OSI_BWD_APPLY(3, false);
+    const int geo = stream_geo(c4n);
+#define OSI_BWD_APPLY_G(MODE_, EMIT_, GEO_) hipLaunchKernelGGL((k_bn_bwd_apply<MODE_, EMIT_, GEO_>), dim3(grid), dim3(NT), 0, st, D, msk, Y, MU, IS, G, C1, C2, DY, GO, n4, c4n, ps)
+#define OSI_BWD_APPLY(MODE_, EMIT_) do { if (geo == 1) OSI_BWD_APPLY_G(MODE_, EMIT_, 1); else if (geo == 2) OSI_BWD_APPLY_G(MODE_, EMIT_, 2); else OSI_BWD_APPLY_G(MODE_, EMIT_, 0); } while (0)
+    if (mode == 3) OSI_BWD_APPLY_G(3, false, 0);   // the stem's pool-gather form (one launch per step) keeps the per-element constants
     else if (mode == 2) { if (gmasked) OSI_BWD_APPLY(2, true); else OSI_BWD_APPLY(2, false); }
     else if (mode == 1) { if (gmasked) OSI_BWD_APPLY(1, true); else OSI_BWD_APPLY(1, false); }
     else { if (gmasked) OSI_BWD_APPLY(0, true); else OSI_BWD_APPLY(0, false); }
 #undef OSI_BWD_APPLY
+#undef OSI_BWD_APPLY_G
     OSI_LAUNCH_CHECK();
     return OSI_OK;
 }
 
-// (psum_g, psum_gx)[P][C] from a dgrad epilogue -> dgamma, dbeta and the two apply coefficients: one launch for P <= bn_wide_p, else two
-static int bwd_reduce_partials(const float* psum_g, const float* psum_gx, int P, int M, int C, float* gb, float* gg, int S, int Pc,
-                               float* dgamma, float* dbeta, float* c1, float* c2, hipStream_t st) {
+// (psum_g, psum_gx)[P][C] from a dgrad epilogue -> dgamma, dbeta and the two apply coefficients of n consumers (the table's pa / pb):
+// one launch for P <= bn_wide_p, else two; blockIdx.y (.z in the group sums) = consumer
+static int bwd_reduce_partials(const BwdConsTable& t, int n, int P, int M, int C, int S, int Pc, hipStream_t st) {
     if (P <= g_osi_tuning.bn_wide_p) {
-        hipLaunchKernelGGL(k_bn_bwd_final_wide, dim3(osi_cdiv(C, 16)), dim3(16 * WPL), 0, st, psum_g, psum_gx, P, M, C, dgamma, dbeta, c1, c2);
+        hipLaunchKernelGGL(k_bn_bwd_final_wide, dim3(osi_cdiv(C, 16), n), dim3(16 * WPL), 0, st, t, P, M, C);
         OSI_LAUNCH_CHECK();
         return OSI_OK;
     }
-    hipLaunchKernelGGL(k_colsum2_group, dim3(osi_cdiv(C, 16), S), dim3(NT), 0, st, psum_g, psum_gx, P, Pc, C, S, gb, gg);
+    hipLaunchKernelGGL(k_colsum2_group, dim3(osi_cdiv(C, 16), S, n), dim3(NT), 0, st, t, P, Pc, C, S);
     OSI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_bn_bwd_final, dim3(osi_cdiv(C, NT / 64)), dim3(NT), 0, st, (const float*)gb, (const float*)gg, S, M, C, dgamma,
-                       dbeta, c1, c2);
+    hipLaunchKernelGGL(k_bn_bwd_final, dim3(osi_cdiv(C, NT / 64), n), dim3(NT), 0, st, t, true, S, M, C);
     OSI_LAUNCH_CHECK();
     return OSI_OK;
+}
+// group geometry of the two-level reduction of P row tiles
+static void bwd_groups(int P, int& S, int& Pc) {
+    S = osi_cdiv(P, 64);
+    if (S > OSI_BN_GROUPS) S = OSI_BN_GROUPS;
+    Pc = osi_cdiv(P, S);
+    S = osi_cdiv(P, Pc);
 }
 
 int osi_bn_backward_fused(const float* g, const float* y, const float* mean, const float* invstd, const float* gamma,
@@ -811,21 +912,65 @@ int osi_bn_backward_fused(const float* g, const float* y, const float* mean, con
                           void* ws, size_t ws_bytes, osi_stream_t stream) {
     OSI_REQUIRE(g && y && mean && invstd && gamma && psum_g && psum_gx && dy && dgamma && dbeta && ws);
     OSI_REQUIRE(M > 0 && C > 0 && C % 4 == 0 && P > 0);
-    int S = osi_cdiv(P, 64);
-    if (S > OSI_BN_GROUPS) S = OSI_BN_GROUPS;
-    const int Pc = osi_cdiv(P, S);
-    S = osi_cdiv(P, Pc);
+    int S, Pc;
+    bwd_groups(P, S, Pc);
     OSI_REQUIRE(ws_bytes >= ((size_t)2 * S * C + 2 * (size_t)C) * sizeof(float));
     hipStream_t st = (hipStream_t)stream;
     float* gb = (float*)ws;               // [C][S] group sums of g
     float* gg = gb + (size_t)S * C;       // [C][S] group sums of g*xhat
     float* c1 = gg + (size_t)S * C;
     float* c2 = c1 + C;
-    if (int e = bwd_reduce_partials(psum_g, psum_gx, P, M, C, gb, gg, S, Pc, dgamma, dbeta, c1, c2, st)) return e;
+    if (int e = bwd_reduce_partials(one_cons(psum_g, psum_gx, gb, gg, dgamma, dbeta, c1, c2), 1, P, M, C, S, Pc, st)) return e;
     const size_t n4 = (size_t)M * C / 4;
-    hipLaunchKernelGGL((k_bn_bwd_apply<0, false>), dim3(stream_grid(n4, true)), dim3(NT), 0, st, (const f32x4*)g, (const void*)nullptr,
-                       (const f32x4*)y, (const f32x4*)mean, (const f32x4*)invstd, (const f32x4*)gamma, (const f32x4*)c1,
-                       (const f32x4*)c2, (f32x4*)dy, (f32x4*)nullptr, n4, C / 4, PoolSrc{});
+    const int c4n = C / 4;
+#define OSI_FUSED_APPLY(GEO_) hipLaunchKernelGGL((k_bn_bwd_apply<0, false, GEO_>), dim3(stream_grid(n4, true)), dim3(NT), 0, st, (const f32x4*)g, \
+                       (const void*)nullptr, (const f32x4*)y, (const f32x4*)mean, (const f32x4*)invstd, (const f32x4*)gamma, (const f32x4*)c1, \
+                       (const f32x4*)c2, (f32x4*)dy, (f32x4*)nullptr, n4, c4n, PoolSrc{})
+    OSI_BY_GEO(stream_geo(c4n), OSI_FUSED_APPLY);
+#undef OSI_FUSED_APPLY
+    OSI_LAUNCH_CHECK();
+    return OSI_OK;
+}
+
+size_t osi_bn_backward_fused2_workspace(int C) {
+    if (C <= 0) return 0;
+    return 2 * ((size_t)2 * OSI_BN_GROUPS * C + 2 * (size_t)C) * sizeof(float);
+}
+
+int osi_bn_backward_fused2(const float* g, const osi_bn_fused_consumer* consumers, const float* psum_g, int P, int M, int C, void* ws,
+                           size_t ws_bytes, osi_stream_t stream) {
+    OSI_REQUIRE(g && consumers && psum_g && ws && M > 0 && C > 0 && C % 4 == 0 && P > 0);
+    for (int k = 0; k < 2; ++k) {
+        const osi_bn_fused_consumer& c = consumers[k];
+        OSI_REQUIRE(c.y && c.mean && c.invstd && c.gamma && c.psum_gx && c.dy && c.dgamma && c.dbeta);
+    }
+    OSI_REQUIRE(consumers[1].dy != consumers[0].dy && consumers[1].dy != g);
+    OSI_REQUIRE(ws_bytes >= osi_bn_backward_fused2_workspace(C));
+    int S, Pc;
+    bwd_groups(P, S, Pc);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t per = (size_t)2 * OSI_BN_GROUPS * C + 2 * (size_t)C;     // one consumer's slice of ws: the layout of osi_bn_backward_fused
+    BwdConsTable t{};
+    BwdApplyCons a[2];
+    for (int k = 0; k < 2; ++k) {
+        const osi_bn_fused_consumer& c = consumers[k];
+        float* gb = (float*)ws + k * per;
+        float* gg = gb + (size_t)S * C;
+        float* c1 = gg + (size_t)S * C;
+        float* c2 = c1 + C;
+        t.k[k] = BwdCons{psum_g, c.psum_gx, gb, gg, c.dgamma, c.dbeta, c1, c2};
+        a[k] = BwdApplyCons{(const f32x4*)c.y, (const f32x4*)c.mean, (const f32x4*)c.invstd, (const f32x4*)c.gamma, (const f32x4*)c1,
+                            (const f32x4*)c2, (f32x4*)c.dy};
+    }
+    if (int e = bwd_reduce_partials(t, 2, P, M, C, S, Pc, st)) return e;
+    const size_t n4 = (size_t)M * C / 4;
+    const int c4n = C / 4;
+    const int grid = stream_grid(n4, true);
+    int geo = stream_geo(c4n);
+    if (geo == 2 && (grid & 1) && (size_t)grid < (n4 + NT - 1) / NT) geo = 0;   // an odd grid that loops mixes tile parities in a workgroup
+#define OSI_FUSED_APPLY2(GEO_) hipLaunchKernelGGL((k_bn_bwd_apply2<GEO_>), dim3(grid), dim3(NT), 0, st, (const f32x4*)g, a[0], a[1], n4, c4n)
+    OSI_BY_GEO(geo, OSI_FUSED_APPLY2);
+#undef OSI_FUSED_APPLY2
     OSI_LAUNCH_CHECK();
     return OSI_OK;
 }
@@ -833,17 +978,15 @@ int osi_bn_backward_fused(const float* g, const float* y, const float* mean, con
 int osi_bn_backward_reduce(const float* psum_g, const float* psum_gx, int P, float* dgamma, float* dbeta, int M, int C, void* ws,
                            size_t ws_bytes, osi_stream_t stream) {
     OSI_REQUIRE(psum_g && psum_gx && dgamma && dbeta && ws && M > 0 && C > 0 && P > 0);
-    int S = osi_cdiv(P, 64);
-    if (S > OSI_BN_GROUPS) S = OSI_BN_GROUPS;
-    const int Pc = osi_cdiv(P, S);
-    S = osi_cdiv(P, Pc);
+    int S, Pc;
+    bwd_groups(P, S, Pc);
     OSI_REQUIRE(ws_bytes >= ((size_t)2 * S * C + 2 * (size_t)C) * sizeof(float));
     hipStream_t st = (hipStream_t)stream;
     float* gb = (float*)ws;
     float* gg = gb + (size_t)S * C;
     float* c1 = gg + (size_t)S * C;
     float* c2 = c1 + C;
-    if (int e = bwd_reduce_partials(psum_g, psum_gx, P, M, C, gb, gg, S, Pc, dgamma, dbeta, c1, c2, st)) return e;
+    if (int e = bwd_reduce_partials(one_cons(psum_g, psum_gx, gb, gg, dgamma, dbeta, c1, c2), 1, P, M, C, S, Pc, st)) return e;
     return OSI_OK;
 }
 
@@ -874,15 +1017,17 @@ static int bn_frozen_impl(const float* dout, const void* msk, int mode, const os
         else if (mode == 2) hipLaunchKernelGGL(k_bn_bwd_partial<2>, dim3(P), dim3(NT), 0, st, dout, msk, cs[k].y, cs[k].mean, cs[k].invstd, M, C, rpb, pdb, pdg, ps);
         else hipLaunchKernelGGL(k_bn_bwd_partial<0>, dim3(P), dim3(NT), 0, st, dout, msk, cs[k].y, cs[k].mean, cs[k].invstd, M, C, rpb, pdb, pdg, ps);
         OSI_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_bn_bwd_final, dim3(osi_cdiv(C, NT / 64)), dim3(NT), 0, st, pdb, pdg, P, M, C, cs[k].dgamma, cs[k].dbeta, c1, c1 + C);
+        hipLaunchKernelGGL(k_bn_bwd_final, dim3(osi_cdiv(C, NT / 64)), dim3(NT), 0, st, one_cons(pdb, pdg, nullptr, nullptr, cs[k].dgamma, cs[k].dbeta, c1, c1 + C), false, P, M, C);
         OSI_LAUNCH_CHECK();
     }
     const size_t n4 = (size_t)M * C / 4;
     const int grid = stream_grid(n4, true), c4n = C / 4;
     auto D = (const f32x4*)dout; auto S0 = (const f32x4*)cs[0].scale; auto S1 = (const f32x4*)(n == 2 ? cs[1].scale : nullptr);
     auto DY0 = (f32x4*)cs[0].dy; auto DY1 = (f32x4*)(n == 2 ? cs[1].dy : nullptr); auto GO = (f32x4*)gmasked;
-#define OSI_FRZ_APPLY(MODE_, EMIT_, TWO_) hipLaunchKernelGGL((k_bn_frozen_apply<MODE_, EMIT_, TWO_>), dim3(grid), dim3(NT), 0, st, D, msk, S0, S1, DY0, DY1, GO, n4, c4n, ps)
-    if (mode == 3) OSI_FRZ_APPLY(3, false, false);
+    const int geo = stream_geo(c4n);
+#define OSI_FRZ_APPLY_G(MODE_, EMIT_, TWO_, GEO_) hipLaunchKernelGGL((k_bn_frozen_apply<MODE_, EMIT_, TWO_, GEO_>), dim3(grid), dim3(NT), 0, st, D, msk, S0, S1, DY0, DY1, GO, n4, c4n, ps)
+#define OSI_FRZ_APPLY(MODE_, EMIT_, TWO_) do { if (geo == 1) OSI_FRZ_APPLY_G(MODE_, EMIT_, TWO_, 1); else if (geo == 2) OSI_FRZ_APPLY_G(MODE_, EMIT_, TWO_, 2); else OSI_FRZ_APPLY_G(MODE_, EMIT_, TWO_, 0); } while (0)
+    if (mode == 3) OSI_FRZ_APPLY_G(3, false, false, 0);
     else if (mode == 2) {
         if (n == 2) { if (gmasked) OSI_FRZ_APPLY(2, true, true); else OSI_FRZ_APPLY(2, false, true); }
         else { if (gmasked) OSI_FRZ_APPLY(2, true, false); else OSI_FRZ_APPLY(2, false, false); }
@@ -891,6 +1036,7 @@ static int bn_frozen_impl(const float* dout, const void* msk, int mode, const os
         else { if (gmasked) OSI_FRZ_APPLY(0, true, false); else OSI_FRZ_APPLY(0, false, false); }
     }
 #undef OSI_FRZ_APPLY
+#undef OSI_FRZ_APPLY_G
     OSI_LAUNCH_CHECK();
     return OSI_OK;
 }

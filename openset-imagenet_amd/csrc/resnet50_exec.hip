@@ -82,7 +82,7 @@ struct osi_resnet50 {
     int t_fc_w, t_fc_b, t_lg_w, t_lg_b;
     // stem
     int Hs, Ws, Hp, Wp;              // stem conv output, maxpool output
-    size_t x4, wpack, gpack, a_pool, pool_idx, pooled, feat, logits_ws;
+    size_t x4, wpack, gpack, a_pool, pool_idx, pooled, feat;
     size_t bn_ws, bn_ws2, bn_ws_bytes, wg_ws, wg_ws_bytes, dg_ws, dg_ws_bytes;   // bn_ws2: BatchNorm scratch of the side-stream branch
     size_t stem_ws = 0, stem_ws_bytes = 0;
     size_t wino_ws = 0, wino_ws_bytes = 0;   // transformed weights of the Winograd forms (main stream only: forward conv2, in-block input gradients)
@@ -342,7 +342,6 @@ int osi_resnet50_create(osi_resnet50_t* out, int B, int H, int W, int fc_dim, in
     n->stage_hi[0] = n->param_floats;  // head gradients are final after stage 0 (head + layer4)
     n->pooled = n->ws_alloc((size_t)B * 2048);
     n->feat = n->ws_alloc((size_t)B * fc_dim);
-    n->logits_ws = n->ws_alloc((size_t)B * out_features);
     n->dfeat = n->ws_alloc((size_t)B * fc_dim);
     n->dpooled = n->ws_alloc((size_t)B * 2048);
     // scratch sizing
@@ -357,6 +356,8 @@ int osi_resnet50_create(osi_resnet50_t* out, int B, int H, int W, int fc_dim, in
         if (b2 > bnws) bnws = b2;
         size_t b3 = osi_conv_fwd_bnstats_workspace(&c.d);
         if (b3 > bnws) bnws = b3;
+        size_t b4 = osi_bn_backward_fused2_workspace(c.d.Cout);   // a projection block's two BatchNorm backwards in one pass
+        if (b4 > bnws) bnws = b4;
         size_t wg = osi_conv_wgrad_workspace(&c.d);
         if (wg > wgws) wgws = wg;
         wg = osi_stem_wgrad_direct_workspace(&c.d);
@@ -547,17 +548,16 @@ int osi_resnet50_bind_input_nhwc4(osi_resnet50_t n, const float* x_nhwc4) {
     return OSI_OK;
 }
 
-// avgpool -> fc -> logits, copies to the caller's tensors
+// avgpool -> fc -> logits; the logits are written to the caller's tensor, the features are copied there
 static int head_fwd(osi_resnet50* n, const float* params, float* ws, float* logits, float* features, hipStream_t st) {
     const float* last = ws + n->blocks.back().out;
     OSI_TRY(osi_avgpool_fwd(last, ws + n->pooled, n->B, n->Hf * n->Wf, 2048, st));
     const Tensor& fw = n->tensors[n->t_fc_w]; const Tensor& fb = n->tensors[n->t_fc_b]; const Tensor& lw = n->tensors[n->t_lg_w];
     OSI_TRY(osi_linear_fwd(ws + n->pooled, params + fw.off, params + fb.off, ws + n->feat, n->B, 2048, n->F, st));
     const float* lb = n->t_lg_b >= 0 ? params + n->tensors[n->t_lg_b].off : nullptr;
-    OSI_TRY(osi_linear_fwd(ws + n->feat, params + lw.off, lb, ws + n->logits_ws, n->B, n->F, n->O, st));
+    // the logits have no later reader in the workspace: straight into the caller's tensor (the features are read by the head's backward)
+    OSI_TRY(osi_linear_fwd(ws + n->feat, params + lw.off, lb, logits, n->B, n->F, n->O, st));
     if (hipMemcpyAsync(features, ws + n->feat, (size_t)n->B * n->F * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
-        return OSI_ERR_LAUNCH;
-    if (hipMemcpyAsync(logits, ws + n->logits_ws, (size_t)n->B * n->O * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
         return OSI_ERR_LAUNCH;
     return OSI_OK;
 }
@@ -866,6 +866,24 @@ static int bn_bwd_fused(osi_resnet50* n, int ci, const float* params, float* gra
     return OSI_OK;
 }
 
+// The same for the two BatchNorms of a projection block in one pass over the gated gradient in buffer gi: conv `ci` (bn3, column 0 of
+// dg_ws) -> buffer dyi, conv `cj` (the shortcut, column 1) -> buffer dyj. Every result is the one of the two bn_bwd_fused calls.
+static int bn_bwd_fused_pair(osi_resnet50* n, int ci, int cj, const float* params, float* grads, float* ws, int gi, int dyi, int dyj,
+                             hipStream_t st) {
+    const float* psum_g = ws + n->dg_ws;
+    osi_bn_fused_consumer cs[2];
+    const int idx[2] = {ci, cj}, out[2] = {dyi, dyj};
+    for (int k = 0; k < 2; ++k) {
+        Conv& c = n->convs[idx[k]];
+        BN& b = n->bns[c.bn];
+        cs[k] = osi_bn_fused_consumer{ws + c.y, ws + b.mean, ws + b.invstd, params + b.g_off, psum_g + (size_t)(1 + k) * n->fused_P * b.C,
+                                      ws + n->scratch[out[k]], n->dgam(grads, ws, b), n->dbet(grads, ws, b)};
+    }
+    BN& b = n->bns[n->convs[ci].bn];
+    OSI_TRY(osi_bn_backward_fused2(ws + n->scratch[gi], cs, psum_g, n->fused_P, b.M, b.C, ws + n->bn_ws, n->bn_ws_bytes, st));
+    return n->mark(OSI_PROF_BN_BWD, st);
+}
+
 // Frozen statistics. Finish the dgamma / dbeta of conv `ci`'s BatchNorm from the row-tile partials a dgrad epilogue left in dg_ws (column
 // `which` as in bn_bwd_fused). Nothing is launched in an input-only backward.
 static int bn_reduce_frozen(osi_resnet50* n, int ci, float* grads, float* ws, int which, hipStream_t st) {
@@ -994,10 +1012,15 @@ static int block_backward(osi_resnet50* n, int bi, const float* params, float* g
         }
     } else if (n->go_fused) {
         if (has_ds) {
+            // projection block: bn3 and the shortcut's BatchNorm read the same gated gradient — one pass streams it once and writes both
+            // dy tensors (four buffers live at once, as in the frozen dataflow above); the weight gradients keep their side-stream order
             Conv& cd = n->convs[k.ds];
             int t1 = n->take(st);
             if (t1 < 0) return t1;
-            OSI_TRY(bn_bwd_fused(n, k.ds, params, grads, ws, go, t1, 1, st));
+            d3 = n->take(st);
+            if (d3 < 0) return d3;
+            OSI_TRY(bn_bwd_fused_pair(n, k.c3, k.ds, params, grads, ws, go, d3, t1, st));
+            n->give(go);
             OSI_TRY(wgrad(n, k.ds, grads, ws, t1, x, st));
             if (!no_dx) {
                 dxbase = n->take(st);
@@ -1005,12 +1028,12 @@ static int block_backward(osi_resnet50* n, int bi, const float* params, float* g
                 OSI_TRY(dgrad_plain(n, &cd.d, S(t1), params + cd.w_off, S(dxbase), ds_sparse ? 2 : 0, st));
             }
             n->give(t1);
+        } else {
+            d3 = n->take(st);
+            if (d3 < 0) return d3;
+            OSI_TRY(bn_bwd_fused(n, k.c3, params, grads, ws, go, d3, 0, st));
+            dxbase = go;           // identity skip: the masked gradient itself continues to the block input
         }
-        d3 = n->take(st);
-        if (d3 < 0) return d3;
-        OSI_TRY(bn_bwd_fused(n, k.c3, params, grads, ws, go, d3, 0, st));
-        if (has_ds) n->give(go);
-        else dxbase = go;          // identity skip: the masked gradient itself continues to the block input
     } else {
         dxbase = n->take(st);
         if (dxbase < 0) return dxbase;

@@ -51,6 +51,12 @@ class BnFrozenConsumer(Structure):
                 ("dbeta", c_void_p)]
 
 
+class BnFusedConsumer(Structure):
+    """osi_bn_fused_consumer"""
+    _fields_ = [("y", c_void_p), ("mean", c_void_p), ("invstd", c_void_p), ("gamma", c_void_p), ("psum_gx", c_void_p), ("dy", c_void_p),
+                ("dgamma", c_void_p), ("dbeta", c_void_p)]
+
+
 class OptSegment(Structure):
     """osi_opt_segment: the 16-byte units [begin4, end4) of the arena belong to kernel group `group`"""
     _fields_ = [("begin4", ctypes.c_uint), ("end4", ctypes.c_uint), ("group", c_int)]
@@ -107,6 +113,8 @@ _SIGS = {
     "osi_conv_dgrad_fused": (c_int, [_PD, P, P, P, P, P, c_int, POINTER(c_int), P]),
     "osi_bn_backward_reduce": (c_int, [P, P, c_int, P, P, c_int, c_int, P, c_size_t, P]),
     "osi_bn_backward_fused": (c_int, [P, P, P, P, P, P, P, c_int, P, P, P, c_int, c_int, P, c_size_t, P]),
+    "osi_bn_backward_fused2_workspace": (c_size_t, [c_int]),
+    "osi_bn_backward_fused2": (c_int, [P, P, P, c_int, c_int, c_int, P, c_size_t, P]),
     "osi_conv_wgrad_workspace": (c_size_t, [_PD]),
     "osi_conv_wgrad": (c_int, [_PD, P, P, P, P, c_size_t, P]),
     "osi_stem_weight_pack": (c_int, [P, P, c_int, P]),
