@@ -37,7 +37,8 @@ const char* osi_strerror(int code);
 /* Process-wide development knobs (A/B measurements; every default is the measured optimum). Launch functions only READ them and never
  * consult the environment. Unknown name or a value outside the knob's range -> OSI_ERR_ARG (nothing is changed). Not to be changed while
  * launches are in flight; an executor (osi_resnet50_create) sizes its workspace for the values in force at create and refuses to run
- * (OSI_ERR_STATE) once a plan-relevant one (marked *) differs.
+ * (OSI_ERR_STATE) once a plan-relevant one (marked *) differs. The table below documents the one list the library is built from
+ * (OSI_TUNING_KNOBS in csrc/osi_common.h); osi_tuning_info enumerates that list, and tests/test_abi.py holds this table to it.
  *   name             range         default  meaning
  *   wgrad_tile *     0 | 64        0        64 forces 64x64 weight-gradient tiles; 0 = 128-wide wherever the channel counts allow
  *   wgrad_blocks *   1 .. 2^20     2048     split-K footprint budget of one weight-gradient launch, in 64x64-workgroup units
@@ -73,6 +74,9 @@ const char* osi_strerror(int code);
  *   dp_reserved_cus * 0 .. 128     0        data parallel: CUs' worth of wave slots the tail plan leaves to co-resident communication kernels */
 int osi_set_tuning(const char* name, int value);
 int osi_get_tuning(const char* name, int* value);
+/* Row i of the knob list: name (a static string), default, inclusive range, and whether the knob is plan-relevant (* above). Any
+ * output pointer may be NULL. OSI_ERR_ARG for i past the end: callers enumerate from 0 until it says so. */
+int osi_tuning_info(int i, const char** name, int* def, int* lo, int* hi, int* plan_relevant);
 
 /* ---- convolution (torchvision.models.resnet50 body constructed at openset_imagenet/model.py:17, run at model.py:37) --- */
 typedef struct {

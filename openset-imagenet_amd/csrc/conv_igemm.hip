@@ -1954,7 +1954,9 @@ static bool desc_ok(const osi_conv_desc* d) {
 }
 static bool is_stem(const osi_conv_desc* d) { return d->Cin == 4 && d->R == 7 && d->S == 7; }
 
-static ConvP make_p(const osi_conv_desc* d) {
+// which two tensors a launch reads through its buffer descriptors (p.x / p.w): their sizes bound the descriptors
+enum ConvDir { DIR_FWD /* x, w */, DIR_DGRAD /* dy, w */, DIR_WGRAD /* x, dy */ };
+static ConvP make_p(const osi_conv_desc* d, ConvDir dir) {
     ConvP p{};
     p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Ho = d->Ho; p.Wo = d->Wo; p.Cout = d->Cout;
     p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad = d->pad;
@@ -1962,6 +1964,10 @@ static ConvP make_p(const osi_conv_desc* d) {
     p.Ktot = is_stem(d) ? 224 : d->R * d->S * d->Cin;
     p.dHoWo = make_fastdiv((uint32_t)(d->Ho * d->Wo));
     p.dWo = make_fastdiv((uint32_t)d->Wo);
+    p.unit = (d->R == 1 && d->S == 1 && d->stride == 1 && d->pad == 0) ? 1 : 0;
+    const int in_bytes = (int)((size_t)d->B * d->H * d->W * d->Cin * 4), out_bytes = (int)((size_t)d->B * d->Ho * d->Wo * d->Cout * 4);
+    p.x_bytes = dir == DIR_DGRAD ? out_bytes : in_bytes;
+    p.w_bytes = dir == DIR_WGRAD ? out_bytes : (int)((size_t)d->Cout * p.Ktot * 4);
 #ifdef OSI_STAMPS
     p.stamps = g_osi_stamps;
 #endif
@@ -2009,35 +2015,31 @@ static TailPlan plan_tail_split(long MT, int NT, int T) {
 }
 static size_t tail_slab_floats(const TailPlan& t) { return t.S > 1 ? (size_t)t.tiles * t.S * 4096 : 0; }
 
-template <int XF, bool W3 = false, bool OE = false>
-static int launch_fwd_split(ConvP p, const TailPlan& tp, float* slab, hipStream_t st) {
-    p.MT = osi_cdiv(p.M, 64); p.NT = p.Cout / 64;
+// K-split tail of a 64x64 launch (p.MT / p.NT set): the full rounds' tiles first, then one key per (remainder row tile, split); the grid
+static int set_tail_split(ConvP& p, const TailPlan& tp, float* slab) {
     p.MT1 = tp.MT1; p.ks_S = tp.S; p.ks_T = tp.ksT; p.ks_slab = slab;
     p.g1 = osi_cdiv(p.MT1, 8) * 8 * p.NT;
     const int keys = (p.MT - p.MT1) * tp.S;
-    const int grid = p.g1 + osi_cdiv(keys, 8) * 8 * p.NT;
-    size_t smem = (size_t)((W3 ? W3_WROWS : 64) + 64) * LDR * sizeof(float);
-    if (XF) smem += (size_t)2 * p.Cin * sizeof(float);
-    if (W3) p.cW[0] = make_fastdiv((uint32_t)p.W + 1);     // row windows: division by the padded row length
-    if (int e = set_smem(k_conv_fwd<1, 1, false, 1, XF, true, W3, OE>, smem)) return e;
-    hipLaunchKernelGGL((k_conv_fwd<1, 1, false, 1, XF, true, W3, OE>), dim3(grid), dim3(256), smem, st, p);
-    OSI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_conv_fwd_tail_fixup, dim3(tp.tiles), dim3(256), 0, st, p);
-    OSI_LAUNCH_CHECK();
-    return OSI_OK;
+    return p.g1 + osi_cdiv(keys, 8) * 8 * p.NT;
 }
 
-template <int WM, int WN, bool STEM, int NST = 2, int XF = 0, bool W3 = false, bool OE = false>
-static int launch_fwd(ConvP p, hipStream_t st) {
+// SPLIT (64x64 single-buffered only): K-split tail per `tp` through `slab`, convolution launch + fix-up pass. With WM = WN = NST = 1 the
+// tile geometry and LDS size below are those the separate split launcher computed; only the grid and the fix-up differ.
+template <int WM, int WN, bool STEM, int NST = 2, int XF = 0, bool W3 = false, bool OE = false, bool SPLIT = false>
+static int launch_fwd(ConvP p, hipStream_t st, const TailPlan* tp = nullptr, float* slab = nullptr) {
     constexpr int BM = 64 * WM, BN = 64 * WN;
     p.MT = osi_cdiv(p.M, BM); p.NT = p.Cout / BN;
     size_t smem = NST * (size_t)((W3 ? W3_WROWS : BM) + BN) * LDR * sizeof(float);
     if (XF) smem += (size_t)2 * p.Cin * sizeof(float);
     if (W3) p.cW[0] = make_fastdiv((uint32_t)p.W + 1);     // row windows: division by the padded row length
-    if (int e = set_smem(k_conv_fwd<WM, WN, STEM, NST, XF, false, W3, OE>, smem)) return e;
-    int grid = osi_cdiv(p.MT, 8) * 8 * p.NT;
-    hipLaunchKernelGGL((k_conv_fwd<WM, WN, STEM, NST, XF, false, W3, OE>), dim3(grid), dim3(256), smem, st, p);
+    if (int e = set_smem(k_conv_fwd<WM, WN, STEM, NST, XF, SPLIT, W3, OE>, smem)) return e;
+    const int grid = SPLIT ? set_tail_split(p, *tp, slab) : osi_cdiv(p.MT, 8) * 8 * p.NT;
+    hipLaunchKernelGGL((k_conv_fwd<WM, WN, STEM, NST, XF, SPLIT, W3, OE>), dim3(grid), dim3(256), smem, st, p);
     OSI_LAUNCH_CHECK();
+    if constexpr (SPLIT) {
+        hipLaunchKernelGGL(k_conv_fwd_tail_fixup, dim3(tp->tiles), dim3(256), 0, st, p);
+        OSI_LAUNCH_CHECK();
+    }
     return OSI_OK;
 }
 // 1x1 stride-1 forward with Cin = 64 / 128 on the persistent row walker (k_conv1x1_rows): four resident workgroups per CU
@@ -2055,14 +2057,18 @@ static int launch_fwd_rows(ConvP p, hipStream_t st) {
 }
 // "fwd_rows": 0 off; 1 (default) Cin = 64 and at least eight row tiles per CU (the 56 x 56 layers of layer1 at batch >= 42: 64->256
 // 78 -> 86 TFLOP/s, 64->64 76.5 -> 79.9; Cin = 128 @28x28 measured 102.5 -> 100.5: stays on k_conv_fwd); 2 every shape the kernel takes (tests)
-static bool rows_rule(const osi_conv_desc* d, bool unit, const float* res) {
+static bool rows_rule(const osi_conv_desc* d, bool shortcut) {
     const int m = g_osi_tuning.fwd_rows;
-    if (!m || !unit || res || d->Cout % 64 || (d->Cin != 64 && d->Cin != 128)) return false;
+    const bool unit = d->R == 1 && d->S == 1 && d->stride == 1 && d->pad == 0;
+    if (!m || !unit || shortcut || d->Cout % 64 || (d->Cin != 64 && d->Cin != 128)) return false;
     return m == 2 || (d->Cin == 64 && (long)d->B * d->Ho * d->Wo >= 64L * 8 * hw_cus());
 }
 
-template <int WM, int WN, int NST, int FUSED, bool POOL = false, bool W3 = false>
-static int launch_dgrad_impl(ConvP p, hipStream_t st) {
+// SPLIT (64x64 single-buffered, stride 1 only): K-split tail per `tp` through `slab`, convolution launch + fix-up pass. With s = 1 and
+// WM = WN = NST = 1 the class divisors, p.unit, MT / NT and the LDS size are those the separate split launcher computed. set_smem is now
+// reached on the split path too: it only acts above 64 KiB and the 64x64 single-buffered tile needs 18 - 27 KiB, so nothing is set.
+template <int WM, int WN, int NST, int FUSED, bool POOL = false, bool W3 = false, bool SPLIT = false>
+static int launch_dgrad(ConvP p, hipStream_t st, const TailPlan* tp = nullptr, float* slab = nullptr) {
     constexpr int BM = 64 * WM, BN = 64 * WN;
     const int s = p.stride;
     for (int ph = 0; ph < s; ++ph)
@@ -2077,51 +2083,17 @@ static int launch_dgrad_impl(ConvP p, hipStream_t st) {
     size_t smem = 2 * (size_t)((W3 ? W3_WROWS : BM) * LDR + BK * (BN + 4)) * sizeof(float);
     smem = smem / 2 * NST;
     if (W3) p.cW[1] = make_fastdiv((uint32_t)p.W + 1);     // row windows: division by the padded row length
-    if (int e = set_smem(k_conv_dgrad<WM, WN, NST, FUSED, false, POOL, W3>, smem)) return e;
-    int grid = osi_cdiv(p.MT, 8) * 8 * p.NT;
-    hipLaunchKernelGGL((k_conv_dgrad<WM, WN, NST, FUSED, false, POOL, W3>), dim3(grid, s * s), dim3(256), smem, st, p, Hc, Wc);
+    if (int e = set_smem(k_conv_dgrad<WM, WN, NST, FUSED, SPLIT, POOL, W3>, smem)) return e;
+    const int grid = SPLIT ? set_tail_split(p, *tp, slab) : osi_cdiv(p.MT, 8) * 8 * p.NT;
+    hipLaunchKernelGGL((k_conv_dgrad<WM, WN, NST, FUSED, SPLIT, POOL, W3>), dim3(grid, s * s), dim3(256), smem, st, p, Hc, Wc);
     OSI_LAUNCH_CHECK();
-    return OSI_OK;
-}
-// 64x64 single-buffered input gradient with a K-split tail (stride 1): convolution launch + fix-up pass
-template <int FUSED, bool W3 = false>
-static int launch_dgrad_split(ConvP p, const TailPlan& tp, float* slab, hipStream_t st) {
-    p.cHW[0] = make_fastdiv((uint32_t)(p.H * p.W)); p.cW[0] = make_fastdiv((uint32_t)p.W);
-    p.unit = (p.R == 1 && p.S == 1 && p.pad == 0) ? 1 : 0;
-    p.MT = osi_cdiv((long)p.B * p.H * p.W, 64); p.NT = p.Cin / 64;
-    p.MT1 = tp.MT1; p.ks_S = tp.S; p.ks_T = tp.ksT; p.ks_slab = slab;
-    p.g1 = osi_cdiv(p.MT1, 8) * 8 * p.NT;
-    const int keys = (p.MT - p.MT1) * tp.S;
-    const int grid = p.g1 + osi_cdiv(keys, 8) * 8 * p.NT;
-    const size_t smem = (size_t)((W3 ? W3_WROWS : 64) * LDR + BK * (64 + 4)) * sizeof(float);
-    if (W3) p.cW[1] = make_fastdiv((uint32_t)p.W + 1);
-    hipLaunchKernelGGL((k_conv_dgrad<1, 1, 1, FUSED, true, false, W3>), dim3(grid, 1), dim3(256), smem, st, p, p.H, p.W);
-    OSI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_conv_dgrad_tail_fixup<FUSED>, dim3(tp.tiles), dim3(256), 0, st, p);
-    OSI_LAUNCH_CHECK();
+    if constexpr (SPLIT) {
+        hipLaunchKernelGGL(k_conv_dgrad_tail_fixup<FUSED>, dim3(tp->tiles), dim3(256), 0, st, p);
+        OSI_LAUNCH_CHECK();
+    }
     return OSI_OK;
 }
 
-static int dgrad_flavour(const ConvP& p) {
-    if (!p.addend && !p.ebits && !p.ey1) return 2;     // in-block: gate recomputed from y0 and / or sums over y0
-    if (!p.escale0) return 3;                          // block input: addend, bitmask, sums over y0 (and y1)
-    return 1;
-}
-template <int WM, int WN, int NST = 2>
-static int launch_dgrad(ConvP p, hipStream_t st) {
-    // the fused epilogue (mask / BatchNorm reductions) is its own instantiation so that plain launches keep the small one
-    if (p.ebits || p.esum || p.escale0) {
-        if (NST != 1 || WM != 1) return OSI_ERR_ARG;   // fusion is built for the single-buffered 64-row tiles the executor uses
-        if (p.epool) return WN == 1 ? launch_dgrad_impl<1, 1, 1, 1, true>(p, st) : OSI_ERR_ARG;
-        if (WN == 1) {   // the two fusion flavours the executor issues have their own instantiations (see dgrad_epilogue64)
-            const int fl = dgrad_flavour(p);
-            if (fl == 2) return launch_dgrad_impl<1, 1, 1, 2>(p, st);
-            if (fl == 3) return launch_dgrad_impl<1, 1, 1, 3>(p, st);
-        }
-        return launch_dgrad_impl<1, WN, 1, 1>(p, st);
-    }
-    return launch_dgrad_impl<WM, WN, NST, false>(p, st);
-}
 template <int WM, int WN, bool STEM, int NST = 2, bool XF = false>
 static int launch_wgrad(ConvP p, int splits, hipStream_t st) {
     constexpr int BM = 64 * WM, BN = 64 * WN;
@@ -2164,19 +2136,6 @@ static bool wgrad3_ok(const osi_conv_desc* d) {
     // stride 2: four parity sub-grids of the input (even H and W), window of 130 + 2 Wo rows in at most six passes
     return d->stride == 2 && g_osi_tuning.wgrad3 >= 2 && d->H % 2 == 0 && d->W % 2 == 0 && 130 + 2 * d->Wo <= 192;
 }
-static void plan_wgrad3(const osi_conv_desc* d, int& splits, int& kchunk) {
-    const long cells = (long)(d->Cout / 64) * (d->Cin / 32);
-    const long M = (long)d->B * d->Ho * d->Wo;
-    // four 256-thread workgroups per CU (register budget of the nine accumulator sets) fill the machine; as for the per-tap kernel
-    // the side stream gets half of that by default
-    long s = (g_osi_tuning.wgrad3_blocks + cells - 1) / cells;
-    const long maxs = (M + 8 * W3_BKP - 1) / (8 * W3_BKP);
-    if (s > maxs) s = maxs;
-    if (s < 1) s = 1;
-    if (s >= 8) { long r8 = (s + 4) / 8 * 8; if (r8 > maxs) r8 = maxs / 8 * 8; if (r8 >= 8) s = r8; }
-    long chunk = ((M + s - 1) / s + W3_BKP - 1) / W3_BKP * W3_BKP;
-    splits = (int)((M + chunk - 1) / chunk); kchunk = (int)chunk;
-}
 template <int NWIN, bool XF, bool S2 = false>
 static int launch_wgrad3_n(ConvP p, int splits, hipStream_t st) {
     p.MT = p.Cout / 64;
@@ -2200,11 +2159,222 @@ static int launch_wgrad3(const ConvP& p, int splits, hipStream_t st) {
     return launch_wgrad3_n<5, XF>(p, splits, st);
 }
 
-// wgrad geometry shared by the workspace query and the launcher
-struct WgradPlan { int wm, wn, splits, kchunk; };
+// ---- run-time values -> template instances ---------------------------------------------------------------------------------------
+// f(Int<V>{}) for the V of the list that equals v, OSI_ERR_ARG when none does: a chain of compares, nothing indirect on the launch path.
+// The dispatchers below guard every combination with `if constexpr (..._exists(...))`: only the kernels those predicates name are built.
+template <int V> using Int = std::integral_constant<int, V>;
+template <int... Vs, class F>
+static int pick(int v, F&& f) {
+    int r = OSI_ERR_ARG;
+    (void)((v == Vs && ((r = f(Int<Vs>{})), true)) || ...);
+    return r;
+}
+struct TileShape { int wm, wn, nst; };       // workgroup tile in 64-row / 64-column units, LDS stages
+static TileShape tile_shape(int tile) {      // by OSI_TILE_* id (128x128, 128x64, 64x128, 64x64, then their _S1 forms); {0, 0, 0}: no such id
+    static const TileShape ids[9] = {{0, 0, 0}, {2, 2, 2}, {2, 1, 2}, {1, 2, 2}, {1, 1, 2}, {1, 1, 1}, {1, 2, 1}, {2, 2, 1}, {2, 1, 1}};
+    return tile >= 1 && tile <= 8 ? ids[tile] : ids[0];
+}
+static int tile_rows(int tile) { return tile_shape(tile).wm == 2 ? 128 : 64; }
+template <class F>
+static int with_shape(TileShape s, F&& f) {   // f(WM, WN, NST) as constants
+    return pick<1, 2>(s.wm, [&](auto WM) {
+        return pick<1, 2>(s.wn, [&](auto WN) {
+            return pick<1, 2>(s.nst, [&](auto NST) { return f(WM, WN, NST); });
+        });
+    });
+}
+// how a 64x64 single-buffered launch differs from the plain tile kernel (bits; pool mode is the input gradient's and excludes the others)
+enum LaunchForm { FORM_PLAIN = 0, FORM_POOL = 1, FORM_W3 = 2, FORM_SPLIT = 4 };
+
+// 3x3 / stride 1 / pad 1 shapes the row-window loaders take (one activation window per tap ROW and channel slice, see k_conv_fwd W3);
+// the forward and the input gradient add their knob and channel conditions
+static bool row_window_shape(const osi_conv_desc* d) {
+    return d->R == 3 && d->S == 3 && d->stride == 1 && d->pad == 1 && d->W >= 7 && d->H == d->Ho && d->W == d->Wo;
+}
+
+// ---- forward: plan ---------------------------------------------------------------------------------------------------------------
+// floats of the statistics part of the forward workspace (row-tile partials + finalize scratch), rounded to 256 B: the slab of a
+// K-split tail starts behind it
+static size_t fwd_stats_floats(const osi_conv_desc* d) {
+    const size_t n = (size_t)2 * osi_cdiv((long)d->B * d->Ho * d->Wo, 64) * d->Cout + (size_t)2 * 32 * d->Cout;
+    return (n + 63) / 64 * 64;
+}
+// K-split plan of the forward (GEMM rows = output pixels, columns Cout, K over Cin) or the stride-1 input gradient (input pixels, Cin, Cout)
+static TailPlan tail_plan(const osi_conv_desc* d, bool dgrad) {
+    const long M = (long)d->B * (dgrad ? d->H * d->W : d->Ho * d->Wo);
+    const int cols = dgrad ? d->Cin : d->Cout, kc = dgrad ? d->Cout : d->Cin;
+    if (is_stem(d) || cols % 64 || kc % BK || (dgrad && d->stride != 1)) return TailPlan{(int)osi_cdiv(M, 64), 1, 0, 0};
+    return plan_tail_split(osi_cdiv(M, 64), cols / 64, d->R * d->S * kc / BK);
+}
+enum FwdKind { FWD_STEM_DIRECT, FWD_STEM_GEMM, FWD_ROWS, FWD_SPLIT, FWD_W3, FWD_TILE };
+struct FwdPlan {
+    FwdKind kind;
+    int tile;           // tile id: the requested one, or the measured rule's (64x64 single-buffered under FWD_SPLIT / FWD_W3)
+    bool w3;            // FWD_SPLIT / FWD_W3: row-window loader (FWD_W3 is its single-pass launch)
+    TailPlan tail;      // K-split plan of the shape: what the workspace queries size the slab for; launched by FWD_SPLIT only
+    int stat_rows;      // rows per statistics partial
+    size_t slab_off;    // floats in front of the slab in the caller's workspace: the statistics part, where statistics are wanted
+};
+// The plan of a forward launch, training or inference form. tile: the caller's tile id, or OSI_TILE_AUTO for the measured plans;
+// shortcut: the loader adds a shortcut to the fused input activation (the fused activation alone changes no plan); stats: BatchNorm
+// partials are wanted; ws_bytes: the workspace the caller offers (statistics and slab; 0 = none, so no K split).
+static FwdPlan plan_fwd(const osi_conv_desc* d, int tile, bool shortcut, bool stats, size_t ws_bytes) {
+    FwdPlan pl{FWD_TILE, tile, false, tail_plan(d, false), 64, stats ? fwd_stats_floats(d) : 0};
+    if (is_stem(d)) {
+        // direct form (stem_direct.hip): full 8 x 16 output tiles only, one BatchNorm partial per tile of 128 pixels
+        const bool direct = tile == OSI_TILE_AUTO && stem_direct_geometry(d);
+        pl.kind = direct ? FWD_STEM_DIRECT : FWD_STEM_GEMM;
+        pl.stat_rows = direct ? STEM_TILE_PIXELS : 128;
+        return pl;
+    }
+    if (tile == OSI_TILE_AUTO) {
+        if (rows_rule(d, shortcut)) { pl.kind = FWD_ROWS; return pl; }      // short-K 1x1 layers: persistent row walker
+        pl.w3 = g_osi_tuning.fwd_w3 && !shortcut && row_window_shape(d);
+        // ragged last round split along K (plan_tail_split) when the caller's workspace has room for the slab [behind the statistics]
+        const bool split = pl.tail.S > 1 && ws_bytes >= (pl.slab_off + tail_slab_floats(pl.tail)) * sizeof(float);
+        if (split || pl.w3) { pl.kind = split ? FWD_SPLIT : FWD_W3; pl.tile = OSI_TILE_64x64_S1; return pl; }
+        // Measured on MI355X over the 22 ResNet-50 shapes at B=128 (tools/bench_conv.py, profiles/conv_layers_r01.txt): many
+        // small workgroups (4 resident per CU) beat large tiles almost everywhere because the ragged last round of the launch is
+        // shorter; only the 7x7-spatial layers with few column tiles prefer the wider 64x128 tile.
+        // Single-buffered LDS (two barriers per K tile, but 7-8 resident workgroups per CU) beats the double-buffered form on
+        // every shape: occupancy, not staging depth, is what hides the barrier and load latency of a 16-MFMA K step.
+        // 64x64 everywhere except the 7x7-spatial layers with few tiles, where the wider column tile halves the A re-reads
+        const long tiles64 = ((long)d->B * d->Ho * d->Wo + 63) / 64 * (d->Cout / 64);
+        pl.tile = (tiles64 < 1024 && d->Cout % 128 == 0) ? OSI_TILE_64x128_S1 : OSI_TILE_64x64_S1;
+        if (g_osi_tuning.fwd_wide && d->Cout % 128 == 0) pl.tile = OSI_TILE_64x128_S1;   // A/B: wide tiles wherever the channel count allows
+    }
+    pl.stat_rows = tile_rows(pl.tile);
+    return pl;
+}
+
+// k_conv_fwd<WM, WN, false, NST, XF, SPLIT, W3, OE> as built: every tile plain; the fused input activation (XF) and the output epilogue
+// (OE) for the single-buffered 64-row tiles the executor uses, never together; K split and row windows on the 64x64 one (no windows
+// under a fused shortcut)
+constexpr bool fwd_kernel_exists(int wm, int wn, int nst, int xf, bool split, bool w3, bool oe) {
+    if ((oe && xf != 0) || (w3 && xf == 2)) return false;
+    if (split || w3) return wm == 1 && wn == 1 && nst == 1;
+    return (xf == 0 && !oe) || (wm == 1 && nst == 1);
+}
+// The one place a forward plan becomes a kernel instance. XF: 0 plain input, 1 relu(bn(x)) in the loader, 2 the same plus a shortcut;
+// OE: inference form (output epilogue). ws: the caller's workspace (the slab lies pl.slab_off floats in).
+template <int XF, bool OE>
+static int launch_fwd_plan(const FwdPlan& pl, const ConvP& p, float* ws, hipStream_t st) {
+    if (pl.kind == FWD_STEM_GEMM) {
+        if constexpr (XF == 0 && !OE) return launch_fwd<2, 1, true>(p, st);
+        return OSI_ERR_ARG;
+    }
+    if (pl.kind == FWD_ROWS) {
+        if constexpr (XF != 2) return p.Cin == 64 ? launch_fwd_rows<2, XF, OE>(p, st) : launch_fwd_rows<4, XF, OE>(p, st);
+        return OSI_ERR_ARG;
+    }
+    auto go = [&](auto WM, auto WN, auto NST, auto FORM) -> int {
+        constexpr int wm = decltype(WM)::value, wn = decltype(WN)::value, nst = decltype(NST)::value;
+        constexpr bool w3 = (decltype(FORM)::value & FORM_W3) != 0, split = (decltype(FORM)::value & FORM_SPLIT) != 0;
+        if constexpr (fwd_kernel_exists(wm, wn, nst, XF, split, w3, OE)) {
+            if (wn == 2 && p.Cout % 128) return OSI_ERR_ARG;
+            return launch_fwd<wm, wn, false, nst, XF, w3, OE, split>(p, st, &pl.tail, ws + pl.slab_off);
+        } else return OSI_ERR_ARG;      // e.g. a fused input activation on a double-buffered tile
+    };
+    const int form = (pl.w3 ? FORM_W3 : FORM_PLAIN) | (pl.kind == FWD_SPLIT ? FORM_SPLIT : FORM_PLAIN);
+    return with_shape(tile_shape(pl.tile), [&](auto WM, auto WN, auto NST) {
+        return pick<FORM_PLAIN, FORM_W3, FORM_SPLIT, FORM_W3 | FORM_SPLIT>(form, [&](auto FORM) { return go(WM, WN, NST, FORM); });
+    });
+}
+
+// ---- input gradient: plan ----------------------------------------------------------------------------------------------------------
+// floats of the partial-sum part of the fused input-gradient workspace, rounded to 256 B: the slab of a K-split tail starts behind it
+static size_t dgrad_partial_floats(const osi_conv_desc* d) {
+    const int s = d->stride;
+    const long mt = osi_cdiv((long)d->B * osi_cdiv(d->H, s) * osi_cdiv(d->W, s), 64);
+    return ((size_t)3 * s * s * mt * d->Cin + 63) / 64 * 64;
+}
+struct DgradPlan {
+    int tile;
+    int flavour;        // fused epilogue (dgrad_epilogue64): 0 none, 1 general, 2 in-block (gate recomputed from y0 and / or sums over y0),
+                        // 3 block input (addend, bitmask, sums over y0 and y1), 4 in-block under frozen statistics
+    bool pool, w3, split;   // pool mode (reductions behind the stem's max-pool) | row-window loader | K-split tail + fix-up pass
+    TailPlan tail;      // K-split plan of the shape (sizes the slab of the workspace query); launched when `split`
+    int P;              // partial-sum row tiles over all stride classes (0: no partial sums asked for)
+};
+// The plan of an input-gradient launch; f / addend / frozen as the entry points take them (f == NULL: plain), before their argument checks.
+static DgradPlan plan_dgrad(const osi_conv_desc* d, int tile, const float* addend, const osi_dgrad_fusion* f, bool frozen) {
+    DgradPlan pl{tile, 0, false, false, false, tail_plan(d, true), 0};
+    // Measured (profiles/conv_layers_r01.txt and the full step): with buffer loads the 64x64 single-buffered tile wins or ties
+    // on every ResNet-50 shape (the dgrad class went 12.1 -> 11.0 ms per step against the 64x128 rule used before).
+    const bool even_addend = f && f->addend_stride == 2;     // built for the 64x64 epilogue only: AUTO never picks the wide tile for it
+    if (tile == OSI_TILE_AUTO) pl.tile = (g_osi_tuning.dgrad_wide && d->Cin % 128 == 0 && !even_addend) ? OSI_TILE_64x128_S1 : OSI_TILE_64x64_S1;
+    const bool t64 = pl.tile == OSI_TILE_64x64_S1;
+    // the fused epilogue (mask / BatchNorm reductions) is its own instantiation so that plain launches keep the small one; the two
+    // flavours the executor issues (2, 3) have theirs on the 64x64 tile, pool mode and the wide tile run the general one
+    if (frozen) pl.flavour = 4;
+    else if (f && (f->relu_mask || f->partials || f->scale0)) {
+        pl.pool = f->pool_idx != nullptr;
+        if (pl.pool || tile_shape(pl.tile).wn == 2) pl.flavour = 1;
+        else pl.flavour = (!addend && !f->relu_mask && !(f->partials && f->y1)) ? 2 : !f->scale0 ? 3 : 1;
+    }
+    // the in-block 3x3 stride-1 input gradients on the row-window form
+    pl.w3 = t64 && !pl.pool && (pl.flavour == 2 || pl.flavour == 4) && g_osi_tuning.dgrad_w3 && row_window_shape(d) && d->Cout % BK == 0 && d->Cin % 64 == 0;
+    if (f && f->partials) {
+        const int s = d->stride;
+        pl.P = s * s * osi_cdiv((long)d->B * osi_cdiv(d->H, s) * osi_cdiv(d->W, s), tile_rows(pl.tile));
+        // ragged last round split along K when the caller's workspace has room for the slab behind the partial sums
+        pl.split = !pl.pool && t64 && pl.tail.S > 1 && f->partials_bytes >= (dgrad_partial_floats(d) + tail_slab_floats(pl.tail)) * sizeof(float);
+    }
+    return pl;
+}
+// k_conv_dgrad<WM, WN, NST, FUSED, SPLIT, POOL, W3> as built
+constexpr bool dgrad_kernel_exists(int wm, int wn, int nst, int fl, bool split, bool pool, bool w3) {
+    if (fl == 0) return !split && !pool && !w3;                      // plain: every tile
+    if (wm != 1 || nst != 1) return false;                           // fusion is built for the single-buffered 64-row tiles the executor uses
+    if (wn == 2 || pool) return fl == 1 && !split && !w3 && !(wn == 2 && pool);
+    return !w3 || fl == 2 || fl == 4;
+}
+// The one place an input-gradient plan becomes a kernel instance; slab: behind the partial sums (read when pl.split)
+static int launch_dgrad_plan(const DgradPlan& pl, const ConvP& p, float* slab, hipStream_t st) {
+    auto go = [&](auto WM, auto WN, auto NST, auto FL, auto FORM) -> int {
+        constexpr int wm = decltype(WM)::value, wn = decltype(WN)::value, nst = decltype(NST)::value, fl = decltype(FL)::value;
+        constexpr bool pool = decltype(FORM)::value == FORM_POOL, w3 = (decltype(FORM)::value & FORM_W3) != 0, split = (decltype(FORM)::value & FORM_SPLIT) != 0;
+        if constexpr (dgrad_kernel_exists(wm, wn, nst, fl, split, pool, w3)) {
+            if (wn == 2 && p.Cin % 128) return OSI_ERR_ARG;
+            return launch_dgrad<wm, wn, nst, fl, pool, w3, split>(p, st, &pl.tail, slab);
+        } else return OSI_ERR_ARG;
+    };
+    const int form = pl.pool ? FORM_POOL : (pl.w3 ? FORM_W3 : FORM_PLAIN) | (pl.split ? FORM_SPLIT : FORM_PLAIN);
+    return with_shape(tile_shape(pl.tile), [&](auto WM, auto WN, auto NST) {
+        return pick<0, 1, 2, 3, 4>(pl.flavour, [&](auto FL) {
+            return pick<FORM_PLAIN, FORM_POOL, FORM_W3, FORM_SPLIT, FORM_W3 | FORM_SPLIT>(form, [&](auto FORM) { return go(WM, WN, NST, FL, FORM); });
+        });
+    });
+}
+
+// ---- weight gradient: plan (shared by the workspace query and the launcher) ------------------------------------------------------------
+struct WgradPlan { bool all_taps; int wm, wn, splits, kchunk; };   // all_taps: k_conv_wgrad3 (64 x 32 cells, wm / wn unused), else per-tap k_conv_wgrad
+// `want` splits of the M rows -> splits of whole bk-row blocks: at least 8 blocks per split (amortises the 64 KiB slab tile); whole
+// splits are dealt to the 8 XCDs (the kernels' block mapping), so with mult8 a multiple of 8 gives every XCD the same number of them
+static void split_rows(WgradPlan& w, long want, long M, int bk, bool mult8) {
+    const long maxs = (M + 8 * bk - 1) / (8 * bk);
+    long s = want;
+    if (s > maxs) s = maxs;
+    if (s < 1) s = 1;
+    if (mult8 && s >= 8) {
+        long r8 = (s + 4) / 8 * 8;
+        if (r8 > maxs) r8 = maxs / 8 * 8;
+        if (r8 >= 8) s = r8;
+    }
+    const long chunk = ((M + s - 1) / s + bk - 1) / bk * bk;
+    w.splits = (int)((M + chunk - 1) / chunk); w.kchunk = (int)chunk;
+}
 static WgradPlan plan_wgrad(const osi_conv_desc* d) {
-    WgradPlan w;
+    WgradPlan w{wgrad3_ok(d), 1, 1, 1, 0};
     const bool stem = is_stem(d);
+    const long M = (long)d->B * d->Ho * d->Wo;
+    if (w.all_taps) {
+        // four 256-thread workgroups per CU (register budget of the nine accumulator sets) fill the machine; as for the per-tap kernel
+        // the side stream gets half of that by default
+        const long cells = (long)(d->Cout / 64) * (d->Cin / 32);
+        split_rows(w, (g_osi_tuning.wgrad3_blocks + cells - 1) / cells, M, W3_BKP, true);
+        return w;
+    }
     // 128-wide tiles wherever the channel counts allow (osi_set_tuning("wgrad_tile", 64) forces 64x64 for A/B runs). Measured with the footprint
     // budget below: 64x64 everywhere is ~8 % faster ALONE (wgrad class 11.1 -> 10.2 ms/step) but 0.4 ms slower inside the
     // overlapped step (36.7-37.0 vs 36.3 ms): six short-lived small workgroups per CU disturb the dgrad chain more than two big ones.
@@ -2214,26 +2384,12 @@ static WgradPlan plan_wgrad(const osi_conv_desc* d) {
     const int BMg = 64 * w.wm, BNg = 64 * w.wn;
     const int Ktot = stem ? 224 : d->R * d->S * d->Cin;
     const long tiles = (long)(d->Cout / BMg) * (stem ? osi_cdiv(Ktot, BNg) : d->R * d->S * (d->Cin / BNg));
-    const long M = (long)d->B * d->Ho * d->Wo;
     // Footprint budget per launch in units of 64x64 workgroups (a 128x128 workgroup counts as four): 2048 = two 128x128 or eight
     // 64x64 workgroups per CU. Alone, twice that is ~10 % faster, but the weight gradients run on the executor's side stream next
     // to the data-gradient chain and must leave half of each CU's LDS, registers and wave slots to the critical path: the whole
     // step is 0.7 ms shorter this way (sweep in DESIGN.md §3). osi_set_tuning("wgrad_blocks", n) overrides (development).
-    const int target64 = g_osi_tuning.wgrad_blocks;
-    const int target = target64 / (w.wm * w.wn);
-    long splits = (target + tiles - 1) / tiles;
-    long maxs = (M + 8 * BK - 1) / (8 * BK);                // at least 8 K tiles per split (amortises the 64 KiB slab tile)
-    if (splits > maxs) splits = maxs;
-    if (splits < 1) splits = 1;
-    // whole splits are dealt to the 8 XCDs (k_conv_wgrad's mapping): a multiple of 8 gives every XCD the same number of them
-    if (g_osi_tuning.wgrad_group == 2 && splits >= 8) {
-        long r8 = (splits + 4) / 8 * 8;
-        if (r8 > maxs) r8 = maxs / 8 * 8;
-        if (r8 >= 8) splits = r8;
-    }
-    long chunk = ((M + splits - 1) / splits + BK - 1) / BK * BK;
-    splits = (M + chunk - 1) / chunk;
-    w.splits = (int)splits; w.kchunk = (int)chunk;
+    const int target = g_osi_tuning.wgrad_blocks / (w.wm * w.wn);
+    split_rows(w, (target + tiles - 1) / tiles, M, BK, g_osi_tuning.wgrad_group == 2);
     return w;
 }
 
@@ -2271,12 +2427,27 @@ extern "C" {
 void osi_debug_set_stamps(unsigned long long* buf) { g_osi_stamps = buf; }
 #endif
 
-static int fwd_tile_rows(int tile) {
-    return (tile == OSI_TILE_128x128 || tile == OSI_TILE_128x64 || tile == OSI_TILE_128x128_S1 || tile == OSI_TILE_128x64_S1) ? 128 : 64;
-}
 static int conv_fwd_impl(const osi_conv_desc* d, const float* x, const float* w, float* y, int tile, float* pstats,
                          size_t pstats_bytes, int* P, int* rows_per_block, osi_stream_t stream, const float* in_scale = nullptr,
-                         const float* in_shift = nullptr, const float* res = nullptr);
+                         const float* in_shift = nullptr, const float* res = nullptr) {
+    OSI_REQUIRE(desc_ok(d) && x && w && y);
+    hipStream_t st = (hipStream_t)stream;
+    ConvP p = make_p(d, DIR_FWD);
+    p.x = x; p.w = w; p.y = y; p.accumulate = 0;
+    p.in_scale = in_scale; p.in_shift = in_shift; p.res = res;
+    OSI_REQUIRE(!in_scale || (!is_stem(d) && d->Cin <= 4096 && d->R * d->S <= 32));
+    OSI_REQUIRE(is_stem(d) ? (d->Cout % 64 == 0 && d->stride >= 1) : (d->Cin % BK == 0 && d->Cout % 64 == 0));
+    const FwdPlan pl = plan_fwd(d, tile, res != nullptr, pstats != nullptr, pstats ? pstats_bytes : 0);
+    const int mt = pl.kind == FWD_STEM_DIRECT ? p.M / STEM_TILE_PIXELS : osi_cdiv(p.M, pl.stat_rows);    // statistics partials
+    if (pstats) {
+        OSI_REQUIRE(pstats_bytes >= (size_t)2 * mt * d->Cout * sizeof(float));
+        p.pmean = pstats; p.pm2 = pstats + (size_t)mt * d->Cout;
+        *P = mt; *rows_per_block = pl.stat_rows;
+    }
+    if (pl.kind == FWD_STEM_DIRECT) return launch_stem_fwd_direct(d, x, w, y, p.pmean, p.pm2, mt, st);
+    if (!in_scale) return launch_fwd_plan<0, false>(pl, p, pstats, st);
+    return res ? launch_fwd_plan<2, false>(pl, p, pstats, st) : launch_fwd_plan<1, false>(pl, p, pstats, st);
+}
 
 int osi_conv_fwd(const osi_conv_desc* d, const float* x, const float* w, float* y, int tile, osi_stream_t stream) {
     return conv_fwd_impl(d, x, w, y, tile, nullptr, 0, nullptr, nullptr, stream);
@@ -2298,22 +2469,10 @@ int osi_conv_fwd_act2(const osi_conv_desc* d, const float* x, const float* in_sc
     return conv_fwd_impl(d, x, w, y, tile, pstats, pstats_bytes, P, rows_per_block, stream, in_scale, in_shift, res);
 }
 
-// floats of the statistics part of the forward workspace (row-tile partials + finalize scratch), rounded to 256 B: the slab of a
-// K-split tail starts behind it
-static size_t fwd_stats_floats(const osi_conv_desc* d) {
-    const size_t n = (size_t)2 * osi_cdiv((long)d->B * d->Ho * d->Wo, 64) * d->Cout + (size_t)2 * 32 * d->Cout;
-    return (n + 63) / 64 * 64;
-}
-static TailPlan fwd_tail_plan(const osi_conv_desc* d) {
-    const long M = (long)d->B * d->Ho * d->Wo;
-    if (is_stem(d) || d->Cout % 64 || d->Cin % BK) return TailPlan{(int)osi_cdiv(M, 64), 1, 0, 0};
-    return plan_tail_split(osi_cdiv(M, 64), d->Cout / 64, d->R * d->S * d->Cin / BK);
-}
-
 size_t osi_conv_fwd_bnstats_workspace(const osi_conv_desc* d) {
     if (!desc_ok(d)) return 0;
     // row-tile partials + the 32 group pairs of osi_bn_finalize_stats' first level [+ the slab of a K-split tail]
-    return (fwd_stats_floats(d) + tail_slab_floats(fwd_tail_plan(d))) * sizeof(float);
+    return (fwd_stats_floats(d) + tail_slab_floats(tail_plan(d, false))) * sizeof(float);     // what plan_fwd places the slab by
 }
 
 int osi_conv_fwd_bnstats(const osi_conv_desc* d, const float* x, const float* w, float* y, int tile, float* pstats,
@@ -2322,103 +2481,10 @@ int osi_conv_fwd_bnstats(const osi_conv_desc* d, const float* x, const float* w,
     return conv_fwd_impl(d, x, w, y, tile, pstats, pstats_bytes, P, rows_per_block, stream);
 }
 
-static int conv_fwd_impl(const osi_conv_desc* d, const float* x, const float* w, float* y, int tile, float* pstats,
-                         size_t pstats_bytes, int* P, int* rows_per_block, osi_stream_t stream, const float* in_scale,
-                         const float* in_shift, const float* res) {
-    OSI_REQUIRE(desc_ok(d) && x && w && y);
-    hipStream_t st = (hipStream_t)stream;
-    ConvP p = make_p(d);
-    p.x = x; p.w = w; p.y = y; p.accumulate = 0;
-    p.in_scale = in_scale; p.in_shift = in_shift; p.res = res;
-    OSI_REQUIRE(!in_scale || (!is_stem(d) && d->Cin <= 4096 && d->R * d->S <= 32));
-    p.unit = (d->R == 1 && d->S == 1 && d->stride == 1 && d->pad == 0) ? 1 : 0;
-    p.x_bytes = (int)((size_t)d->B * d->H * d->W * d->Cin * 4);
-    p.w_bytes = (int)((size_t)d->Cout * p.Ktot * 4);
-    auto with_stats = [&](int bm) -> int {
-        if (!pstats) return OSI_OK;
-        const int mt = osi_cdiv(p.M, bm);
-        if (pstats_bytes < (size_t)2 * mt * d->Cout * sizeof(float)) return OSI_ERR_ARG;
-        p.pmean = pstats; p.pm2 = pstats + (size_t)mt * d->Cout;
-        *P = mt; *rows_per_block = bm;
-        return OSI_OK;
-    };
-    if (is_stem(d)) {
-        OSI_REQUIRE(d->Cout % 64 == 0 && d->stride >= 1);
-        if (tile == OSI_TILE_AUTO && stem_direct_geometry(d)) {
-            // direct form (stem_direct.hip): full 8 x 16 output tiles only, one BatchNorm partial per tile of 128 pixels
-            const int ntiles = d->B * d->Ho * d->Wo / STEM_TILE_PIXELS;
-            float *pm = nullptr, *pq = nullptr;
-            if (pstats) {
-                if (pstats_bytes < (size_t)2 * ntiles * 64 * sizeof(float)) return OSI_ERR_ARG;
-                pm = pstats; pq = pstats + (size_t)ntiles * 64;
-                *P = ntiles; *rows_per_block = STEM_TILE_PIXELS;
-            }
-            return launch_stem_fwd_direct(d, x, w, y, pm, pq, ntiles, st);
-        }
-        if (int e = with_stats(128)) return e;
-        return launch_fwd<2, 1, true>(p, st);
-    }
-    OSI_REQUIRE(d->Cin % BK == 0 && d->Cout % 64 == 0);
-    if (tile == OSI_TILE_AUTO && rows_rule(d, p.unit != 0, res)) {      // short-K 1x1 layers: persistent row walker
-        if (int e = with_stats(64)) return e;
-        if (d->Cin == 64) return in_scale ? launch_fwd_rows<2, 1>(p, st) : launch_fwd_rows<2, 0>(p, st);
-        return in_scale ? launch_fwd_rows<4, 1>(p, st) : launch_fwd_rows<4, 0>(p, st);
-    }
-    // 3x3 / stride 1 / pad 1 on the row-window form (one activation window per tap ROW and channel slice, see k_conv_fwd W3)
-    const bool w3 = tile == OSI_TILE_AUTO && g_osi_tuning.fwd_w3 && !res && d->R == 3 && d->S == 3 && d->stride == 1 && d->pad == 1 && d->W >= 7 &&
-                    d->H == d->Ho && d->W == d->Wo;
-    if (tile == OSI_TILE_AUTO && pstats) {
-        // ragged last round split along K (plan_tail_split) when the caller's workspace has room for the slab behind the statistics
-        const TailPlan tp = fwd_tail_plan(d);
-        if (tp.S > 1 && pstats_bytes >= (fwd_stats_floats(d) + tail_slab_floats(tp)) * sizeof(float)) {
-            if (int e = with_stats(64)) return e;
-            float* slab = pstats + fwd_stats_floats(d);
-            if (w3) return in_scale ? launch_fwd_split<1, true>(p, tp, slab, st) : launch_fwd_split<0, true>(p, tp, slab, st);
-            if (in_scale) return res ? launch_fwd_split<2>(p, tp, slab, st) : launch_fwd_split<1>(p, tp, slab, st);
-            return launch_fwd_split<0>(p, tp, slab, st);
-        }
-    }
-    if (w3) {
-        if (int e = with_stats(64)) return e;
-        return in_scale ? launch_fwd<1, 1, false, 1, 1, true>(p, st) : launch_fwd<1, 1, false, 1, 0, true>(p, st);
-    }
-    if (tile == OSI_TILE_AUTO) {
-        // Measured on MI355X over the 22 ResNet-50 shapes at B=128 (tools/bench_conv.py, profiles/conv_layers_r01.txt): many
-        // small workgroups (4 resident per CU) beat large tiles almost everywhere because the ragged last round of the launch is
-        // shorter; only the 7x7-spatial layers with few column tiles prefer the wider 64x128 tile.
-        // Single-buffered LDS (two barriers per K tile, but 7-8 resident workgroups per CU) beats the double-buffered form on
-        // every shape: occupancy, not staging depth, is what hides the barrier and load latency of a 16-MFMA K step.
-        // 64x64 everywhere except the 7x7-spatial layers with few tiles, where the wider column tile halves the A re-reads
-        const long tiles64 = ((long)p.M + 63) / 64 * (d->Cout / 64);
-        tile = (tiles64 < 1024 && d->Cout % 128 == 0) ? OSI_TILE_64x128_S1 : OSI_TILE_64x64_S1;
-        if (g_osi_tuning.fwd_wide && d->Cout % 128 == 0) tile = OSI_TILE_64x128_S1;   // A/B: wide tiles wherever the channel count allows
-    }
-    if (int e = with_stats(fwd_tile_rows(tile))) return e;
-    if (in_scale) {   // fused input activation: built for the single-buffered 64-row tiles the executor uses
-        if (tile == OSI_TILE_64x64_S1) return res ? launch_fwd<1, 1, false, 1, 2>(p, st) : launch_fwd<1, 1, false, 1, 1>(p, st);
-        if (tile == OSI_TILE_64x128_S1) {
-            OSI_REQUIRE(d->Cout % 128 == 0);
-            return res ? launch_fwd<1, 2, false, 1, 2>(p, st) : launch_fwd<1, 2, false, 1, 1>(p, st);
-        }
-        return OSI_ERR_ARG;
-    }
-    switch (tile) {
-        case OSI_TILE_128x128: OSI_REQUIRE(d->Cout % 128 == 0); return launch_fwd<2, 2, false>(p, st);
-        case OSI_TILE_128x64: return launch_fwd<2, 1, false>(p, st);
-        case OSI_TILE_64x128: OSI_REQUIRE(d->Cout % 128 == 0); return launch_fwd<1, 2, false>(p, st);
-        case OSI_TILE_64x64: return launch_fwd<1, 1, false>(p, st);
-        case OSI_TILE_64x64_S1: return launch_fwd<1, 1, false, 1>(p, st);
-        case OSI_TILE_64x128_S1: OSI_REQUIRE(d->Cout % 128 == 0); return launch_fwd<1, 2, false, 1>(p, st);
-        case OSI_TILE_128x128_S1: OSI_REQUIRE(d->Cout % 128 == 0); return launch_fwd<2, 2, false, 1>(p, st);
-        case OSI_TILE_128x64_S1: return launch_fwd<2, 1, false, 1>(p, st);
-        default: return OSI_ERR_ARG;
-    }
-}
-
 // ---- inference form: the convolution's own BatchNorm (eval coefficients), shortcut and ReLU in the epilogue --------------------------
 size_t osi_conv_fwd_epilogue_workspace(const osi_conv_desc* d) {
     if (!desc_ok(d) || is_stem(d)) return 0;
-    return tail_slab_floats(fwd_tail_plan(d)) * sizeof(float);     // slab of a K-split tail; 0: the launch is single-pass
+    return tail_slab_floats(tail_plan(d, false)) * sizeof(float);     // slab of a K-split tail; 0: the launch is single-pass
 }
 
 int osi_conv_fwd_epilogue(const osi_conv_desc* d, const float* x, const float* w, float* out, const osi_conv_epilogue* e, void* ws,
@@ -2426,90 +2492,23 @@ int osi_conv_fwd_epilogue(const osi_conv_desc* d, const float* x, const float* w
     OSI_REQUIRE(desc_ok(d) && !is_stem(d) && x && w && out && e && e->scale && e->shift);
     OSI_REQUIRE(d->Cin % BK == 0 && d->Cout % 64 == 0);
     OSI_REQUIRE(e->residual != out);
-    hipStream_t st = (hipStream_t)stream;
-    ConvP p = make_p(d);
+    ConvP p = make_p(d, DIR_FWD);
     p.x = x; p.w = w; p.y = out; p.accumulate = 0;
     p.osc = e->scale; p.osh = e->shift; p.ores = e->residual; p.orelu = e->relu ? 1 : 0;
-    p.unit = (d->R == 1 && d->S == 1 && d->stride == 1 && d->pad == 0) ? 1 : 0;
-    p.x_bytes = (int)((size_t)d->B * d->H * d->W * d->Cin * 4);
-    p.w_bytes = (int)((size_t)d->Cout * p.Ktot * 4);
-    // the same launch plans as the training forward (conv_fwd_impl with OSI_TILE_AUTO): row walker, row windows, K-split tail, tile rule
-    if (rows_rule(d, p.unit != 0, nullptr)) return d->Cin == 64 ? launch_fwd_rows<2, 0, true>(p, st) : launch_fwd_rows<4, 0, true>(p, st);
-    const bool w3 = g_osi_tuning.fwd_w3 && d->R == 3 && d->S == 3 && d->stride == 1 && d->pad == 1 && d->W >= 7 && d->H == d->Ho && d->W == d->Wo;
-    const TailPlan tp = fwd_tail_plan(d);
-    if (tp.S > 1 && ws && ws_bytes >= tail_slab_floats(tp) * sizeof(float))
-        return w3 ? launch_fwd_split<0, true, true>(p, tp, (float*)ws, st) : launch_fwd_split<0, false, true>(p, tp, (float*)ws, st);
-    if (w3) return launch_fwd<1, 1, false, 1, 0, true, true>(p, st);
-    const long tiles64 = ((long)p.M + 63) / 64 * (d->Cout / 64);
-    if (d->Cout % 128 == 0 && (tiles64 < 1024 || g_osi_tuning.fwd_wide)) return launch_fwd<1, 2, false, 1, 0, false, true>(p, st);
-    return launch_fwd<1, 1, false, 1, 0, false, true>(p, st);
-}
-
-static bool dgrad_w3(const osi_conv_desc* d) {
-    return g_osi_tuning.dgrad_w3 && d->R == 3 && d->S == 3 && d->stride == 1 && d->pad == 1 && d->W >= 7 && d->H == d->Ho && d->W == d->Wo &&
-           d->Cout % BK == 0 && d->Cin % 64 == 0;
-}
-static int dgrad_rows(int tile) {
-    return (tile == OSI_TILE_128x128 || tile == OSI_TILE_128x64 || tile == OSI_TILE_128x128_S1 || tile == OSI_TILE_128x64_S1) ? 128 : 64;
-}
-static int conv_dgrad_impl(const osi_conv_desc* d, const float* dy, const float* w, float* dx, const float* addend,
-                           const osi_dgrad_fusion* f, int tile, int* P, osi_stream_t stream, bool sparse = false, bool frozen = false);
-
-int osi_conv_dgrad(const osi_conv_desc* d, const float* dy, const float* w, float* dx, int accumulate, int tile,
-                   osi_stream_t stream) {
-    OSI_REQUIRE(accumulate >= 0 && accumulate <= 2);
-    return conv_dgrad_impl(d, dy, w, dx, accumulate == 1 ? dx : nullptr, nullptr, tile, nullptr, stream, accumulate == 2);
-}
-
-// floats of the partial-sum part of the fused input-gradient workspace, rounded to 256 B: the slab of a K-split tail starts behind it
-static size_t dgrad_partial_floats(const osi_conv_desc* d) {
-    const int s = d->stride;
-    const long mt = osi_cdiv((long)d->B * osi_cdiv(d->H, s) * osi_cdiv(d->W, s), 64);
-    return ((size_t)3 * s * s * mt * d->Cin + 63) / 64 * 64;
-}
-static TailPlan dgrad_tail_plan(const osi_conv_desc* d) {
-    const long M = (long)d->B * d->H * d->W;
-    if (d->stride != 1 || is_stem(d) || d->Cin % 64 || d->Cout % BK) return TailPlan{(int)osi_cdiv(M, 64), 1, 0, 0};
-    return plan_tail_split(osi_cdiv(M, 64), d->Cin / 64, d->R * d->S * d->Cout / BK);
-}
-
-size_t osi_conv_dgrad_fused_workspace(const osi_conv_desc* d) {
-    if (!desc_ok(d)) return 0;
-    return (dgrad_partial_floats(d) + tail_slab_floats(dgrad_tail_plan(d))) * sizeof(float);
-}
-
-int osi_conv_dgrad_fused(const osi_conv_desc* d, const float* dy, const float* w, float* dx, const float* addend,
-                         const osi_dgrad_fusion* f, int tile, int* P, osi_stream_t stream) {
-    OSI_REQUIRE(f && P);
-    return conv_dgrad_impl(d, dy, w, dx, addend, f, tile, P, stream);
-}
-
-// In-block input gradient under frozen BatchNorm statistics (flavour 4 of dgrad_epilogue64): the in-block fusion only — gate recomputed
-// from y0, one consumer, no addend / bitmask / pool mode — on the 64x64 single-buffered tile in each of its forms (plain, stride-2
-// parity classes, 3x3 row windows, K-split tail + fix-up). *P is written only when partials are asked for.
-int osi_conv_dgrad_fused_frozen(const osi_conv_desc* d, const float* dy, const float* w, float* dx, const osi_dgrad_fusion* f, int tile,
-                                int* P, osi_stream_t stream) {
-    OSI_REQUIRE(f && f->scale0 && f->shift0 && f->y0 && !f->relu_mask && !f->y1 && !f->pool_idx && f->addend_stride <= 1);
-    OSI_REQUIRE(!f->partials || P);
-    OSI_REQUIRE(tile == OSI_TILE_AUTO || tile == OSI_TILE_64x64_S1);
-    return conv_dgrad_impl(d, dy, w, dx, nullptr, f, OSI_TILE_64x64_S1, P, stream, false, true);
+    // the launch plans of the training forward under OSI_TILE_AUTO (plan_fwd), no statistics in front of the slab
+    return launch_fwd_plan<0, true>(plan_fwd(d, OSI_TILE_AUTO, false, false, ws ? ws_bytes : 0), p, (float*)ws, (hipStream_t)stream);
 }
 
 static int conv_dgrad_impl(const osi_conv_desc* d, const float* dy, const float* w, float* dx, const float* addend,
-                           const osi_dgrad_fusion* f, int tile, int* P, osi_stream_t stream, bool sparse, bool frozen) {
+                           const osi_dgrad_fusion* f, int tile, int* P, osi_stream_t stream, bool sparse = false, bool frozen = false) {
     OSI_REQUIRE(desc_ok(d) && dy && w && dx);
     OSI_REQUIRE(!is_stem(d));  // the image needs no gradient (train.py:128-139: input is a leaf without grad)
     OSI_REQUIRE(d->Cout % BK == 0 && d->Cin % 64 == 0 && d->stride <= 2);
-    hipStream_t st = (hipStream_t)stream;
-    ConvP p = make_p(d);
+    ConvP p = make_p(d, DIR_DGRAD);
     p.x = dy; p.w = w; p.y = dx; p.addend = addend;
     p.skip_empty = sparse ? 1 : 0;
-    p.x_bytes = (int)((size_t)d->B * d->Ho * d->Wo * d->Cout * 4);
-    p.w_bytes = (int)((size_t)d->Cout * p.Ktot * 4);
-    // Measured (profiles/conv_layers_r01.txt and the full step): with buffer loads the 64x64 single-buffered tile wins or ties
-    // on every ResNet-50 shape (the dgrad class went 12.1 -> 11.0 ms per step against the 64x128 rule used before).
-    const bool even_addend = f && f->addend_stride == 2;     // built for the 64x64 epilogue only: AUTO never picks the wide tile for it
-    if (tile == OSI_TILE_AUTO) tile = (g_osi_tuning.dgrad_wide && d->Cin % 128 == 0 && !even_addend) ? OSI_TILE_64x128_S1 : OSI_TILE_64x64_S1;
+    const DgradPlan pl = plan_dgrad(d, tile, addend, f, frozen);
+    tile = pl.tile;
     if (f) {
         OSI_REQUIRE(f->relu_mask || f->scale0 || !f->partials || f->pool_idx);
         if (f->pool_idx) {   // pool mode: stride-1 conv behind the stem's max-pool, reductions only (no gate on dx), one consumer
@@ -2530,39 +2529,41 @@ static int conv_dgrad_impl(const osi_conv_desc* d, const float* dy, const float*
         if (f->partials) {
             OSI_REQUIRE(f->y0 && f->mean0 && f->invstd0 && (!f->y1 || (f->mean1 && f->invstd1)));
             p.emean0 = f->mean0; p.einv0 = f->invstd0; p.emean1 = f->mean1; p.einv1 = f->invstd1;
-            const int s = d->stride;
-            const int mt = osi_cdiv((long)d->B * osi_cdiv(d->H, s) * osi_cdiv(d->W, s), dgrad_rows(tile));
-            p.eP = s * s * mt;
+            p.eP = pl.P;
             OSI_REQUIRE(f->partials_bytes >= (size_t)3 * p.eP * d->Cin * sizeof(float));
             p.ey0 = f->y0; p.ey1 = f->y1; p.esum = f->partials;
             *P = p.eP;
-            // ragged last round split along K when the caller's workspace has room for the slab behind the partial sums
-            const TailPlan tp = dgrad_tail_plan(d);
-            if (!f->pool_idx && tile == OSI_TILE_64x64_S1 && tp.S > 1 && f->partials_bytes >= (dgrad_partial_floats(d) + tail_slab_floats(tp)) * sizeof(float))
-            {
-                float* slab = f->partials + dgrad_partial_floats(d);
-                const int fl = dgrad_flavour(p);
-                if (frozen) return dgrad_w3(d) ? launch_dgrad_split<4, true>(p, tp, slab, st) : launch_dgrad_split<4>(p, tp, slab, st);
-                if (fl == 2 && dgrad_w3(d)) return launch_dgrad_split<2, true>(p, tp, slab, st);
-                return fl == 2 ? launch_dgrad_split<2>(p, tp, slab, st) : fl == 3 ? launch_dgrad_split<3>(p, tp, slab, st) : launch_dgrad_split<1>(p, tp, slab, st);
-            }
         }
     }
-    if (frozen) return dgrad_w3(d) ? launch_dgrad_impl<1, 1, 1, 4, false, true>(p, st) : launch_dgrad_impl<1, 1, 1, 4>(p, st);
-    // the executor's in-block 3x3 stride-1 input gradients on the row-window form
-    if (tile == OSI_TILE_64x64_S1 && dgrad_w3(d) && (p.ebits || p.esum || p.escale0) && !p.epool && dgrad_flavour(p) == 2)
-        return launch_dgrad_impl<1, 1, 1, 2, false, true>(p, st);
-    switch (tile) {
-        case OSI_TILE_128x128: OSI_REQUIRE(d->Cin % 128 == 0); return launch_dgrad<2, 2>(p, st);
-        case OSI_TILE_128x64: return launch_dgrad<2, 1>(p, st);
-        case OSI_TILE_64x128: OSI_REQUIRE(d->Cin % 128 == 0); return launch_dgrad<1, 2>(p, st);
-        case OSI_TILE_64x64: return launch_dgrad<1, 1>(p, st);
-        case OSI_TILE_64x64_S1: return launch_dgrad<1, 1, 1>(p, st);
-        case OSI_TILE_64x128_S1: OSI_REQUIRE(d->Cin % 128 == 0); return launch_dgrad<1, 2, 1>(p, st);
-        case OSI_TILE_128x128_S1: OSI_REQUIRE(d->Cin % 128 == 0); return launch_dgrad<2, 2, 1>(p, st);
-        case OSI_TILE_128x64_S1: return launch_dgrad<2, 1, 1>(p, st);
-        default: return OSI_ERR_ARG;
-    }
+    return launch_dgrad_plan(pl, p, pl.split ? f->partials + dgrad_partial_floats(d) : nullptr, (hipStream_t)stream);
+}
+
+int osi_conv_dgrad(const osi_conv_desc* d, const float* dy, const float* w, float* dx, int accumulate, int tile,
+                   osi_stream_t stream) {
+    OSI_REQUIRE(accumulate >= 0 && accumulate <= 2);
+    return conv_dgrad_impl(d, dy, w, dx, accumulate == 1 ? dx : nullptr, nullptr, tile, nullptr, stream, accumulate == 2);
+}
+
+size_t osi_conv_dgrad_fused_workspace(const osi_conv_desc* d) {
+    if (!desc_ok(d)) return 0;
+    return (dgrad_partial_floats(d) + tail_slab_floats(tail_plan(d, true))) * sizeof(float);     // what plan_dgrad places the slab by
+}
+
+int osi_conv_dgrad_fused(const osi_conv_desc* d, const float* dy, const float* w, float* dx, const float* addend,
+                         const osi_dgrad_fusion* f, int tile, int* P, osi_stream_t stream) {
+    OSI_REQUIRE(f && P);
+    return conv_dgrad_impl(d, dy, w, dx, addend, f, tile, P, stream);
+}
+
+// In-block input gradient under frozen BatchNorm statistics (flavour 4 of dgrad_epilogue64): the in-block fusion only — gate recomputed
+// from y0, one consumer, no addend / bitmask / pool mode — on the 64x64 single-buffered tile in each of its forms (plain, stride-2
+// parity classes, 3x3 row windows, K-split tail + fix-up). *P is written only when partials are asked for.
+int osi_conv_dgrad_fused_frozen(const osi_conv_desc* d, const float* dy, const float* w, float* dx, const osi_dgrad_fusion* f, int tile,
+                                int* P, osi_stream_t stream) {
+    OSI_REQUIRE(f && f->scale0 && f->shift0 && f->y0 && !f->relu_mask && !f->y1 && !f->pool_idx && f->addend_stride <= 1);
+    OSI_REQUIRE(!f->partials || P);
+    OSI_REQUIRE(tile == OSI_TILE_AUTO || tile == OSI_TILE_64x64_S1);
+    return conv_dgrad_impl(d, dy, w, dx, nullptr, f, OSI_TILE_64x64_S1, P, stream, false, true);
 }
 
 // shapes the weight-gradient kernels take: Cout in 64s; Cin in 64s (per-tap kernel), in 32s for the all-taps 3x3 form, 4 for the stem
@@ -2572,15 +2573,41 @@ static bool wgrad_shape_ok(const osi_conv_desc* d) {
 
 size_t osi_conv_wgrad_workspace(const osi_conv_desc* d) {
     if (!desc_ok(d) || !wgrad_shape_ok(d)) return 0;
-    WgradPlan w{1, 1, 1, 0};
-    if (wgrad3_ok(d)) plan_wgrad3(d, w.splits, w.kchunk);
-    else w = plan_wgrad(d);
+    const WgradPlan w = plan_wgrad(d);
     const size_t n = (size_t)d->Cout * (is_stem(d) ? 224 : d->R * d->S * d->Cin);
     return w.splits > 1 ? (size_t)w.splits * n * sizeof(float) : 0;
 }
 
 static int conv_wgrad_impl(const osi_conv_desc* d, const float* dy, const float* x, float* dw, void* ws, size_t ws_bytes,
-                           osi_stream_t stream, const float* in_scale, const float* in_shift);
+                           osi_stream_t stream, const float* in_scale, const float* in_shift) {
+    OSI_REQUIRE(desc_ok(d) && dy && x && dw);
+    OSI_REQUIRE(!in_scale || !is_stem(d));
+    OSI_REQUIRE(wgrad_shape_ok(d));
+    hipStream_t st = (hipStream_t)stream;
+    const WgradPlan w = plan_wgrad(d);
+    ConvP p = make_p(d, DIR_WGRAD);
+    const size_t n = (size_t)d->Cout * p.Ktot;
+    OSI_REQUIRE(n % 4 == 0);
+    if (w.splits > 1) OSI_REQUIRE(ws && ws_bytes >= (size_t)w.splits * n * sizeof(float));
+    p.x = x; p.w = dy; p.y = w.splits > 1 ? (float*)ws : dw;
+    p.kchunk = w.kchunk; p.slab_stride = n;
+    p.in_scale = in_scale; p.in_shift = in_shift;
+    int e;
+    if (w.all_taps) e = in_scale ? launch_wgrad3<true>(p, w.splits, st) : launch_wgrad3<false>(p, w.splits, st);
+    else if (is_stem(d)) e = launch_wgrad<1, 1, true>(p, w.splits, st);
+    else {
+        // Single-buffered LDS by default (as in fwd/dgrad: twice the resident workgroups beat staging depth): 11.4 -> 10.3 ms per step
+        // for the wgrad class and -0.45 ms on the overlapped step, measured with the side-stream schedule of the executor.
+        // The fused input activation is built for the single-buffered forms only (the ones the executor uses).
+        e = with_shape({w.wm, w.wn, in_scale ? 1 : g_osi_tuning.wgrad_nst}, [&](auto WM, auto WN, auto NST) -> int {
+            constexpr int wm = decltype(WM)::value, wn = decltype(WN)::value, nst = decltype(NST)::value;
+            if constexpr (nst == 1) { if (in_scale) return launch_wgrad<wm, wn, false, 1, true>(p, w.splits, st); }
+            return launch_wgrad<wm, wn, false, nst>(p, w.splits, st);
+        });
+    }
+    if (e) return e;
+    return w.splits > 1 ? launch_slab_reduce((const float*)ws, dw, n / 4, n / 4, w.splits, st) : OSI_OK;
+}
 
 int osi_conv_wgrad(const osi_conv_desc* d, const float* dy, const float* x, float* dw, void* ws, size_t ws_bytes,
                    osi_stream_t stream) {
@@ -2591,52 +2618,6 @@ int osi_conv_wgrad_act(const osi_conv_desc* d, const float* dy, const float* x, 
                        void* ws, size_t ws_bytes, osi_stream_t stream) {
     OSI_REQUIRE(in_scale && in_shift);
     return conv_wgrad_impl(d, dy, x, dw, ws, ws_bytes, stream, in_scale, in_shift);
-}
-
-static int conv_wgrad_impl(const osi_conv_desc* d, const float* dy, const float* x, float* dw, void* ws, size_t ws_bytes,
-                           osi_stream_t stream, const float* in_scale, const float* in_shift) {
-    OSI_REQUIRE(desc_ok(d) && dy && x && dw);
-    OSI_REQUIRE(!in_scale || !is_stem(d));
-    const bool stem = is_stem(d);
-    OSI_REQUIRE(wgrad_shape_ok(d));
-    hipStream_t st = (hipStream_t)stream;
-    const bool all_taps = !stem && wgrad3_ok(d);
-    WgradPlan w{1, 1, 1, 0};
-    if (all_taps) plan_wgrad3(d, w.splits, w.kchunk);
-    else w = plan_wgrad(d);
-    ConvP p = make_p(d);
-    const size_t n = (size_t)d->Cout * p.Ktot;
-    OSI_REQUIRE(n % 4 == 0);
-    if (w.splits > 1) OSI_REQUIRE(ws && ws_bytes >= (size_t)w.splits * n * sizeof(float));
-    p.x = x; p.w = dy; p.y = w.splits > 1 ? (float*)ws : dw;
-    p.unit = (!stem && d->R == 1 && d->S == 1 && d->stride == 1 && d->pad == 0) ? 1 : 0;
-    p.x_bytes = (int)((size_t)d->B * d->H * d->W * d->Cin * 4);
-    p.w_bytes = (int)((size_t)d->B * d->Ho * d->Wo * d->Cout * 4);
-    p.kchunk = w.kchunk; p.slab_stride = n;
-    p.in_scale = in_scale; p.in_shift = in_shift;
-    int e;
-    // Single-buffered LDS by default (as in fwd/dgrad: twice the resident workgroups beat staging depth): 11.4 -> 10.3 ms per step
-    // for the wgrad class and -0.45 ms on the overlapped step, measured with the side-stream schedule of the executor.
-    const int nst = g_osi_tuning.wgrad_nst;
-    if (all_taps) e = in_scale ? launch_wgrad3<true>(p, w.splits, st) : launch_wgrad3<false>(p, w.splits, st);
-    else if (in_scale) {   // fused input activation: single-buffered forms only (the ones the executor uses)
-        if (w.wm == 2 && w.wn == 2) e = launch_wgrad<2, 2, false, 1, true>(p, w.splits, st);
-        else if (w.wm == 2) e = launch_wgrad<2, 1, false, 1, true>(p, w.splits, st);
-        else if (w.wn == 2) e = launch_wgrad<1, 2, false, 1, true>(p, w.splits, st);
-        else e = launch_wgrad<1, 1, false, 1, true>(p, w.splits, st);
-    }
-    else if (stem) e = launch_wgrad<1, 1, true>(p, w.splits, st);
-    else if (w.wm == 2 && w.wn == 2) e = nst == 1 ? launch_wgrad<2, 2, false, 1>(p, w.splits, st) : launch_wgrad<2, 2, false>(p, w.splits, st);
-    else if (w.wm == 2) e = nst == 1 ? launch_wgrad<2, 1, false, 1>(p, w.splits, st) : launch_wgrad<2, 1, false>(p, w.splits, st);
-    else if (w.wn == 2) e = nst == 1 ? launch_wgrad<1, 2, false, 1>(p, w.splits, st) : launch_wgrad<1, 2, false>(p, w.splits, st);
-    else e = nst == 1 ? launch_wgrad<1, 1, false, 1>(p, w.splits, st) : launch_wgrad<1, 1, false>(p, w.splits, st);
-    if (e) return e;
-    if (w.splits > 1) {
-        size_t n4 = n / 4;
-        hipLaunchKernelGGL(k_slab_reduce, dim3((unsigned)((n4 + 15) / 16)), dim3(256), 0, st, (const float*)ws, dw, n4, n4, w.splits);
-        OSI_LAUNCH_CHECK();
-    }
-    return OSI_OK;
 }
 
 int osi_stem_weight_pack(const float* w_krsc3, float* w_packed, int Cout, osi_stream_t stream) {

@@ -22,34 +22,44 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // Process-wide tuning knobs (development A/B switches). Written only by osi_set_tuning() (abi.hip); launch functions read them
 // and never touch the environment, so they stay stateless and re-entrant as include/osi.h promises. Defaults = measured optimum.
+// THE list: one row per knob, X(name, default, lo, hi, plan_relevant). The fields of OsiTuning and their defaults, the name lookup and
+// range check of osi_set_tuning / osi_tuning_info (abi.hip) and the executor's plan_unchanged() (resnet50_exec.hip) are generated from
+// it; the Python binding reads it through osi_tuning_info, and tests/test_abi.py holds the table in include/osi.h to it.
+// plan_relevant: an executor sizes its workspace for the value in force at create and refuses to run under another one.
+#define OSI_TUNING_KNOBS(X)                                                                                                              \
+    X(wgrad_tile, 0, 0, 64, 1)        /* 64 forces 64x64 weight-gradient tiles, 0 = 128-wide tiles wherever the channel counts allow (0 or 64 only: osi_set_tuning) */ \
+    X(wgrad_blocks, 2048, 1, 1 << 20, 1)   /* split-K footprint budget of one weight-gradient launch, in 64x64-workgroup units */       \
+    X(wgrad_nst, 1, 1, 2, 0)          /* LDS stages of the weight-gradient kernel (1 or 2) */                                           \
+    X(bn_grid, 1024, 1, 1 << 20, 0)   /* grid cap of the BatchNorm stream kernels */                                                    \
+    X(bn_single_p, 128, 1, 1 << 20, 0)     /* BatchNorm statistics: row-tile partials merged by ONE launch up to this count, two-level above it */ \
+    X(wgrad3, 2, 0, 2, 1)             /* 0 = per-tap kernel everywhere, 1 = 3x3 stride-1 weight gradients use the all-taps kernel (k_conv_wgrad3), 2 = stride 2 too */ \
+    X(wgrad3_blocks, 768, 1, 1 << 20, 1)   /* workgroups per launch the all-taps kernel's split-K plan aims for */                      \
+    X(fwd_wide, 0, 0, 1, 0)           /* A/B: 64x128 forward tiles wherever the channel count allows (default 0: measured rule) */      \
+    X(dgrad_wide, 0, 0, 1, 0)         /* A/B: the same for the input gradient */                                                        \
+    X(wgrad_group, 2, 0, 2, 1)        /* weight-gradient block -> XCD mapping: 0 plain 2-D grid, 1 the R*S taps of a cell share an XCD, 2 whole K splits do */ \
+    X(tail_split, 1, 0, 1, 1)         /* 1 = forward / input-gradient launches split the tiles of their ragged last round along K (plan_tail_split) */ \
+    X(tail_cus, 0, 0, 4096, 1)        /* CU count the tail plan balances for; 0 = ask the device (256 on MI355X) */                     \
+    X(tail_smax, 8, 1, 64, 1)         /* most K splits a remainder tile is cut into */                                                  \
+    X(tail_mint, 16, 1, 4096, 1)      /* fewest K tiles (of 32) a split keeps */                                                        \
+    X(stem_direct, 1, 0, 1, 1)        /* 1 = the stem convolution runs its direct form (k_stem_fwd_direct) where the geometry allows, 0 = implicit GEMM */ \
+    X(tail_gain, 8, 0, 100, 1)        /* balanced remainder: least modelled gain of a launch, in percent, for its ragged round to be split */ \
+    X(tail_qmax, 8, 0, 4096, 1)       /* ... and most full rounds a launch may have */                                                  \
+    X(bn_grid_bwd, 1024, 1, 1 << 20, 0)    /* grid cap of the BatchNorm BACKWARD apply kernels (they run beside the weight gradients) */ \
+    X(bn_wide_p, 2048, 0, 2048, 0)    /* BatchNorm finalisation (forward statistics and backward sums): ONE 1024-thread launch up to this many partials */ \
+    X(fwd_rows, 1, 0, 2, 0)           /* fwd: 1x1 stride-1 convolutions with Cin = 64 / 128 on the persistent row walker (k_conv1x1_rows): 0 off, 1 Cin = 64 at >= 8 row tiles per CU, 2 every eligible shape (tests) */ \
+    X(fwd_w3, 1, 0, 1, 0)             /* fwd: 3x3 stride-1 convolutions stage one activation window per tap row (k_conv_fwd W3): 0 off, 1 on */ \
+    X(dgrad_w3, 1, 0, 1, 0)           /* dgrad: the same for the in-block fused 3x3 stride-1 input gradients (k_conv_dgrad W3): 0 off, 1 on */ \
+    X(fwd_wino, 1, 0, 1, 1)           /* fwd: the executor runs its 3x3 stride-1 convolutions in the Winograd F(2x2,3x3) form (conv_wino.hip): 0 off, 1 on */ \
+    X(dgrad_wino, 1, 0, 1, 1)         /* dgrad: the same for the in-block fused 3x3 stride-1 input gradients */                         \
+    X(wgrad_wino, 1, 0, 1, 1)         /* wgrad: the executor's 3x3 stride-1 weight gradients (conv2, fused input activation) in the Winograd F(3x3,2x2) form */ \
+    X(wino_wide, 1, 0, 1, 0)          /* Winograd fwd / dgrad: units of 32 tiles x 128 channels where the channel count allows (the patch transform serves 2x the channels) */ \
+    X(wino_streamk, 2, 0, 3, 0)       /* Winograd forms: the units of the ragged last round are cut along K over all workgroups (stream-K): 0 = never, 1 = forward and input gradient, 2 = forward only (default), 3 = input gradient only */ \
+    X(dp_reserved_cus, 0, 0, 128, 1)  /* CUs' worth of wave slots the launch plans leave to co-resident communication kernels (data parallel); 0 = none */
+
 struct OsiTuning {
-    int wgrad_tile;     // 64 forces 64x64 weight-gradient tiles, 0 = 128-wide tiles wherever the channel counts allow
-    int wgrad_blocks;   // split-K footprint budget of one weight-gradient launch, in 64x64-workgroup units
-    int wgrad_nst;      // LDS stages of the weight-gradient kernel (1 or 2)
-    int bn_grid;        // grid cap of the BatchNorm stream kernels
-    int bn_single_p;    // BatchNorm statistics: row-tile partials merged by ONE launch up to this count, two-level above it
-    int wgrad3;         // 0 = per-tap kernel everywhere, 1 = 3x3 stride-1 weight gradients use the all-taps kernel (k_conv_wgrad3), 2 = stride 2 too
-    int wgrad3_blocks;  // workgroups per launch the all-taps kernel's split-K plan aims for
-    int fwd_wide, dgrad_wide;  // A/B: 64x128 forward / input-gradient tiles wherever the channel count allows (default 0: measured rule)
-    int wgrad_group;    // weight-gradient block -> XCD mapping: 0 plain 2-D grid, 1 the R*S taps of a cell share an XCD, 2 whole K splits do
-    int tail_split;     // 1 = forward / input-gradient launches split the tiles of their ragged last round along K (plan_tail_split)
-    int tail_cus;       // CU count the tail plan balances for; 0 = ask the device (256 on MI355X)
-    int tail_smax;      // most K splits a remainder tile is cut into
-    int tail_mint;      // fewest K tiles (of 32) a split keeps
-    int stem_direct;    // 1 = the stem convolution runs its direct form (k_stem_fwd_direct) where the geometry allows, 0 = implicit GEMM
-    int tail_gain;      // balanced remainder: least modelled gain of a launch, in percent, for its ragged round to be split
-    int tail_qmax;      // ... and most full rounds a launch may have
-    int bn_grid_bwd;    // grid cap of the BatchNorm BACKWARD apply kernels (they run beside the weight gradients)
-    int bn_wide_p;      // BatchNorm finalisation (forward statistics and backward sums): ONE 1024-thread launch up to this many partials
-    int fwd_rows;         // fwd: 1x1 stride-1 convolutions with Cin = 64 / 128 on the persistent row walker (k_conv1x1_rows): 0 off, 1 Cin = 64 at >= 8 row tiles per CU, 2 every eligible shape (tests)
-    int fwd_w3;           // fwd: 3x3 stride-1 convolutions stage one activation window per tap row (k_conv_fwd W3): 0 off, 1 on
-    int dgrad_w3;         // dgrad: the same for the in-block fused 3x3 stride-1 input gradients (k_conv_dgrad W3): 0 off, 1 on
-    int fwd_wino;         // fwd: the executor runs its 3x3 stride-1 convolutions in the Winograd F(2x2,3x3) form (conv_wino.hip): 0 off, 1 on
-    int dgrad_wino;       // dgrad: the same for the in-block fused 3x3 stride-1 input gradients
-    int wgrad_wino;       // wgrad: the executor's 3x3 stride-1 weight gradients (conv2, fused input activation) in the Winograd F(3x3,2x2) form
-    int wino_wide;        // Winograd fwd / dgrad: units of 32 tiles x 128 channels where the channel count allows (the patch transform serves 2x the channels)
-    int wino_streamk;     // Winograd forms: the units of the ragged last round are cut along K over all workgroups (stream-K): 0 = never, 1 = forward and input gradient, 2 = forward only (default), 3 = input gradient only
-    int dp_reserved_cus;  // CUs' worth of wave slots the launch plans leave to co-resident communication kernels (data parallel); 0 = none
+#define OSI_KNOB_FIELD(name, def, lo, hi, plan) int name = def;
+    OSI_TUNING_KNOBS(OSI_KNOB_FIELD)
+#undef OSI_KNOB_FIELD
 };
 extern OsiTuning g_osi_tuning;
 

@@ -214,12 +214,13 @@ struct osi_resnet50 {
     OsiTuning plan_knobs;            // the process-wide knobs the workspace was sized for (osi_resnet50_create); a launch under other
     int plan_hw_cus = 0;             // values (or on a device with another CU count) is refused (OSI_ERR_STATE) instead of running a
                                      // plan the workspace does not fit
-    bool plan_unchanged() const {
+    bool plan_unchanged() const {      // the rows of OSI_TUNING_KNOBS flagged plan-relevant, and the CU count
         const OsiTuning &a = plan_knobs, &b = g_osi_tuning;
-        return plan_hw_cus == device_cus() && a.wgrad_tile == b.wgrad_tile && a.wgrad_blocks == b.wgrad_blocks && a.wgrad3 == b.wgrad3 && a.wgrad3_blocks == b.wgrad3_blocks &&
-               a.tail_split == b.tail_split && a.tail_cus == b.tail_cus && a.tail_smax == b.tail_smax && a.tail_mint == b.tail_mint &&
-               a.tail_gain == b.tail_gain && a.tail_qmax == b.tail_qmax && a.stem_direct == b.stem_direct && a.wgrad_group == b.wgrad_group &&
-               a.dp_reserved_cus == b.dp_reserved_cus && a.fwd_wino == b.fwd_wino && a.dgrad_wino == b.dgrad_wino && a.wgrad_wino == b.wgrad_wino;
+        bool same = plan_hw_cus == device_cus();
+#define OSI_KNOB_SAME(name, def, lo, hi, plan) same = same && (!(plan) || a.name == b.name);
+        OSI_TUNING_KNOBS(OSI_KNOB_SAME)
+#undef OSI_KNOB_SAME
+        return same;
     }
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_rmain = nullptr, ev_rside = nullptr, ev_wt = nullptr;

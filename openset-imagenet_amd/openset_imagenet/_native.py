@@ -86,6 +86,7 @@ _SIGS = {
     "osi_strerror": (c_char_p, [c_int]),
     "osi_set_tuning": (c_int, [c_char_p, c_int]),
     "osi_get_tuning": (c_int, [c_char_p, POINTER(c_int)]),
+    "osi_tuning_info": (c_int, [c_int, POINTER(c_char_p), POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "osi_conv_fwd": (c_int, [_PD, P, P, P, c_int, P]),
     "osi_conv_fwd_act": (c_int, [_PD, P, P, P, P, P, c_int, P, c_size_t, POINTER(c_int), POINTER(c_int), P]),
     "osi_conv_fwd_act2": (c_int, [_PD, P, P, P, P, P, P, c_int, P, c_size_t, POINTER(c_int), POINTER(c_int), P]),
@@ -232,12 +233,21 @@ def lib():
             fn.restype = res
             fn.argtypes = args
         _lib = handle
-        # development A/B switches: the environment is read HERE, once, and handed to the library explicitly
-        for env, knob in (("OSI_WGRAD_TILE", b"wgrad_tile"), ("OSI_WGRAD_BLOCKS", b"wgrad_blocks"), ("OSI_WGRAD_NST", b"wgrad_nst"),
-                          ("OSI_WGRAD_GROUP", b"wgrad_group"), ("OSI_BN_GRID", b"bn_grid"), ("OSI_BN_GRID_BWD", b"bn_grid_bwd"), ("OSI_BN_SINGLE_P", b"bn_single_p"), ("OSI_BN_WIDE_P", b"bn_wide_p"), ("OSI_TAIL_GAIN", b"tail_gain"), ("OSI_TAIL_QMAX", b"tail_qmax"), ("OSI_WGRAD3", b"wgrad3"), ("OSI_WGRAD3_BLOCKS", b"wgrad3_blocks"), ("OSI_FWD_WIDE", b"fwd_wide"), ("OSI_DGRAD_WIDE", b"dgrad_wide"), ("OSI_TAIL_SPLIT", b"tail_split"), ("OSI_TAIL_CUS", b"tail_cus"), ("OSI_TAIL_SMAX", b"tail_smax"), ("OSI_TAIL_MINT", b"tail_mint"), ("OSI_STEM_DIRECT", b"stem_direct"), ("OSI_DP_RESERVED_CUS", b"dp_reserved_cus"), ("OSI_FWD_ROWS", b"fwd_rows"), ("OSI_FWD_W3", b"fwd_w3"), ("OSI_DGRAD_W3", b"dgrad_w3"), ("OSI_FWD_WINO", b"fwd_wino"), ("OSI_DGRAD_WINO", b"dgrad_wino"), ("OSI_WINO_STREAMK", b"wino_streamk"), ("OSI_WGRAD_WINO", b"wgrad_wino"), ("OSI_WINO_WIDE", b"wino_wide")):
+        # development A/B switches: the environment is read HERE, once, and handed to the library explicitly: OSI_<KNOB NAME>
+        for name, _, _, _, _ in tuning_knobs(handle):
+            env = "OSI_" + name.upper()
             if os.environ.get(env):
-                check(handle.osi_set_tuning(knob, int(os.environ[env])), f"osi_set_tuning({knob.decode()})")
+                check(handle.osi_set_tuning(name.encode(), int(os.environ[env])), f"osi_set_tuning({name})")
     return _lib
+
+
+def tuning_knobs(handle=None):
+    """The library's knob list (osi_tuning_info): [(name, default, lo, hi, plan_relevant)]."""
+    handle = handle or lib()
+    rows, name, v = [], c_char_p(), [c_int() for _ in range(4)]
+    while handle.osi_tuning_info(len(rows), ctypes.byref(name), *(ctypes.byref(x) for x in v)) == OSI_OK:
+        rows.append((name.value.decode(), v[0].value, v[1].value, v[2].value, bool(v[3].value)))
+    return rows
 
 
 _ops = None

@@ -109,3 +109,41 @@ def test_backward_winograd_plans_leave_the_channel_count_of_cus_free():
     if not torch.cuda.is_available():                          # 256 CUs assumed
         assert seen == {0: (256, 256), 4: (224, 224), 8: (192, 192), 32: (192, 192)}, seen
     assert seen[0][0] > seen[4][0] > seen[8][0] == seen[32][0] and seen[0][0] - seen[4][0] == 32
+
+
+def header_knob_table():
+    """The documentation table of include/osi.h: {name: (default, lo, hi, plan_relevant)}; ranges read `a | b` or `a .. b`, 2^20 as written."""
+    text = open(os.path.join(ROOT, "include", "osi.h")).read()
+    table = text[text.index("name             range"):text.index("int osi_set_tuning")]
+    num = lambda s: 2 ** int(s[2:]) if s.startswith("2^") else int(s)
+    rows = {}
+    for m in re.finditer(r"^ \*   (\w+) (\*?)\s+(\d+) (?:\||\.\.) (\d+|2\^\d+)\s+(\d+)\s+\S", table, flags=re.M):
+        assert m.group(1) not in rows, m.group(1)
+        rows[m.group(1)] = (int(m.group(5)), int(m.group(3)), num(m.group(4)), m.group(2) == "*")
+    return rows
+
+
+def test_header_knob_table_matches_the_library():
+    """The library is built from one knob list (osi_tuning_info enumerates it); the table in include/osi.h documents that list and
+    may not drift from it: same names, and per knob the same default, range and plan-relevance mark."""
+    lib = N.lib()
+    knobs = {name: (d, lo, hi, plan) for name, d, lo, hi, plan in N.tuning_knobs()}
+    assert len(knobs) == len(N.tuning_knobs()) >= 28
+    assert lib.osi_tuning_info(len(knobs), None, None, None, None, None) == -1 and lib.osi_tuning_info(-1, None, None, None, None, None) == -1
+    assert lib.osi_tuning_info(0, None, None, None, None, None) == 0          # every output is optional
+    doc = header_knob_table()
+    assert sorted(doc) == sorted(knobs)
+    for name in knobs:
+        assert doc[name] == knobs[name], (name, doc[name], knobs[name])
+
+
+def test_every_knob_starts_at_its_default_and_refuses_values_outside_its_range():
+    lib = N.lib()
+    v = ctypes.c_int()
+    for name, default, lo, hi, _ in N.tuning_knobs():
+        key = name.encode()
+        assert lib.osi_get_tuning(key, ctypes.byref(v)) == 0 and v.value == default, name
+        for bad in (lo - 1, hi + 1):
+            assert lib.osi_set_tuning(key, bad) == -1, (name, bad)
+            assert lib.osi_get_tuning(key, ctypes.byref(v)) == 0 and v.value == default, (name, bad)
+    assert lib.osi_set_tuning(b"wgrad_tile", 32) == -1 and lib.osi_get_tuning(b"wgrad_tile", ctypes.byref(v)) == 0 and v.value == 0
