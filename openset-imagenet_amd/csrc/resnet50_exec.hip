@@ -21,6 +21,8 @@
 
 namespace {
 
+constexpr size_t WS_NONE = (size_t)-1;   // workspace offset of a tensor the layer does not have
+
 struct Tensor {
     std::string name;
     int ndim; int shape[4];
@@ -41,9 +43,9 @@ struct Conv {
     size_t w_off;  // param arena
     int bn;
     size_t y;      // workspace: conv output (pre-BN)
-    size_t a;      // workspace: BN(+res)+ReLU output (SIZE_MAX for downsample: goes to scratch)
+    size_t a;      // workspace: BN(+res)+ReLU output (WS_NONE unless it is a block output)
     size_t mask;   // workspace: ReLU bitmask of `a` (1 bit per element)
-    size_t u_fw = (size_t)-1, u_bw = (size_t)-1;   // workspace: Winograd-transformed weights (forward / input-gradient form), 3x3 stride-1 layers only
+    size_t u_fw = WS_NONE, u_bw = WS_NONE;   // workspace: Winograd-transformed weights (forward / input-gradient form), 3x3 stride-1 layers only
     int unit;
 };
 struct Block {
@@ -63,11 +65,26 @@ constexpr unsigned EV_FLAGS = hipEventDisableTiming | hipEventDisableSystemFence
 // peers read this device's gradient arena over xGMI. They keep the system-scope release (<= 8 records per step).
 constexpr unsigned EV_FLAGS_HANDOFF = hipEventDisableTiming;
 static size_t up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+static void grow(size_t& m, size_t v) { if (v > m) m = v; }
 static int device_cus() {   // CUs of the CURRENT device (the launch plans are balanced for them): 0 when no device answers
     int v = 0, dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
     return v;
 }
+
+// What a backward is asked for (osi_resnet50_backward_ex / _adv). dimage != NULL: the stem tail materialises dY and its input gradient
+// writes dJ/dimage. param_grads = 0: input-only (no weight gradient, nothing into grads). x_adv != NULL: the stem tail materialises dY as
+// for dJ/dimage and the stem's input gradient ends in the FGSM epilogue (osi_stem_dgrad_fgsm) that writes the adversarial NHWC4 batch;
+// dJ/dimage itself is never written.
+struct BwRequest {
+    float* dimage = nullptr;
+    int param_grads = 1;
+    float* x_adv = nullptr;
+    float eps = 0.f, lo = 0.f, hi = 0.f;
+    bool operator==(const BwRequest& o) const {
+        return dimage == o.dimage && param_grads == o.param_grads && x_adv == o.x_adv && eps == o.eps && lo == o.lo && hi == o.hi;
+    }
+};
 
 }  // namespace
 
@@ -93,15 +110,25 @@ struct osi_resnet50 {
     // stage bookkeeping
     int n_stages = 4;
     size_t stage_lo[4], stage_hi[4];
-    // run state
-    bool fwd_done = false;
+    // (everything above is the layout osi_resnet50_create builds and nothing changes afterwards)
+
+    // ---- run state: what one forward leaves for its backward, and one backward stage for the next --------------------------------------
+    bool fwd_done = false;           // a differentiable forward ran and its backward has not finished
     bool any_fwd = false;            // the workspace holds the ReLU / arg-max decisions of a forward (osi_resnet50_debug_gate refuses to read an
                                      // empty workspace — or one an inference forward ran in: that one stores activations, not pre-BN tensors or bitmasks)
+    bool frozen = false;             // osi_resnet50_forward_frozen ran last: every BatchNorm's mean / invstd slots hold the running statistics and
+                                     // the backward that follows takes the frozen dataflow (dy = scale * g; the fused stem tail and the Winograd
+                                     // input gradients are training-only)
+    int fw_prefix = 0;               // eval_prefix of the latest differentiable forward: the gates of those units do not exist
+    const float* x4_cur = nullptr;   // input of the step in flight (forward sets it, the stem weight gradient reads it)
     int next_stage = 0;
+    BwRequest rq;                    // request of the backward in flight, fixed by the call that runs stage 0 (block 0's dgrad form depends on it)
     int cur_grad = -1;               // scratch index holding the upstream gradient between stages
     bool go_fused = false;           // cur_grad is already ReLU-masked and its BatchNorm reductions wait in dg_ws
     int fused_P = 0;                 // row tiles of the partials in dg_ws
-    std::vector<int> free_list;
+    int stem_stats_P = 0;            // row tiles of bn1's backward partial sums in dg_ws (left by the pool-mode epilogue of layer1.0.conv1's dgrad)
+    std::vector<int> free_list;      // scratch buffers nobody holds, oldest release first
+    // --------------------------------------------------------------------------------------------------------------------------------------
     // optional HIP-event instrumentation: one event after every op, tagged with the op's class
     bool prof_on = false;
     bool prof_timeline = false;      // mode 2: keep the side-stream overlap, record where each op ran (osi_resnet50_timeline_read)
@@ -131,11 +158,10 @@ struct osi_resnet50 {
     int cur_unit = 0;                // unit of the tensors being registered (osi_resnet50_create)
     unsigned unit_mask = (1u << NUNITS) - 1;
     int eval_prefix = 0;
-    int fw_prefix = 0;               // eval_prefix of the latest differentiable forward: the gates of those units do not exist
     bool trainable(int unit) const { return (unit_mask >> unit) & 1u; }
     int cut() const { int c = 0; while (!((unit_mask >> c) & 1u)) ++c; return c; }
     // first unit the backward in flight computes: the cut, unless the image gradient is wanted (then full depth)
-    int bw_stop() const { return (bw_pg && !bw_dimage && !bw_adv) ? cut() : 0; }
+    int bw_stop() const { return (rq.param_grads && !rq.dimage && !rq.x_adv) ? cut() : 0; }
 
     size_t add_tensor(const std::string& name, int ndim, const int* shape) {
         Tensor t; t.name = name; t.ndim = ndim; t.numel = 1;
@@ -171,8 +197,8 @@ struct osi_resnet50 {
         bns.push_back(b);
         size_t n = (size_t)b.M * Cout;
         c.y = ws_alloc(n);
-        c.a = keep_act ? ws_alloc(n) : (size_t)-1;
-        c.mask = keep_act ? ws_alloc(osi_bn_relu_mask_bytes(b.M, Cout) / sizeof(float)) : (size_t)-1;
+        c.a = keep_act ? ws_alloc(n) : WS_NONE;
+        c.mask = keep_act ? ws_alloc(osi_bn_relu_mask_bytes(b.M, Cout) / sizeof(float)) : WS_NONE;
         convs.push_back(c);
         return (int)convs.size() - 1;
     }
@@ -184,28 +210,20 @@ struct osi_resnet50 {
     bool fwd_fork = true;            // projection shortcut of the forward pass on the side stream
     bool side_prio_normal = false;   // side stream at default instead of lowest priority (read when the stream is created)
     const float* x4_ext = nullptr;   // external NHWC4 input bound by osi_resnet50_bind_input_nhwc4 (consumed by one forward)
-    const float* x4_cur = nullptr;   // input of the step in flight (forward sets it, the stem weight gradient reads it)
-    int stem_stats_P = 0;            // row tiles of bn1's backward partial sums in dg_ws (left by the pool-mode epilogue of layer1.0.conv1's dgrad)
-    // request of the backward in flight (osi_resnet50_backward_ex), fixed by the call that runs stage 0: bw_dimage != NULL -> the stem
-    // tail materialises dY and its input gradient writes dJ/dimage; bw_pg = 0 -> input-only (no weight gradient, nothing into grads)
-    float* bw_dimage = nullptr;
-    bool bw_pg = true;
-    // osi_resnet50_backward_adv: bw_adv != NULL -> the stem tail materialises dY as for dJ/dimage, and the stem's input gradient ends in
-    // the FGSM epilogue (osi_stem_dgrad_fgsm) that writes the adversarial NHWC4 batch; dJ/dimage itself is never written
-    float* bw_adv = nullptr;
-    float bw_eps = 0.f, bw_lo = 0.f, bw_hi = 0.f;
-    // (a frozen unit's reductions, which the batch-statistics dx still needs, land in the sink as well)
-    float* dgam(float* grads, float* ws, const BN& b) const { return bw_pg && trainable(b.unit) ? grads + b.g_off : ws + b.dsink; }
-    float* dbet(float* grads, float* ws, const BN& b) const { return bw_pg && trainable(b.unit) ? grads + b.b_off : ws + b.dsink + b.C; }
+    // does the backward in flight write the parameter gradients of `unit`? (input-only request, frozen unit: nobody reads that slice of the arena)
+    bool wants_grads(int unit) const { return rq.param_grads && trainable(unit); }
+    // where a BatchNorm backward writes dgamma / dbeta (reductions the batch-statistics dx needs but nobody reads land in the layer's sink)
+    float* dgam(float* grads, float* ws, const BN& b) const { return wants_grads(b.unit) ? grads + b.g_off : ws + b.dsink; }
+    float* dbet(float* grads, float* ws, const BN& b) const { return wants_grads(b.unit) ? grads + b.b_off : ws + b.dsink + b.C; }
+    // column `col` of the [P row tiles][C] partial sums a dgrad epilogue left in dg_ws: 0 = sum g (shared by both consumers),
+    // 1 = sum g * xhat of the main branch, 2 = of the downsample branch
+    const float* dg_col(const float* ws, int col, int P, int C) const { return ws + dg_ws + (size_t)col * P * C; }
     // The stem tail's form, decided by what the backward can observe. Block 0's last input gradient and the tail both ask here, so they
     // cannot disagree: the fused form (bn1's reductions out of that input gradient's pool-mode epilogue, dY built inside
     // osi_stem_wgrad_fused's loader) unless dJ/dimage (or the adversarial batch made from it) needs dY in memory or the geometry /
     // knobs leave the fused form no workspace.
-    bool stem_tail_fused() const { return !frozen && !bw_dimage && !bw_adv && stem_ws_bytes > 0; }
-    // osi_resnet50_forward_frozen ran last: every BatchNorm's mean / invstd slots hold the running statistics and the backward that follows
-    // takes the frozen dataflow (dy = scale * g; the fused stem tail and the Winograd input gradients are training-only)
-    bool frozen = false;
-    bool eval_fused = true;          // option "eval_fused": a forward with training = 0 runs the inference forms (forward_eval_fused); 0 = the
+    bool stem_tail_fused() const { return !frozen && !rq.dimage && !rq.x_adv && stem_ws_bytes > 0; }
+    bool eval_fused = true;          // option "eval_fused": a forward with training = 0 runs the inference forms (block_fwd_eval); 0 = the
                                      // training topology on running statistics (A/B: the same bits when both run the same launch plans,
                                      // i.e. tail_split off; fp32-rounding-level differences otherwise)
     bool stage_join = true;          // option "stage_join": a staged backward call (stage_hi < stages) ends by joining the side stream into
@@ -241,10 +259,11 @@ struct osi_resnet50 {
             if (hipEventCreateWithFlags(&buf_ev[i], EV_FLAGS) != hipSuccess) return OSI_ERR_LAUNCH;
         return OSI_OK;
     }
-    bool async_wgrad() const { return overlap && (!prof_on || prof_timeline) && side != nullptr; }
-    // a scratch buffer may only be rewritten on `st` after its last side-stream reader has finished
-    // returns the buffer index, or a negative OSI_ERR_* code
-    int take(hipStream_t st) {
+    // the side stream is wanted (the class-attributing profile serialises everything on the caller's stream; the timeline mode does not)
+    bool wants_side() const { return overlap && (!prof_on || prof_timeline); }
+    bool async_wgrad() const { return wants_side() && side != nullptr; }
+    // *idx = a free scratch buffer; it may only be rewritten on `st` after its last side-stream reader has finished
+    int take(hipStream_t st, int* idx) {
         if (free_list.empty()) return OSI_ERR_STATE;
         // FIFO: hand out the buffer that was released longest ago, so its side-stream reader has most likely finished
         int i = free_list.front(); free_list.erase(free_list.begin());
@@ -252,7 +271,8 @@ struct osi_resnet50 {
             if (hipStreamWaitEvent(st, buf_ev[i], 0) != hipSuccess) return OSI_ERR_LAUNCH;
             buf_pending[i] = false;
         }
-        return i;
+        *idx = i;
+        return OSI_OK;
     }
     void give(int i) { free_list.push_back(i); }
     // the side stream continues from everything enqueued on `st` so far
@@ -348,36 +368,25 @@ int osi_resnet50_create(osi_resnet50_t* out, int B, int H, int W, int fc_dim, in
     // scratch sizing
     size_t maxact = 0, bnws = 0, wgws = 0, dgws = 0, winows = 0;
     for (auto& c : n->convs) {
-        size_t e = (size_t)c.d.B * c.d.Ho * c.d.Wo * c.d.Cout;
-        if (e > maxact) maxact = e;
-        size_t ein = (size_t)c.d.B * c.d.H * c.d.W * c.d.Cin;
-        if (ein > maxact) maxact = ein;
-        size_t b1 = osi_bn_workspace(n->bns[c.bn].M, c.d.Cout), b2 = osi_bn_backward_workspace(n->bns[c.bn].M, c.d.Cout);
-        if (b1 > bnws) bnws = b1;
-        if (b2 > bnws) bnws = b2;
-        size_t b3 = osi_conv_fwd_bnstats_workspace(&c.d);
-        if (b3 > bnws) bnws = b3;
-        size_t b4 = osi_bn_backward_fused2_workspace(c.d.Cout);   // a projection block's two BatchNorm backwards in one pass
-        if (b4 > bnws) bnws = b4;
-        size_t wg = osi_conv_wgrad_workspace(&c.d);
-        if (wg > wgws) wgws = wg;
-        wg = osi_stem_wgrad_direct_workspace(&c.d);
-        if (wg > wgws) wgws = wg;
-        wg = osi_conv_wgrad_wino_workspace(&c.d);
-        if (wg > wgws) wgws = wg;
-        if (!(c.d.Cin == 4 && c.d.R == 7)) { size_t dg = osi_conv_dgrad_fused_workspace(&c.d); if (dg > dgws) dgws = dg; }
+        grow(maxact, (size_t)c.d.B * c.d.Ho * c.d.Wo * c.d.Cout);
+        grow(maxact, (size_t)c.d.B * c.d.H * c.d.W * c.d.Cin);
+        grow(bnws, osi_bn_workspace(n->bns[c.bn].M, c.d.Cout));
+        grow(bnws, osi_bn_backward_workspace(n->bns[c.bn].M, c.d.Cout));
+        grow(bnws, osi_conv_fwd_bnstats_workspace(&c.d));
+        grow(bnws, osi_bn_backward_fused2_workspace(c.d.Cout));   // a projection block's two BatchNorm backwards in one pass
+        grow(wgws, osi_conv_wgrad_workspace(&c.d));
+        grow(wgws, osi_stem_wgrad_direct_workspace(&c.d));
+        grow(wgws, osi_conv_wgrad_wino_workspace(&c.d));
+        if (!(c.d.Cin == 4 && c.d.R == 7)) grow(dgws, osi_conv_dgrad_fused_workspace(&c.d));
         if (osi_conv_wino_eligible(&c.d, 0) || osi_conv_wino_eligible(&c.d, 1)) {
             // Winograd forms: one (mean, M2) / (sum g, sum g xhat) partial per 16 tiles (+ the merge scratch behind the statistics); the
             // transformed weights of both directions live per layer (built on the side stream at the start of a forward pass)
             const size_t Pw = ((size_t)c.d.B * ((c.d.H + 1) / 2) * ((c.d.W + 1) / 2) + 15) / 16;
             if (osi_conv_wino_eligible(&c.d, 0)) c.u_fw = n->ws_alloc(osi_conv_wino_weights_bytes(&c.d) / sizeof(float));
             if (osi_conv_wino_eligible(&c.d, 1)) c.u_bw = n->ws_alloc(osi_conv_wino_weights_bytes(&c.d) / sizeof(float));
-            size_t w = osi_conv_wino_slab_bytes();
-            if (w > winows) winows = w;
-            w = (2 * Pw + 64) * c.d.Cout * sizeof(float);
-            if (w > bnws) bnws = w;
-            w = 3 * Pw * c.d.Cin * sizeof(float);
-            if (w > dgws) dgws = w;
+            grow(winows, osi_conv_wino_slab_bytes());
+            grow(bnws, (2 * Pw + 64) * c.d.Cout * sizeof(float));
+            grow(dgws, 3 * Pw * c.d.Cin * sizeof(float));
         }
     }
     n->wino_ws_bytes = winows; n->wino_ws = n->ws_alloc(winows / 4 + 4);
@@ -499,38 +508,39 @@ int osi_resnet50_profile_read(osi_resnet50_t n, double* ms, int* count) {
     return OSI_OK;
 }
 
-// conv ci + its BatchNorm statistics. in_bn >= 0: the conv's input is the PRE-BN output of the layer whose BatchNorm is `in_bn`;
+// How a forward finishes its BatchNorms: on the running statistics without backward state (validate()), on batch statistics with the
+// running-statistics update (training), or on the running statistics with the backward state kept (osi_resnet50_forward_frozen).
+enum class BnMode { Inference, Batch, Frozen };
+
+// conv ci + its BatchNorm coefficients. in_bn >= 0: the conv's input is the PRE-BN output of the layer whose BatchNorm is `in_bn`;
 // that BatchNorm + ReLU is applied inside the conv's operand loader (osi_conv_fwd_act) — the activation never exists in HBM.
 static int conv_bn_fwd(osi_resnet50* n, int ci, const float* params, float* buffers, float* ws, const float* x, const float* w,
-                       int training, hipStream_t st, size_t bn_ws_off, int in_bn = -1) {
+                       BnMode mode, hipStream_t st, size_t bn_ws_off, int in_bn = -1) {
     Conv& c = n->convs[ci];
     BN& b = n->bns[c.bn];
     const float* isc = in_bn >= 0 ? ws + n->bns[in_bn].scale : nullptr;
     const float* ish = in_bn >= 0 ? ws + n->bns[in_bn].shift : nullptr;
     // 3x3 / stride 1 (conv2 of a bottleneck without a stride): Winograd F(2x2,3x3), 2.25x fewer multiplies (csrc/conv_wino.hip); main stream only
-    const bool wino = n->plan_knobs.fwd_wino && isc && (n->side == nullptr || st != n->side) && c.u_fw != (size_t)-1;
+    const bool wino = n->plan_knobs.fwd_wino && isc && (n->side == nullptr || st != n->side) && c.u_fw != WS_NONE;
     if (wino) OSI_TRY(n->wait_weight_transforms(st));
-    if (training == 1) {
-        // batch statistics come out of the conv epilogue (per row tile), only a tiny per-channel merge follows
-        int P = 0, rows = 0;
-        if (isc && wino) OSI_TRY(osi_conv_fwd_wino_pre(&c.d, x, isc, ish, ws + c.u_fw, ws + c.y, ws + n->wino_ws, n->wino_ws_bytes, ws + bn_ws_off, n->bn_ws_bytes, &P, &rows, st));
-        else if (isc) OSI_TRY(osi_conv_fwd_act(&c.d, x, isc, ish, w, ws + c.y, OSI_TILE_AUTO, ws + bn_ws_off, n->bn_ws_bytes, &P, &rows, st));
-        else OSI_TRY(osi_conv_fwd_bnstats(&c.d, x, w, ws + c.y, OSI_TILE_AUTO, ws + bn_ws_off, n->bn_ws_bytes, &P, &rows, st));
-        OSI_TRY(n->mark(OSI_PROF_CONV_FWD, st));
-        OSI_TRY(osi_bn_finalize_stats(ws + bn_ws_off, n->bn_ws_bytes, P, rows, b.M, b.C, params + b.g_off, params + b.b_off, 1e-5f, 0.1f,
-                                      buffers + b.rm_off, buffers + b.rv_off, ws + b.mean, ws + b.invstd, ws + b.scale,
-                                      ws + b.shift, st));
-    } else {
-        if (isc && wino) OSI_TRY(osi_conv_fwd_wino_pre(&c.d, x, isc, ish, ws + c.u_fw, ws + c.y, ws + n->wino_ws, n->wino_ws_bytes, nullptr, 0, nullptr, nullptr, st));
-        else if (isc) OSI_TRY(osi_conv_fwd_act(&c.d, x, isc, ish, w, ws + c.y, OSI_TILE_AUTO, nullptr, 0, nullptr, nullptr, st));
-        else OSI_TRY(osi_conv_fwd(&c.d, x, w, ws + c.y, OSI_TILE_AUTO, st));
-        OSI_TRY(n->mark(OSI_PROF_CONV_FWD, st));
-        if (training != 2)   // (2 = frozen forward: one launch wrote every layer's coefficients up front)
-        OSI_TRY(osi_bn_eval_coeffs(buffers + b.rm_off, buffers + b.rv_off, params + b.g_off, params + b.b_off, 1e-5f, b.C,
-                                   ws + b.scale, ws + b.shift, st));
-    }
-    OSI_TRY(n->mark(OSI_PROF_BN_FWD, st));
-    return OSI_OK;
+    // batch statistics come out of the conv epilogue (per row tile), only a tiny per-channel merge follows; the other modes pass no slab
+    const bool stats = mode == BnMode::Batch;
+    float* sws = stats ? ws + bn_ws_off : nullptr;
+    const size_t sbytes = stats ? n->bn_ws_bytes : 0;
+    int P = 0, rows = 0;
+    int *pP = stats ? &P : nullptr, *prows = stats ? &rows : nullptr;
+    if (wino) OSI_TRY(osi_conv_fwd_wino_pre(&c.d, x, isc, ish, ws + c.u_fw, ws + c.y, ws + n->wino_ws, n->wino_ws_bytes, sws, sbytes, pP, prows, st));
+    else if (isc) OSI_TRY(osi_conv_fwd_act(&c.d, x, isc, ish, w, ws + c.y, OSI_TILE_AUTO, sws, sbytes, pP, prows, st));
+    else if (stats) OSI_TRY(osi_conv_fwd_bnstats(&c.d, x, w, ws + c.y, OSI_TILE_AUTO, sws, sbytes, pP, prows, st));
+    else OSI_TRY(osi_conv_fwd(&c.d, x, w, ws + c.y, OSI_TILE_AUTO, st));
+    OSI_TRY(n->mark(OSI_PROF_CONV_FWD, st));
+    if (mode == BnMode::Batch)
+        OSI_TRY(osi_bn_finalize_stats(sws, sbytes, P, rows, b.M, b.C, params + b.g_off, params + b.b_off, 1e-5f, 0.1f, buffers + b.rm_off,
+                                      buffers + b.rv_off, ws + b.mean, ws + b.invstd, ws + b.scale, ws + b.shift, st));
+    else if (mode == BnMode::Inference)   // (frozen: one launch wrote every layer's coefficients up front)
+        OSI_TRY(osi_bn_eval_coeffs(buffers + b.rm_off, buffers + b.rv_off, params + b.g_off, params + b.b_off, 1e-5f, b.C, ws + b.scale,
+                                   ws + b.shift, st));
+    return n->mark(OSI_PROF_BN_FWD, st);
 }
 
 // Input staged from a uint8 [B][H][W][3] batch (+ optional per-image horizontal flip flags) straight into the executor's NHWC4
@@ -587,90 +597,144 @@ static int eval_coeffs(osi_resnet50* n, const float* params, const float* buffer
     OSI_TRY(osi_bn_eval_coeffs_multi(tab, nb, 1e-5f, st));
     return n->mark(OSI_PROF_BN_FWD, st);
 }
-static int stem_fwd_eval(osi_resnet50* n, float* ws, const float* x4, hipStream_t st) {
+// The same for the frozen forward: scale / shift (forward) and mean / invstd (backward) of the BatchNorms of units [from, NUNITS)
+static int frozen_coeffs(osi_resnet50* n, const float* params, const float* buffers, float* ws, int from, hipStream_t st) {
+    osi_bn_frozen_layer tab[OSI_BN_FROZEN_MAX];
+    int nb = 0;
+    for (const BN& b : n->bns) {
+        if (b.unit < from) continue;
+        if (nb == OSI_BN_FROZEN_MAX) return OSI_ERR_STATE;
+        tab[nb++] = osi_bn_frozen_layer{buffers + b.rm_off, buffers + b.rv_off, params + b.g_off, params + b.b_off, ws + b.scale, ws + b.shift,
+                                        ws + b.mean, ws + b.invstd, b.C};
+    }
+    if (!nb) return OSI_OK;
+    OSI_TRY(osi_bn_frozen_coeffs_multi(tab, nb, 1e-5f, st));
+    return n->mark(OSI_PROF_BN_FWD, st);
+}
+
+// Winograd weight transforms of every 3x3 stride-1 layer, both directions: the weights are the same for this forward and its backward.
+// On the side stream beside the stem (26 launches of 4 - 16 us that used to sit in front of their convolutions); the first Winograd
+// convolution waits for them. `p`: units below it run the inference forms and no backward ever reaches them.
+static int transform_weights(osi_resnet50* n, const float* params, float* ws, BnMode mode, int p, hipStream_t st) {
+    const bool bw = mode == BnMode::Batch && n->plan_knobs.dgrad_wino;   // (a frozen backward has no Winograd input gradient)
+    if (!n->plan_knobs.fwd_wino && !bw) return OSI_OK;
+    // (training forwards only: an inference forward has 13 transforms and nothing but the stem beside them — the fork / join costs more
+    // than they do: 7.96 in line vs 8.00 ms aside per batch of 128, profiles/NOTES_r06.md)
+    const bool aside = mode == BnMode::Batch && n->async_wgrad();
+    hipStream_t wt = aside ? n->side : st;
+    if (aside) OSI_TRY(n->fork_side(st));
+    for (auto& c : n->convs)
+        if (n->plan_knobs.fwd_wino && c.u_fw != WS_NONE)
+            OSI_TRY(osi_conv_wino_transform_weights(&c.d, params + c.w_off, 0, ws + c.u_fw, osi_conv_wino_weights_bytes(&c.d), wt));
+    OSI_TRY(n->mark(OSI_PROF_CONV_FWD, wt));
+    if (bw) {
+        int nt = 0;
+        for (auto& c : n->convs)
+            if (c.u_bw != WS_NONE && c.unit >= p) {
+                OSI_TRY(osi_conv_wino_transform_weights(&c.d, params + c.w_off, 1, ws + c.u_bw, osi_conv_wino_weights_bytes(&c.d), wt));
+                ++nt;
+            }
+        if (nt) OSI_TRY(n->mark(OSI_PROF_CONV_DGRAD, wt));
+    }
+    if (aside) {
+        if (hipEventRecord(n->ev_wt, n->side) != hipSuccess) return OSI_ERR_LAUNCH;
+        n->wt_pending = true;
+    }
+    return OSI_OK;
+}
+
+// conv1 + bn1 + relu + maxpool in one pass: the 112x112x64 post-ReLU tensor is never materialised. inference_form: bn1's coefficients
+// already exist (eval_coeffs), so the plain convolution is all that precedes the pass; otherwise `mode` finishes bn1 after the convolution.
+static int stem_fwd(osi_resnet50* n, const float* params, float* buffers, float* ws, const float* x4, BnMode mode, bool inference_form,
+                    hipStream_t st) {
     Conv& c0 = n->convs[0];
-    OSI_TRY(osi_conv_fwd(&c0.d, x4, ws + n->wpack, ws + c0.y, OSI_TILE_AUTO, st));
-    OSI_TRY(n->mark(OSI_PROF_CONV_FWD, st));
     BN& b0 = n->bns[c0.bn];
+    if (inference_form) {
+        OSI_TRY(osi_conv_fwd(&c0.d, x4, ws + n->wpack, ws + c0.y, OSI_TILE_AUTO, st));
+        OSI_TRY(n->mark(OSI_PROF_CONV_FWD, st));
+    } else {
+        OSI_TRY(conv_bn_fwd(n, 0, params, buffers, ws, x4, ws + n->wpack, mode, st, n->bn_ws));
+    }
     OSI_TRY(osi_bn_relu_maxpool_fwd(ws + c0.y, ws + b0.scale, ws + b0.shift, ws + n->a_pool, ws + n->pool_idx, n->B, n->Hs, n->Ws, 64, st));
     return n->mark(OSI_PROF_BN_FWD, st);
 }
+
+// The projection shortcut of block k only depends on the block input: it runs beside the main branch where a side stream exists (own
+// BatchNorm scratch). launch(stream, BatchNorm scratch offset) enqueues it; *forked: the main branch calls shortcut_wait before it reads
+// the shortcut. An identity block launches nothing.
+extern "C++" template <class Launch>
+static int shortcut_beside(osi_resnet50* n, const Block& k, hipStream_t st, bool* forked, Launch launch) {
+    *forked = k.ds >= 0 && n->fwd_fork && n->async_wgrad();
+    if (k.ds < 0) return OSI_OK;
+    if (*forked) OSI_TRY(n->fork_side(st));
+    OSI_TRY(launch(*forked ? n->side : st, *forked ? n->bn_ws2 : n->bn_ws));
+    if (*forked && hipEventRecord(n->ev_join, n->side) != hipSuccess) return OSI_ERR_LAUNCH;
+    return OSI_OK;
+}
+static int shortcut_wait(osi_resnet50* n, bool forked, hipStream_t st) {
+    return forked && hipStreamWaitEvent(st, n->ev_join, 0) != hipSuccess ? OSI_ERR_LAUNCH : OSI_OK;
+}
+
+// One bottleneck in the inference form; it leaves the finished block output where the next block reads it.
 static int block_fwd_eval(osi_resnet50* n, Block& k, const float* params, float* ws, hipStream_t st) {
-    auto epi = [&](int ci, const float* res, int relu) {
-        const BN& b = n->bns[n->convs[ci].bn];
-        return osi_conv_epilogue{ws + b.scale, ws + b.shift, res, relu};
-    };
     const float* x = ws + k.x_in;
     Conv &c1 = n->convs[k.c1], &c2 = n->convs[k.c2], &c3 = n->convs[k.c3];
-    const bool fork = k.ds >= 0 && n->fwd_fork && n->async_wgrad();
-    if (k.ds >= 0) {            // the projection shortcut only depends on the block input: beside the main branch where a side stream exists
+    // conv `c` with its BatchNorm (+ residual) (+ ReLU) in the epilogue
+    auto conv = [&](Conv& c, const float* in, float* out, const float* res, int relu, hipStream_t s, size_t bn_ws_off) {
+        const BN& b = n->bns[c.bn];
+        const osi_conv_epilogue e{ws + b.scale, ws + b.shift, res, relu};
+        OSI_TRY(osi_conv_fwd_epilogue(&c.d, in, params + c.w_off, out, &e, ws + bn_ws_off, n->bn_ws_bytes, s));
+        return n->mark(OSI_PROF_CONV_FWD, s);
+    };
+    bool forked = false;
+    OSI_TRY(shortcut_beside(n, k, st, &forked, [&](hipStream_t s, size_t bn_ws_off) {
         Conv& cd = n->convs[k.ds];
-        hipStream_t ds_st = st;
-        if (fork) {
-            OSI_TRY(n->fork_side(st));
-            ds_st = n->side;
-        }
-        const osi_conv_epilogue e = epi(k.ds, nullptr, 0);
-        OSI_TRY(osi_conv_fwd_epilogue(&cd.d, x, params + cd.w_off, ws + cd.y, &e, ws + (fork ? n->bn_ws2 : n->bn_ws), n->bn_ws_bytes, ds_st));
-        OSI_TRY(n->mark(OSI_PROF_CONV_FWD, ds_st));
-        if (fork && hipEventRecord(n->ev_join, n->side) != hipSuccess) return OSI_ERR_LAUNCH;
-    }
-    {
-        const osi_conv_epilogue e = epi(k.c1, nullptr, 1);
-        OSI_TRY(osi_conv_fwd_epilogue(&c1.d, x, params + c1.w_off, ws + c1.y, &e, ws + n->bn_ws, n->bn_ws_bytes, st));
+        return conv(cd, x, ws + cd.y, nullptr, 0, s, bn_ws_off);
+    }));
+    OSI_TRY(conv(c1, x, ws + c1.y, nullptr, 1, st, n->bn_ws));
+    if (n->plan_knobs.fwd_wino && c2.u_fw != WS_NONE) {     // 3x3 / stride 1: Winograd F(2x2,3x3)
+        const BN& b2 = n->bns[c2.bn];
+        const osi_conv_epilogue e{ws + b2.scale, ws + b2.shift, nullptr, 1};
+        OSI_TRY(n->wait_weight_transforms(st));
+        OSI_TRY(osi_conv_fwd_wino_epilogue_pre(&c2.d, ws + c1.y, ws + c2.u_fw, ws + c2.y, &e, ws + n->wino_ws, n->wino_ws_bytes, st));
         OSI_TRY(n->mark(OSI_PROF_CONV_FWD, st));
+    } else {
+        OSI_TRY(conv(c2, ws + c1.y, ws + c2.y, nullptr, 1, st, n->bn_ws));
     }
-    {
-        const osi_conv_epilogue e = epi(k.c2, nullptr, 1);
-        if (n->plan_knobs.fwd_wino && c2.u_fw != (size_t)-1) {     // 3x3 / stride 1: Winograd F(2x2,3x3)
-            OSI_TRY(n->wait_weight_transforms(st));
-            OSI_TRY(osi_conv_fwd_wino_epilogue_pre(&c2.d, ws + c1.y, ws + c2.u_fw, ws + c2.y, &e, ws + n->wino_ws, n->wino_ws_bytes, st));
-        } else {
-            OSI_TRY(osi_conv_fwd_epilogue(&c2.d, ws + c1.y, params + c2.w_off, ws + c2.y, &e, ws + n->bn_ws, n->bn_ws_bytes, st));
-        }
-        OSI_TRY(n->mark(OSI_PROF_CONV_FWD, st));
+    OSI_TRY(shortcut_wait(n, forked, st));
+    return conv(c3, ws + c2.y, ws + c3.a, k.ds >= 0 ? ws + n->convs[k.ds].y : x, 1, st, n->bn_ws);
+}
+
+// One bottleneck in the training topology. Only the block output (the residual sum) is materialised: conv2 / conv3 read the pre-BN output
+// of the conv before them and apply its BatchNorm + ReLU in their operand loader; the projection shortcut's BatchNorm is applied inside the
+// block-output kernel. 3 (4) convs + one block-output pass instead of 3 (4) convs + 3 (4) apply passes.
+static int block_fwd_train(osi_resnet50* n, Block& k, const float* params, float* buffers, float* ws, BnMode mode, hipStream_t st) {
+    const float* x = ws + k.x_in;
+    Conv &c1 = n->convs[k.c1], &c2 = n->convs[k.c2], &c3 = n->convs[k.c3];
+    bool forked = false;
+    OSI_TRY(shortcut_beside(n, k, st, &forked, [&](hipStream_t s, size_t bn_ws_off) {
+        return conv_bn_fwd(n, k.ds, params, buffers, ws, x, params + n->convs[k.ds].w_off, mode, s, bn_ws_off);
+    }));
+    OSI_TRY(conv_bn_fwd(n, k.c1, params, buffers, ws, x, params + c1.w_off, mode, st, n->bn_ws));
+    OSI_TRY(conv_bn_fwd(n, k.c2, params, buffers, ws, ws + c1.y, params + c2.w_off, mode, st, n->bn_ws, c1.bn));
+    OSI_TRY(conv_bn_fwd(n, k.c3, params, buffers, ws, ws + c2.y, params + c3.w_off, mode, st, n->bn_ws, c2.bn));
+    OSI_TRY(shortcut_wait(n, forked, st));
+    BN& b3 = n->bns[c3.bn];
+    if (k.ds >= 0) {
+        Conv& cd = n->convs[k.ds];
+        BN& bd = n->bns[cd.bn];
+        OSI_TRY(osi_bn_apply_relu_mask2(ws + c3.y, ws + b3.scale, ws + b3.shift, ws + cd.y, ws + bd.scale, ws + bd.shift, ws + c3.a,
+                                        ws + c3.mask, b3.M, b3.C, st));
+    } else {
+        OSI_TRY(osi_bn_apply_relu_mask(ws + c3.y, x, ws + b3.scale, ws + b3.shift, ws + c3.a, ws + c3.mask, b3.M, b3.C, st));
     }
-    if (fork && hipStreamWaitEvent(st, n->ev_join, 0) != hipSuccess) return OSI_ERR_LAUNCH;
-    {
-        const osi_conv_epilogue e = epi(k.c3, k.ds >= 0 ? ws + n->convs[k.ds].y : x, 1);
-        OSI_TRY(osi_conv_fwd_epilogue(&c3.d, ws + c2.y, params + c3.w_off, ws + c3.a, &e, ws + n->bn_ws, n->bn_ws_bytes, st));
-        OSI_TRY(n->mark(OSI_PROF_CONV_FWD, st));
-    }
-    return OSI_OK;
-}
-static int forward_eval_fused(osi_resnet50* n, const float* params, const float* buffers, float* ws, const float* x4, float* logits,
-                              float* features, hipStream_t st) {
-    OSI_TRY(eval_coeffs(n, params, buffers, ws, osi_resnet50::NUNITS, st));
-    OSI_TRY(stem_fwd_eval(n, ws, x4, st));
-    for (Block& k : n->blocks) OSI_TRY(block_fwd_eval(n, k, params, ws, st));
-    OSI_TRY(head_fwd(n, params, ws, logits, features, st));
-    n->any_fwd = false;           // no pre-BN tensors, bitmasks or arg-max decisions of a training forward remain (osi_resnet50_debug_gate)
-    OSI_TRY(n->mark(OSI_PROF_OTHER, st));
-    return OSI_OK;
+    return n->mark(OSI_PROF_BN_FWD, st);
 }
 
-static int forward_impl(osi_resnet50_t n, const float* params, float* buffers, long long* nbt, const float* image,
-                        void* workspace, float* logits, float* features, int training, osi_stream_t stream);
-
-int osi_resnet50_forward(osi_resnet50_t n, const float* params, float* buffers, long long* nbt, const float* image,
-                         void* workspace, float* logits, float* features, int training, osi_stream_t stream) {
-    OSI_REQUIRE(n && params && buffers && workspace && logits && features);
-    OSI_REQUIRE(!training || nbt);
-    return forward_impl(n, params, buffers, nbt, image, workspace, logits, features, training ? 1 : 0, stream);
-}
-
-// The training topology on the running statistics, differentiable: `buffers` are only read (mode 2 of forward_impl never passes them to a
-// kernel that writes), num_batches_tracked is not touched, and the backward that follows runs the frozen dataflow.
-int osi_resnet50_forward_frozen(osi_resnet50_t n, const float* params, const float* buffers, const float* image, void* workspace,
-                                float* logits, float* features, osi_stream_t stream) {
-    OSI_REQUIRE(n && params && buffers && workspace && logits && features);
-    return forward_impl(n, params, const_cast<float*>(buffers), nullptr, image, workspace, logits, features, 2, stream);
-}
-
-// training: 0 = inference, 1 = batch statistics + running-statistics update, 2 = frozen (running statistics, backward state kept)
-static int forward_impl(osi_resnet50_t n, const float* params, float* buffers, long long* nbt, const float* image,
-                        void* workspace, float* logits, float* features, int training, osi_stream_t stream) {
+static int forward_impl(osi_resnet50_t n, const float* params, float* buffers, long long* nbt, const float* image, void* workspace,
+                        float* logits, float* features, BnMode mode, osi_stream_t stream) {
     if (!n->plan_unchanged()) return OSI_ERR_STATE;   // a plan-relevant knob changed after create: the workspace no longer fits the plans
+    // input binding
     const float* ext = n->x4_ext;
     n->x4_ext = nullptr;
     if (!image && !ext && n->staged_ws != workspace) return OSI_ERR_STATE;   // image = NULL needs a staged or bound input
@@ -681,114 +745,56 @@ static int forward_impl(osi_resnet50_t n, const float* params, float* buffers, l
     n->x4_cur = x4;
     n->fwd_done = false;
     n->frozen = false;
-    // units [0, p) of a differentiable forward run the inference forms on the running statistics (an inference forward ignores it)
-    const int p = training ? n->eval_prefix : 0;
-    if (training && n->overlap && (!n->prof_on || n->prof_timeline)) OSI_TRY(n->ensure_side());
+    const bool differentiable = mode != BnMode::Inference;
+    // units [0, p) of a differentiable forward run the inference forms on the running statistics (an inference forward ignores the setting);
+    // units [0, ev) run them in this forward: all of them in an inference forward under option eval_fused
+    const int p = differentiable ? n->eval_prefix : 0;
+    const int ev = !differentiable && n->eval_fused ? osi_resnet50::NUNITS : p;
+    if (differentiable && n->wants_side()) OSI_TRY(n->ensure_side());
     OSI_TRY(n->mark(OSI_PROF_START, st));
-    // Winograd weight transforms of every 3x3 stride-1 layer, both directions: the weights are the same for this forward and its backward.
-    // On the side stream beside the stem (26 launches of 4 - 16 us that used to sit in front of their convolutions); the first Winograd
-    // convolution waits for them.
-    if (n->plan_knobs.fwd_wino || (training == 1 && n->plan_knobs.dgrad_wino)) {
-        // (training forwards only: an inference forward has 13 transforms and nothing but the stem beside them — the fork / join costs more
-        // than they do: 7.96 in line vs 8.00 ms aside per batch of 128, profiles/NOTES_r06.md)
-        const bool aside = training == 1 && n->async_wgrad();
-        hipStream_t wt = aside ? n->side : st;
-        if (aside) OSI_TRY(n->fork_side(st));
-        for (auto& c : n->convs)
-            if (n->plan_knobs.fwd_wino && c.u_fw != (size_t)-1)
-                OSI_TRY(osi_conv_wino_transform_weights(&c.d, params + c.w_off, 0, ws + c.u_fw, osi_conv_wino_weights_bytes(&c.d), wt));
-        OSI_TRY(n->mark(OSI_PROF_CONV_FWD, wt));
-        if (training == 1 && n->plan_knobs.dgrad_wino) {   // (a frozen backward has no Winograd input gradient)
-            int nt = 0;      // (no backward ever reaches the inference-form prefix)
-            for (auto& c : n->convs)
-                if (c.u_bw != (size_t)-1 && c.unit >= p) {
-                    OSI_TRY(osi_conv_wino_transform_weights(&c.d, params + c.w_off, 1, ws + c.u_bw, osi_conv_wino_weights_bytes(&c.d), wt));
-                    ++nt;
-                }
-            if (nt) OSI_TRY(n->mark(OSI_PROF_CONV_DGRAD, wt));
-        }
-        if (aside) {
-            if (hipEventRecord(n->ev_wt, n->side) != hipSuccess) return OSI_ERR_LAUNCH;
-            n->wt_pending = true;
-        }
-    }
-    // stem
+    OSI_TRY(transform_weights(n, params, ws, mode, p, st));
+    // stem: input layout, packed weights, every coefficient set that exists up front, conv1 + bn1 + relu + maxpool
     if (image) OSI_TRY(osi_nchw3_to_nhwc4(image, ws + n->x4, n->B, n->H, n->W, st));
-    Conv& c0 = n->convs[0];
-    OSI_TRY(osi_stem_weight_pack(params + c0.w_off, ws + n->wpack, 64, st));
+    OSI_TRY(osi_stem_weight_pack(params + n->convs[0].w_off, ws + n->wpack, 64, st));
     OSI_TRY(n->mark(OSI_PROF_OTHER, st));
-    if (!training && n->eval_fused) return forward_eval_fused(n, params, buffers, ws, x4, logits, features, st);
-    if (p > 0) OSI_TRY(eval_coeffs(n, params, buffers, ws, p, st));
-    if (training == 2) {      // frozen: every BatchNorm's scale / shift (forward) and mean / invstd (backward) from ONE launch
-        osi_bn_frozen_layer tab[OSI_BN_FROZEN_MAX];
-        int nb = 0;
-        for (const BN& b : n->bns) {
-            if (b.unit < p) continue;
-            if (nb == OSI_BN_FROZEN_MAX) return OSI_ERR_STATE;
-            tab[nb++] = osi_bn_frozen_layer{buffers + b.rm_off, buffers + b.rv_off, params + b.g_off, params + b.b_off, ws + b.scale, ws + b.shift,
-                                            ws + b.mean, ws + b.invstd, b.C};
-        }
-        if (nb) {
-            OSI_TRY(osi_bn_frozen_coeffs_multi(tab, nb, 1e-5f, st));
-            OSI_TRY(n->mark(OSI_PROF_BN_FWD, st));
-        }
-    }
-    if (p > 0) {
-        OSI_TRY(stem_fwd_eval(n, ws, x4, st));
-    } else {
-    OSI_TRY(conv_bn_fwd(n, 0, params, buffers, ws, x4, ws + n->wpack, training, st, n->bn_ws));
-    BN& b0 = n->bns[c0.bn];
-    // bn1 + relu + maxpool in one pass: the 112x112x64 post-ReLU tensor is never materialised
-    OSI_TRY(osi_bn_relu_maxpool_fwd(ws + c0.y, ws + b0.scale, ws + b0.shift, ws + n->a_pool, ws + n->pool_idx, n->B, n->Hs, n->Ws, 64, st));
-    OSI_TRY(n->mark(OSI_PROF_BN_FWD, st));
-    }
-    // bottleneck blocks. Only the block outputs (residual sums) are materialised: conv2 / conv3 read the pre-BN output of the conv
-    // before them and apply its BatchNorm + ReLU in their operand loader; the projection shortcut's BatchNorm is applied inside the
-    // block-output kernel. Per block: 3 (4) convs + one block-output pass instead of 3 (4) convs + 3 (4) apply passes.
+    if (ev > 0) OSI_TRY(eval_coeffs(n, params, buffers, ws, ev, st));
+    if (mode == BnMode::Frozen) OSI_TRY(frozen_coeffs(n, params, buffers, ws, p, st));
+    OSI_TRY(stem_fwd(n, params, buffers, ws, x4, mode, ev > 0, st));
+    // bottleneck blocks
     for (Block& k : n->blocks) {
-        if (n->convs[k.c1].unit < p) {      // frozen prefix: the inference form; it leaves the finished block output where the next block reads it
-            OSI_TRY(block_fwd_eval(n, k, params, ws, st));
-            continue;
-        }
-        const float* x = ws + k.x_in;
-        const bool fork = k.ds >= 0 && n->fwd_fork && n->async_wgrad();
-        if (k.ds >= 0) {            // the projection shortcut only depends on the block input: beside the main branch (own BN scratch)
-            Conv& c = n->convs[k.ds];
-            if (fork) OSI_TRY(n->fork_side(st));
-            OSI_TRY(conv_bn_fwd(n, k.ds, params, buffers, ws, x, params + c.w_off, training, fork ? n->side : st, fork ? n->bn_ws2 : n->bn_ws));
-            if (fork && hipEventRecord(n->ev_join, n->side) != hipSuccess) return OSI_ERR_LAUNCH;
-        }
-        Conv &c1 = n->convs[k.c1], &c2 = n->convs[k.c2], &c3 = n->convs[k.c3];
-        OSI_TRY(conv_bn_fwd(n, k.c1, params, buffers, ws, x, params + c1.w_off, training, st, n->bn_ws));
-        OSI_TRY(conv_bn_fwd(n, k.c2, params, buffers, ws, ws + c1.y, params + c2.w_off, training, st, n->bn_ws, c1.bn));
-        OSI_TRY(conv_bn_fwd(n, k.c3, params, buffers, ws, ws + c2.y, params + c3.w_off, training, st, n->bn_ws, c2.bn));
-        if (fork && hipStreamWaitEvent(st, n->ev_join, 0) != hipSuccess) return OSI_ERR_LAUNCH;
-        BN& b3 = n->bns[c3.bn];
-        if (k.ds >= 0) {
-            Conv& cd = n->convs[k.ds];
-            BN& bd = n->bns[cd.bn];
-            OSI_TRY(osi_bn_apply_relu_mask2(ws + c3.y, ws + b3.scale, ws + b3.shift, ws + cd.y, ws + bd.scale, ws + bd.shift, ws + c3.a,
-                                            ws + c3.mask, b3.M, b3.C, st));
-        } else {
-            OSI_TRY(osi_bn_apply_relu_mask(ws + c3.y, x, ws + b3.scale, ws + b3.shift, ws + c3.a, ws + c3.mask, b3.M, b3.C, st));
-        }
-        OSI_TRY(n->mark(OSI_PROF_BN_FWD, st));
+        if (n->convs[k.c1].unit < ev) OSI_TRY(block_fwd_eval(n, k, params, ws, st));
+        else OSI_TRY(block_fwd_train(n, k, params, buffers, ws, mode, st));
     }
     OSI_TRY(head_fwd(n, params, ws, logits, features, st));
-    n->any_fwd = true;
-    if (training) {
-        if (training == 1) {      // the BatchNorms that ran on batch statistics: those of units >= p, the tail of the forward-ordered table
-            int j0 = 0;
-            while (j0 < (int)n->bns.size() && n->bns[j0].unit < p) ++j0;
-            if (j0 < (int)n->bns.size()) OSI_TRY(osi_i64_add(nbt + j0, (int)n->bns.size() - j0, 1, st));
-        }
+    // state. An all-inference-form forward leaves no pre-BN tensors, bitmasks or arg-max decisions of a training forward (osi_resnet50_debug_gate)
+    n->any_fwd = ev < osi_resnet50::NUNITS;
+    if (mode == BnMode::Batch) {      // the BatchNorms that ran on batch statistics: those of units >= p, the tail of the forward-ordered table
+        int j0 = 0;
+        while (j0 < (int)n->bns.size() && n->bns[j0].unit < p) ++j0;
+        if (j0 < (int)n->bns.size()) OSI_TRY(osi_i64_add(nbt + j0, (int)n->bns.size() - j0, 1, st));
+    }
+    if (differentiable) {
         n->fw_prefix = p;
-        n->frozen = training == 2;
+        n->frozen = mode == BnMode::Frozen;
         n->fwd_done = true;
         n->next_stage = 0;
     }
-    OSI_TRY(n->mark(OSI_PROF_OTHER, st));
-    return OSI_OK;
+    return n->mark(OSI_PROF_OTHER, st);
+}
+
+int osi_resnet50_forward(osi_resnet50_t n, const float* params, float* buffers, long long* nbt, const float* image,
+                         void* workspace, float* logits, float* features, int training, osi_stream_t stream) {
+    OSI_REQUIRE(n && params && buffers && workspace && logits && features);
+    OSI_REQUIRE(!training || nbt);
+    return forward_impl(n, params, buffers, nbt, image, workspace, logits, features, training ? BnMode::Batch : BnMode::Inference, stream);
+}
+
+// The training topology on the running statistics, differentiable: `buffers` are only read (the frozen mode of forward_impl never passes them
+// to a kernel that writes), num_batches_tracked is not touched, and the backward that follows runs the frozen dataflow.
+int osi_resnet50_forward_frozen(osi_resnet50_t n, const float* params, const float* buffers, const float* image, void* workspace,
+                                float* logits, float* features, osi_stream_t stream) {
+    OSI_REQUIRE(n && params && buffers && workspace && logits && features);
+    return forward_impl(n, params, const_cast<float*>(buffers), nullptr, image, workspace, logits, features, BnMode::Frozen, stream);
 }
 
 // weight gradient of conv `ci` from dy (scratch buffer index gi): on the side stream when overlap is on
@@ -829,8 +835,7 @@ static int wgrad_launch(osi_resnet50* n, int ci, float* grads, float* ws, int gi
 }
 
 static int wgrad(osi_resnet50* n, int ci, float* grads, float* ws, int gi, const float* conv_in, hipStream_t st, int in_bn = -1) {
-    if (!n->bw_pg) return OSI_OK;      // input-only backward: no weight gradient of any kind
-    if (!n->trainable(n->convs[ci].unit)) return OSI_OK;   // frozen unit: nobody reads its slice of the gradient arena
+    if (!n->wants_grads(n->convs[ci].unit)) return OSI_OK;   // input-only backward, or a frozen unit: no weight gradient of any kind
     return wgrad_launch(n, ci, grads, ws, gi, conv_in, st, in_bn, n->async_wgrad());
 }
 
@@ -840,16 +845,15 @@ static int dgrad_plain(osi_resnet50* n, const osi_conv_desc* d, const float* dy,
     return n->mark(OSI_PROF_CONV_DGRAD, st);
 }
 
-// backward of conv+BN(+ReLU mask): dout (in scratch buffer gi) -> dy in place, then wgrad; returns with dy still in the buffer
-static int bn_conv_wgrad(osi_resnet50* n, int ci, const float* params, float* grads, float* ws, int gi,
-                         float* gmasked, const float* conv_in, hipStream_t st) {
+// BatchNorm backward of conv `ci` from a RAW block-output gradient in buffer gi: gated by the stored bitmask here, dy in place, the gated
+// gradient itself (it continues down the identity shortcut) into buffer `gmasked`
+static int bn_bwd_raw(osi_resnet50* n, int ci, const float* params, float* grads, float* ws, int gi, int gmasked, hipStream_t st) {
     Conv& c = n->convs[ci];
     BN& b = n->bns[c.bn];
     float* g = ws + n->scratch[gi];
-    OSI_TRY(osi_bn_backward_relu_mask(g, ws + c.mask, ws + c.y, ws + b.mean, ws + b.invstd, params + b.g_off, g, gmasked,
+    OSI_TRY(osi_bn_backward_relu_mask(g, ws + c.mask, ws + c.y, ws + b.mean, ws + b.invstd, params + b.g_off, g, ws + n->scratch[gmasked],
                                       n->dgam(grads, ws, b), n->dbet(grads, ws, b), b.M, b.C, ws + n->bn_ws, n->bn_ws_bytes, st));
-    OSI_TRY(n->mark(OSI_PROF_BN_BWD, st));
-    return wgrad(n, ci, grads, ws, gi, conv_in, st);
+    return n->mark(OSI_PROF_BN_BWD, st);
 }
 
 // BatchNorm backward of conv `ci` from a gradient buffer that the producing dgrad epilogue already ReLU-masked, with the
@@ -858,42 +862,39 @@ static int bn_bwd_fused(osi_resnet50* n, int ci, const float* params, float* gra
                         hipStream_t st) {
     Conv& c = n->convs[ci];
     BN& b = n->bns[c.bn];
-    const float* psum_g = ws + n->dg_ws;
-    const float* psum_gx = psum_g + (size_t)(1 + which) * n->fused_P * b.C;
-    OSI_TRY(osi_bn_backward_fused(ws + n->scratch[gi], ws + c.y, ws + b.mean, ws + b.invstd, params + b.g_off, psum_g, psum_gx,
-                                  n->fused_P, ws + n->scratch[dyi], n->dgam(grads, ws, b), n->dbet(grads, ws, b), b.M, b.C, ws + n->bn_ws,
-                                  n->bn_ws_bytes, st));
-    OSI_TRY(n->mark(OSI_PROF_BN_BWD, st));
-    return OSI_OK;
+    const int P = n->fused_P;
+    OSI_TRY(osi_bn_backward_fused(ws + n->scratch[gi], ws + c.y, ws + b.mean, ws + b.invstd, params + b.g_off, n->dg_col(ws, 0, P, b.C),
+                                  n->dg_col(ws, 1 + which, P, b.C), P, ws + n->scratch[dyi], n->dgam(grads, ws, b), n->dbet(grads, ws, b),
+                                  b.M, b.C, ws + n->bn_ws, n->bn_ws_bytes, st));
+    return n->mark(OSI_PROF_BN_BWD, st);
 }
 
 // The same for the two BatchNorms of a projection block in one pass over the gated gradient in buffer gi: conv `ci` (bn3, column 0 of
 // dg_ws) -> buffer dyi, conv `cj` (the shortcut, column 1) -> buffer dyj. Every result is the one of the two bn_bwd_fused calls.
 static int bn_bwd_fused_pair(osi_resnet50* n, int ci, int cj, const float* params, float* grads, float* ws, int gi, int dyi, int dyj,
                              hipStream_t st) {
-    const float* psum_g = ws + n->dg_ws;
     osi_bn_fused_consumer cs[2];
     const int idx[2] = {ci, cj}, out[2] = {dyi, dyj};
     for (int k = 0; k < 2; ++k) {
         Conv& c = n->convs[idx[k]];
         BN& b = n->bns[c.bn];
-        cs[k] = osi_bn_fused_consumer{ws + c.y, ws + b.mean, ws + b.invstd, params + b.g_off, psum_g + (size_t)(1 + k) * n->fused_P * b.C,
+        cs[k] = osi_bn_fused_consumer{ws + c.y, ws + b.mean, ws + b.invstd, params + b.g_off, n->dg_col(ws, 1 + k, n->fused_P, b.C),
                                       ws + n->scratch[out[k]], n->dgam(grads, ws, b), n->dbet(grads, ws, b)};
     }
     BN& b = n->bns[n->convs[ci].bn];
-    OSI_TRY(osi_bn_backward_fused2(ws + n->scratch[gi], cs, psum_g, n->fused_P, b.M, b.C, ws + n->bn_ws, n->bn_ws_bytes, st));
+    OSI_TRY(osi_bn_backward_fused2(ws + n->scratch[gi], cs, n->dg_col(ws, 0, n->fused_P, b.C), n->fused_P, b.M, b.C, ws + n->bn_ws,
+                                   n->bn_ws_bytes, st));
     return n->mark(OSI_PROF_BN_BWD, st);
 }
 
 // Frozen statistics. Finish the dgamma / dbeta of conv `ci`'s BatchNorm from the row-tile partials a dgrad epilogue left in dg_ws (column
 // `which` as in bn_bwd_fused). Nothing is launched in an input-only backward.
 static int bn_reduce_frozen(osi_resnet50* n, int ci, float* grads, float* ws, int which, hipStream_t st) {
-    if (!n->bw_pg) return OSI_OK;
     BN& b = n->bns[n->convs[ci].bn];
-    if (!n->trainable(b.unit)) return OSI_OK;    // parameter-only reduction of a frozen unit
-    const float* psum_g = ws + n->dg_ws;
-    const float* psum_gx = psum_g + (size_t)(1 + which) * n->fused_P * b.C;
-    OSI_TRY(osi_bn_backward_reduce(psum_g, psum_gx, n->fused_P, grads + b.g_off, grads + b.b_off, b.M, b.C, ws + n->bn_ws, n->bn_ws_bytes, st));
+    if (!n->wants_grads(b.unit)) return OSI_OK;    // parameter-only reduction: input-only backward, or a frozen unit
+    const int P = n->fused_P;
+    OSI_TRY(osi_bn_backward_reduce(n->dg_col(ws, 0, P, b.C), n->dg_col(ws, 1 + which, P, b.C), P, grads + b.g_off, grads + b.b_off, b.M, b.C,
+                                   ws + n->bn_ws, n->bn_ws_bytes, st));
     return n->mark(OSI_PROF_BN_BWD, st);
 }
 // Frozen statistics. BatchNorm backward of conv `ci` (and `cj` >= 0, the projection shortcut: same gated gradient) from buffer gi:
@@ -907,7 +908,7 @@ static int bn_bwd_frozen(osi_resnet50* n, int ci, int cj, float* grads, float* w
     for (int k = 0; k < nc; ++k) {
         Conv& c = n->convs[idx[k]];
         BN& b = n->bns[c.bn];
-        const bool red = masked && n->bw_pg && n->trainable(b.unit);
+        const bool red = masked && n->wants_grads(b.unit);
         cs[k] = osi_bn_frozen_consumer{ws + c.y, ws + b.mean, ws + b.invstd, ws + b.scale, ws + n->scratch[out[k]],
                                        red ? grads + b.g_off : nullptr, red ? grads + b.b_off : nullptr};
     }
@@ -944,7 +945,7 @@ static int dgrad_fused(osi_resnet50* n, int ci, const float* params, float* ws, 
     Conv& p0 = n->convs[pc];
     BN& b0 = n->bns[p0.bn];
     osi_dgrad_fusion f{};
-    if (p0.mask != (size_t)-1) f.relu_mask = ws + p0.mask;           // block output: stored ReLU bitmask
+    if (p0.mask != WS_NONE) f.relu_mask = ws + p0.mask;           // block output: stored ReLU bitmask
     else { f.scale0 = ws + b0.scale; f.shift0 = ws + b0.shift; }     // in-block activation: gate recomputed from y0
     f.y0 = ws + p0.y; f.mean0 = ws + b0.mean; f.invstd0 = ws + b0.invstd;
     if (pd >= 0) {
@@ -957,7 +958,7 @@ static int dgrad_fused(osi_resnet50* n, int ci, const float* params, float* ws, 
     int P = 0;
     // the in-block 3x3 / stride 1 input gradients (gate recomputed, one consumer, no addend) take the Winograd form
     OSI_TRY(n->wait_weight_transforms(st));   // (forward Winograd off: nobody has waited for the side-stream weight transforms yet)
-    if (n->plan_knobs.dgrad_wino && f.scale0 && pd < 0 && addi < 0 && c.u_bw != (size_t)-1)
+    if (n->plan_knobs.dgrad_wino && f.scale0 && pd < 0 && addi < 0 && c.u_bw != WS_NONE)
         OSI_TRY(osi_conv_dgrad_fused_wino_pre(&c.d, ws + n->scratch[dyi], ws + c.u_bw, ws + n->scratch[dxi], &f, ws + n->wino_ws,
                                               n->wino_ws_bytes, &P, st));
     else
@@ -967,122 +968,63 @@ static int dgrad_fused(osi_resnet50* n, int ci, const float* params, float* ws, 
     return n->mark(OSI_PROF_CONV_DGRAD, st);
 }
 
-// One bottleneck block of the backward pass. On entry n->cur_grad holds the gradient w.r.t. the block output: raw (stage entry
-// from the average pool) or, when n->go_fused, already masked by the block's final ReLU with the bn3 / downsample-BN reductions
-// in dg_ws (left there by the conv1 dgrad epilogue of the block above).
-// no_dx: the block is the first trainable unit of a backward that stops at the cut: nothing below reads the gradient w.r.t. its
-// input, so the two launches that produce it (the shortcut's and conv1's input gradient) are left out and the gradient chain ends here.
-static int block_backward(osi_resnet50* n, int bi, const float* params, float* grads, float* ws, hipStream_t st, bool no_dx) {
-    Block& k = n->blocks[bi];
-    auto S = [&](int i) { return ws + n->scratch[i]; };
-    Conv &c1 = n->convs[k.c1], &c2 = n->convs[k.c2], &c3 = n->convs[k.c3];
-    const float* x = ws + k.x_in;
+// In-block step of the backward chain: input gradient of conv `ci` (dy in buffer dyi) into buffer dxi, then the BatchNorm backward of its
+// in-block producer `pc` in place, so that dxi holds dy of `pc`. Frozen statistics: both in the epilogue (dgrad_frozen).
+static int dgrad_bn_inblock(osi_resnet50* n, int ci, int pc, const float* params, float* grads, float* ws, int dyi, int dxi, hipStream_t st) {
+    if (n->frozen) return dgrad_frozen(n, ci, params, grads, ws, dyi, dxi, pc, st);
+    OSI_TRY(dgrad_fused(n, ci, params, ws, dyi, dxi, -1, pc, -1, st));
+    return bn_bwd_fused(n, pc, params, grads, ws, dxi, dxi, 0, st);
+}
+
+// Block backward, entry: the block-output gradient in n->cur_grad becomes *d3 (dy of bn3) and, for a projection block, *t1 (dy of the
+// shortcut's BatchNorm: both BatchNorms read the same gated gradient, one pass streams it once and writes both), for an identity block
+// *dxbase (the gated gradient itself continues to the block input). The gradient is gated already, its reductions in dg_ws
+// (n->go_fused, left by the conv1 dgrad epilogue of the block above), or raw (from the average pool), gated by the stored bitmask here.
+static int block_bwd_entry(osi_resnet50* n, const Block& k, const float* params, float* grads, float* ws, hipStream_t st, int* d3, int* t1,
+                           int* dxbase) {
+    const int go = n->cur_grad;
     const bool has_ds = k.ds >= 0;
-    // A stride-2 1x1 shortcut reaches only the even-even pixels of the block input: its input gradient writes just those (a quarter
-    // of the tensor, no zero fill) and conv1's input gradient, which completes the sum in place, reads the addend only there.
-    // bi == 0 keeps the dense form (pool mode).
-    const bool ds_sparse = has_ds && bi > 0 && n->convs[k.ds].d.stride == 2 && n->convs[k.ds].d.R == 1;
-    int go = n->cur_grad;
-    int d3 = -1, dxbase = -1;
-    if (n->frozen) {
-        // Frozen statistics: one pass turns the (gated) block-output gradient into dy of bn3 and of the shortcut's BatchNorm
-        int t1 = -1;
-        if (has_ds) { t1 = n->take(st); if (t1 < 0) return t1; }
-        if (n->go_fused) {          // already gated, reductions in dg_ws
-            OSI_TRY(bn_reduce_frozen(n, k.c3, grads, ws, 0, st));
-            if (has_ds) OSI_TRY(bn_reduce_frozen(n, k.ds, grads, ws, 1, st));
-            d3 = n->take(st);
-            if (d3 < 0) return d3;
-            OSI_TRY(bn_bwd_frozen(n, k.c3, k.ds, grads, ws, go, d3, t1, -1, false, st));
-            if (has_ds) n->give(go);
-            else dxbase = go;       // identity skip: the gated gradient itself continues to the block input
-        } else {                    // stage entry: raw gradient, gated by the stored bitmask here
-            if (!has_ds) { dxbase = n->take(st); if (dxbase < 0) return dxbase; }
-            OSI_TRY(bn_bwd_frozen(n, k.c3, k.ds, grads, ws, go, go, t1, has_ds ? -1 : dxbase, true, st));
-            d3 = go;
-        }
-        if (has_ds) {
-            Conv& cd = n->convs[k.ds];
-            OSI_TRY(wgrad(n, k.ds, grads, ws, t1, x, st));
-            if (!no_dx) {
-                dxbase = n->take(st);
-                if (dxbase < 0) return dxbase;
-                OSI_TRY(dgrad_plain(n, &cd.d, S(t1), params + cd.w_off, S(dxbase), ds_sparse ? 2 : 0, st));
-            }
-            n->give(t1);
-        }
-    } else if (n->go_fused) {
-        if (has_ds) {
-            // projection block: bn3 and the shortcut's BatchNorm read the same gated gradient — one pass streams it once and writes both
-            // dy tensors (four buffers live at once, as in the frozen dataflow above); the weight gradients keep their side-stream order
-            Conv& cd = n->convs[k.ds];
-            int t1 = n->take(st);
-            if (t1 < 0) return t1;
-            d3 = n->take(st);
-            if (d3 < 0) return d3;
-            OSI_TRY(bn_bwd_fused_pair(n, k.c3, k.ds, params, grads, ws, go, d3, t1, st));
-            n->give(go);
-            OSI_TRY(wgrad(n, k.ds, grads, ws, t1, x, st));
-            if (!no_dx) {
-                dxbase = n->take(st);
-                if (dxbase < 0) return dxbase;
-                OSI_TRY(dgrad_plain(n, &cd.d, S(t1), params + cd.w_off, S(dxbase), ds_sparse ? 2 : 0, st));
-            }
-            n->give(t1);
-        } else {
-            d3 = n->take(st);
-            if (d3 < 0) return d3;
-            OSI_TRY(bn_bwd_fused(n, k.c3, params, grads, ws, go, d3, 0, st));
-            dxbase = go;           // identity skip: the masked gradient itself continues to the block input
-        }
-    } else {
-        dxbase = n->take(st);
-        if (dxbase < 0) return dxbase;
-        if (has_ds) {
-            Conv& cd = n->convs[k.ds];
-            BN& bd = n->bns[cd.bn];
-            int t1 = n->take(st);
-            if (t1 < 0) return t1;
-            OSI_TRY(osi_bn_backward_relu_mask(S(go), ws + c3.mask, ws + cd.y, ws + bd.mean, ws + bd.invstd, params + bd.g_off,
-                                              S(t1), nullptr, n->dgam(grads, ws, bd), n->dbet(grads, ws, bd), bd.M, bd.C, ws + n->bn_ws,
-                                              n->bn_ws_bytes, st));
-            OSI_TRY(n->mark(OSI_PROF_BN_BWD, st));
-            OSI_TRY(wgrad(n, k.ds, grads, ws, t1, x, st));
-            if (!no_dx) OSI_TRY(dgrad_plain(n, &cd.d, S(t1), params + cd.w_off, S(dxbase), ds_sparse ? 2 : 0, st));
-            n->give(t1);
-        }
-        BN& b3 = n->bns[c3.bn];
-        OSI_TRY(osi_bn_backward_relu_mask(S(go), ws + c3.mask, ws + c3.y, ws + b3.mean, ws + b3.invstd, params + b3.g_off, S(go),
-                                          has_ds ? nullptr : S(dxbase), n->dgam(grads, ws, b3), n->dbet(grads, ws, b3), b3.M, b3.C,
-                                          ws + n->bn_ws, n->bn_ws_bytes, st));
-        OSI_TRY(n->mark(OSI_PROF_BN_BWD, st));
-        d3 = go;
+    if (!n->go_fused) {
+        // A raw gradient reaches a block in one place only, the stage-0 entry from the average pool, and the block it reaches is the last
+        // one (layer4.2), an identity block: every block with bi > 0 hands a gated gradient down (go_fused survives stage boundaries), and
+        // where the chain ends earlier (no_dx, block 0) no block follows. A raw gradient at a projection block is a broken invariant.
+        if (has_ds) return OSI_ERR_STATE;
+        OSI_TRY(n->take(st, dxbase));
+        if (n->frozen) OSI_TRY(bn_bwd_frozen(n, k.c3, -1, grads, ws, go, go, -1, *dxbase, true, st));
+        else OSI_TRY(bn_bwd_raw(n, k.c3, params, grads, ws, go, *dxbase, st));
+        *d3 = go;
+        return OSI_OK;
     }
-    // conv3 -> (mask a2, bn2) -> conv2 -> (mask a1, bn1) -> conv1
-    OSI_TRY(wgrad(n, k.c3, grads, ws, d3, ws + c2.y, st, c2.bn));
-    int t2 = n->take(st);
-    if (t2 < 0) return t2;
-    if (n->frozen) OSI_TRY(dgrad_frozen(n, k.c3, params, grads, ws, d3, t2, k.c2, st));
-    else OSI_TRY(dgrad_fused(n, k.c3, params, ws, d3, t2, -1, k.c2, -1, st));
-    n->give(d3);
-    if (!n->frozen) OSI_TRY(bn_bwd_fused(n, k.c2, params, grads, ws, t2, t2, 0, st));
-    OSI_TRY(wgrad(n, k.c2, grads, ws, t2, ws + c1.y, st, c1.bn));
-    int t3 = n->take(st);
-    if (t3 < 0) return t3;
-    if (n->frozen) OSI_TRY(dgrad_frozen(n, k.c2, params, grads, ws, t2, t3, k.c1, st));
-    else OSI_TRY(dgrad_fused(n, k.c2, params, ws, t2, t3, -1, k.c1, -1, st));
-    n->give(t2);
-    if (!n->frozen) OSI_TRY(bn_bwd_fused(n, k.c1, params, grads, ws, t3, t3, 0, st));
-    OSI_TRY(wgrad(n, k.c1, grads, ws, t3, x, st));
+    if (has_ds) OSI_TRY(n->take(st, t1));
+    if (n->frozen) {            // parameter-only reductions; dy = scale * g needs none
+        OSI_TRY(bn_reduce_frozen(n, k.c3, grads, ws, 0, st));
+        if (has_ds) OSI_TRY(bn_reduce_frozen(n, k.ds, grads, ws, 1, st));
+    }
+    OSI_TRY(n->take(st, d3));
+    if (n->frozen) OSI_TRY(bn_bwd_frozen(n, k.c3, k.ds, grads, ws, go, *d3, *t1, -1, false, st));
+    else if (has_ds) OSI_TRY(bn_bwd_fused_pair(n, k.c3, k.ds, params, grads, ws, go, *d3, *t1, st));
+    else OSI_TRY(bn_bwd_fused(n, k.c3, params, grads, ws, go, *d3, 0, st));
+    if (has_ds) n->give(go);
+    else *dxbase = go;
+    return OSI_OK;
+}
+
+// Block backward, exit: conv1's input gradient (dy in buffer t3) completes the gradient w.r.t. the block input on top of `dxbase` (the
+// shortcut's share) and leaves it in n->cur_grad for the block below.
+static int block_bwd_exit(osi_resnet50* n, int bi, const float* params, float* ws, hipStream_t st, int t3, int dxbase, bool no_dx,
+                          bool ds_sparse) {
+    const Block& k = n->blocks[bi];
+    Conv& c1 = n->convs[k.c1];
+    auto S = [&](int i) { return ws + n->scratch[i]; };
     if (no_dx) {                   // the chain ends: no launch, the buffers go back
         if (dxbase >= 0) n->give(dxbase);
         n->cur_grad = -1;
         n->go_fused = false;
     } else if (bi > 0) {
         // the block input is the previous block's output: fuse that block's final ReLU mask and its bn3 (+ downsample BN) reductions
-        Block& pk = n->blocks[bi - 1];
-        int dxn = has_ds ? dxbase : n->take(st);   // downsample case: add in place (each lane reads then writes its own element)
-        if (dxn < 0) return dxn;
+        const Block& pk = n->blocks[bi - 1];
+        int dxn = dxbase;          // downsample case: add in place (each lane reads then writes its own element)
+        if (k.ds < 0) OSI_TRY(n->take(st, &dxn));
         OSI_TRY(dgrad_fused(n, k.c1, params, ws, t3, dxn, dxbase, pk.c3, pk.ds, st, ds_sparse));
         if (dxn != dxbase) n->give(dxbase);
         n->cur_grad = dxn;
@@ -1091,9 +1033,9 @@ static int block_backward(osi_resnet50* n, int bi, const float* params, float* g
         // first block: its input is the stem's max-pooled activation. With the fused stem tail the epilogue of this LAST input gradient
         // (it completes the gradient w.r.t. the pooled activation) also emits bn1's backward reductions through the arg-max bytes, so the
         // stem needs no reduction pass over its 112 x 112 tensor (pool mode of osi_conv_dgrad_fused)
-        Conv& c0 = n->convs[0];
         // (not when this backward also writes dJ/dimage: the stem tail then materialises dY and reduces bn1 itself)
         if (n->stem_tail_fused()) {
+            Conv& c0 = n->convs[0];
             BN& b0 = n->bns[c0.bn];
             osi_dgrad_fusion f{};
             f.y0 = ws + c0.y; f.mean0 = ws + b0.mean; f.invstd0 = ws + b0.invstd;
@@ -1109,7 +1051,162 @@ static int block_backward(osi_resnet50* n, int bi, const float* params, float* g
         n->cur_grad = dxbase;
         n->go_fused = false;
     }
+    return OSI_OK;
+}
+
+// One bottleneck block of the backward pass: entry, shortcut, chain, exit.
+// no_dx: the block is the first trainable unit of a backward that stops at the cut: nothing below reads the gradient w.r.t. its
+// input, so the two launches that produce it (the shortcut's and conv1's input gradient) are left out and the gradient chain ends here.
+// The order of take / give is part of the schedule (FIFO free list: it decides which buffer a launch gets and which reader event it
+// waits for): projection block t1, d3, dxbase; identity block d3 (gated) or dxbase (raw); then t2, t3 and the exit's buffer.
+static int block_backward(osi_resnet50* n, int bi, const float* params, float* grads, float* ws, hipStream_t st, bool no_dx) {
+    const Block& k = n->blocks[bi];
+    Conv &c1 = n->convs[k.c1], &c2 = n->convs[k.c2];
+    const float* x = ws + k.x_in;
+    int d3 = -1, t1 = -1, dxbase = -1, t2 = -1, t3 = -1;
+    OSI_TRY(block_bwd_entry(n, k, params, grads, ws, st, &d3, &t1, &dxbase));
+    // A stride-2 1x1 shortcut reaches only the even-even pixels of the block input: its input gradient writes just those (a quarter
+    // of the tensor, no zero fill) and conv1's input gradient, which completes the sum in place, reads the addend only there.
+    // bi == 0 keeps the dense form (pool mode).
+    const bool ds_sparse = k.ds >= 0 && bi > 0 && n->convs[k.ds].d.stride == 2 && n->convs[k.ds].d.R == 1;
+    if (k.ds >= 0) {               // shortcut: its weight gradient, and its share of the gradient w.r.t. the block input
+        Conv& cd = n->convs[k.ds];
+        OSI_TRY(wgrad(n, k.ds, grads, ws, t1, x, st));
+        if (!no_dx) {
+            OSI_TRY(n->take(st, &dxbase));
+            OSI_TRY(dgrad_plain(n, &cd.d, ws + n->scratch[t1], params + cd.w_off, ws + n->scratch[dxbase], ds_sparse ? 2 : 0, st));
+        }
+        n->give(t1);
+    }
+    // chain: conv3 -> (mask a2, bn2) -> conv2 -> (mask a1, bn1) -> conv1
+    OSI_TRY(wgrad(n, k.c3, grads, ws, d3, ws + c2.y, st, c2.bn));
+    OSI_TRY(n->take(st, &t2));
+    OSI_TRY(dgrad_bn_inblock(n, k.c3, k.c2, params, grads, ws, d3, t2, st));
+    n->give(d3);
+    OSI_TRY(wgrad(n, k.c2, grads, ws, t2, ws + c1.y, st, c1.bn));
+    OSI_TRY(n->take(st, &t3));
+    OSI_TRY(dgrad_bn_inblock(n, k.c2, k.c1, params, grads, ws, t2, t3, st));
+    n->give(t2);
+    OSI_TRY(wgrad(n, k.c1, grads, ws, t3, x, st));
+    OSI_TRY(block_bwd_exit(n, bi, params, ws, st, t3, dxbase, no_dx, ds_sparse));
     n->give(t3);
+    return OSI_OK;
+}
+
+// Stage 0 opens the backward: logits -> fc -> average pool. Leaves the raw gradient w.r.t. the last block's output in n->cur_grad
+// (-1 when the backward stops at the head: nobody below reads the gradient w.r.t. the pooled features).
+static int head_backward(osi_resnet50* n, const float* params, float* grads, float* ws, const float* dlogits, const float* dfeatures,
+                         hipStream_t st) {
+    OSI_REQUIRE(dlogits);
+    const int head = osi_resnet50::NUNITS - 1;
+    n->free_list.clear();
+    for (int i = 0; i < osi_resnet50::NSCR; ++i) { n->free_list.push_back(i); n->buf_pending[i] = false; }
+    const Tensor& fw = n->tensors[n->t_fc_w]; const Tensor& fb = n->tensors[n->t_fc_b]; const Tensor& lw = n->tensors[n->t_lg_w];
+    float* dfeat = ws + n->dfeat;
+    int acc = 0;
+    if (dfeatures) {
+        if (hipMemcpyAsync(dfeat, dfeatures, (size_t)n->B * n->F * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+            return OSI_ERR_LAUNCH;
+        acc = 1;
+    }
+    const bool pg = n->wants_grads(head);
+    float* dlb = pg && n->t_lg_b >= 0 ? grads + n->tensors[n->t_lg_b].off : nullptr;
+    OSI_TRY(osi_linear_bwd(dlogits, ws + n->feat, params + lw.off, dfeat, acc, pg ? grads + lw.off : nullptr, dlb, n->B, n->F, n->O, st));
+    const bool below = n->bw_stop() < head;
+    OSI_TRY(osi_linear_bwd(dfeat, ws + n->pooled, params + fw.off, below ? ws + n->dpooled : nullptr, 0, pg ? grads + fw.off : nullptr,
+                           pg ? grads + fb.off : nullptr, n->B, 2048, n->F, st));
+    n->cur_grad = -1;
+    n->go_fused = false;
+    if (below) {
+        OSI_TRY(n->take(st, &n->cur_grad));
+        OSI_TRY(osi_avgpool_bwd(ws + n->dpooled, ws + n->scratch[n->cur_grad], n->B, n->Hf * n->Wf, 2048, st));
+    }
+    return n->mark(OSI_PROF_OTHER, st);
+}
+
+// The last stage closes the backward: max-pool + stem from the gradient w.r.t. the pooled activation in n->cur_grad.
+static int stem_tail(osi_resnet50* n, const float* params, float* grads, float* ws, hipStream_t st) {
+    auto S = [&](int i) { return ws + n->scratch[i]; };
+    Conv& c0 = n->convs[0];
+    BN& b0 = n->bns[c0.bn];
+    const BwRequest& rq = n->rq;
+    const int go = n->cur_grad;
+    int t = -1;
+    OSI_TRY(n->take(st, &t));
+    const float* x4c = n->x4_cur ? n->x4_cur : ws + n->x4;
+    if (n->stem_tail_fused()) {      // its own slab, sized at create: never the side stream's wg_ws
+        // reductions of bn1's backward (dgamma, dbeta) on the main stream: they arrived with block 0's last input gradient, two tiny
+        // merge launches. Then the weight gradient with the max-pool scatter, ReLU gate and BatchNorm backward applied inside its
+        // operand loader: the 112x112x64 gradient is never written
+        n->give(t);
+        const int P = n->stem_stats_P;
+        OSI_TRY(osi_bn_backward_reduce(n->dg_col(ws, 0, P, 64), n->dg_col(ws, 1, P, 64), P, grads + b0.g_off, grads + b0.b_off,
+                                       n->B * n->Hs * n->Ws, 64, ws + n->bn_ws, n->bn_ws_bytes, st));
+        OSI_TRY(n->mark(OSI_PROF_BN_BWD, st));
+        // the stem's weight gradient is the last kernel of the step; on the MAIN stream it runs beside the side stream's
+        // backlog (layer1's weight gradients) instead of behind it
+        OSI_TRY(osi_stem_wgrad_fused(&c0.d, S(go), ws + n->pool_idx, ws + c0.y, x4c, params + b0.g_off, ws + b0.mean, ws + b0.invstd,
+                                     grads + b0.g_off, grads + b0.b_off, grads + c0.w_off, ws + n->stem_ws, n->stem_ws_bytes, st));
+        OSI_TRY(n->mark(OSI_PROF_CONV_WGRAD, st));
+        n->give(go);
+        return OSI_OK;
+    }
+    // dJ/dimage (or the adversarial batch) wanted, or a geometry the fused form does not take: the stem's dY is materialised (max-pool
+    // scatter + ReLU gate + bn1 backward gathered on the fly from the pooled gradient into a scratch buffer), its weight gradient comes
+    // from that dY unless input-only, then — for dJ/dimage — the stem's input gradient straight into the caller's NCHW tensor
+    if (n->frozen) {   // frozen statistics: dY = scale * (scattered, gated gradient); reductions only for the parameter gradients
+        const bool red = n->wants_grads(0);
+        OSI_TRY(osi_bn_relu_maxpool_bwd_frozen(S(go), ws + n->pool_idx, ws + c0.y, ws + b0.mean, ws + b0.invstd, ws + b0.scale, S(t),
+                                               red ? grads + b0.g_off : nullptr, red ? grads + b0.b_off : nullptr, n->B, n->Hs, n->Ws, 64,
+                                               ws + n->bn_ws, n->bn_ws_bytes, st));
+    } else {
+        OSI_TRY(osi_bn_relu_maxpool_bwd(S(go), ws + n->pool_idx, ws + c0.y, ws + b0.mean, ws + b0.invstd, params + b0.g_off, S(t),
+                                        n->dgam(grads, ws, b0), n->dbet(grads, ws, b0), n->B, n->Hs, n->Ws, 64, ws + n->bn_ws,
+                                        n->bn_ws_bytes, st));
+    }
+    OSI_TRY(n->mark(OSI_PROF_BN_BWD, st));
+    n->give(go);
+    OSI_TRY(wgrad(n, 0, grads, ws, t, x4c, st));
+    if (rq.dimage) {
+        OSI_TRY(osi_stem_dgrad(S(t), params + c0.w_off, rq.dimage, n->B, n->H, n->W, st));
+        OSI_TRY(n->mark(OSI_PROF_CONV_DGRAD, st));
+    } else if (rq.x_adv) {     // the same input gradient, ending in the FGSM epilogue: x_adv from the batch the forward read
+        OSI_TRY(osi_stem_dgrad_fgsm(S(t), params + c0.w_off, x4c, rq.x_adv, rq.eps, rq.lo, rq.hi, n->B, n->H, n->W, st));
+        OSI_TRY(n->mark(OSI_PROF_CONV_DGRAD, st));
+    }
+    n->give(t);
+    return OSI_OK;
+}
+
+static int backward_stages(osi_resnet50_t n, const float* params, float* grads, void* workspace, const float* dlogits,
+                           const float* dfeatures, const BwRequest& rq, int stage_lo, int stage_hi, osi_stream_t stream) {
+    OSI_REQUIRE(stage_lo >= 0 && stage_lo < stage_hi && stage_hi <= n->n_stages);
+    if (!n->fwd_done || stage_lo != n->next_stage || !n->plan_unchanged()) return OSI_ERR_STATE;
+    // the inference-form prefix of the forward kept no backward state: no image gradient exists behind it
+    if (n->fw_prefix > 0 && (rq.dimage || rq.x_adv)) return OSI_ERR_STATE;
+    // the request is fixed by the call that runs stage 0 (block 0's dgrad form depends on it)
+    if (stage_lo == 0) n->rq = rq;
+    else if (!(n->rq == rq)) return OSI_ERR_STATE;
+    hipStream_t st = (hipStream_t)stream;
+    float* ws = (float*)workspace;
+    if (n->wants_side()) OSI_TRY(n->ensure_side());
+    OSI_TRY(n->mark(OSI_PROF_START, st));
+    // Units below `stop` launch nothing; unit `stop` leaves out its input gradient. A stage wholly below it is still accepted in order.
+    const int stop = n->bw_stop();
+    for (int stage = stage_lo; stage < stage_hi; ++stage) {
+        if (stage == 0) OSI_TRY(head_backward(n, params, grads, ws, dlogits, dfeatures, st));
+        for (int bi = (int)n->blocks.size() - 1; bi >= 0; --bi)
+            if (n->blocks[bi].stage == stage && bi + 1 >= stop) OSI_TRY(block_backward(n, bi, params, grads, ws, st, bi + 1 == stop));
+        if (stage == n->n_stages - 1) {
+            if (stop == 0) OSI_TRY(stem_tail(n, params, grads, ws, st));   // (else the stem is frozen and nobody wants the image gradient)
+            n->cur_grad = -1;
+            n->fwd_done = false;
+        }
+        n->next_stage = stage + 1;
+    }
+    // Join once per call: every gradient of the stages just run is final on `st` from here on. A data-parallel caller issues
+    // one stage per call (and reduces that slice next); a single-GPU caller issues all stages in one call and pays one join.
+    if (n->stage_join || stage_hi == n->n_stages) OSI_TRY(n->join_side(st));
     return OSI_OK;
 }
 
@@ -1117,17 +1214,6 @@ int osi_resnet50_backward(osi_resnet50_t n, const float* params, float* grads, v
                           const float* dfeatures, int stage_lo, int stage_hi, osi_stream_t stream) {
     return osi_resnet50_backward_ex(n, params, grads, workspace, dlogits, dfeatures, nullptr, 1, stage_lo, stage_hi, stream);
 }
-
-// what a backward is asked for besides the parameter gradients (osi_resnet50_backward_ex / _adv)
-struct BwRequest {
-    float* dimage;
-    int param_grads;
-    float* x_adv;
-    float eps, lo, hi;
-};
-
-static int backward_stages(osi_resnet50_t n, const float* params, float* grads, void* workspace, const float* dlogits,
-                           const float* dfeatures, const BwRequest& rq, int stage_lo, int stage_hi, osi_stream_t stream);
 
 int osi_resnet50_backward_ex(osi_resnet50_t n, const float* params, float* grads, void* workspace, const float* dlogits,
                              const float* dfeatures, float* dimage, int param_grads, int stage_lo, int stage_hi, osi_stream_t stream) {
@@ -1156,128 +1242,6 @@ int osi_resnet50_backward_adv(osi_resnet50_t n, const float* params, float* grad
     OSI_REQUIRE(!n->x4_cur || apart(n->x4_cur, img_bytes));
     return backward_stages(n, params, grads, workspace, dlogits, dfeatures, BwRequest{nullptr, 1, x_adv_nhwc4, eps, lo, hi}, stage_lo,
                            stage_hi, stream);
-}
-
-static int backward_stages(osi_resnet50_t n, const float* params, float* grads, void* workspace, const float* dlogits,
-                           const float* dfeatures, const BwRequest& rq, int stage_lo, int stage_hi, osi_stream_t stream) {
-    float* const dimage = rq.dimage;
-    const int param_grads = rq.param_grads;
-    OSI_REQUIRE(stage_lo >= 0 && stage_lo < stage_hi && stage_hi <= n->n_stages);
-    if (!n->fwd_done || stage_lo != n->next_stage || !n->plan_unchanged()) return OSI_ERR_STATE;
-    // the inference-form prefix of the forward kept no backward state: no image gradient exists behind it
-    if (n->fw_prefix > 0 && (dimage || rq.x_adv)) return OSI_ERR_STATE;
-    if (stage_lo == 0) {                                // the request is fixed by the call that runs stage 0 (block 0's dgrad form depends on it)
-        n->bw_dimage = dimage;
-        n->bw_pg = param_grads != 0;
-        n->bw_adv = rq.x_adv; n->bw_eps = rq.eps; n->bw_lo = rq.lo; n->bw_hi = rq.hi;
-    } else if (n->bw_dimage != dimage || n->bw_pg != (param_grads != 0) || n->bw_adv != rq.x_adv || n->bw_eps != rq.eps ||
-               n->bw_lo != rq.lo || n->bw_hi != rq.hi) {
-        return OSI_ERR_STATE;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    float* ws = (float*)workspace;
-    auto S = [&](int i) { return ws + n->scratch[i]; };
-    if (n->overlap && (!n->prof_on || n->prof_timeline)) OSI_TRY(n->ensure_side());
-    OSI_TRY(n->mark(OSI_PROF_START, st));
-    // Units below `stop` launch nothing; unit `stop` leaves out its input gradient. A stage wholly below it is still accepted in order.
-    const int stop = n->bw_stop();
-    const int head = osi_resnet50::NUNITS - 1;
-
-    for (int stage = stage_lo; stage < stage_hi; ++stage) {
-        if (stage == 0) {
-            OSI_REQUIRE(dlogits);
-            n->free_list.clear();
-            for (int i = 0; i < osi_resnet50::NSCR; ++i) { n->free_list.push_back(i); n->buf_pending[i] = false; }
-            const Tensor& fw = n->tensors[n->t_fc_w]; const Tensor& fb = n->tensors[n->t_fc_b]; const Tensor& lw = n->tensors[n->t_lg_w];
-            float* dfeat = ws + n->dfeat;
-            int acc = 0;
-            if (dfeatures) {
-                if (hipMemcpyAsync(dfeat, dfeatures, (size_t)n->B * n->F * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
-                    return OSI_ERR_LAUNCH;
-                acc = 1;
-            }
-            const bool pg = n->bw_pg && n->trainable(head);
-            float* dlb = pg && n->t_lg_b >= 0 ? grads + n->tensors[n->t_lg_b].off : nullptr;
-            OSI_TRY(osi_linear_bwd(dlogits, ws + n->feat, params + lw.off, dfeat, acc, pg ? grads + lw.off : nullptr, dlb, n->B, n->F,
-                                   n->O, st));
-            const bool below = stop < head;      // somebody below the head reads the gradient w.r.t. the pooled features
-            OSI_TRY(osi_linear_bwd(dfeat, ws + n->pooled, params + fw.off, below ? ws + n->dpooled : nullptr, 0, pg ? grads + fw.off : nullptr,
-                                   pg ? grads + fb.off : nullptr, n->B, 2048, n->F, st));
-            n->cur_grad = -1;
-            if (below) {
-                int g = n->take(st);
-                if (g < 0) return g;
-                OSI_TRY(osi_avgpool_bwd(ws + n->dpooled, S(g), n->B, n->Hf * n->Wf, 2048, st));
-                n->cur_grad = g;
-            }
-            OSI_TRY(n->mark(OSI_PROF_OTHER, st));
-            n->go_fused = false;
-        }
-        for (int bi = (int)n->blocks.size() - 1; bi >= 0; --bi) {
-            Block& k = n->blocks[bi];
-            if (k.stage != stage || bi + 1 < stop) continue;
-            OSI_TRY(block_backward(n, bi, params, grads, ws, st, bi + 1 == stop));
-        }
-        if (stage == n->n_stages - 1 && stop > 0) {
-            n->cur_grad = -1;      // the stem is frozen and nobody wants the image gradient: the stem tail is not run
-            n->fwd_done = false;
-        } else if (stage == n->n_stages - 1) {
-            // maxpool + stem
-            Conv& c0 = n->convs[0];
-            int go = n->cur_grad;
-            int t = n->take(st);
-            if (t < 0) return t;
-            BN& b0 = n->bns[c0.bn];
-            const float* x4c = n->x4_cur ? n->x4_cur : ws + n->x4;
-            if (n->stem_tail_fused()) {      // its own slab, sized at create: never the side stream's wg_ws
-                // reductions of bn1's backward (dgamma, dbeta) on the main stream: they arrived with block 0's last input gradient, two tiny
-                // merge launches. Then the weight gradient with the max-pool scatter, ReLU gate and BatchNorm backward applied inside its
-                // operand loader: the 112x112x64 gradient is never written
-                n->give(t);
-                const float* psum_g = ws + n->dg_ws;
-                OSI_TRY(osi_bn_backward_reduce(psum_g, psum_g + (size_t)n->stem_stats_P * 64, n->stem_stats_P, grads + b0.g_off,
-                                               grads + b0.b_off, n->B * n->Hs * n->Ws, 64, ws + n->bn_ws, n->bn_ws_bytes, st));
-                OSI_TRY(n->mark(OSI_PROF_BN_BWD, st));
-                // the stem's weight gradient is the last kernel of the step; on the MAIN stream it runs beside the side stream's
-                // backlog (layer1's weight gradients) instead of behind it
-                OSI_TRY(osi_stem_wgrad_fused(&c0.d, S(go), ws + n->pool_idx, ws + c0.y, x4c, params + b0.g_off, ws + b0.mean, ws + b0.invstd,
-                                             grads + b0.g_off, grads + b0.b_off, grads + c0.w_off, ws + n->stem_ws, n->stem_ws_bytes, st));
-                OSI_TRY(n->mark(OSI_PROF_CONV_WGRAD, st));
-                n->give(go);
-            } else {
-                // dJ/dimage (or the adversarial batch) wanted, or a geometry the fused form does not take: the stem's dY is materialised (max-pool scatter + ReLU gate
-                // + bn1 backward gathered on the fly from the pooled gradient into a scratch buffer), its weight gradient comes from that
-                // dY unless input-only, then — for dJ/dimage — the stem's input gradient straight into the caller's NCHW tensor
-                if (n->frozen)   // frozen statistics: dY = scale * (scattered, gated gradient); reductions only for the parameter gradients
-                    OSI_TRY(osi_bn_relu_maxpool_bwd_frozen(S(go), ws + n->pool_idx, ws + c0.y, ws + b0.mean, ws + b0.invstd, ws + b0.scale, S(t),
-                                                           n->bw_pg && n->trainable(0) ? grads + b0.g_off : nullptr,
-                                                           n->bw_pg && n->trainable(0) ? grads + b0.b_off : nullptr, n->B,
-                                                           n->Hs, n->Ws, 64, ws + n->bn_ws, n->bn_ws_bytes, st));
-                else
-                OSI_TRY(osi_bn_relu_maxpool_bwd(S(go), ws + n->pool_idx, ws + c0.y, ws + b0.mean, ws + b0.invstd, params + b0.g_off, S(t),
-                                                n->dgam(grads, ws, b0), n->dbet(grads, ws, b0), n->B, n->Hs, n->Ws, 64, ws + n->bn_ws,
-                                                n->bn_ws_bytes, st));
-                OSI_TRY(n->mark(OSI_PROF_BN_BWD, st));
-                n->give(go);
-                OSI_TRY(wgrad(n, 0, grads, ws, t, x4c, st));
-                if (n->bw_dimage) {
-                    OSI_TRY(osi_stem_dgrad(S(t), params + c0.w_off, n->bw_dimage, n->B, n->H, n->W, st));
-                    OSI_TRY(n->mark(OSI_PROF_CONV_DGRAD, st));
-                } else if (n->bw_adv) {     // the same input gradient, ending in the FGSM epilogue: x_adv from the batch the forward read
-                    OSI_TRY(osi_stem_dgrad_fgsm(S(t), params + c0.w_off, x4c, n->bw_adv, n->bw_eps, n->bw_lo, n->bw_hi, n->B, n->H, n->W, st));
-                    OSI_TRY(n->mark(OSI_PROF_CONV_DGRAD, st));
-                }
-                n->give(t);
-            }
-            n->cur_grad = -1;
-            n->fwd_done = false;
-        }
-        n->next_stage = stage + 1;
-    }
-    // Join once per call: every gradient of the stages just run is final on `st` from here on. A data-parallel caller issues
-    // one stage per call (and reduces that slice next); a single-GPU caller issues all stages in one call and pays one join.
-    if (n->stage_join || stage_hi == n->n_stages) OSI_TRY(n->join_side(st));
-    return OSI_OK;
 }
 
 // Hand the gradients of the stages enqueued so far to another stream WITHOUT stalling the compute stream: `waiter` waits for the
