@@ -31,7 +31,7 @@ extern "C" {
 
 typedef void* osi_stream_t; /* hipStream_t */
 
-int osi_abi_version(void);            /* bumped on any signature change */
+int osi_abi_version(void);            /* bumped on any signature change; 16 = the ROC-AUC entry points (osi_auc_*) */
 const char* osi_build_arch(void);     /* "gfx950" */
 const char* osi_strerror(int code);
 /* Process-wide development knobs (A/B measurements; every default is the measured optimum). Launch functions only READ them and never
@@ -421,6 +421,26 @@ int osi_oscr_f32(const float* scores, const long long* gt, int N, int C, long lo
                  float* taus, long long* ccr_count, long long* fpr_count, long long* totals, osi_stream_t stream);
 int osi_oscr_f64(const double* scores, const long long* gt, int N, int C, long long unk_label, void* ws, size_t ws_bytes,
                  double* taus, long long* ccr_count, long long* fpr_count, long long* totals, osi_stream_t stream);
+
+/* ABI 16. ROC-AUC counting for metrics.auc_score_binary / auc_score_multiclass (metrics.py:65-106, sklearn.metrics.roc_auc_score) on
+ * device-resident scores[N][C] (f32 or f64) and int64 labels. The device counts pairs in integers; the host forms the Mann-Whitney
+ * quotient (2 * gt + eq) / (2 * P * Nn) with one division. ws: osi_auc_workspace(N) bytes for either entry point. Every output is
+ * zeroed by the call. OSI_ERR_ARG before any launch on a null pointer, N <= 0, C <= 0 or a short workspace.
+ *   binary: positives are the rows with gt != unk_class, everything else is a negative, the compared value is the row maximum over
+ *     all C columns. counts5 = {gt = #{max_pos > max_neg}, eq = #{max_pos == max_neg}, P, Nn, rows holding a NaN}.
+ *   one-vs-rest: for class c the positives are the rows with gt == c, the negatives all other rows, the compared value column c;
+ *     O(N^2) comparisons in total. gt_c / eq_c / pos_c hold C entries each (pairs above, pairs tied, positives of class c; the
+ *     negatives of class c are N - pos_c[c]); flags3 = {rows whose label is outside [0, C), rows holding a NaN, rows whose fp64 sum s
+ *     violates |s - 1| <= 1e-8 + 1e-5}. C above 2048 does not fit the LDS tiling: OSI_ERR_ARG. */
+size_t osi_auc_workspace(int N);
+int osi_auc_binary_f32(const float* scores, const long long* gt, int N, int C, long long unk_class, void* ws, size_t ws_bytes,
+                       long long* counts5, osi_stream_t stream);
+int osi_auc_binary_f64(const double* scores, const long long* gt, int N, int C, long long unk_class, void* ws, size_t ws_bytes,
+                       long long* counts5, osi_stream_t stream);
+int osi_auc_ovr_f32(const float* scores, const long long* gt, int N, int C, void* ws, size_t ws_bytes, long long* gt_c,
+                    long long* eq_c, long long* pos_c, long long* flags3, osi_stream_t stream);
+int osi_auc_ovr_f64(const double* scores, const long long* gt, int N, int C, void* ws, size_t ws_bytes, long long* gt_c,
+                    long long* eq_c, long long* pos_c, long long* flags3, osi_stream_t stream);
 
 /* ---- optimizer + arena utilities (train.py:356-359 construction, train.py:127,139 zero_grad/step) --- */
 int osi_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,

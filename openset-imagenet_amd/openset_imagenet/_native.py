@@ -156,6 +156,11 @@ _SIGS = {
     "osi_oscr_workspace": (c_size_t, [c_int]),
     "osi_oscr_f32": (c_int, [P, P, c_int, c_int, c_longlong, P, c_size_t, P, P, P, P, P]),
     "osi_oscr_f64": (c_int, [P, P, c_int, c_int, c_longlong, P, c_size_t, P, P, P, P, P]),
+    "osi_auc_workspace": (c_size_t, [c_int]),
+    "osi_auc_binary_f32": (c_int, [P, P, c_int, c_int, c_longlong, P, c_size_t, P, P]),
+    "osi_auc_binary_f64": (c_int, [P, P, c_int, c_int, c_longlong, P, c_size_t, P, P]),
+    "osi_auc_ovr_f32": (c_int, [P, P, c_int, c_int, P, c_size_t, P, P, P, P, P]),
+    "osi_auc_ovr_f64": (c_int, [P, P, c_int, c_int, P, c_size_t, P, P, P, P, P]),
     "osi_adam_step": (c_int, [P, P, P, P, c_size_t, c_double, c_double, c_double, c_double, c_longlong, c_float, P]),
     "osi_sgd_step": (c_int, [P, P, P, c_size_t, c_float, c_float, c_int, c_float, P]),
     "osi_adam_step_groups": (c_int, [P, P, P, P, P, c_size_t, POINTER(OptSegment), c_int, POINTER(AdamGroup), c_int, c_float, P]),

@@ -2,14 +2,15 @@
 and options, same checkpoint naming (`{loss}_best.pth` / `{loss}_curr.pth` in the output directory), same output files
 `{loss}_{val,test}_arr{suffix}.npz` with `gt`, `logits`, `features`, `scores`. The forward passes run on the MI355X executor in
 eval mode (train.get_arrays); there is no CPU evaluation path. `--oscr` (this build's addition) also prints the area-free summary
-of the OSCR curve computed on the GPU (util.calculate_oscr)."""
+of the OSCR curve computed on the GPU (util.calculate_oscr); `--auc` (likewise) prints the binary ROC-AUC of known against negative
+(-1) and against unknown (-2) samples, counted on the GPU (metrics.auc_score_binary)."""
 import argparse
 import pathlib
 
 import numpy as np
 import torch
 
-from .. import tools, util
+from .. import metrics, tools, util
 from ..model import ResNet50
 from ..train import _image_loader, get_arrays, load_checkpoint
 
@@ -26,6 +27,7 @@ def get_args(command_line_options=None):
     p.add_argument("--batch-size", type=int, default=64)
     p.add_argument("--workers", type=int, default=4)
     p.add_argument("--oscr", action="store_true", help="also compute the OSCR curve of each split on the GPU")
+    p.add_argument("--auc", action="store_true", help="also compute the binary ROC-AUC of each split (known vs -1, known vs -2) on the GPU")
     args = p.parse_args(command_line_options)
     try:
         args.output_directory = str(args.output_directory).format(args.protocol)
@@ -33,6 +35,18 @@ def get_args(command_line_options=None):
         pass
     args.output_directory = pathlib.Path(args.output_directory)
     return args
+
+
+def auc_rows(gt, scores, unk, loss):
+    """What `--auc` hands to metrics.auc_score_binary for the label `unk` (-1 or -2): the known rows (gt >= 0) and the rows labelled
+    `unk` only - auc_score_binary counts every label other than unk_class as known, so the rows of the OTHER negative label have to
+    go - and, for the garbage loss, the scores without the background column (as `--oscr`). None when no row carries `unk`."""
+    gt = np.asarray(gt)
+    if not (gt == unk).any():
+        return None
+    keep = (gt >= 0) | (gt == unk)
+    s = scores[:, :-1] if loss == "garbage" else scores
+    return gt[keep], s[keep]
 
 
 def main(command_line_options=None):
@@ -67,6 +81,11 @@ def main(command_line_options=None):
                     ccr, fpr = util.calculate_oscr(gt, s, unk_label=unk)
                     at = ccr[np.searchsorted(-fpr, -0.1)] if len(ccr) and np.isfinite(fpr).all() and (fpr <= 0.1).any() else float("nan")
                     print(f"{split}: OSCR vs label {unk}: {len(ccr)} points, CCR@FPR<=0.1 = {at:.4f}")
+        if args.auc:
+            for unk in (-1, -2):
+                sel = auc_rows(gt, scores, unk, args.loss)
+                if sel is not None:
+                    print(f"{split}: AUC known vs label {unk}: {metrics.auc_score_binary(sel[0], sel[1], unk_class=unk):.6f}")
     return written
 
 
