@@ -23,6 +23,11 @@
 //   "C" image  [32][cols]      k major, read with ds_read_b32 (lanes walk 32 consecutive floats)
 // The K order inside a stage is permuted identically for both operands (lane half h of MFMA (j,e) consumes
 // k = 8j + 4h + e), which a dot product does not care about.
+//
+// Exit path of a 64x64 tile (the form the executor uses), one definition per piece for k_conv_fwd, k_conv_dgrad, k_conv1x1_rows and the
+// fix-up passes of a K-split tail: tile64_to_lds (accumulators -> LDS transpose) -> tile64_to_slab (K split) | fwd_store64 (16-byte
+// output stores, optional inference epilogue) | dgrad_epilogue64; BatchNorm partials bn_block32 -> bn_merge_rows. The wider tiles keep
+// their scalar epilogues in the kernels.
 #include "conv_common.h"
 #include <algorithm>
 #include <type_traits>
@@ -226,6 +231,165 @@ __device__ __forceinline__ void mma_CC(const float* sA, const float* sB, int aco
 }
 
 // ======================================================================================================
+// Pieces the 64x64-tile kernels share. Each exists ONCE so that a kernel and the pass that finishes its work (K-split fix-up, row
+// walker vs. k_conv_fwd) agree bit for bit by construction; all are inlined, the callers' instruction streams are what they were.
+// ======================================================================================================
+constexpr int LDT = 64 + 4;    // row stride of a transposed 64x64 tile in LDS, floats
+
+// Accumulators of the 2x2 wave grid -> [64][LDT] tile in LDS, so that every lane can then move 4 consecutive channels of a pixel (16
+// bytes). LIVE: rows at or past M are stored as exact zeros (a loader without range-checked rows, see k_conv_dgrad's row windows).
+template <bool LIVE = false>
+__device__ __forceinline__ void tile64_to_lds(float* tile, const f32x16& acc, int wm, int wn, int lane, int m0 = 0, int M = 0) {
+#pragma unroll
+    for (int rr = 0; rr < 16; ++rr) {
+        const bool live = !LIVE || m0 + wm * 32 + acc_row(rr, lane) < M;
+        tile[(wm * 32 + acc_row(rr, lane)) * LDT + wn * 32 + (lane & 31)] = live ? acc[rr] : 0.f;
+    }
+}
+// K split of a remainder tile (tile_of_block_split): the raw transposed tile goes to its slab entry, dense [64][64]; output,
+// statistics and row bounds are the fix-up pass's business
+__device__ __forceinline__ void tile64_to_slab(const ConvP& p, const float* tile, int mt, int nt, int ks) {
+    float* dst = p.ks_slab + ((size_t)((mt - p.MT1) * p.NT + nt) * p.ks_S + ks) * 4096;
+    const int tid = threadIdx.x, c4 = tid & 15, rg = tid >> 4;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int rl = rg + 16 * k;
+        *reinterpret_cast<f32x4*>(dst + rl * 64 + c4 * 4) = *reinterpret_cast<const f32x4*>(tile + rl * LDT + c4 * 4);
+    }
+}
+// Forward output of one 64x64 tile, 16 bytes per lane and row. `rd(row, c4)` returns the float4 of tile row `row`, channel quad `c4`
+// (the convolution kernels read their transposed tile, the fix-up pass its summed slab entries). oe: the inference epilogue
+// [relu](fma(a, osc, osh) [+ ores]) — the four rows' shortcut values first (all in flight together; no shortcut = zero records = zeros),
+// then one fma, one add, one max per element: the roundings of k_bn_apply<RES = 1> (fma, add) and of the fused loaders (fma, max).
+template <typename RD>
+__device__ __forceinline__ void fwd_store64(const ConvP& p, int m0, int n0, bool oe, RD rd) {
+    const int tid = threadIdx.x, c4 = tid & 15, rg = tid >> 4;
+    float* const y = p.y + n0 + c4 * 4;     // this lane's channel quad in row 0
+    if (oe) {
+        const __amdgpu_buffer_rsrc_t ro = make_rsrc(p.ores ? p.ores : p.y, p.ores ? p.M * p.Cout * 4 : 0);
+        const f32x4 sc = ld4(p.osc + n0 + c4 * 4), sh = ld4(p.osh + n0 + c4 * 4);
+        f32x4 rv[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int m = m0 + rg + 16 * k;
+            rv[k] = bld4(ro, m < p.M ? (uint32_t)((m * p.Cout + n0 + c4 * 4) * 4) : OOB, 0);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int rl = rg + 16 * k, m = m0 + rl;
+            const f32x4 a = rd(rl, c4);
+            f32x4 v;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { const float t = __builtin_fmaf(a[e], sc[e], sh[e]) + rv[k][e]; v[e] = p.orelu ? fmaxf(t, 0.f) : t; }
+            if (m < p.M) *reinterpret_cast<f32x4*>(y + (size_t)m * p.Cout) = v;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int rl = rg + 16 * k, m = m0 + rl;
+            if (m < p.M) *reinterpret_cast<f32x4*>(y + (size_t)m * p.Cout) = rd(rl, c4);
+        }
+    }
+}
+
+// BatchNorm batch statistics straight from the accumulators: (count, mean, M2) of the columns of ONE 32x32 block whose first row is
+// row0. FULL: the block lies wholly inside the tensor and needs no row masks — 16 compares and 32 selects that are paid in matrix-pipe
+// time (fp32 MFMAs hide no vector work, profiles/r06_mfma_valu_coexec.txt); same sums in the same order. The fma of the full path is
+// explicit because the compiler would contract there and not in the masked one.
+struct BnPart { float cnt, mu, q; };
+template <bool FULL>
+__device__ __forceinline__ BnPart bn_block32(const f32x16& acc, int row0, int M, int lane) {
+    const float cnt = FULL ? 32.f : (float)min(32, max(0, M - row0));
+    float s = 0.f;
+#pragma unroll
+    for (int rr = 0; rr < 16; ++rr) s += (FULL || row0 + acc_row(rr, lane) < M) ? acc[rr] : 0.f;
+    s += __shfl_xor(s, 32, 64);
+    const float mu = cnt > 0.f ? s / cnt : 0.f;
+    float q = 0.f;
+#pragma unroll
+    for (int rr = 0; rr < 16; ++rr) {
+        const float dlt = acc[rr] - mu;
+        if constexpr (FULL) q = __builtin_fmaf(dlt, dlt, q);
+        else q += (row0 + acc_row(rr, lane) < M) ? dlt * dlt : 0.f;
+    }
+    q += __shfl_xor(q, 32, 64);
+    return {cnt, mu, q};
+}
+// ... -> over the two wave rows through LDS: st = [2][BN][3], wave row wm leaves column c's triple at st + (wm * BN + c) * 3, and after
+// the caller's barrier the first BN threads Chan-merge the pair into one (mean, M2) per column of pmean/pm2[mt][Cout]. Fixed order.
+__device__ __forceinline__ void bn_put(float* st, int slot, float cnt, float mu, float q) {
+    float* dst = st + slot * 3;
+    dst[0] = cnt; dst[1] = mu; dst[2] = q;
+}
+template <int BN>
+__device__ __forceinline__ void bn_merge_rows(const ConvP& p, const float* st, int mt, int n0) {
+    const int tid = threadIdx.x;
+    if (tid < BN) {
+        const float* a = st + tid * 3;
+        const float* b = st + (BN + tid) * 3;
+        float cn = a[0], cm = a[1], cs = a[2];
+        chan_merge(cn, cm, cs, b[0], b[1], b[2]);
+        p.pmean[(size_t)mt * p.Cout + n0 + tid] = cm;
+        p.pm2[(size_t)mt * p.Cout + n0 + tid] = cs;
+    }
+}
+
+// Fused input activation: the per-input-channel scale | shift tables -> LDS (visible after the caller's next barrier)
+__device__ __forceinline__ void load_in_tables(const ConvP& p, float* s_sc, float* s_sh) {
+    const int tid = threadIdx.x;
+    for (int c = tid * 4; c < p.Cin; c += 1024) {
+        *reinterpret_cast<f32x4*>(s_sc + c) = ld4(p.in_scale + c);
+        *reinterpret_cast<f32x4*>(s_sh + c) = ld4(p.in_shift + c);
+    }
+}
+
+// ROW WINDOWS (3x3, stride 1, pad 1, 64x64 tile; forward and input gradient). For a fixed tap row the three tap columns read the same
+// rows of the A tensor shifted by one pixel, so ONE window per (tap row, 32-channel slice) is staged — in column-padded coordinates:
+// slot of pixel m = m + m div W, i.e. one zero slot behind every image row, which is the left / right neighbour a border pixel must
+// see: no mask on the MFMA side; the vertical validity stays the loader's select — and the three K tiles run from it, the A fragment
+// of a lane read at its own base row + the tap column's shift. K-tile order (tap row, slice, tap column) instead of (row, column,
+// slice). Rows loaded / transformed / stored per slice: 9 x 64 -> 3 x <= 78.
+constexpr int W3_WROWS = 78;   // 64 pixels + a pad slot per image row they cross (<= 64 / W + 1, W >= 7) + the two outer neighbours
+// Window slot u = lr + 32 i <-> padded index q(m0) - 1 + u. a_base[i]: byte offset (C channels per pixel, this thread's float4 slot kq
+// included) of the slot's pixel in the MIDDLE tap row, OOB for a pad slot / past the M pixels / past the window. The validity of the
+// three tap rows rides in the low bits of the 16-byte-aligned offset (one register per slot): bit 1 the middle row, bit UP the row
+// above the pixel (h > 0), bit 2 - UP the row below (h < H - 1) — the forward's tap row r reads row h + r - 1 (UP = 0), the input
+// gradient's jr reads h + 1 - jr (UP = 2). dWp divides by W + 1, dHW / dW by H W / W.
+template <int UP>
+__device__ __forceinline__ void w3_slots(int (&a_base)[3], bool (&a_ok)[3], int m0, int lr, int kq, int H, int W, int C, int M,
+                                         const FastDiv& dWp, const FastDiv& dHW, const FastDiv& dW) {
+    const uint32_t Wp = (uint32_t)W + 1u, q0 = (uint32_t)m0 + fdiv((uint32_t)m0, dW);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const int u = lr + 32 * i, Q = (int)q0 - 1 + u;
+        bool ok = u < W3_WROWS && Q >= 0;
+        const uint32_t Qq = ok ? (uint32_t)Q : 0u, irow = fdiv(Qq, dWp), col = Qq - irow * Wp, mm = irow * (uint32_t)W + col;
+        ok = ok && col < (uint32_t)W && mm < (uint32_t)M;
+        const uint32_t mq = ok ? mm : 0u, b = fdiv(mq, dHW), h = fdiv(mq - b * dHW.d, dW);
+        a_ok[i] = ok;
+        a_base[i] = ok ? (int)(((mq * (uint32_t)C + kq * 4) * 4) | (h > 0 ? 1u << UP : 0u) | 2u | ((int)h < H - 1 ? 4u >> UP : 0u)) : (int)OOB;
+    }
+}
+// window row of the pixel whose accumulator row lane `lane` of wave row wm feeds, for the unshifted tap column (= its padded index
+// relative to the tile's first pixel)
+__device__ __forceinline__ int w3_prow(int m0, int wm, int lane, int M, const FastDiv& dW) {
+    const uint32_t m = (uint32_t)min(m0 + wm * 32 + (lane & 31), M - 1);
+    return (int)(m - (uint32_t)m0 + fdiv(m, dW) - fdiv((uint32_t)m0, dW));
+}
+// K-split start: K tile t0 -> (tap row r, tap column s, channel offset c0); KC = K tiles per tap, nS = tap columns. W3: tile order
+// (r, slice, s), else (r, s, slice)
+template <bool W3>
+__device__ __forceinline__ void ksplit_start(int t0, int KC, int nS, int& r, int& s, int& c0) {
+    if constexpr (W3) {
+        const int rem = t0 % (3 * KC);
+        r = t0 / (3 * KC); c0 = (rem / 3) * BK; s = rem % 3;
+    } else {
+        const int tap = t0 / KC;
+        c0 = (t0 - tap * KC) * BK; r = tap / nS; s = tap - r * nS;
+    }
+}
+
+// ======================================================================================================
 // Forward
 // ======================================================================================================
 // NST = LDS stages: 2 = double buffered (one barrier per K tile), 1 = single buffered (two barriers, half the LDS, twice the
@@ -237,12 +401,8 @@ __device__ __forceinline__ void mma_CC(const float* sA, const float* sB, int aco
 // cost occupancy, which is what these kernels live on)
 // KS: the launch carries a K-split tail (tile_of_block_split); its own instantiation so that the plain kernels keep their scalar
 // register count (<= 80 SGPRs = eight resident 256-thread workgroups per CU)
-// W3 (3x3, stride 1, pad 1, 64x64 tile): ROW WINDOWS. For a fixed tap row r the taps s = 0, 1, 2 read the same activation rows shifted by
-// one pixel, so ONE window per (r, 32-channel slice) is staged — in column-padded coordinates: slot of pixel m = m + m div W, i.e. one
-// zero slot behind every image row, which is the left / right neighbour a border pixel must see: no mask on the MFMA side; the
-// vertical validity stays the loader's select — and the three K tiles run from it, the A fragment of a lane read at its own base row + s.
-// K-tile order (r, slice, s) instead of (r, s, slice). Activation rows loaded / transformed / stored per slice: 9 x 64 -> 3 x <= 78.
-constexpr int W3_WROWS = 78;   // 64 pixels + a pad slot per image row they cross (<= 64 / W + 1, W >= 7) + the two outer neighbours
+// W3 (3x3, stride 1, pad 1, 64x64 tile): row windows (w3_slots): one activation window per (r, 32-channel slice), the A fragment of a
+// lane read at its own base row + s. K-tile order (r, slice, s).
 // OE (inference, plain input only): output epilogue [relu](fma(acc, osc, osh) [+ ores]) instead of the raw accumulators, see ConvP
 template <int WM, int WN, bool STEM, int NST, int XF = 0, bool KS = false, bool W3 = false, bool OE = false>
 __global__ __launch_bounds__(256, XF ? (WM * WN == 1 ? 8 : 5) : (NST == 1 ? (WM * WN >= 4 ? 3 : 4) : 2)) void k_conv_fwd(ConvP p) {
@@ -257,13 +417,7 @@ __global__ __launch_bounds__(256, XF ? (WM * WN == 1 ? 8 : 5) : (NST == 1 ? (WM 
     OSI_STAMP(p, blockIdx.x, 0); OSI_STAMP_ID(p, blockIdx.x);
     float* s_sc = smem + NST * STAGE;          // XF: per-input-channel scale | shift tables, behind the operand stages
     float* s_sh = s_sc + p.Cin;
-    if (XF) {
-        for (int c = threadIdx.x * 4; c < p.Cin; c += 1024) {
-            *reinterpret_cast<f32x4*>(s_sc + c) = ld4(p.in_scale + c);
-            *reinterpret_cast<f32x4*>(s_sh + c) = ld4(p.in_shift + c);
-        }
-        // visible to every wave after the first __syncthreads() below (before any sstore of transformed data is read)
-    }
+    if (XF) load_in_tables(p, s_sc, s_sh);   // visible to every wave after the first __syncthreads() below (before any sstore of transformed data is read)
 
     static_assert(!KS || (WM == 1 && WN == 1 && !STEM && NST == 1), "the K-split tail is built for the single-buffered 64x64 tile");
     int mt, nt, ks = -1;
@@ -282,22 +436,10 @@ __global__ __launch_bounds__(256, XF ? (WM * WN == 1 ? 8 : 5) : (NST == 1 ? (WM 
     bool a_ok[AR];
     const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, p.x_bytes), rw = make_rsrc(p.w, p.w_bytes);
     const __amdgpu_buffer_rsrc_t rres = make_rsrc(XF == 2 ? p.res : p.x, p.x_bytes);   // XF = 2: the shortcut tensor, same shape as x
-    if constexpr (W3) {
-        // window slot u = lr + 32 i <-> padded index q(m0) - 1 + u; a_base: byte offset of the slot's pixel in tap row r = 1 (OOB: pad slot,
-        // past the tensor, past the window); a_taps: bit r set when the pixel's row h + r - 1 is inside the image
-        const uint32_t Wp = (uint32_t)p.W + 1u, q0 = (uint32_t)m0 + fdiv((uint32_t)m0, p.dWo);
+    if constexpr (W3) {    // bit r of a_base: the pixel's row h + r - 1 is inside the image (cW[0] holds the padded divisor W + 1)
+        w3_slots<0>(a_base, a_ok, m0, lr, kq, p.H, p.W, p.Cin, p.M, p.cW[0], p.dHoWo, p.dWo);
 #pragma unroll
-        for (int i = 0; i < AR; ++i) {
-            const int u = lr + 32 * i, Q = (int)q0 - 1 + u;
-            bool ok = u < W3_WROWS && Q >= 0;
-            const uint32_t Qq = ok ? (uint32_t)Q : 0u, irow = fdiv(Qq, p.cW[0]), col = Qq - irow * Wp, mm = irow * (uint32_t)p.W + col;
-            ok = ok && col < (uint32_t)p.W && mm < (uint32_t)p.M;
-            const uint32_t mq = ok ? mm : 0u, b = fdiv(mq, p.dHoWo), h = fdiv(mq - b * p.dHoWo.d, p.dWo);
-            a_ok[i] = ok; a_h0[i] = 0; a_w0[i] = 0;
-            // (the three validity bits ride in the low bits of the 16-byte-aligned offset: one register per window slot)
-            a_base[i] = ok ? (int)(((mq * (uint32_t)p.Cin + kq * 4) * 4) | (h > 0 ? 1u : 0u) | 2u | ((int)h < p.H - 1 ? 4u : 0u)) : (int)OOB;
-            a_taps[i] = 0;
-        }
+        for (int i = 0; i < AR; ++i) { a_h0[i] = 0; a_w0[i] = 0; a_taps[i] = 0; }
     } else
 #pragma unroll
     for (int i = 0; i < AR; ++i) {
@@ -338,22 +480,11 @@ __global__ __launch_bounds__(256, XF ? (WM * WN == 1 ? 8 : 5) : (NST == 1 ? (WM 
     const int t0 = (!KS || ks < 0) ? 0 : ks * p.ks_T;            // this workgroup's K tiles [t0, T)
     const int T = (!KS || ks < 0) ? Tall : min(Tall, t0 + p.ks_T);
     int r = 0, s = 0, c0 = 0;  // current tap / channel offset (non-stem)
-    if (KS && !STEM && ks > 0) {
-        if constexpr (W3) {            // tile t = (r, slice, s)
-            const int KC3 = 3 * (p.Cin / BK), rem = t0 % KC3;
-            r = t0 / KC3; c0 = (rem / 3) * BK; s = rem % 3;
-        } else {
-            const int tap = (t0 * BK) / p.Cin;
-            c0 = t0 * BK - tap * p.Cin; r = tap / p.S; s = tap - r * p.S;
-        }
-    }
+    if (KS && !STEM && ks > 0) ksplit_start<W3>(t0, p.Cin / BK, p.S, r, s, c0);
     int cs = s;              // W3: tap column of the tile the MFMAs are working on (the loader state runs one tile ahead)
     bool ld_new = false;     // W3: the loaded tile starts a new window (its activation rows sit in ra)
     int prow = 0;            // W3: window row of this lane's pixel for s = 0 (= its padded index relative to the tile's first)
-    if constexpr (W3) {
-        const uint32_t m = (uint32_t)min(m0 + wm * 32 + (lane & 31), p.M - 1);
-        prow = (int)(m - (uint32_t)m0 + fdiv(m, p.dWo) - fdiv((uint32_t)m0, p.dWo));
-    }
+    if constexpr (W3) prow = w3_prow(m0, wm, lane, p.M, p.dWo);
     int ld_c0 = 0, ld_tap = 0; // XF: channel offset / tap index of the tile sitting in ra (set by gload, used by sstore)
     f32x4 ra[AR], rb[BR];
     f32x4 rr[XF == 2 ? AR : 1];   // XF = 2: the shortcut rows of the tile sitting in ra
@@ -497,58 +628,30 @@ __global__ __launch_bounds__(256, XF ? (WM * WN == 1 ? 8 : 5) : (NST == 1 ? (WM 
 
     bool stored = false;
     if constexpr (WM == 1 && WN == 1) {
-        if (KS && ks >= 0) {
-            // K split of a remainder tile: the raw accumulators go to the slab as a dense 64x64 tile (16-byte stores through the
-            // same LDS transpose as below); output, statistics and row bounds are the fix-up pass's business
-            constexpr int LDT = BN + 4;
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) smem[(wm * 32 + acc_row(rr, lane)) * LDT + wn * 32 + (lane & 31)] = acc[0][0][rr];
+        static_assert(64 * LDT <= STAGE, "transposed tile must fit the operand stage");
+        if (KS && ks >= 0) {   // K split of a remainder tile: the epilogue runs in k_conv_fwd_tail_fixup
+            tile64_to_lds(smem, acc[0][0], wm, wn, lane);
             __syncthreads();
-            float* dst = p.ks_slab + ((size_t)((mt - p.MT1) * p.NT + nt) * p.ks_S + ks) * (BM * BN);
-            const int c4 = tid & 15, rg = tid >> 4;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int rl = rg + 16 * k;
-                *reinterpret_cast<f32x4*>(dst + rl * BN + c4 * 4) = *reinterpret_cast<const f32x4*>(smem + rl * LDT + c4 * 4);
-            }
+            tile64_to_slab(p, smem, mt, nt, ks);
             OSI_STAMP(p, blockIdx.x, 3);
             return;
         }
         if (!p.accumulate) {
-            // 64x64 tile: transpose through LDS so each lane stores 16 bytes (4 consecutive channels of a pixel), see k_conv_dgrad
-            constexpr int LDT = BN + 4;
-            static_assert(BM * LDT <= STAGE, "transposed tile must fit the operand stage");
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) smem[(wm * 32 + acc_row(rr, lane)) * LDT + wn * 32 + (lane & 31)] = acc[0][0][rr];
+            tile64_to_lds(smem, acc[0][0], wm, wn, lane);
             __syncthreads();
-            const int c4 = tid & 15, rg = tid >> 4;
-            if constexpr (OE) {
-                // the four rows' shortcut values first (all in flight together; no shortcut = zero records = zeros), then one fma, one
-                // add, one max per element: the roundings of k_bn_apply<RES = 1> (fma, add) and of the fused loaders (fma, max)
-                const __amdgpu_buffer_rsrc_t ro = make_rsrc(p.ores ? p.ores : p.y, p.ores ? p.M * p.Cout * 4 : 0);
-                const f32x4 sc = ld4(p.osc + n0 + c4 * 4), sh = ld4(p.osh + n0 + c4 * 4);
-                f32x4 rv[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int m = m0 + rg + 16 * k;
-                    rv[k] = bld4(ro, m < p.M ? (uint32_t)((m * p.Cout + n0 + c4 * 4) * 4) : OOB, 0);
-                }
+            if constexpr (XF == 1) {
+                // NOT through fwd_store64: with the shared helper this form (and only this one) measured 3 % slower on 512->2048 @7x7 at
+                // B = 128 with statistics — 117.5 -> 120.6 us per launch against a parent-vs-parent spread of 0.5 us, same stores, another
+                // schedule around them (profiles/NOTES_r12.md). The text the helper's plain arm was cut from stays here for XF = 1.
+                const int c4 = tid & 15, rg = tid >> 4;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int rl = rg + 16 * k, m = m0 + rl;
-                    const f32x4 a = *reinterpret_cast<const f32x4*>(smem + rl * LDT + c4 * 4);
-                    f32x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { const float t = __builtin_fmaf(a[e], sc[e], sh[e]) + rv[k][e]; v[e] = p.orelu ? fmaxf(t, 0.f) : t; }
-                    if (m < p.M) *reinterpret_cast<f32x4*>(p.y + (size_t)m * p.Cout + n0 + c4 * 4) = v;
+                    if (m < p.M)
+                        *reinterpret_cast<f32x4*>(p.y + (size_t)m * p.Cout + n0 + c4 * 4) = *reinterpret_cast<const f32x4*>(smem + rl * LDT + c4 * 4);
                 }
             } else
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int rl = rg + 16 * k, m = m0 + rl;
-                if (m < p.M)
-                    *reinterpret_cast<f32x4*>(p.y + (size_t)m * p.Cout + n0 + c4 * 4) = *reinterpret_cast<const f32x4*>(smem + rl * LDT + c4 * 4);
-            }
+            fwd_store64(p, m0, n0, OE, [&](int rl, int c4) { return *reinterpret_cast<const f32x4*>(smem + rl * LDT + c4 * 4); });
             __syncthreads();   // the statistics below reuse the LDS
             stored = true;
         }
@@ -591,50 +694,22 @@ __global__ __launch_bounds__(256, XF ? (WM * WN == 1 ? 8 : 5) : (NST == 1 ? (WM 
     // two wave rows through LDS -> one (mean, M2) pair per column in pmean/pm2[mt][Cout]. Fixed order, no atomics.
     if (p.pmean) {
         // Two code paths behind ONE uniform branch: a row tile that lies wholly inside the tensor (every tile of every network shape at
-        // the usual batches: M is a multiple of 64) needs no row masks — 16 compares and 32 selects per 32 x 32 accumulator block that are
-        // paid in matrix-pipe time (fp32 MFMAs hide no vector work, profiles/r06_mfma_valu_coexec.txt); same sums in the same order.
+        // the usual batches: M is a multiple of 64) takes the unmasked form of bn_block32
         auto stats = [&](auto FULLC) {
-            constexpr bool full = decltype(FULLC)::value;
 #pragma unroll
             for (int n = 0; n < WN; ++n) {
                 float cn = 0.f, cm = 0.f, cs = 0.f;
 #pragma unroll
                 for (int i = 0; i < WM; ++i) {
-                    const int row0 = m0 + wm * 32 * WM + i * 32;
-                    const float cnt = full ? 32.f : (float)min(32, max(0, p.M - row0));
-                    float s = 0.f;
-#pragma unroll
-                    for (int rr = 0; rr < 16; ++rr) s += (full || row0 + acc_row(rr, lane) < p.M) ? acc[i][n][rr] : 0.f;
-                    s += __shfl_xor(s, 32, 64);
-                    const float mu = cnt > 0.f ? s / cnt : 0.f;
-                    float q = 0.f;
-#pragma unroll
-                    for (int rr = 0; rr < 16; ++rr) {
-                        const float dlt = acc[i][n][rr] - mu;
-                        // (explicit fma in the unmasked path: the compiler would contract here and not there — the row walker and this
-                        // kernel must agree bit for bit)
-                        if constexpr (full) q = __builtin_fmaf(dlt, dlt, q);
-                        else q += (row0 + acc_row(rr, lane) < p.M) ? dlt * dlt : 0.f;
-                    }
-                    q += __shfl_xor(q, 32, 64);
-                    chan_merge(cn, cm, cs, cnt, mu, q);
+                    const BnPart b = bn_block32<decltype(FULLC)::value>(acc[i][n], m0 + wm * 32 * WM + i * 32, p.M, lane);
+                    chan_merge(cn, cm, cs, b.cnt, b.mu, b.q);
                 }
-                if (lane < 32) {
-                    float* dst = smem + (wm * BN + wn * 32 * WN + n * 32 + lane) * 3;  // the K loop ended with a barrier: LDS is free
-                    dst[0] = cn; dst[1] = cm; dst[2] = cs;
-                }
+                if (lane < 32) bn_put(smem, wm * BN + wn * 32 * WN + n * 32 + lane, cn, cm, cs);  // the K loop ended with a barrier: LDS is free
             }
         };
         if (m0 + BM <= p.M) stats(std::true_type{}); else stats(std::false_type{});
         __syncthreads();
-        if (tid < BN) {
-            const float* a = smem + tid * 3;
-            const float* b = smem + (BN + tid) * 3;
-            float cn = a[0], cm = a[1], cs = a[2];
-            chan_merge(cn, cm, cs, b[0], b[1], b[2]);
-            p.pmean[(size_t)mt * p.Cout + n0 + tid] = cm;
-            p.pm2[(size_t)mt * p.Cout + n0 + tid] = cs;
-        }
+        bn_merge_rows<BN>(p, smem, mt, n0);
     }
     OSI_STAMP(p, blockIdx.x, 3);
 }
@@ -807,9 +882,8 @@ __device__ __forceinline__ void dgrad_epilogue64(const ConvP& p, float* smem, in
 // KS: the launch carries a K-split tail (stride 1 only; see tile_of_block_split), its own instantiation like k_conv_fwd's
 // POOL: pool-mode reductions in the epilogue (osi_dgrad_fusion.pool_idx) — one launch per step, its own instantiation so that the
 // workhorse keeps its 8 waves per SIMD
-// W3 (3x3, stride 1, pad 1, 64x64 tile): row windows as in k_conv_fwd — for a fixed tap row jr the taps js = 0, 1, 2 read the same dY rows
-// shifted by one pixel (dY pixel of (m, jr, js) = m + (1 - jr) W + (1 - js)): one window per (jr, 32-cout slice) in column-padded
-// coordinates, the A fragment of a lane read at its base row + 2 - js. K-tile order (jr, slice, js).
+// W3 (3x3, stride 1, pad 1, 64x64 tile): row windows (w3_slots) over dY — the dY pixel of (m, jr, js) is m + (1 - jr) W + (1 - js): one
+// window per (jr, 32-cout slice), the A fragment of a lane read at its base row + 2 - js. K-tile order (jr, slice, js).
 template <int WM, int WN, int NST, int FUSED, bool KS = false, bool POOL = false, bool W3 = false>
 __global__ __launch_bounds__(256, NST == 1 ? (WM * WN >= 4 ? 3 : (WM * WN == 1 ? 8 : 4)) : 2) void k_conv_dgrad(ConvP p, int Hc0, int Wc0) {
     static_assert(!KS || (WM == 1 && WN == 1 && NST == 1), "the K-split tail is built for the single-buffered 64x64 tile");
@@ -857,25 +931,15 @@ __global__ __launch_bounds__(256, NST == 1 ? (WM * WN >= 4 ? 3 : (WM * WN == 1 ?
 
     const FastDiv dHW = p.cHW[cls], dW = p.cW[cls];
     // a_base = offset of the dY pixel reached through the class's first tap (jr = js = 0); a_taps = bit (jr*nS+js) set when
-    // tap (jr, js) lands inside dY: one add and one bit test per load (see k_conv_fwd)
+    // tap (jr, js) lands inside dY: one add and one bit test per load
     int a_base[AR];
     unsigned a_taps[AR];
     bool a_ok[AR];
     const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, p.x_bytes), rw = make_rsrc(p.w, p.w_bytes);
-    if constexpr (W3) {
-        // window slot u = lr + 32 i <-> padded index q(m0) - 1 + u (see k_conv_fwd): a_base = byte offset of the slot's pixel in dY for
-        // jr = 1, with bit jr set in its low bits when row h + 1 - jr is inside the image; OOB: pad slot / past the tensor / past the window
-        const uint32_t Wp = (uint32_t)p.W + 1u, q0 = (uint32_t)m0 + fdiv((uint32_t)m0, dW);
+    if constexpr (W3) {    // bit jr of a_base: the pixel's row h + 1 - jr is inside the image (cW[1] holds the padded divisor W + 1)
+        w3_slots<2>(a_base, a_ok, m0, lr, kq, p.H, p.W, p.Cout, Mc, p.cW[1], dHW, dW);
 #pragma unroll
-        for (int i = 0; i < AR; ++i) {
-            const int u = lr + 32 * i, Q = (int)q0 - 1 + u;
-            bool ok = u < W3_WROWS && Q >= 0;
-            const uint32_t Qq = ok ? (uint32_t)Q : 0u, irow = fdiv(Qq, p.cW[1]), col = Qq - irow * Wp, mm = irow * (uint32_t)p.W + col;
-            ok = ok && col < (uint32_t)p.W && mm < (uint32_t)Mc;
-            const uint32_t mq = ok ? mm : 0u, b = fdiv(mq, dHW), h = fdiv(mq - b * dHW.d, dW);
-            a_ok[i] = ok; a_taps[i] = 0;
-            a_base[i] = ok ? (int)(((mq * (uint32_t)p.Cout + kq * 4) * 4) | ((int)h < p.H - 1 ? 1u : 0u) | 2u | (h > 0 ? 4u : 0u)) : (int)OOB;
-        }
+        for (int i = 0; i < AR; ++i) a_taps[i] = 0;
     } else
 #pragma unroll
     for (int i = 0; i < AR; ++i) {
@@ -912,22 +976,11 @@ __global__ __launch_bounds__(256, NST == 1 ? (WM * WN >= 4 ? 3 : (WM * WN == 1 ?
     const int t0 = (!KS || ks < 0) ? 0 : ks * p.ks_T;            // this workgroup's K tiles [t0, T)
     const int T = (!KS || ks < 0) ? Tall : min(Tall, t0 + p.ks_T);
     int jr = 0, js = 0, c0 = 0;
-    if (KS && ks > 0) {
-        if constexpr (W3) {            // tile t = (jr, slice, js)
-            const int rem = t0 % (3 * KC);
-            jr = t0 / (3 * KC); c0 = (rem / 3) * BK; js = rem % 3;
-        } else {
-            const int tap = t0 / KC;
-            c0 = (t0 - tap * KC) * BK; jr = tap / nS; js = tap - jr * nS;
-        }
-    }
+    if (KS && ks > 0) ksplit_start<W3>(t0, KC, nS, jr, js, c0);
     int cjs = js;            // W3: tap column of the tile the MFMAs are working on (the loader state runs one tile ahead)
     bool ld_new = false, first = true;     // W3: the loaded tile starts a new window (its dY rows sit in ra)
     int prow = 0;            // W3: window row of this lane's pixel for js = 2 (its padded index relative to the tile's first)
-    if constexpr (W3) {
-        const uint32_t m = (uint32_t)min(m0 + wm * 32 + (lane & 31), Mc - 1);
-        prow = (int)(m - (uint32_t)m0 + fdiv(m, dW) - fdiv((uint32_t)m0, dW));
-    }
+    if constexpr (W3) prow = w3_prow(m0, wm, lane, Mc, dW);
     f32x4 ra[AR], rbv[BRN];
     const int bk_row = tid / BV, bk_col = (tid % BV) * 4;
 
@@ -944,7 +997,7 @@ __global__ __launch_bounds__(256, NST == 1 ? (WM * WN >= 4 ? 3 : (WM * WN == 1 ?
                 }
             }
         } else
-        if (p.unit) {   // the form is chosen once per tile, outside the unrolled loop (see k_conv_fwd's gload)
+        if (p.unit) {   // the form is chosen once per tile, outside the unrolled loop (see the forward's gload)
 #pragma unroll
             for (int i = 0; i < AR; ++i) ra[i] = bld4(rx, (uint32_t)a_base[i], (uint32_t)(c0 * 4));
         } else {
@@ -1026,25 +1079,14 @@ __global__ __launch_bounds__(256, NST == 1 ? (WM * WN >= 4 ? 3 : (WM * WN == 1 ?
         // that every lane owns 4 consecutive channels of a pixel — addend, activation(s) and output move as 16-byte accesses
         // (a quarter of the memory instructions of the accumulator layout), the ReLU mask words of a float4 are 32 contiguous
         // bytes, and the BatchNorm column sums start as float4 per lane.
-        constexpr int LDT = BN + 4;
         static_assert(BM * LDT <= STAGE, "transposed tile must fit the operand stage");
         float* tile = smem;   // the K loop ended with a barrier: LDS is free
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) {
-            // rows past the end of the tensor must be exact zeros for the epilogue's column sums: the per-tap loader gets that from its
-            // range-checked loads, the row-window form reads SOME window row for such a lane and clears the result here
-            const bool live = !W3 || m0 + wm * 32 + acc_row(rr, lane) < Mc;
-            tile[(wm * 32 + acc_row(rr, lane)) * LDT + wn * 32 + (lane & 31)] = live ? acc[0][0][rr] : 0.f;
-        }
+        // rows past the end of the tensor must be exact zeros for the epilogue's column sums: the per-tap loader gets that from its
+        // range-checked loads, the row-window form reads SOME window row for such a lane and clears the result here
+        tile64_to_lds<W3>(tile, acc[0][0], wm, wn, lane, m0, Mc);
         __syncthreads();
-        if (KS && ks >= 0) {   // K split of a remainder tile: raw accumulators to the slab, the epilogue runs in k_conv_dgrad_tail_fixup
-            float* dst = p.ks_slab + ((size_t)((mt - p.MT1) * p.NT + nt) * p.ks_S + ks) * (BM * BN);
-            const int c4 = tid & 15, rg = tid >> 4;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int rl = rg + 16 * k;
-                *reinterpret_cast<f32x4*>(dst + rl * BN + c4 * 4) = *reinterpret_cast<const f32x4*>(tile + rl * LDT + c4 * 4);
-            }
+        if (KS && ks >= 0) {   // K split of a remainder tile: the epilogue runs in k_conv_dgrad_tail_fixup
+            tile64_to_slab(p, tile, mt, nt, ks);
             OSI_STAMP(p, sidx, 3);
             return;
         }
@@ -1635,13 +1677,13 @@ __global__ __launch_bounds__(256, 3) void k_conv_wgrad3(ConvP p) {   // 72 accum
 // (all of K) in LDS for its whole life, and walks row tiles mt = walker, walker + walkers, ...: the next tile's activation rows are
 // fetched into registers BEFORE the MFMAs and the epilogue of the current one, so the load round trip hides behind them and no
 // per-tile prologue is left. The four (Cout / 64) workgroups of a walker take consecutive dispatch slots of one XCD: they stream the
-// same rows at about the same time and three of four reads hit that L2. Epilogue as in k_conv_fwd (LDS transpose -> 16-byte
-// stores, BatchNorm (mean, M2) partials per row tile straight from the accumulators).
+// same rows at about the same time and three of four reads hit that L2. Exit path of a row tile: the shared one of the 64x64 tile
+// (tile64_to_lds, fwd_store64, bn_block32, bn_merge_rows).
 // ======================================================================================================
 template <int KT, int XF, bool OE = false>   // KT = Cin / 32 K tiles (2 or 4); XF = 1: the A operand is relu(x * in_scale[c] + in_shift[c]); OE: output epilogue (ConvP)
 __global__ __launch_bounds__(256, 4) void k_conv1x1_rows(ConvP p, int walkers) {
     static_assert(!OE || XF == 0, "output epilogue: plain input");
-    constexpr int BN = 64, IMG = 64 * LDR, LDT = BN + 4;
+    constexpr int BN = 64, IMG = 64 * LDR;
     static_assert(64 * LDT <= KT * IMG, "the transposed output tile reuses the activation images");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* sB = smem;                    // [KT][64][LDR] the column tile's weights, resident
@@ -1662,12 +1704,7 @@ __global__ __launch_bounds__(256, 4) void k_conv1x1_rows(ConvP p, int walkers) {
         for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
             for (int i = 0; i < 2; ++i) rb[kt][i] = bld4(rw, ((uint32_t)(n0 + lr + 32 * i) * p.Ktot + kq * 4) * 4, (uint32_t)(kt * BK * 4));
-        if (XF) {
-            for (int c = tid * 4; c < p.Cin; c += 1024) {
-                *reinterpret_cast<f32x4*>(s_sc + c) = ld4(p.in_scale + c);
-                *reinterpret_cast<f32x4*>(s_sh + c) = ld4(p.in_shift + c);
-            }
-        }
+        if (XF) load_in_tables(p, s_sc, s_sh);
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
@@ -1716,72 +1753,20 @@ __global__ __launch_bounds__(256, 4) void k_conv1x1_rows(ConvP p, int walkers) {
         for (int kt = 0; kt < KT; ++kt) mma_RR<1, 1>(sA + kt * IMG, sB + kt * IMG, wm * 32, wn * 32, lane, acc);
         __syncthreads();                 // every wave is done reading the row tile: its LDS becomes the transposed output tile
         const int m0 = mt * 64;
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) sA[(wm * 32 + acc_row(rr, lane)) * LDT + wn * 32 + (lane & 31)] = acc[0][0][rr];
+        tile64_to_lds(sA, acc[0][0], wm, wn, lane);
         __syncthreads();
-        {   // 16-byte stores of 4 consecutive channels per lane (measured against 4-byte stores straight from the accumulators, which
-            // save two barriers per tile: 86 vs 82 TFLOP/s on 64->256 @56x56)
-            const int c4 = tid & 15, rg = tid >> 4;
-            if constexpr (OE) {          // [relu](fma(acc, osc, osh) [+ ores]) as in k_conv_fwd
-                const __amdgpu_buffer_rsrc_t ro = make_rsrc(p.ores ? p.ores : p.y, p.ores ? p.M * p.Cout * 4 : 0);
-                const f32x4 sc = ld4(p.osc + n0 + c4 * 4), sh = ld4(p.osh + n0 + c4 * 4);
-                f32x4 rv[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int m = m0 + rg + 16 * k;
-                    rv[k] = bld4(ro, m < p.M ? (uint32_t)((m * p.Cout + n0 + c4 * 4) * 4) : OOB, 0);
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int rl = rg + 16 * k, m = m0 + rl;
-                    const f32x4 a = *reinterpret_cast<const f32x4*>(sA + rl * LDT + c4 * 4);
-                    f32x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { const float t = __builtin_fmaf(a[e], sc[e], sh[e]) + rv[k][e]; v[e] = p.orelu ? fmaxf(t, 0.f) : t; }
-                    if (m < p.M) *reinterpret_cast<f32x4*>(p.y + (size_t)m * p.Cout + n0 + c4 * 4) = v;
-                }
-            } else
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int rl = rg + 16 * k, m = m0 + rl;
-                if (m < p.M)
-                    *reinterpret_cast<f32x4*>(p.y + (size_t)m * p.Cout + n0 + c4 * 4) = *reinterpret_cast<const f32x4*>(sA + rl * LDT + c4 * 4);
-            }
-        }
-        if (p.pmean) {                   // BatchNorm (mean, M2) partials of this row tile's 64 columns (see k_conv_fwd: full tiles unmasked)
+        // 16-byte stores of 4 consecutive channels per lane (measured against 4-byte stores straight from the accumulators, which
+        // save two barriers per tile: 86 vs 82 TFLOP/s on 64->256 @56x56)
+        fwd_store64(p, m0, n0, OE, [&](int rl, int c4) { return *reinterpret_cast<const f32x4*>(sA + rl * LDT + c4 * 4); });
+        if (p.pmean) {                   // BatchNorm (mean, M2) partials of this row tile's 64 columns: one 32x32 block per wave
             auto stats = [&](auto FULLC) {
-                constexpr bool full = decltype(FULLC)::value;
-                const int row0 = m0 + wm * 32;
-                const float cnt = full ? 32.f : (float)min(32, max(0, p.M - row0));
-                float sm = 0.f;
-#pragma unroll
-                for (int rr = 0; rr < 16; ++rr) sm += (full || row0 + acc_row(rr, lane) < p.M) ? acc[0][0][rr] : 0.f;
-                sm += __shfl_xor(sm, 32, 64);
-                const float mu = cnt > 0.f ? sm / cnt : 0.f;
-                float q = 0.f;
-#pragma unroll
-                for (int rr = 0; rr < 16; ++rr) {
-                    const float dlt = acc[0][0][rr] - mu;
-                    if constexpr (full) q = __builtin_fmaf(dlt, dlt, q);
-                    else q += (row0 + acc_row(rr, lane) < p.M) ? dlt * dlt : 0.f;
-                }
-                q += __shfl_xor(q, 32, 64);
-                if (lane < 32) {
-                    float* dst = s_st + (wm * BN + wn * 32 + lane) * 3;
-                    dst[0] = cnt; dst[1] = mu; dst[2] = q;
-                }
+                const BnPart b = bn_block32<decltype(FULLC)::value>(acc[0][0], m0 + wm * 32, p.M, lane);
+                if (lane < 32) bn_put(s_st, wm * BN + wn * 32 + lane, b.cnt, b.mu, b.q);
             };
             if (m0 + 64 <= p.M) stats(std::true_type{}); else stats(std::false_type{});
         }
         __syncthreads();                 // transposed tile read, statistics of both wave rows written
-        if (p.pmean && tid < BN) {
-            const float* a = s_st + tid * 3;
-            const float* b = s_st + (BN + tid) * 3;
-            float cn = a[0], cm = a[1], cs = a[2];
-            chan_merge(cn, cm, cs, b[0], b[1], b[2]);
-            p.pmean[(size_t)mt * p.Cout + n0 + tid] = cm;
-            p.pm2[(size_t)mt * p.Cout + n0 + tid] = cs;
-        }
+        if (p.pmean) bn_merge_rows<BN>(p, s_st, mt, n0);
         if (mt_next < p.MT) sstoreA();   // (s_st is rewritten only behind the next tile's barriers, which its readers reach after reading)
         mt = mt_next;
     }
@@ -1815,25 +1800,8 @@ __global__ __launch_bounds__(256) void k_conv_fwd_tail_fixup(ConvP p) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) v[k] += t[j][k];
     }
-    if (p.osc) {      // inference launch: the output epilogue [relu](fma(acc, osc, osh) [+ ores]) on the summed tile (as k_conv_fwd<OE>); no statistics
-        const __amdgpu_buffer_rsrc_t ro = make_rsrc(p.ores ? p.ores : p.y, p.ores ? p.M * p.Cout * 4 : 0);
-        const f32x4 sc = ld4(p.osc + n0 + c4 * 4), sh = ld4(p.osh + n0 + c4 * 4);
-        f32x4 rv[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int m = m0 + rg + 16 * k;
-            rv[k] = bld4(ro, m < p.M ? (uint32_t)((m * p.Cout + n0 + c4 * 4) * 4) : OOB, 0);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { const float t = __builtin_fmaf(v[k][e], sc[e], sh[e]) + rv[k][e]; v[k][e] = p.orelu ? fmaxf(t, 0.f) : t; }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int rl = rg + 16 * k;
-        if (m0 + rl < p.M) *reinterpret_cast<f32x4*>(p.y + (size_t)(m0 + rl) * p.Cout + n0 + c4 * 4) = v[k];
-    }
+    // output rows through the convolution's own store; an inference launch (osc set) applies the output epilogue there and has no statistics
+    fwd_store64(p, m0, n0, p.osc != nullptr, [&](int rl, int) { return v[(rl - rg) >> 4]; });   // row rg + 16 k sits in v[k]
     if (!p.pmean) return;
     const float cnt = (float)min(64, p.M - m0);
     f32x4 sm = {0, 0, 0, 0};
@@ -2186,7 +2154,7 @@ static int with_shape(TileShape s, F&& f) {   // f(WM, WN, NST) as constants
 // how a 64x64 single-buffered launch differs from the plain tile kernel (bits; pool mode is the input gradient's and excludes the others)
 enum LaunchForm { FORM_PLAIN = 0, FORM_POOL = 1, FORM_W3 = 2, FORM_SPLIT = 4 };
 
-// 3x3 / stride 1 / pad 1 shapes the row-window loaders take (one activation window per tap ROW and channel slice, see k_conv_fwd W3);
+// 3x3 / stride 1 / pad 1 shapes the row-window loaders take (one activation window per tap ROW and channel slice, see w3_slots);
 // the forward and the input gradient add their knob and channel conditions
 static bool row_window_shape(const osi_conv_desc* d) {
     return d->R == 3 && d->S == 3 && d->stride == 1 && d->pad == 1 && d->W >= 7 && d->H == d->Ho && d->W == d->Wo;
