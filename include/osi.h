@@ -31,7 +31,7 @@ extern "C" {
 
 typedef void* osi_stream_t; /* hipStream_t */
 
-int osi_abi_version(void);            /* bumped on any signature change; 16 = the ROC-AUC entry points (osi_auc_*) */
+int osi_abi_version(void);            /* bumped on any signature change; 17 = gradient-norm clipping (osi_grad_clip_scale, osi_*_step_groups_dev); 16 = the ROC-AUC entry points (osi_auc_*) */
 const char* osi_build_arch(void);     /* "gfx950" */
 const char* osi_strerror(int code);
 /* Process-wide development knobs (A/B measurements; every default is the measured optimum). Launch functions only READ them and never
@@ -480,6 +480,44 @@ int osi_adam_step_groups(float* param, const float* grad, float* exp_avg, float*
                          float grad_scale, osi_stream_t stream);
 int osi_sgd_step_groups(float* param, const float* grad, float* momentum_buf, size_t n, const osi_opt_segment* segments,
                         int n_segments, const osi_sgd_group* groups, int n_groups, float grad_scale, osi_stream_t stream);
+/* ABI 17. Gradient-norm clipping without a host read: osi_grad_clip_scale leaves the norm and the scalar of the step in device memory,
+ * and the *_dev forms of the grouped steps take that scalar from there.
+ *
+ * osi_grad_clip_scale writes two floats: out2[0] = |grad_scale| * ||g||, the norm (OSI_NORM_L2, or OSI_NORM_INF: the largest |g|)
+ * over the elements inside the spans, and out2[1] = grad_scale * min(1, max_norm / (out2[0] + 1e-6f)), evaluated in fp32 as
+ * torch.nn.utils.clip_grad_norm_ evaluates its coefficient on the gradients grad_scale * g (the quotient with torch's roundings:
+ * reciprocal(out2[0] + 1e-6f) * max_norm). A NaN norm gives a NaN scalar (torch's clamp keeps a NaN); max_norm = +inf gives exactly grad_scale for a finite norm ("measure only").
+ * A span is one tensor: numel floats from float index begin (begin % 4 == 0, numel >= 1). spans is a HOST table of 1 ..
+ * OSI_OPT_MAX_SEGMENTS entries, sorted and not overlapping, read during the call (it travels in the kernel arguments); spans == NULL
+ * with n_spans == 0 means [0, n). The up to 3 alignment floats behind a span with numel % 4 != 0, and every float outside every span,
+ * contribute nothing, whatever bits they hold.
+ * L2 squares and sums in double ((double)g * g is exact), so magnitudes whose squares leave the fp32 range give correct norms. The
+ * reduction has a fixed order and no atomics: the arena is cut into one contiguous chunk of whole 256-unit tiles per workgroup (at most
+ * 2048, as the grouped steps cut it); per lane in index order, then wave, workgroup, one 8-byte partial in ws per workgroup; a second
+ * launch of one workgroup adds the partials, eight consecutive ones per lane in index order, then the same tree, and writes out2. Two
+ * calls on the same data give the same bits. Two launches, nothing allocated, nothing synchronised (graph-capturable).
+ * ws: osi_grad_norm_workspace(n) bytes (0 for an n the call would refuse), 8-byte aligned, overwritten. grad 16-byte aligned.
+ * OSI_ERR_ARG before any launch on: a null or misaligned grad, ws or out2; n == 0, n % 4 != 0 or n/4 > 2^32 - 512; ws_bytes too
+ * small; a malformed span table (begin % 4 != 0, numel == 0, unsorted, overlapping, past n, n_spans outside 1..OSI_OPT_MAX_SEGMENTS,
+ * or NULL with n_spans != 0); a norm_type other than the two constants; max_norm negative or NaN; a non-finite grad_scale.
+ *
+ * osi_adam_step_groups_dev / osi_sgd_step_groups_dev: the contract of osi_adam_step_groups / osi_sgd_step_groups, with the scalar
+ * read by the kernel from *grad_scale_dev (device memory, 4-byte aligned, written by earlier work on the stream, e.g. out2 + 1): the
+ * result is the bits of the host-scalar entry point called with grad_scale = that value. */
+#define OSI_NORM_INF 0
+#define OSI_NORM_L2 2
+typedef struct {
+    unsigned long long begin, numel; /* in floats; begin % 4 == 0, numel >= 1 */
+} osi_grad_span;
+size_t osi_grad_norm_workspace(size_t n);
+int osi_grad_clip_scale(const float* grad, size_t n, const osi_grad_span* spans, int n_spans, int norm_type, float grad_scale,
+                        float max_norm, void* ws, size_t ws_bytes, float* out2, osi_stream_t stream);
+int osi_adam_step_groups_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, size_t n,
+                             const osi_opt_segment* segments, int n_segments, const osi_adam_group* groups, int n_groups,
+                             const float* grad_scale_dev, osi_stream_t stream);
+int osi_sgd_step_groups_dev(float* param, const float* grad, float* momentum_buf, size_t n, const osi_opt_segment* segments,
+                            int n_segments, const osi_sgd_group* groups, int n_groups, const float* grad_scale_dev,
+                            osi_stream_t stream);
 int osi_fill_f32(float* p, size_t n, float value, osi_stream_t stream);
 int osi_scale_f32(float* p, size_t n, float s, osi_stream_t stream);
 /* ABI 10. dst[i] += src[i] (one fp32 add per element): the sum of two gradient arenas, e.g. the clean and the adversarial backward of

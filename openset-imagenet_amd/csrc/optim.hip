@@ -7,6 +7,7 @@
 // sum of two gradient arenas: the clean and the adversarial backward of one step, openset_imagenet/adversary.py).
 #include "osi_common.h"
 
+#include <cmath>
 #include <cstring>
 
 namespace {
@@ -140,9 +141,17 @@ struct SegWalker {
     }
 };
 
+// GS: the gradient scalar as the kernels take it. float = in the kernel arguments (osi_*_step_groups); const float* = one float in
+// device memory, written by an earlier launch on the stream (osi_*_step_groups_dev, after osi_grad_clip_scale): a uniform load, after
+// which the body is the same code on the same value, hence the same bits.
+__device__ __forceinline__ float gs_value(float s) { return s; }
+__device__ __forceinline__ float gs_value(const float* s) { return *s; }
+
+template <class GS>
 __global__ __launch_bounds__(256) void k_adam_groups(f32x4* __restrict__ p, const f32x4* __restrict__ g, f32x4* __restrict__ m,
                                                     f32x4* __restrict__ v, f32x4* __restrict__ vmax, uint32_t n4, uint32_t chunk4,
-                                                    float gscale, SegTable tab, AdamGroups grp) {
+                                                    GS gs, SegTable tab, AdamGroups grp) {
+    const float gscale = gs_value(gs);
     __shared__ uint32_t s_begin[OSI_OPT_MAX_SEGMENTS], s_end[OSI_OPT_MAX_SEGMENTS], s_group[OSI_OPT_MAX_SEGMENTS];
     __shared__ AdamScal s_scal[OSI_OPT_MAX_GROUPS];
     SegWalker<AdamScal, AdamGroups> w{s_begin, s_end, s_group, s_scal};
@@ -162,8 +171,10 @@ __global__ __launch_bounds__(256) void k_adam_groups(f32x4* __restrict__ p, cons
     }
 }
 
+template <class GS>
 __global__ __launch_bounds__(256) void k_sgd_groups(f32x4* __restrict__ p, const f32x4* __restrict__ g, f32x4* __restrict__ buf,
-                                                   uint32_t n4, uint32_t chunk4, float gscale, SegTable tab, SgdGroups grp) {
+                                                   uint32_t n4, uint32_t chunk4, GS gs, SegTable tab, SgdGroups grp) {
+    const float gscale = gs_value(gs);
     __shared__ uint32_t s_begin[OSI_OPT_MAX_SEGMENTS], s_end[OSI_OPT_MAX_SEGMENTS], s_group[OSI_OPT_MAX_SEGMENTS];
     __shared__ SgdScal s_scal[OSI_OPT_MAX_GROUPS];
     SegWalker<SgdScal, SgdGroups> w{s_begin, s_end, s_group, s_scal};
@@ -232,6 +243,189 @@ static int chunk_grid(size_t n4, uint32_t& chunk4) {
     return (int)((tiles + per - 1) / per);
 }
 
+// ---- gradient norm over spans of the arena, and the clipping scalar (osi_grad_clip_scale) ---------------------------------------
+// A span is a tensor: units [begin, end) of 4 floats, of whose last unit only `last` floats (1..4) belong to it; the alignment lanes
+// behind them, like every unit outside every span, are skipped by selection (never multiplied by zero: they may hold anything).
+// The arena is cut as chunk_grid cuts it for the grouped kernels. Fixed order, no atomics: a lane adds its units in index order,
+// xor-butterfly over the wave, the four waves in order, one 8-byte partial per workgroup; k_grad_norm_final gives eight consecutive
+// partials to a lane, added in index order, then the same tree. L2 squares and sums in double ((double)g * g is exact); the
+// maximum norm compares the bit patterns of |g| as integers: the order of the non-negative floats with every NaN above +inf, so a NaN
+// element comes out as a NaN norm, as torch's does.
+struct SpanTable {
+    uint32_t begin[OSI_OPT_MAX_SEGMENTS], end[OSI_OPT_MAX_SEGMENTS];
+    uint8_t last[OSI_OPT_MAX_SEGMENTS];
+    int n;
+};
+
+template <int NORM> struct NormAcc;
+template <> struct NormAcc<OSI_NORM_L2> {
+    double v = 0.0;
+    __device__ __forceinline__ void add(float x, bool on) { const double d = (double)x; v += on ? d * d : 0.0; }
+    __device__ __forceinline__ void merge(unsigned long long bits) { v += __longlong_as_double((long long)bits); }
+    __device__ __forceinline__ void wave() {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    }
+    __device__ __forceinline__ unsigned long long bits() const { return (unsigned long long)__double_as_longlong(v); }
+    __device__ __forceinline__ double norm() const { return sqrt(v); }
+};
+template <> struct NormAcc<OSI_NORM_INF> {
+    uint32_t v = 0;
+    __device__ __forceinline__ void add(float x, bool on) { const uint32_t b = __float_as_uint(x) & 0x7FFFFFFFu; v = on && b > v ? b : v; }
+    __device__ __forceinline__ void merge(unsigned long long bits) { v = (uint32_t)bits > v ? (uint32_t)bits : v; }
+    __device__ __forceinline__ void wave() {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const uint32_t u = __shfl_xor(v, o, 64); v = u > v ? u : v; }
+    }
+    __device__ __forceinline__ unsigned long long bits() const { return v; }
+    __device__ __forceinline__ double norm() const { return (double)__uint_as_float(v); }
+};
+
+// wave, then the four waves in order; the total is valid in thread 0
+template <int NORM>
+__device__ __forceinline__ void block_reduce(NormAcc<NORM>& acc, unsigned long long* s_part) {
+    acc.wave();
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc.bits();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        acc = NormAcc<NORM>();
+        for (int w = 0; w < 4; ++w) acc.merge(s_part[w]);
+    }
+}
+
+template <int NORM>
+__global__ __launch_bounds__(256) void k_grad_norm(const f32x4* __restrict__ g, uint32_t n4, uint32_t chunk4, SpanTable tab,
+                                                  unsigned long long* __restrict__ ws) {
+    __shared__ uint32_t s_begin[OSI_OPT_MAX_SEGMENTS], s_end[OSI_OPT_MAX_SEGMENTS], s_last[OSI_OPT_MAX_SEGMENTS];
+    __shared__ unsigned long long s_part[4];
+    const int t = threadIdx.x;
+    if (t < OSI_OPT_MAX_SEGMENTS) { s_begin[t] = tab.begin[t]; s_end[t] = tab.end[t]; s_last[t] = tab.last[t]; }
+    __syncthreads();
+    const int nseg = tab.n;
+    const uint32_t lo = blockIdx.x * chunk4;                       // as in k_adam_groups: n4 <= 2^32 - 512, i += 256 cannot wrap
+    const uint32_t hi = n4 - lo < chunk4 ? n4 : lo + chunk4;
+    uint32_t i = lo + t;
+    int a = 0, b = nseg;                                           // first span that ends after unit i
+    while (a < b) { const int mid = (a + b) >> 1; if (s_end[mid] <= i) a = mid + 1; else b = mid; }
+    int st = a;
+    uint32_t cb = ~0u, ce = ~0u, cl = 4;
+    if (st < nseg) { cb = s_begin[st]; ce = s_end[st]; cl = s_last[st]; }
+    NormAcc<NORM> acc;
+    for (; i < hi && st < nseg; i += 256) {
+        if (i >= ce) {
+            do ++st; while (st < nseg && s_end[st] <= i);
+            if (st < nseg) { cb = s_begin[st]; ce = s_end[st]; cl = s_last[st]; }
+            else cb = ce = ~0u;
+        }
+        if (i < cb) continue;
+        const f32x4 x = g[i];
+        const uint32_t keep = i + 1 == ce ? cl : 4u;
+        acc.add(x.x, true); acc.add(x.y, keep > 1); acc.add(x.z, keep > 2); acc.add(x.w, keep > 3);
+    }
+    block_reduce(acc, s_part);
+    if (t == 0) ws[blockIdx.x] = acc.bits();                       // every workgroup writes its slot, an empty chunk its zero
+}
+
+// out2[0] = |grad_scale| * norm; out2[1] = grad_scale * min(1, max_norm / (out2[0] + 1e-6f)) in fp32 with torch's roundings: its
+// `max_norm / tensor` is reciprocal(tensor) * max_norm, and its clamp keeps a NaN
+template <int NORM>
+__global__ __launch_bounds__(256) void k_grad_norm_final(const unsigned long long* __restrict__ ws, int parts, float grad_scale,
+                                                        float max_norm, float* __restrict__ out2) {
+    __shared__ unsigned long long s_part[4];
+    NormAcc<NORM> acc;
+    const int first = threadIdx.x * 8;
+    for (int k = first; k < first + 8 && k < parts; ++k) acc.merge(ws[k]);
+    block_reduce(acc, s_part);
+    if (threadIdx.x == 0) {
+        const float norm = (float)(fabs((double)grad_scale) * acc.norm());
+        float coef = (1.0f / (norm + 1e-6f)) * max_norm;
+        coef = coef != coef ? coef : (coef < 1.0f ? coef : 1.0f);
+        out2[0] = norm;
+        out2[1] = grad_scale * coef;
+    }
+}
+
+static bool norm_arena_ok(size_t n) { return n > 0 && n % 4 == 0 && n / 4 <= 0xFFFFFFFFull - 511; }
+
+// Validates the caller's span table against the arena (n floats) and packs it; spans == NULL with n_spans == 0 is [0, n).
+static bool fill_span_table(SpanTable& tab, const osi_grad_span* spans, int n_spans, size_t n) {
+    memset(&tab, 0, sizeof tab);
+    if (!spans) {
+        if (n_spans != 0) return false;
+        tab.begin[0] = 0; tab.end[0] = (uint32_t)(n / 4); tab.last[0] = 4; tab.n = 1;
+        return true;
+    }
+    if (n_spans < 1 || n_spans > OSI_OPT_MAX_SEGMENTS) return false;
+    unsigned long long prev_end = 0;
+    for (int i = 0; i < n_spans; ++i) {
+        const unsigned long long b = spans[i].begin, m = spans[i].numel;
+        if (b % 4 != 0 || m < 1 || b < prev_end || b >= n || m > n - b) return false;
+        tab.begin[i] = (uint32_t)(b / 4); tab.end[i] = (uint32_t)((b + m + 3) / 4); tab.last[i] = (uint8_t)(m % 4 ? m % 4 : 4);
+        prev_end = b + m;
+    }
+    tab.n = n_spans;
+    return true;
+}
+
+// The per-group scalars of osi_*_step_groups(_dev), prepared in double; false = a refused option.
+static bool fill_adam_groups(AdamGroups& gs, const osi_adam_group* groups, int n_groups, const float* max_exp_avg_sq) {
+    memset(&gs, 0, sizeof gs);
+    for (int i = 0; i < n_groups; ++i) {
+        const osi_adam_group& u = groups[i];
+        if (!(u.step >= 1 && (!u.amsgrad || max_exp_avg_sq))) return false;
+        const double bc1 = 1.0 - pow(u.beta1, (double)u.step);
+        const double bc2 = 1.0 - pow(u.beta2, (double)u.step);
+        gs.g[i] = AdamScal{(float)(u.lr / bc1), (float)sqrt(bc2), (float)u.beta2, (float)(1.0 - u.beta1), (float)(1.0 - u.beta2),
+                           (float)u.eps, (float)u.weight_decay, (float)(1.0 - u.lr * u.weight_decay),
+                           (u.decoupled ? OPT_DECOUPLED : 0u) | (u.amsgrad ? OPT_AMSGRAD : 0u) | (u.maximize ? OPT_MAXIMIZE : 0u)};
+    }
+    return true;
+}
+static bool fill_sgd_groups(SgdGroups& gs, const osi_sgd_group* groups, int n_groups) {
+    memset(&gs, 0, sizeof gs);
+    for (int i = 0; i < n_groups; ++i) {
+        const osi_sgd_group& u = groups[i];
+        if (!(!u.nesterov || (u.momentum > 0.0 && u.dampening == 0.0))) return false;
+        gs.g[i] = SgdScal{(float)u.lr, (float)u.momentum, (float)(1.0 - u.dampening), (float)u.weight_decay,
+                          (u.nesterov ? OPT_NESTEROV : 0u) | (u.maximize ? OPT_MAXIMIZE : 0u) |
+                              (u.momentum != 0.0 ? OPT_MOMENTUM | (u.first_step ? OPT_FIRST : 0u) : 0u)};
+    }
+    return true;
+}
+
+// GS = float (the scalar by value) or const float* (in device memory): one host path for both forms of the grouped steps
+template <class GS>
+static int adam_groups_launch(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, size_t n,
+                              const osi_opt_segment* segments, int n_segments, const osi_adam_group* groups, int n_groups, GS gs_arg,
+                              osi_stream_t stream) {
+    OSI_REQUIRE(param && grad && exp_avg && exp_avg_sq && groups);
+    SegTable tab;
+    OSI_REQUIRE(fill_seg_table(tab, segments, n_segments, n_groups, n));
+    AdamGroups gs;
+    OSI_REQUIRE(fill_adam_groups(gs, groups, n_groups, max_exp_avg_sq));
+    uint32_t chunk4;
+    const int grid = chunk_grid(n / 4, chunk4);
+    hipLaunchKernelGGL(k_adam_groups<GS>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (f32x4*)param, (const f32x4*)grad,
+                       (f32x4*)exp_avg, (f32x4*)exp_avg_sq, (f32x4*)max_exp_avg_sq, (uint32_t)(n / 4), chunk4, gs_arg, tab, gs);
+    OSI_LAUNCH_CHECK();
+    return OSI_OK;
+}
+template <class GS>
+static int sgd_groups_launch(float* param, const float* grad, float* momentum_buf, size_t n, const osi_opt_segment* segments,
+                             int n_segments, const osi_sgd_group* groups, int n_groups, GS gs_arg, osi_stream_t stream) {
+    OSI_REQUIRE(param && grad && momentum_buf && groups);
+    SegTable tab;
+    OSI_REQUIRE(fill_seg_table(tab, segments, n_segments, n_groups, n));
+    SgdGroups gs;
+    OSI_REQUIRE(fill_sgd_groups(gs, groups, n_groups));
+    uint32_t chunk4;
+    const int grid = chunk_grid(n / 4, chunk4);
+    hipLaunchKernelGGL(k_sgd_groups<GS>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (f32x4*)param, (const f32x4*)grad,
+                       (f32x4*)momentum_buf, (uint32_t)(n / 4), chunk4, gs_arg, tab, gs);
+    OSI_LAUNCH_CHECK();
+    return OSI_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -260,46 +454,61 @@ int osi_sgd_step(float* param, const float* grad, float* momentum_buf, size_t n,
 int osi_adam_step_groups(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, size_t n,
                          const osi_opt_segment* segments, int n_segments, const osi_adam_group* groups, int n_groups,
                          float grad_scale, osi_stream_t stream) {
-    OSI_REQUIRE(param && grad && exp_avg && exp_avg_sq && groups);
-    SegTable tab;
-    OSI_REQUIRE(fill_seg_table(tab, segments, n_segments, n_groups, n));
-    AdamGroups gs;
-    memset(&gs, 0, sizeof gs);
-    for (int i = 0; i < n_groups; ++i) {
-        const osi_adam_group& u = groups[i];
-        OSI_REQUIRE(u.step >= 1 && (!u.amsgrad || max_exp_avg_sq));
-        const double bc1 = 1.0 - pow(u.beta1, (double)u.step);
-        const double bc2 = 1.0 - pow(u.beta2, (double)u.step);
-        gs.g[i] = AdamScal{(float)(u.lr / bc1), (float)sqrt(bc2), (float)u.beta2, (float)(1.0 - u.beta1), (float)(1.0 - u.beta2),
-                           (float)u.eps, (float)u.weight_decay, (float)(1.0 - u.lr * u.weight_decay),
-                           (u.decoupled ? OPT_DECOUPLED : 0u) | (u.amsgrad ? OPT_AMSGRAD : 0u) | (u.maximize ? OPT_MAXIMIZE : 0u)};
-    }
-    uint32_t chunk4;
-    const int grid = chunk_grid(n / 4, chunk4);
-    hipLaunchKernelGGL(k_adam_groups, dim3(grid), dim3(256), 0, (hipStream_t)stream, (f32x4*)param, (const f32x4*)grad,
-                       (f32x4*)exp_avg, (f32x4*)exp_avg_sq, (f32x4*)max_exp_avg_sq, (uint32_t)(n / 4), chunk4, grad_scale, tab, gs);
-    OSI_LAUNCH_CHECK();
-    return OSI_OK;
+    return adam_groups_launch<float>(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, n, segments, n_segments, groups, n_groups,
+                                     grad_scale, stream);
 }
 
 int osi_sgd_step_groups(float* param, const float* grad, float* momentum_buf, size_t n, const osi_opt_segment* segments,
                         int n_segments, const osi_sgd_group* groups, int n_groups, float grad_scale, osi_stream_t stream) {
-    OSI_REQUIRE(param && grad && momentum_buf && groups);
-    SegTable tab;
-    OSI_REQUIRE(fill_seg_table(tab, segments, n_segments, n_groups, n));
-    SgdGroups gs;
-    memset(&gs, 0, sizeof gs);
-    for (int i = 0; i < n_groups; ++i) {
-        const osi_sgd_group& u = groups[i];
-        OSI_REQUIRE(!u.nesterov || (u.momentum > 0.0 && u.dampening == 0.0));
-        gs.g[i] = SgdScal{(float)u.lr, (float)u.momentum, (float)(1.0 - u.dampening), (float)u.weight_decay,
-                          (u.nesterov ? OPT_NESTEROV : 0u) | (u.maximize ? OPT_MAXIMIZE : 0u) |
-                              (u.momentum != 0.0 ? OPT_MOMENTUM | (u.first_step ? OPT_FIRST : 0u) : 0u)};
-    }
+    return sgd_groups_launch<float>(param, grad, momentum_buf, n, segments, n_segments, groups, n_groups, grad_scale, stream);
+}
+
+int osi_adam_step_groups_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, size_t n,
+                             const osi_opt_segment* segments, int n_segments, const osi_adam_group* groups, int n_groups,
+                             const float* grad_scale_dev, osi_stream_t stream) {
+    OSI_REQUIRE(grad_scale_dev && ((uintptr_t)grad_scale_dev & 3) == 0);
+    return adam_groups_launch<const float*>(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, n, segments, n_segments, groups,
+                                            n_groups, grad_scale_dev, stream);
+}
+
+int osi_sgd_step_groups_dev(float* param, const float* grad, float* momentum_buf, size_t n, const osi_opt_segment* segments,
+                            int n_segments, const osi_sgd_group* groups, int n_groups, const float* grad_scale_dev,
+                            osi_stream_t stream) {
+    OSI_REQUIRE(grad_scale_dev && ((uintptr_t)grad_scale_dev & 3) == 0);
+    return sgd_groups_launch<const float*>(param, grad, momentum_buf, n, segments, n_segments, groups, n_groups, grad_scale_dev, stream);
+}
+
+size_t osi_grad_norm_workspace(size_t n) {
+    if (!norm_arena_ok(n)) return 0;
+    uint32_t chunk4;
+    return (size_t)chunk_grid(n / 4, chunk4) * sizeof(unsigned long long);
+}
+
+int osi_grad_clip_scale(const float* grad, size_t n, const osi_grad_span* spans, int n_spans, int norm_type, float grad_scale,
+                        float max_norm, void* ws, size_t ws_bytes, float* out2, osi_stream_t stream) {
+    OSI_REQUIRE(grad && ws && out2 && norm_arena_ok(n));
+    OSI_REQUIRE(((uintptr_t)grad & 15) == 0 && ((uintptr_t)ws & 7) == 0 && ((uintptr_t)out2 & 3) == 0);
+    OSI_REQUIRE(ws_bytes >= osi_grad_norm_workspace(n));
+    OSI_REQUIRE(norm_type == OSI_NORM_L2 || norm_type == OSI_NORM_INF);
+    OSI_REQUIRE(max_norm >= 0.0f && std::isfinite(grad_scale));      // a NaN max_norm fails the comparison
+    SpanTable tab;
+    OSI_REQUIRE(fill_span_table(tab, spans, n_spans, n));
     uint32_t chunk4;
     const int grid = chunk_grid(n / 4, chunk4);
-    hipLaunchKernelGGL(k_sgd_groups, dim3(grid), dim3(256), 0, (hipStream_t)stream, (f32x4*)param, (const f32x4*)grad,
-                       (f32x4*)momentum_buf, (uint32_t)(n / 4), chunk4, grad_scale, tab, gs);
+    unsigned long long* parts = (unsigned long long*)ws;
+    if (norm_type == OSI_NORM_L2) {
+        hipLaunchKernelGGL(k_grad_norm<OSI_NORM_L2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const f32x4*)grad,
+                           (uint32_t)(n / 4), chunk4, tab, parts);
+        OSI_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_grad_norm_final<OSI_NORM_L2>, dim3(1), dim3(256), 0, (hipStream_t)stream, parts, grid, grad_scale,
+                           max_norm, out2);
+    } else {
+        hipLaunchKernelGGL(k_grad_norm<OSI_NORM_INF>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const f32x4*)grad,
+                           (uint32_t)(n / 4), chunk4, tab, parts);
+        OSI_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_grad_norm_final<OSI_NORM_INF>, dim3(1), dim3(256), 0, (hipStream_t)stream, parts, grid, grad_scale,
+                           max_norm, out2);
+    }
     OSI_LAUNCH_CHECK();
     return OSI_OK;
 }

@@ -8,7 +8,8 @@
 //   torch.ops.osi.resnet50_backward_adv the same, the last stage writing the FGSM batch; torch.ops.osi.grad_accumulate sums two arenas
 //   torch.ops.osi.resnet50_grads_ready  config/train.yaml:18,35-39 (hand a finished stage's gradients to the communication stream)
 //   torch.ops.osi.loss_fwd_bwd        losses.py:16-29, train.py:343-347 (the three losses + objectosphere term, value and gradient)
-//   torch.ops.osi.adam_step / sgd_step    train.py:139, 356-359; adam_step_groups / sgd_step_groups: the same with parameter groups
+//   torch.ops.osi.adam_step / sgd_step    train.py:139, 356-359; adam_step_groups / sgd_step_groups: the same with parameter groups;
+//                                         grad_clip_scale + *_step_groups_dev: gradient-norm clipping, the scalar left on the device
 //   torch.ops.osi.stage_canvas        train.py:259-263 after decode + resize (crop, flip, ToTensor, NHWC4)
 //   torch.ops.osi.softmax / confidence_accumulate    train.py:177, metrics.py:8-42
 //
@@ -262,8 +263,9 @@ std::vector<osi_opt_segment> opt_segments(c10::ArrayRef<int64_t> segments) {
     return seg;
 }
 
-void adam_step_groups(Tensor params, const Tensor& grads, Tensor exp_avg, Tensor exp_avg_sq, const std::optional<Tensor>& max_exp_avg_sq,
-                      c10::ArrayRef<int64_t> segments, c10::ArrayRef<double> groups, double grad_scale) {
+// grad_scale_dev == nullptr: the scalar by value (osi_adam_step_groups); else the kernel reads it from device memory (_dev)
+void adam_groups_common(Tensor& params, const Tensor& grads, Tensor& exp_avg, Tensor& exp_avg_sq, const std::optional<Tensor>& max_exp_avg_sq,
+                        c10::ArrayRef<int64_t> segments, c10::ArrayRef<double> groups, double grad_scale, const Tensor* grad_scale_dev) {
     need(params, at::kFloat, "params"); need(grads, at::kFloat, "grads"); need(exp_avg, at::kFloat, "exp_avg"); need(exp_avg_sq, at::kFloat, "exp_avg_sq");
     TORCH_CHECK(grads.numel() == params.numel() && exp_avg.numel() == params.numel() && exp_avg_sq.numel() == params.numel());
     float* vmax = nullptr;
@@ -280,13 +282,18 @@ void adam_step_groups(Tensor params, const Tensor& grads, Tensor exp_avg, Tensor
         gs[i] = osi_adam_group{r[0], r[1], r[2], r[3], r[4], (long long)r[5], r[6] != 0.0, r[7] != 0.0, r[8] != 0.0};
     }
     c10::hip::HIPGuardMasqueradingAsCUDA guard(params.device());
-    ok(osi_adam_step_groups(params.data_ptr<float>(), grads.data_ptr<float>(), exp_avg.data_ptr<float>(), exp_avg_sq.data_ptr<float>(), vmax,
-                            (size_t)params.numel(), seg.data(), (int)seg.size(), gs.data(), (int)gs.size(), (float)grad_scale,
-                            stream_of(params)), "osi_adam_step_groups");
+    if (grad_scale_dev)
+        ok(osi_adam_step_groups_dev(params.data_ptr<float>(), grads.data_ptr<float>(), exp_avg.data_ptr<float>(), exp_avg_sq.data_ptr<float>(),
+                                    vmax, (size_t)params.numel(), seg.data(), (int)seg.size(), gs.data(), (int)gs.size(),
+                                    grad_scale_dev->data_ptr<float>(), stream_of(params)), "osi_adam_step_groups_dev");
+    else
+        ok(osi_adam_step_groups(params.data_ptr<float>(), grads.data_ptr<float>(), exp_avg.data_ptr<float>(), exp_avg_sq.data_ptr<float>(), vmax,
+                                (size_t)params.numel(), seg.data(), (int)seg.size(), gs.data(), (int)gs.size(), (float)grad_scale,
+                                stream_of(params)), "osi_adam_step_groups");
 }
 
-void sgd_step_groups(Tensor params, const Tensor& grads, Tensor momentum_buffer, c10::ArrayRef<int64_t> segments,
-                     c10::ArrayRef<double> groups, double grad_scale) {
+void sgd_groups_common(Tensor& params, const Tensor& grads, Tensor& momentum_buffer, c10::ArrayRef<int64_t> segments,
+                       c10::ArrayRef<double> groups, double grad_scale, const Tensor* grad_scale_dev) {
     need(params, at::kFloat, "params"); need(grads, at::kFloat, "grads"); need(momentum_buffer, at::kFloat, "momentum_buffer");
     TORCH_CHECK(grads.numel() == params.numel() && momentum_buffer.numel() == params.numel());
     TORCH_CHECK(groups.size() % 7 == 0, "groups: rows of (lr, momentum, dampening, weight_decay, nesterov, first_step, maximize)");
@@ -297,9 +304,62 @@ void sgd_step_groups(Tensor params, const Tensor& grads, Tensor momentum_buffer,
         gs[i] = osi_sgd_group{r[0], r[1], r[2], r[3], r[4] != 0.0, r[5] != 0.0, r[6] != 0.0};
     }
     c10::hip::HIPGuardMasqueradingAsCUDA guard(params.device());
-    ok(osi_sgd_step_groups(params.data_ptr<float>(), grads.data_ptr<float>(), momentum_buffer.data_ptr<float>(), (size_t)params.numel(),
-                           seg.data(), (int)seg.size(), gs.data(), (int)gs.size(), (float)grad_scale, stream_of(params)),
-       "osi_sgd_step_groups");
+    if (grad_scale_dev)
+        ok(osi_sgd_step_groups_dev(params.data_ptr<float>(), grads.data_ptr<float>(), momentum_buffer.data_ptr<float>(), (size_t)params.numel(),
+                                   seg.data(), (int)seg.size(), gs.data(), (int)gs.size(), grad_scale_dev->data_ptr<float>(),
+                                   stream_of(params)), "osi_sgd_step_groups_dev");
+    else
+        ok(osi_sgd_step_groups(params.data_ptr<float>(), grads.data_ptr<float>(), momentum_buffer.data_ptr<float>(), (size_t)params.numel(),
+                               seg.data(), (int)seg.size(), gs.data(), (int)gs.size(), (float)grad_scale, stream_of(params)),
+           "osi_sgd_step_groups");
+}
+
+void adam_step_groups(Tensor params, const Tensor& grads, Tensor exp_avg, Tensor exp_avg_sq, const std::optional<Tensor>& max_exp_avg_sq,
+                      c10::ArrayRef<int64_t> segments, c10::ArrayRef<double> groups, double grad_scale) {
+    adam_groups_common(params, grads, exp_avg, exp_avg_sq, max_exp_avg_sq, segments, groups, grad_scale, nullptr);
+}
+
+void sgd_step_groups(Tensor params, const Tensor& grads, Tensor momentum_buffer, c10::ArrayRef<int64_t> segments,
+                     c10::ArrayRef<double> groups, double grad_scale) {
+    sgd_groups_common(params, grads, momentum_buffer, segments, groups, grad_scale, nullptr);
+}
+
+// the scalar of a *_dev step: one fp32 element on the arena's device (e.g. the second element of grad_clip_scale's out2)
+void need_scalar(const Tensor& s, const Tensor& params) {
+    need(s, at::kFloat, "grad_scale", NATURAL);
+    TORCH_CHECK(s.numel() == 1 && s.device() == params.device(), "osi: grad_scale must be one fp32 element on the arena's device");
+}
+
+void adam_step_groups_dev(Tensor params, const Tensor& grads, Tensor exp_avg, Tensor exp_avg_sq, const std::optional<Tensor>& max_exp_avg_sq,
+                          c10::ArrayRef<int64_t> segments, c10::ArrayRef<double> groups, const Tensor& grad_scale) {
+    need_scalar(grad_scale, params);
+    adam_groups_common(params, grads, exp_avg, exp_avg_sq, max_exp_avg_sq, segments, groups, 0.0, &grad_scale);
+}
+
+void sgd_step_groups_dev(Tensor params, const Tensor& grads, Tensor momentum_buffer, c10::ArrayRef<int64_t> segments,
+                         c10::ArrayRef<double> groups, const Tensor& grad_scale) {
+    need_scalar(grad_scale, params);
+    sgd_groups_common(params, grads, momentum_buffer, segments, groups, 0.0, &grad_scale);
+}
+
+// spans: flat (begin, numel) pairs in floats, empty = the whole arena. out2 <- (norm of grad_scale * g over the spans, the scalar a
+// clipped step multiplies the gradients by); nothing is read back. Everything else is validated by the C ABI.
+void grad_clip_scale(const Tensor& grads, c10::ArrayRef<int64_t> spans, int64_t norm_type, double grad_scale, double max_norm,
+                     Tensor workspace, Tensor out2) {
+    need(grads, at::kFloat, "grads"); need(workspace, at::kByte, "workspace"); need(out2, at::kFloat, "out2", NATURAL);
+    TORCH_CHECK(out2.numel() == 2, "osi::grad_clip_scale: out2 holds two floats (norm, scalar)");
+    TORCH_CHECK(workspace.device() == grads.device() && out2.device() == grads.device(), "osi::grad_clip_scale: tensors on different devices");
+    TORCH_CHECK((size_t)workspace.numel() >= osi_grad_norm_workspace((size_t)grads.numel()), "osi::grad_clip_scale: workspace too small");
+    TORCH_CHECK(spans.size() % 2 == 0, "spans: flat (begin, numel) pairs");
+    std::vector<osi_grad_span> sp(spans.size() / 2);
+    for (size_t i = 0; i < sp.size(); ++i) {
+        TORCH_CHECK(spans[2 * i] >= 0 && spans[2 * i + 1] >= 0, "span bounds out of range");
+        sp[i] = osi_grad_span{(unsigned long long)spans[2 * i], (unsigned long long)spans[2 * i + 1]};
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(grads.device());
+    ok(osi_grad_clip_scale(grads.data_ptr<float>(), (size_t)grads.numel(), sp.empty() ? nullptr : sp.data(), (int)sp.size(), (int)norm_type,
+                           (float)grad_scale, (float)max_norm, workspace.data_ptr(), (size_t)workspace.numel(), out2.data_ptr<float>(),
+                           stream_of(grads)), "osi_grad_clip_scale");
 }
 
 Tensor stage_canvas(const Tensor& canvas, const std::optional<Tensor>& crop_xy, const std::optional<Tensor>& flip, int64_t H, int64_t W) {
@@ -357,6 +417,11 @@ TORCH_LIBRARY(osi, m) {
     m.def("adam_step_groups(Tensor(a!) params, Tensor grads, Tensor(b!) exp_avg, Tensor(c!) exp_avg_sq, Tensor(d!)? max_exp_avg_sq, "
           "int[] segments, float[] groups, float grad_scale) -> ()");
     m.def("sgd_step_groups(Tensor(a!) params, Tensor grads, Tensor(b!) momentum_buffer, int[] segments, float[] groups, float grad_scale) -> ()");
+    m.def("adam_step_groups_dev(Tensor(a!) params, Tensor grads, Tensor(b!) exp_avg, Tensor(c!) exp_avg_sq, Tensor(d!)? max_exp_avg_sq, "
+          "int[] segments, float[] groups, Tensor grad_scale) -> ()");
+    m.def("sgd_step_groups_dev(Tensor(a!) params, Tensor grads, Tensor(b!) momentum_buffer, int[] segments, float[] groups, Tensor grad_scale) -> ()");
+    m.def("grad_clip_scale(Tensor grads, int[] spans, int norm_type, float grad_scale, float max_norm, Tensor(a!) workspace, "
+          "Tensor(b!) out2) -> ()");
     m.def("stage_canvas(Tensor canvas, Tensor? crop_xy, Tensor? flip, int H, int W) -> Tensor");   // crop corners are read-only (clamped in registers)
     m.def("softmax(Tensor logits) -> Tensor");
     m.def("confidence_accumulate(Tensor logits, Tensor target, float offset, int unknown_class, int last_valid_class, Tensor(a!) acc4) -> ()");
@@ -376,6 +441,9 @@ TORCH_LIBRARY_IMPL(osi, CUDA, m) {
     m.impl("sgd_step", &sgd_step);
     m.impl("adam_step_groups", &adam_step_groups);
     m.impl("sgd_step_groups", &sgd_step_groups);
+    m.impl("adam_step_groups_dev", &adam_step_groups_dev);
+    m.impl("sgd_step_groups_dev", &sgd_step_groups_dev);
+    m.impl("grad_clip_scale", &grad_clip_scale);
     m.impl("stage_canvas", &stage_canvas);
     m.impl("softmax", &softmax);
     m.impl("confidence_accumulate", &confidence_accumulate);

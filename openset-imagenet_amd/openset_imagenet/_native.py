@@ -74,7 +74,13 @@ class SgdGroup(Structure):
                 ("nesterov", c_int), ("first_step", c_int), ("maximize", c_int)]
 
 
+class GradSpan(Structure):
+    """osi_grad_span: one tensor of the gradient arena, `numel` floats from float index `begin` (begin % 4 == 0)"""
+    _fields_ = [("begin", ctypes.c_ulonglong), ("numel", ctypes.c_ulonglong)]
+
+
 OPT_MAX_SEGMENTS, OPT_MAX_GROUPS = 192, 16
+NORM_INF, NORM_L2 = 0, 2
 
 P = c_void_p
 _PD = POINTER(ConvDesc)
@@ -165,6 +171,10 @@ _SIGS = {
     "osi_sgd_step": (c_int, [P, P, P, c_size_t, c_float, c_float, c_int, c_float, P]),
     "osi_adam_step_groups": (c_int, [P, P, P, P, P, c_size_t, POINTER(OptSegment), c_int, POINTER(AdamGroup), c_int, c_float, P]),
     "osi_sgd_step_groups": (c_int, [P, P, P, c_size_t, POINTER(OptSegment), c_int, POINTER(SgdGroup), c_int, c_float, P]),
+    "osi_grad_norm_workspace": (c_size_t, [c_size_t]),
+    "osi_grad_clip_scale": (c_int, [P, c_size_t, POINTER(GradSpan), c_int, c_int, c_float, c_float, P, c_size_t, P, P]),
+    "osi_adam_step_groups_dev": (c_int, [P, P, P, P, P, c_size_t, POINTER(OptSegment), c_int, POINTER(AdamGroup), c_int, P, P]),
+    "osi_sgd_step_groups_dev": (c_int, [P, P, P, c_size_t, POINTER(OptSegment), c_int, POINTER(SgdGroup), c_int, P, P]),
     "osi_fill_f32": (c_int, [P, c_size_t, c_float, P]),
     "osi_scale_f32": (c_int, [P, c_size_t, c_float, P]),
     "osi_grad_accumulate": (c_int, [P, P, c_size_t, P]),

@@ -124,10 +124,11 @@ class Plan:
         return torch.full_like(labels, negative_label(self.loss_type, n_logits))
 
 
-def two_pass_step(model, net, images, labels, loss, plan):
+def two_pass_step(model, net, images, labels, loss, plan, accumulate=False):
     """The clean and the adversarial pass of one step (between zero_grad() and optimizer.step()); returns (j, j_adv) detached.
     `loss(logits, features, labels)` is the loop's loss; `net` is the MI355X ResNet50 behind `model` (fused route), or None: any
-    torch model on the autograd route."""
+    torch model on the autograd route. `accumulate`: this is a later micro-step of a gradient-accumulation group (train(), key
+    opt.accumulate), so the clean pass adds to the gradients in place as well (autograd does that by itself)."""
     fgsm = plan.who == "fgsm"
     if net is None:
         x = images.detach().requires_grad_() if fgsm else images
@@ -141,8 +142,8 @@ def two_pass_step(model, net, images, labels, loss, plan):
         return j.detach(), j_adv.detach()
     logits, features = model(images)
     j = loss(logits, features, labels)
-    if fgsm:
-        net.next_backward(fgsm=plan.strength)
+    if fgsm or accumulate:
+        net.next_backward(fgsm=plan.strength if fgsm else None, accumulate=accumulate)
     j.backward()
     negatives = net.adversarial_batch() if fgsm else noise_negatives(images, plan.who, plan.strength, plan.generator)
     logits_n, features_n = model(negatives)

@@ -12,6 +12,13 @@ dicts with per-group options, `add_param_group`, weight decay (L2 and decoupled:
 `maximize`, and torch's skipping rule for parameters with `requires_grad == False`. Whatever the layout, a step is one launch:
 the plain `osi_adam_step` / `osi_sgd_step` when one group holds the whole arena with the reference's options (bit for bit the
 launch of earlier releases), `osi_adam_step_groups` / `osi_sgd_step_groups` with a segment table otherwise.
+
+`step(clip_norm=x, norm_type=2 | inf)` clips the gradient norm as `torch.nn.utils.clip_grad_norm_(params, x, norm_type)` followed by
+`step()` would, without a host read: one streaming pass leaves the norm of `grad_scale * g` over the tensors this step updates and
+the step's scalar `grad_scale * min(1, x / (norm + 1e-6))` in device memory (`osi_grad_clip_scale`, two launches), and the grouped
+kernel reads that scalar there (`osi_*_step_groups_dev`). `opt.grad_norm` holds the pre-clip norm (a 0-dim device tensor), what
+`clip_grad_norm_` returns; `clip_norm=float("inf")` only measures. The gradient arena itself is left as the backward wrote it: the
+clipped gradients exist only inside the step. Without `clip_norm` a step is the launch it always was and `grad_norm` is None.
 """
 import torch
 
@@ -39,6 +46,16 @@ def _only_off(**flags):
             raise ValueError(f"{k}={v!r}: the fused optimizers are their own implementation; pass None / False or use torch.optim.*")
 
 
+def _check_clip(clip_norm, norm_type):
+    """(max_norm, OSI_NORM_*) of step(clip_norm=, norm_type=); ValueError on anything clip_grad_norm_ would not make sense of"""
+    if isinstance(clip_norm, bool) or not isinstance(clip_norm, (int, float)) or not clip_norm > 0:      # NaN fails the comparison
+        raise ValueError(f"clip_norm must be a number > 0 (float('inf') measures only), got {clip_norm!r}")
+    x = float(clip_norm)
+    if isinstance(norm_type, bool) or not isinstance(norm_type, (int, float)) or norm_type not in (2, float("inf")):
+        raise ValueError(f"norm_type must be 2 or float('inf'), got {norm_type!r}")
+    return x, (N.NORM_L2 if norm_type == 2 else N.NORM_INF)
+
+
 def split_decay(model, weight_decay, no_decay="norm_bias"):
     """The two-group ImageNet recipe: [{params with ndim > 1, weight_decay}, {BatchNorm weights and biases, linear biases,
     weight_decay 0}]. `model` may be a DistributedDataParallel wrapper."""
@@ -63,6 +80,9 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self._bound = -1             # the _version whose parameters have their state views bound
         self._plan = None
         self._held_cache = None
+        self._spans = ()             # flat (begin, numel) pairs of the tensors of the current table: what a clipped step takes its norm over
+        self._clip_buf = None        # (workspace, out2) of osi_grad_clip_scale, allocated once per device
+        self.grad_norm = None        # the pre-clip norm of the latest step(clip_norm=...), a 0-dim device tensor; None otherwise
         if isinstance(model_or_params, torch.nn.Module):
             model_or_params = model_or_params.parameters()
         super().__init__(model_or_params, defaults)   # reference spelling: Adam(params=model.parameters(), lr=...)
@@ -170,7 +190,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
         m = self._model
         self._counts()      # the counts of the table that goes away, before _active changes
         active = sorted((idx, gi) for (gi, idx, p), on in zip(held, flags) if on)
-        kgroups, kindex, segments = [], {}, []
+        kgroups, kindex, segments, spans = [], {}, [], []
         for idx, gi in active:
             k = (gi, self._class_of(idx, self.param_groups[gi]))
             if k not in kindex:
@@ -178,6 +198,10 @@ class _FlatOptimizer(torch.optim.Optimizer):
                 kgroups.append((gi, idx))
             name, off, numel, shape = m._pinfo[idx]
             b4, e4, kg = off // 4, (off + numel + 3) // 4, kindex[k]
+            if spans and spans[-2] + spans[-1] == off:   # the tensor before ends here, on a unit boundary: no alignment lanes between
+                spans[-1] += numel
+            else:
+                spans += [off, numel]
             if segments and segments[-1][2] == kg and segments[-1][1] == b4:
                 segments[-1][1] = e4
             else:
@@ -189,7 +213,18 @@ class _FlatOptimizer(torch.optim.Optimizer):
         plain = len(self.param_groups) == 1 and len(active) == len(m._plist) == len(held) and len(kgroups) == 1
         self._plan = (key, plain, [v for s in segments for v in s], kgroups)
         self._active = active
+        self._spans = spans
         return self._plan[1:]
+
+    def _clip_scalar(self, grads, grad_scale, max_norm, norm):
+        """Launch the norm over this step's tensors; returns the step's scalar (one device float) and sets grad_norm. No host read."""
+        buf = self._clip_buf
+        if buf is None or buf[1].device != grads.device:
+            ws = torch.empty(max(int(N.lib().osi_grad_norm_workspace(grads.numel())), 16), dtype=torch.uint8, device=grads.device)
+            buf = self._clip_buf = (ws, torch.zeros(2, device=grads.device))
+        N.ops().grad_clip_scale(grads, self._spans, norm, float(grad_scale), max_norm, buf[0], buf[1])
+        self.grad_norm = buf[1][0].clone()
+        return buf[1][1:]
 
     def _stepped(self):
         """Count the step on every parameter that took part (those of the table: held and requiring grad)."""
@@ -269,8 +304,10 @@ class Adam(_FlatOptimizer):
         return not (g.get("weight_decay", 0) or g.get("amsgrad", False) or g.get("maximize", False))
 
     @torch.no_grad()
-    def step(self, closure=None, grad_scale=1.0):
+    def step(self, closure=None, grad_scale=1.0, clip_norm=None, norm_type=2.0):
         m = self._model
+        self.grad_norm = None
+        clip = None if clip_norm is None else _check_clip(clip_norm, norm_type)
         if self._skip_step():
             return
         plain, segments, kgroups = self._plan_for()
@@ -279,7 +316,8 @@ class Adam(_FlatOptimizer):
         self._ensure_state()
         p, gr = m.flat_parameters(), m.flat_gradients()
         fs = self._flat_state
-        if plain and self._plain_options(self.param_groups[0]):
+        scalar = None if clip is None else self._clip_scalar(gr, grad_scale, *clip)
+        if scalar is None and plain and self._plain_options(self.param_groups[0]):
             g = self.param_groups[0]
             N.ops().adam_step(p, gr, fs["exp_avg"], fs["exp_avg_sq"], float(g["lr"]), float(g["betas"][0]),
                               float(g["betas"][1]), float(g["eps"]), self._pstep[kgroups[0][1]] + self._lag + 1, float(grad_scale))
@@ -290,7 +328,10 @@ class Adam(_FlatOptimizer):
                 rows += [float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g.get("weight_decay", 0)),
                          float(self._pstep[idx] + self._lag + 1), float(bool(g.get("decoupled_weight_decay", False))),
                          float(bool(g.get("amsgrad", False))), float(bool(g.get("maximize", False)))]
-            N.ops().adam_step_groups(p, gr, fs["exp_avg"], fs["exp_avg_sq"], fs.get("max_exp_avg_sq"), segments, rows, float(grad_scale))
+            if scalar is None:
+                N.ops().adam_step_groups(p, gr, fs["exp_avg"], fs["exp_avg_sq"], fs.get("max_exp_avg_sq"), segments, rows, float(grad_scale))
+            else:    # the same launch over the same table, the scalar read from device memory
+                N.ops().adam_step_groups_dev(p, gr, fs["exp_avg"], fs["exp_avg_sq"], fs.get("max_exp_avg_sq"), segments, rows, scalar)
         self._stepped()
 
 
@@ -349,8 +390,10 @@ class SGD(_FlatOptimizer):
             self._has_buf[idx] = self.state.get(p, {}).get("momentum_buffer") is not None
 
     @torch.no_grad()
-    def step(self, closure=None, grad_scale=1.0):
+    def step(self, closure=None, grad_scale=1.0, clip_norm=None, norm_type=2.0):
         m = self._model
+        self.grad_norm = None
+        clip = None if clip_norm is None else _check_clip(clip_norm, norm_type)
         if self._skip_step():
             return
         plain, segments, kgroups = self._plan_for()
@@ -359,7 +402,8 @@ class SGD(_FlatOptimizer):
         self._ensure_state()
         p, gr = m.flat_parameters(), m.flat_gradients()
         buf = self._flat_state["momentum_buffer"]
-        if plain and self._plain_options(self.param_groups[0]):
+        scalar = None if clip is None else self._clip_scalar(gr, grad_scale, *clip)
+        if scalar is None and plain and self._plain_options(self.param_groups[0]):
             # k_sgd writes the buffer whatever the momentum, so `first` is the first step of a fresh optimizer, momentum 0 included
             g = self.param_groups[0]
             started = plain_first = not self._has_buf.get(kgroups[0][1], False)
@@ -372,7 +416,10 @@ class SGD(_FlatOptimizer):
                 started = started or first
                 rows += [float(g["lr"]), float(g["momentum"]), float(g.get("dampening", 0)), float(g.get("weight_decay", 0)),
                          float(bool(g.get("nesterov", False))), float(first), float(bool(g.get("maximize", False)))]
-            N.ops().sgd_step_groups(p, gr, buf, segments, rows, float(grad_scale))
+            if scalar is None:
+                N.ops().sgd_step_groups(p, gr, buf, segments, rows, float(grad_scale))
+            else:
+                N.ops().sgd_step_groups_dev(p, gr, buf, segments, rows, scalar)
         self._stepped()
         if started:
             for idx, gi in self._active:

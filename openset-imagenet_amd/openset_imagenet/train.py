@@ -129,51 +129,125 @@ def build_optimizer(cfg, model):
     return (_optim.AdamW if kind == "adamw" else _optim.Adam)(params, lr=opt.lr, **extra)
 
 
+def step_options(cfg):
+    """(accumulate, clip_norm, norm_type) of the optional keys opt.accumulate (int >= 1, default 1), opt.clip_norm (> 0, inf allowed;
+    absent: no clipping) and opt.clip_norm_type (2 | inf, default 2). A cfg without an `opt` block has none of them. ValueError on
+    anything else, when the loop is set up."""
+    opt = getattr(cfg, "opt", None)
+    k = getattr(opt, "accumulate", None)
+    if k is None:
+        k = 1
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"opt.accumulate must be an integer >= 1, got {k!r}")
+    kind = getattr(opt, "clip_norm_type", None)
+    if kind is None:
+        kind = 2
+    if isinstance(kind, str) and kind.strip().lower() in ("inf", ".inf", "2", "2.0"):
+        kind = float(kind.strip().lower().lstrip("."))
+    if isinstance(kind, bool) or not isinstance(kind, (int, float)) or kind not in (2, float("inf")):
+        raise ValueError(f"opt.clip_norm_type must be 2 or inf, got {kind!r}")
+    clip = getattr(opt, "clip_norm", None)
+    if clip is not None:
+        if isinstance(clip, str) and clip.strip().lower() in ("inf", ".inf"):
+            clip = float("inf")
+        if isinstance(clip, bool) or not isinstance(clip, (int, float)) or not clip > 0:
+            raise ValueError(f"opt.clip_norm must be a number > 0 (inf: measure only), got {clip!r}")
+        clip = float(clip)
+    return k, clip, float(kind)
+
+
 def train(model, data_loader, optimizer, loss_fn, trackers, cfg, epsilon=None):
     """One epoch of training (reference train.py:104-139).
 
     With `cfg.adv.who` in {fgsm, gaussian, uniform} (new; absent block or `no_adv`: the loop below is the reference's) every step
     trains on the batch AND on negatives generated from it (adversary.py): clean forward / loss j / backward, negatives, second
     training-mode forward / loss j_adv on the negative label / backward adding to the clean gradients, one optimizer.step().
-    `epsilon` overrides cfg.adv.epsilon (worker() passes the scheduled value); trackers["j_adv"] receives j_adv like trackers["j"]."""
+    `epsilon` overrides cfg.adv.epsilon (worker() passes the scheduled value); trackers["j_adv"] receives j_adv like trackers["j"].
+
+    Optional keys under `opt:` (new; all absent: the loop is the one above, with its tracker set):
+      accumulate: k      one optimizer step per k consecutive batches on the mean of their gradients: zero_grad() once per group, every
+                         backward after the group's first adds to the gradients (ResNet50.next_backward(accumulate=True); autograd's own
+                         accumulation on any other model; with an adversary both passes of those micro-steps), a ragged last group of
+                         r < k batches steps with 1 / r. BatchNorm statistics are per micro-batch; trackers["j"] sees every batch.
+      clip_norm: x, clip_norm_type: 2 | inf     every step clips the gradient norm to x; trackers["grad_norm"] (created only with
+                         the key) receives each step's pre-clip norm at the end of the epoch, from the stacked device values.
+    A fused optimizer (optim.Adam / AdamW / SGD) takes both in its launch: step(grad_scale=1 / r, clip_norm=x, norm_type=...), nothing
+    read back. Any other optimizer: p.grad.mul_(1 / r) over its parameters when r > 1, torch.nn.utils.clip_grad_norm_ over them, step().
+    Under data parallel every micro-backward averages its own buckets (correct by linearity) and the norm is launched on the compute
+    stream after the backward's GradSync.finish(), so every rank derives the same scalar from the same averaged arena."""
     plan = _adversary.Plan(cfg, epsilon) if _adversary.who_of(cfg) != "no_adv" else None
+    group, clip, norm_type = step_options(cfg)
     if plan is not None:
         trackers.setdefault("j_adv", _losses.AverageMeter())
+    if clip is not None:
+        trackers.setdefault("grad_norm", _losses.AverageMeter())
     for metric in trackers.values():
         metric.reset()
     if not cfg.parallel:
         import tqdm
         data_loader = tqdm.tqdm(data_loader)
     wants_features = isinstance(loss_fn, _losses.ObjectosphereLoss)
-    pending, counts, pending_adv = [], [], []
+    pending, counts, pending_adv, norms = [], [], [], []
     from .pipeline import device_batch
+    net = _unwrap(model) if isinstance(_unwrap(model), ResNet50) else None
     if plan is not None:
-        net = _unwrap(model) if isinstance(_unwrap(model), ResNet50) else None
         loss = (lambda lg, ft, y: loss_fn(lg, y, ft)) if wants_features else (lambda lg, ft, y: loss_fn(lg, y))
+    fused = isinstance(optimizer, _optim._FlatOptimizer)
+
+    def step(r):
+        """the optimizer step that closes a group of r batches"""
+        if r == 1 and clip is None:
+            optimizer.step()
+        elif fused:
+            optimizer.step(grad_scale=1.0 / r, clip_norm=clip, norm_type=norm_type)
+            if optimizer.grad_norm is not None:
+                norms.append(optimizer.grad_norm)
+        else:
+            params = [p for g in optimizer.param_groups for p in g["params"]]
+            if r > 1:
+                with torch.no_grad():
+                    for p in params:
+                        if p.grad is not None:
+                            p.grad.mul_(1.0 / r)
+            if clip is not None:
+                norms.append(torch.nn.utils.clip_grad_norm_(params, clip, norm_type).detach())
+            optimizer.step()
+
+    filled = 0                                 # batches whose gradients the current group holds
     for batch in data_loader:
         model.train()  # batch-norm uses and collects batch statistics
-        optimizer.zero_grad()
+        if filled == 0:
+            optimizer.zero_grad()
         images, labels = device_batch(batch)   # device(images), device(labels) of train.py:128-129; canvas batches are staged
         batch_len = labels.shape[0]
         if plan is not None:
-            j, j_adv = _adversary.two_pass_step(model, net, images, labels, loss, plan)
+            j, j_adv = _adversary.two_pass_step(model, net, images, labels, loss, plan, accumulate=filled > 0)
             pending.append(j)
             pending_adv.append(j_adv)
             counts.append(batch_len)
-            optimizer.step()
-            continue
-        logits, features = model(images)
-        j = loss_fn(logits, labels, features) if wants_features else loss_fn(logits, labels)
-        pending.append(j.detach())
-        counts.append(batch_len)
-        j.backward()
-        optimizer.step()
+        else:
+            logits, features = model(images)
+            j = loss_fn(logits, labels, features) if wants_features else loss_fn(logits, labels)
+            pending.append(j.detach())
+            counts.append(batch_len)
+            if filled > 0 and net is not None:     # the executor overwrites the gradient arena unless asked to add
+                net.next_backward(accumulate=True)
+            j.backward()
+        filled += 1
+        if filled == group:
+            step(filled)
+            filled = 0
+    if filled:                                 # a ragged last group
+        step(filled)
     if pending:
         for value, n in zip(torch.stack(pending).cpu().tolist(), counts):
             trackers["j"].update(value, n)
     if pending_adv:
         for value, n in zip(torch.stack(pending_adv).cpu().tolist(), counts):
             trackers["j_adv"].update(value, n)
+    if norms:
+        for value in torch.stack(norms).cpu().tolist():
+            trackers["grad_norm"].update(value, 1)
 
 
 class ShardedEvalBatches(torch.utils.data.Sampler):
