@@ -395,7 +395,8 @@ int osi_linear_bwd(const float* dy, const float* x, const float* w, float* dx, i
 /* ---- losses (losses.py:16-29; train.py:343; train.py:344-347; objectosphere term: SURVEY.md §8 a9) --- */
 enum { OSI_LOSS_ENTROPIC = 0, OSI_LOSS_SOFTMAX = 1, OSI_LOSS_GARBAGE = 2 };
 /* loss (1 float) and dlogits = dJ/dlogits in one launch. features != NULL adds alpha/B * sum r_i^2 and writes dfeatures.
- * dlogits may be NULL (validation: loss only). */
+ * dlogits may be NULL (validation: loss only). A row with target >= C has no term in the loss and an all-zero dlogits row in
+ * every mode (entropic: the divisor stays B). B <= 15360 (OSI_ERR_ARG above, nothing written). */
 int osi_loss_fwd_bwd(int mode, const float* logits, const long long* target, int B, int C, float unk_weight,
                      long long ignore_index, const float* class_weights, const float* features, int F, float xi, float alpha,
                      float* loss, float* dlogits, float* dfeatures, osi_stream_t stream);

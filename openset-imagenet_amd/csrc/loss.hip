@@ -10,6 +10,11 @@
 //                      r_i = max(xi - |f_i|, 0) for y >= 0, |f_i| otherwise.
 // With p = softmax(z):  dJ/dz_i = coef_i * p - t_i  (closed forms of SURVEY.md Appendix B).
 //
+// Contract for labels outside the logits (y >= C), in every mode: dlogits is the gradient of the loss value that the same
+// launch reports. Such a row adds nothing to J and its dlogits row is all zeros. Softmax and garbage modes also leave it out
+// of the normaliser (count / sum of weights); entropic mode keeps its divisor B, which counts every row of the batch. The
+// objectosphere term looks only at the sign of y, so the row's dfeat follows the known-row rule.
+//
 // One workgroup of 16 waves handles the whole batch: a wave per row (lanes stride over C), two sweeps
 // separated by a workgroup barrier because the normaliser (count / sum of class weights) is a batch quantity.
 // Fixed summation order -> bitwise reproducible loss; no host synchronisation, no [B,C] target matrix.
@@ -93,7 +98,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_loss(LossP p) {
         const bool lab_ok = yi >= 0 && yi < C;
         float coef, tval = 0.f, tuni = 0.f;  // grad = coef*p - (c==y ? tval : 0) - tuni
         if (p.mode == OSI_LOSS_ENTROPIC) {
-            if (yi >= 0) { coef = inv; tval = inv; }
+            if (yi >= 0) { coef = lab_ok ? inv : 0.f; tval = coef; }  // y >= C: no term in J, so no gradient either
             else { coef = p.unk_w * inv; tuni = (p.unk_w / (float)C) * inv; }
         } else if (p.mode == OSI_LOSS_SOFTMAX) {
             const bool use = lab_ok && yi != p.ignore_index;
