@@ -31,7 +31,7 @@ extern "C" {
 
 typedef void* osi_stream_t; /* hipStream_t */
 
-int osi_abi_version(void);            /* bumped on any signature change; 17 = gradient-norm clipping (osi_grad_clip_scale, osi_*_step_groups_dev); 16 = the ROC-AUC entry points (osi_auc_*) */
+int osi_abi_version(void);            /* bumped on any signature change; 18 = evaluation histograms (osi_eval_values_*, osi_hist_*); 17 = gradient-norm clipping (osi_grad_clip_scale, osi_*_step_groups_dev); 16 = the ROC-AUC entry points (osi_auc_*) */
 const char* osi_build_arch(void);     /* "gfx950" */
 const char* osi_strerror(int code);
 /* Process-wide development knobs (A/B measurements; every default is the measured optimum). Launch functions only READ them and never
@@ -442,6 +442,43 @@ int osi_auc_ovr_f32(const float* scores, const long long* gt, int N, int C, void
                     long long* eq_c, long long* pos_c, long long* flags3, osi_stream_t stream);
 int osi_auc_ovr_f64(const double* scores, const long long* gt, int N, int C, void* ws, size_t ws_bytes, long long* gt_c,
                     long long* eq_c, long long* pos_c, long long* flags3, osi_stream_t stream);
+
+/* ABI 18. Evaluation histograms for util.get_histogram (util.py:202-228): the softmax-score and feature-norm histograms of known
+ * against negative / unknown samples, on device-resident scores[N][C], features[N][F] (f32 or f64, type T) and int64 labels. All
+ * results are integer counts or min / max of stored values: order-free. Every output is zeroed or written by the call; no
+ * allocation, no host synchronisation. OSI_ERR_ARG before any launch on a null pointer, N <= 0, a short workspace or a bad enum.
+ *
+ * osi_eval_values_*: per row the value each side compares, and side[i]: bit 0 = known (gt >= 0), bit 1 = gt == unk_label. The bits are
+ *   independent (unk_label >= 0 gives rows that carry both). Both values are written for every row, whatever its side byte.
+ *   OSI_EVAL_SCORE: Cc = C - drop_last class columns (drop_last = 1: the last column is the background class, not a class; Cc >= 1).
+ *     kn_val = scores[i][gt], 0 on a row without the known bit; a row with gt >= Cc gets no known bit and counts as a bad label
+ *     (the reference raises IndexError).
+ *     unk_val = maximum over the first Cc columns, NaN if one of them is NaN (np.amax). features may be NULL.
+ *   OSI_EVAL_NORM: both values are the L2 norm of features[i]: squares and their sum in fp64 in index order, one fp64 sqrt, one
+ *     rounding to T. scores may be NULL; labels are not range-checked.
+ *   range4 = {kn_min, kn_max, unk_min, unk_max} over the non-NaN values of each side, infinities included; +inf / -inf for an empty
+ *     side, which the caller does not read. counts6 = {#known, #unk, NaN values among known, NaN among unk, bad labels, 0}.
+ *   ws: osi_eval_values_workspace(N) bytes (per-workgroup min / max partials, reduced by a finishing launch).
+ *
+ * osi_hist_*: np.histogram over the rows with side[i] & side_bit, for an explicit edge table: edges is double[nb + 1] in device
+ *   memory, non-decreasing; counts is int64[nb]; 1 <= nb <= OSI_HIST_MAX_BINS (edges as fp64 plus 32-bit counters stay inside 64 KB
+ *   of LDS). Bin i counts edges[i] <= x < edges[i + 1], the last bin is closed on the right, NaN and values outside
+ *   [edges[0], edges[nb]] are not counted, a zero-width bin stays empty except that x == edges[nb] always lands in bin nb - 1.
+ *   Comparisons run in fp64 (a float converts exactly). A table that is not sorted causes no out-of-range access; its counts are
+ *   unspecified. val must be aligned to its element size. */
+enum { OSI_EVAL_SCORE = 0, OSI_EVAL_NORM = 1 };
+#define OSI_HIST_MAX_BINS 4096
+size_t osi_eval_values_workspace(int N);
+int osi_eval_values_f32(const float* scores, const float* features, const long long* gt, int N, int C, int F, int metric,
+                        long long unk_label, int drop_last, float* kn_val, float* unk_val, unsigned char* side, double* range4,
+                        long long* counts6, void* ws, size_t ws_bytes, osi_stream_t stream);
+int osi_eval_values_f64(const double* scores, const double* features, const long long* gt, int N, int C, int F, int metric,
+                        long long unk_label, int drop_last, double* kn_val, double* unk_val, unsigned char* side, double* range4,
+                        long long* counts6, void* ws, size_t ws_bytes, osi_stream_t stream);
+int osi_hist_f32(const float* val, const unsigned char* side, int side_bit, int N, const double* edges, int nb, long long* counts,
+                 osi_stream_t stream);
+int osi_hist_f64(const double* val, const unsigned char* side, int side_bit, int N, const double* edges, int nb, long long* counts,
+                 osi_stream_t stream);
 
 /* ---- optimizer + arena utilities (train.py:356-359 construction, train.py:127,139 zero_grad/step) --- */
 int osi_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,

@@ -81,6 +81,8 @@ class GradSpan(Structure):
 
 OPT_MAX_SEGMENTS, OPT_MAX_GROUPS = 192, 16
 NORM_INF, NORM_L2 = 0, 2
+EVAL_SCORE, EVAL_NORM = 0, 1
+HIST_MAX_BINS = 4096
 
 P = c_void_p
 _PD = POINTER(ConvDesc)
@@ -167,6 +169,11 @@ _SIGS = {
     "osi_auc_binary_f64": (c_int, [P, P, c_int, c_int, c_longlong, P, c_size_t, P, P]),
     "osi_auc_ovr_f32": (c_int, [P, P, c_int, c_int, P, c_size_t, P, P, P, P, P]),
     "osi_auc_ovr_f64": (c_int, [P, P, c_int, c_int, P, c_size_t, P, P, P, P, P]),
+    "osi_eval_values_workspace": (c_size_t, [c_int]),
+    "osi_eval_values_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_longlong, c_int, P, P, P, P, P, P, c_size_t, P]),
+    "osi_eval_values_f64": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_longlong, c_int, P, P, P, P, P, P, c_size_t, P]),
+    "osi_hist_f32": (c_int, [P, P, c_int, c_int, P, c_int, P, P]),
+    "osi_hist_f64": (c_int, [P, P, c_int, c_int, P, c_int, P, P]),
     "osi_adam_step": (c_int, [P, P, P, P, c_size_t, c_double, c_double, c_double, c_double, c_longlong, c_float, P]),
     "osi_sgd_step": (c_int, [P, P, P, c_size_t, c_float, c_float, c_int, c_float, P]),
     "osi_adam_step_groups": (c_int, [P, P, P, P, P, c_size_t, POINTER(OptSegment), c_int, POINTER(AdamGroup), c_int, c_float, P]),

@@ -3,8 +3,11 @@ and options, same checkpoint naming (`{loss}_best.pth` / `{loss}_curr.pth` in th
 `{loss}_{val,test}_arr{suffix}.npz` with `gt`, `logits`, `features`, `scores`. The forward passes run on the MI355X executor in
 eval mode (train.get_arrays); there is no CPU evaluation path. `--oscr` (this build's addition) also prints the area-free summary
 of the OSCR curve computed on the GPU (util.calculate_oscr); `--auc` (likewise) prints the binary ROC-AUC of known against negative
-(-1) and against unknown (-2) samples, counted on the GPU (metrics.auc_score_binary)."""
+(-1) and against unknown (-2) samples, counted on the GPU (metrics.auc_score_binary); `--report` (likewise) writes `{loss}_{split}_report{suffix}.json` with
+the confidences, the CCR at FPR 1e-3 / 1e-2 / 0.1 / 1 and the 30-bin score and feature-norm histograms (evaluation_report), and
+prints the row of the reference's table (script/plot_all.py:344-385)."""
 import argparse
+import json
 import pathlib
 
 import numpy as np
@@ -28,6 +31,8 @@ def get_args(command_line_options=None):
     p.add_argument("--workers", type=int, default=4)
     p.add_argument("--oscr", action="store_true", help="also compute the OSCR curve of each split on the GPU")
     p.add_argument("--auc", action="store_true", help="also compute the binary ROC-AUC of each split (known vs -1, known vs -2) on the GPU")
+    p.add_argument("--report", action="store_true", help="also write {loss}_{split}_report{suffix}.json (confidences, CCR at FPR, score and "
+                   "norm histograms, all counted on the GPU) next to the .npz and print the row of the reference's table")
     args = p.parse_args(command_line_options)
     try:
         args.output_directory = str(args.output_directory).format(args.protocol)
@@ -47,6 +52,55 @@ def auc_rows(gt, scores, unk, loss):
     keep = (gt >= 0) | (gt == unk)
     s = scores[:, :-1] if loss == "garbage" else scores
     return gt[keep], s[keep]
+
+
+FPR_QUERIES = (1e-3, 1e-2, 0.1, 1.0)      # the "CCR at FPR" columns of the reference's table (plot_all.py:352)
+REPORT_BINS = 30                          # plot_all.plot_softmax
+
+
+def evaluation_report(gt, scores, features, loss):
+    """The numbers behind the reference's table row and histogram page (script/plot_all.py:277-385) for one split, as a dict of
+    plain Python values (JSON-ready), all counted on the GPU:
+
+      conf_kn, conf_unk     metrics.confidence under plot_all.py:366-372: offset 0 for the garbage loss and 1 / (max(gt) + 1) otherwise,
+                            unknown_class -2, last_valid_class -1 for garbage (conf_kn_count / conf_unk_count: the samples behind them)
+      ccr_at_fpr            {"-1": [...], "-2": [...]}: util.ccr_at_fpr at FPR_QUERIES for each of the two labels present in gt
+      score_hist, norm_hist {"-1": {...}, "-2": {...}}: util.get_histogram with 30 bins (kn_hist, kn_edges, unk_hist, unk_edges)
+
+    For the garbage loss the background column is dropped for the curve and the score histograms, as plot_oscr and `--oscr` do (the
+    reference's table keeps it in the curve: DESIGN.md, divergences). Inputs: numpy arrays or torch tensors, host or device."""
+    dev = util._need_gpu("evaluation_report")
+    y = gt.detach().cpu().numpy() if isinstance(gt, torch.Tensor) else np.asarray(gt)
+    y = y.astype(np.int64)
+    if len(y) == 0:
+        raise ValueError("evaluation_report needs at least one sample")
+    s = torch.as_tensor(scores).detach().to(dev)
+    f = torch.as_tensor(features).detach().to(dev)
+    y_dev = torch.from_numpy(y).to(dev)
+    garbage = loss == "garbage"
+    offset = 0 if garbage else 1 / (int(y.max()) + 1)
+    conf = metrics.confidence(s.float(), y_dev, offset=offset, unknown_class=-2, last_valid_class=-1 if garbage else None)
+    report = {"loss": loss, "samples": int(len(y)), "conf_kn": conf[0], "conf_kn_count": conf[1], "conf_unk": conf[2],
+              "conf_unk_count": conf[3], "fpr_values": list(FPR_QUERIES), "ccr_at_fpr": {}, "score_hist": {}, "norm_hist": {}}
+    curve_scores = s[:, :-1] if garbage else s
+    arrays = {"scores": s, "gt": y_dev, "features": f}
+    names = ("kn_hist", "kn_edges", "unk_hist", "unk_edges")
+    for unk in (-1, -2):
+        if not (y == unk).any():
+            continue
+        report["ccr_at_fpr"][str(unk)] = util.ccr_at_fpr(y_dev, curve_scores, fpr_values=FPR_QUERIES, unk_label=unk)
+        for key, metric in (("score_hist", "score"), ("norm_hist", "norm")):
+            hist = util.get_histogram(arrays, unk_label=unk, metric=metric, bins=REPORT_BINS, drop_bg=garbage)
+            report[key][str(unk)] = {n: v.tolist() for n, v in zip(names, hist)}
+    return report
+
+
+def table_row(report, protocol, label, epoch, unk=-2):
+    """One row of the reference's table (plot_all.py:376-385): `$P_n$ - label & epoch & conf_kn & conf_unk & ccr...`, `---` where no
+    curve point is near the FPR (or the split has no sample labelled `unk`)."""
+    ccr = report["ccr_at_fpr"].get(str(unk), [None] * len(report["fpr_values"]))
+    row = f"$P_{protocol}$ - {label} & {epoch} & {report['conf_kn']:1.3f} & {report['conf_unk']:1.3f}"
+    return row + "".join(" & ---" if v is None else f" & {v:1.3f}" for v in ccr) + "\\\\"
 
 
 def main(command_line_options=None):
@@ -86,6 +140,15 @@ def main(command_line_options=None):
                 sel = auc_rows(gt, scores, unk, args.loss)
                 if sel is not None:
                     print(f"{split}: AUC known vs label {unk}: {metrics.auc_score_binary(sel[0], sel[1], unk_class=unk):.6f}")
+        if args.report:
+            report = evaluation_report(gt, scores, features, args.loss)
+            report.update(split=split, protocol=args.protocol, epoch=start_epoch)
+            report_path = args.output_directory / f"{args.loss}_{split}_report{suffix}.json"
+            with open(report_path, "w") as handle:
+                json.dump(report, handle, default=str)
+            print(f"Evaluation report saved in: {report_path}")
+            unk = -2 if "-2" in report["ccr_at_fpr"] else -1
+            print(f"{split}: table row (CCR vs label {unk}): {table_row(report, args.protocol, args.loss, start_epoch, unk)}")
     return written
 
 
