@@ -14,7 +14,6 @@
 namespace {
 
 constexpr int NT = 256;
-constexpr int OSI_BN_GROUPS = 32;  // level-1 groups of the two-level statistics finalisation
 
 struct RowSplit { int CV, RL, G; };  // float4 columns per pass, row lanes, column groups
 __host__ __device__ inline RowSplit row_split(int C) {
@@ -513,6 +512,25 @@ __global__ __launch_bounds__(NT) void k_bn_bwd_final(BwdConsTable t, bool groupe
     }
 }
 
+// The backward finalisers' walk over two row-major [P][C] partial matrices (pa / pb: already at the lane's channel): lane pl of the L lanes
+// of a channel takes rows b0 + pl, b0 + pl + L, ... below b1, four rows in flight on two accumulator chains (rows 0 and 2 of a round on
+// chain 0, rows 1 and 3 on chain 1), the scalar tail on chain 0, result = chain 0 + chain 1. The summation order is the contract (bitwise
+// reproducible sums), so it is written down once. The statistics finalisers (k_bn_stats_final_wide, k_bn_stats_group) walk the same way
+// with their own accumulation rule and keep their loops: see profiles/NOTES_r14.md.
+struct Pair { float a, b; };
+template <int L>
+__device__ __forceinline__ Pair walk_sum2(const float* __restrict__ pa, const float* __restrict__ pb, int C, int b0, int b1, int pl) {
+    float xa0 = 0.f, xa1 = 0.f, xb0 = 0.f, xb1 = 0.f;
+    int r = b0 + pl;
+    for (; r + 3 * L < b1; r += 4 * L) {
+        const float a0 = pa[(size_t)r * C], a1 = pa[(size_t)(r + L) * C], a2 = pa[(size_t)(r + 2 * L) * C], a3 = pa[(size_t)(r + 3 * L) * C];
+        const float v0 = pb[(size_t)r * C], v1 = pb[(size_t)(r + L) * C], v2 = pb[(size_t)(r + 2 * L) * C], v3 = pb[(size_t)(r + 3 * L) * C];
+        xa0 += a0; xa1 += a1; xa0 += a2; xa1 += a3;
+        xb0 += v0; xb1 += v1; xb0 += v2; xb1 += v3;
+    }
+    for (; r < b1; r += L) { xa0 += pa[(size_t)r * C]; xb0 += pb[(size_t)r * C]; }
+    return Pair{xa0 + xa1, xb0 + xb1};
+}
 // dy = gamma*invstd * ( g - c1 - xhat*c2 ) ; optionally also emits g (the masked upstream gradient) for the skip path
 // Column sums of two row-major [P][C] partial matrices over row group s (blockIdx.y) -> channel-major [C][S] for k_bn_bwd_final.
 __global__ __launch_bounds__(NT) void k_colsum2_group(BwdConsTable t, int P, int Pc, int C, int S) {
@@ -526,16 +544,8 @@ __global__ __launch_bounds__(NT) void k_colsum2_group(BwdConsTable t, int P, int
     const int b0 = s * Pc, b1 = min(P, b0 + Pc);
     const float* __restrict__ pa = o.pa + c;
     const float* __restrict__ pb = o.pb + c;
-    float xa0 = 0.f, xa1 = 0.f, xb0 = 0.f, xb1 = 0.f;
-    int r = b0 + pl;
-    for (; r + 48 < b1; r += 64) {     // four rows in flight per lane
-        const float a0 = pa[(size_t)r * C], a1 = pa[(size_t)(r + 16) * C], a2 = pa[(size_t)(r + 32) * C], a3 = pa[(size_t)(r + 48) * C];
-        const float v0 = pb[(size_t)r * C], v1 = pb[(size_t)(r + 16) * C], v2 = pb[(size_t)(r + 32) * C], v3 = pb[(size_t)(r + 48) * C];
-        xa0 += a0; xa1 += a1; xa0 += a2; xa1 += a3;
-        xb0 += v0; xb1 += v1; xb0 += v2; xb1 += v3;
-    }
-    for (; r < b1; r += 16) { xa0 += pa[(size_t)r * C]; xb0 += pb[(size_t)r * C]; }
-    float xa = xa0 + xa1, xb = xb0 + xb1;
+    const Pair lane = walk_sum2<16>(pa, pb, C, b0, b1, pl);
+    float xa = lane.a, xb = lane.b;
     ra[pl][cl] = xa; rb[pl][cl] = xb;
     __syncthreads();
     if (pl == 0 && ok) {
@@ -553,17 +563,9 @@ __global__ __launch_bounds__(16 * WPL) void k_bn_bwd_final_wide(BwdConsTable t, 
     const bool ok = blockIdx.x * 16 + cl < C;
     const float* __restrict__ pa = o.pa + c;
     const float* __restrict__ pb = o.pb + c;
-    float xa0 = 0.f, xa1 = 0.f, xb0 = 0.f, xb1 = 0.f;
-    int r = pl;
-    for (; r + 3 * WPL < P; r += 4 * WPL) {
-        const float a0 = pa[(size_t)r * C], a1 = pa[(size_t)(r + WPL) * C], a2 = pa[(size_t)(r + 2 * WPL) * C], a3 = pa[(size_t)(r + 3 * WPL) * C];
-        const float b0 = pb[(size_t)r * C], b1 = pb[(size_t)(r + WPL) * C], b2 = pb[(size_t)(r + 2 * WPL) * C], b3 = pb[(size_t)(r + 3 * WPL) * C];
-        xa0 += a0; xa1 += a1; xa0 += a2; xa1 += a3;
-        xb0 += b0; xb1 += b1; xb0 += b2; xb1 += b3;
-    }
-    for (; r < P; r += WPL) { xa0 += pa[(size_t)r * C]; xb0 += pb[(size_t)r * C]; }
-    const float sa = wide_reduce(red, xa0 + xa1, pl, cl);
-    const float sb = wide_reduce(red, xb0 + xb1, pl, cl);
+    const Pair lane = walk_sum2<WPL>(pa, pb, C, 0, P, pl);
+    const float sa = wide_reduce(red, lane.a, pl, cl);
+    const float sb = wide_reduce(red, lane.b, pl, cl);
     if (pl == 0 && ok) {
         o.dbeta[c] = sa; o.dgamma[c] = sb;
         o.c1[c] = sa / (float)M; o.c2[c] = sb / (float)M;
@@ -663,7 +665,6 @@ __global__ __launch_bounds__(NT) void k_bn_frozen_apply(const f32x4* dA, const v
 
 // which of the three forms a streaming pass takes for a channel count (see k_bn_apply)
 static int stream_geo(int c4n) { return NT % c4n == 0 ? 1 : c4n == 2 * NT ? 2 : 0; }
-#define OSI_BY_GEO(geo_, X_) do { if ((geo_) == 1) { X_(1); } else if ((geo_) == 2) { X_(2); } else { X_(0); } } while (0)
 
 static int rows_per_block(int M, int C, int& P) {
     // ~256 KiB of activations per workgroup, at most 1024 workgroups
@@ -683,6 +684,31 @@ static int stream_grid(size_t n4, bool backward = false) {
     return (int)(g > cap ? cap : g);
 }
 
+// group geometry of the two-level reductions of P row tiles: S <= OSI_BN_GROUPS groups of Pc consecutive tiles
+static void bwd_groups(int P, int& S, int& Pc) {
+    S = osi_cdiv(P, 64);
+    if (S > OSI_BN_GROUPS) S = OSI_BN_GROUPS;
+    Pc = osi_cdiv(P, S);
+    S = osi_cdiv(P, Pc);
+}
+// THE workspace layout: two [rows][C] matrices, then (coef) the two per-channel coefficient vectors of the backward apply. rows = P for
+// row-tile partials (pa | pb), S for the [C][S] group sums of the two-level backward reduction (ga | gb); one consumer's slice of the
+// two-consumer form is sized for S = OSI_BN_GROUPS. The statistics' partials are the two matrices alone.
+struct BwdWs { float *a, *b, *c1, *c2; };
+static size_t ws_floats(int rows, int C, bool coef = true) { return (size_t)2 * rows * C + (coef ? 2 * (size_t)C : 0); }
+static BwdWs carve_ws(void* ws, int rows, int C) {
+    float* a = (float*)ws;
+    const size_t n = (size_t)rows * C;
+    return BwdWs{a, a + n, a + 2 * n, a + 2 * n + C};
+}
+static PoolSrc make_pool_src(const void* idx, int H, int W) {
+    PoolSrc ps;
+    ps.idx = (const uint32_t*)idx;
+    ps.dW = make_fastdiv((uint32_t)W); ps.dH = make_fastdiv((uint32_t)H);
+    ps.H = H; ps.W = W; ps.Ho = (H + 2 - 3) / 2 + 1; ps.Wo = (W + 2 - 3) / 2 + 1;
+    return ps;
+}
+
 }  // namespace
 
 extern "C" {
@@ -691,7 +717,7 @@ size_t osi_bn_workspace(int M, int C) {
     if (M <= 0 || C <= 0) return 0;
     int P;
     rows_per_block(M, C, P);
-    return (size_t)2 * P * C * sizeof(float);
+    return ws_floats(P, C, false) * sizeof(float);
 }
 
 int osi_bn_train_stats(const float* y, int M, int C, const float* gamma, const float* beta, float eps, float momentum,
@@ -702,7 +728,7 @@ int osi_bn_train_stats(const float* y, int M, int C, const float* gamma, const f
     OSI_REQUIRE((running_mean == nullptr) == (running_var == nullptr));
     int P;
     int rpb = rows_per_block(M, C, P);
-    OSI_REQUIRE(ws_bytes >= (size_t)2 * P * C * sizeof(float));
+    OSI_REQUIRE(ws_bytes >= ws_floats(P, C, false) * sizeof(float));
     hipStream_t st = (hipStream_t)stream;
     float* pmean = (float*)ws;
     float* pm2 = pmean + (size_t)P * C;
@@ -720,7 +746,7 @@ int osi_bn_finalize_stats(float* pstats, size_t pstats_bytes, int P, int rows_pe
     OSI_REQUIRE(pstats && gamma && beta && mean && invstd && scale && shift);
     OSI_REQUIRE(P > 0 && rows_per_block > 0 && M > 0 && C > 0 && (long)(P - 1) * rows_per_block < M && (long)P * rows_per_block >= M);
     OSI_REQUIRE((running_mean == nullptr) == (running_var == nullptr));
-    OSI_REQUIRE(pstats_bytes >= ((size_t)2 * P * C + 2 * (size_t)OSI_BN_GROUPS * C) * sizeof(float));
+    OSI_REQUIRE(pstats_bytes >= bn_pstats_floats(P, C) * sizeof(float));
     hipStream_t st = (hipStream_t)stream;
     const float* pmean = pstats;
     const float* pm2 = pstats + (size_t)P * C;
@@ -737,10 +763,8 @@ int osi_bn_finalize_stats(float* pstats, size_t pstats_bytes, int P, int rows_pe
         return OSI_OK;
     }
     // two levels: S groups of Pc consecutive row tiles are reduced by S x C/16 workgroups, then one wave per channel merges them
-    int S = osi_cdiv(P, 64);
-    if (S > OSI_BN_GROUPS) S = OSI_BN_GROUPS;
-    const int Pc = osi_cdiv(P, S);
-    S = osi_cdiv(P, Pc);
+    int S, Pc;
+    bwd_groups(P, S, Pc);
     float* gmean = pstats + (size_t)2 * P * C;
     float* gm2 = gmean + (size_t)S * C;
     hipLaunchKernelGGL(k_bn_stats_group, dim3(osi_cdiv(C, 16), S), dim3(NT), 0, st, pmean, pm2, P, Pc, rows_per_block, M, C, S, gmean, gm2);
@@ -800,20 +824,22 @@ static int bn_apply_impl(const float* y, const float* residual, const float* sca
     auto Y = (const f32x4*)y; auto R = (const f32x4*)residual; auto S = (const f32x4*)scale; auto H = (const f32x4*)shift;
     auto RS = (const f32x4*)rscale; auto RH = (const f32x4*)rshift;
     auto O = (f32x4*)out; auto B = (u64*)bits;
-    const int geo = stream_geo(c4n);
-#define OSI_APPLY_G(RES_, RELU_, BITS_, GEO_) hipLaunchKernelGGL((k_bn_apply<RES_, RELU_, BITS_, GEO_>), dim3(grid), dim3(NT), 0, st, Y, R, S, H, RS, RH, O, B, n4, c4n)
-#define OSI_APPLY(RES_, RELU_, BITS_) do { if (geo == 1) OSI_APPLY_G(RES_, RELU_, BITS_, 1); else if (geo == 2) OSI_APPLY_G(RES_, RELU_, BITS_, 2); else OSI_APPLY_G(RES_, RELU_, BITS_, 0); } while (0)
-    if (rscale) OSI_APPLY(2, true, true);
-    else if (bits && residual) OSI_APPLY(1, true, true);
-    else if (bits) OSI_APPLY(0, true, true);
-    else if (residual && relu) OSI_APPLY(1, true, false);
-    else if (residual) OSI_APPLY(1, false, false);
-    else if (relu) OSI_APPLY(0, true, false);
-    else OSI_APPLY(0, false, false);
-#undef OSI_APPLY
-#undef OSI_APPLY_G
-    OSI_LAUNCH_CHECK();
-    return OSI_OK;
+    auto go = [&](auto RES, auto RELU, auto BITS, auto GEO) -> int {
+        constexpr int res = decltype(RES)::value;
+        constexpr bool rl = decltype(RELU)::value != 0, bt = decltype(BITS)::value != 0;
+        if constexpr ((!bt || rl) && (res != 2 || bt)) {     // the bitmask is the ReLU's; the fused shortcut is built with both
+            hipLaunchKernelGGL((k_bn_apply<res, rl, bt, decltype(GEO)::value>), dim3(grid), dim3(NT), 0, st, Y, R, S, H, RS, RH, O, B, n4, c4n);
+            OSI_LAUNCH_CHECK();
+            return OSI_OK;
+        } else return OSI_ERR_ARG;
+    };
+    return pick<0, 1, 2>(rscale ? 2 : residual ? 1 : 0, [&](auto RES) {
+        return pick<0, 1>(relu != 0, [&](auto RELU) {
+            return pick<0, 1>(bits != nullptr, [&](auto BITS) {
+                return pick<0, 1, 2>(stream_geo(c4n), [&](auto GEO) { return go(RES, RELU, BITS, GEO); });
+            });
+        });
+    });
 }
 
 int osi_bn_apply(const float* y, const float* residual, const float* scale, const float* shift, float* out, int M, int C,
@@ -845,44 +871,53 @@ static BwdConsTable one_cons(const float* pa, const float* pb, float* ga, float*
     return t;
 }
 
+// Row-tile partials of g (the gradient gated by `mode`, see bn_frozen_impl; 1 = by the activation, osi_bn_backward only) and g * xhat into
+// w.a / w.b, finished into dgamma, dbeta and the apply coefficients w.c1 / w.c2
+static int launch_bwd_partial(int mode, const float* dout, const void* msk, const float* y, const float* mean, const float* invstd, float* dgamma,
+                              float* dbeta, int M, int C, int rpb, int P, const BwdWs& w, const PoolSrc& ps, hipStream_t st) {
+    if (int e = pick<0, 1, 2, 3>(mode, [&](auto MODE) -> int {
+            hipLaunchKernelGGL(k_bn_bwd_partial<decltype(MODE)::value>, dim3(P), dim3(NT), 0, st, dout, msk, y, mean, invstd, M, C, rpb, w.a, w.b, ps);
+            OSI_LAUNCH_CHECK();
+            return OSI_OK;
+        })) return e;
+    hipLaunchKernelGGL(k_bn_bwd_final, dim3(osi_cdiv(C, NT / 64)), dim3(NT), 0, st, one_cons(w.a, w.b, nullptr, nullptr, dgamma, dbeta, w.c1, w.c2), false, P, M, C);
+    OSI_LAUNCH_CHECK();
+    return OSI_OK;
+}
+// the backward apply pass; the stem's pool-gather form (mode 3, one launch per step) keeps the per-element constants and emits no g
+static int launch_bwd_apply(int mode, const float* dout, const void* msk, const float* y, const float* mean, const float* invstd, const float* gamma,
+                            const BwdWs& w, float* dy, float* gmasked, int M, int C, const PoolSrc& ps, hipStream_t st) {
+    const size_t n4 = (size_t)M * C / 4;
+    const int grid = stream_grid(n4, true), c4n = C / 4;
+    auto go = [&](auto MODE, auto EMITG, auto GEO) -> int {
+        constexpr int md = decltype(MODE)::value, geo = decltype(GEO)::value;
+        constexpr bool emit = decltype(EMITG)::value != 0;
+        if constexpr (md != 3 || (geo == 0 && !emit)) {
+            hipLaunchKernelGGL((k_bn_bwd_apply<md, emit, geo>), dim3(grid), dim3(NT), 0, st, (const f32x4*)dout, msk, (const f32x4*)y, (const f32x4*)mean,
+                               (const f32x4*)invstd, (const f32x4*)gamma, (const f32x4*)w.c1, (const f32x4*)w.c2, (f32x4*)dy, (f32x4*)gmasked, n4, c4n, ps);
+            OSI_LAUNCH_CHECK();
+            return OSI_OK;
+        } else return OSI_ERR_ARG;
+    };
+    return pick<0, 1, 2, 3>(mode, [&](auto MODE) {
+        return pick<0, 1>(gmasked && mode != 3, [&](auto EMITG) {
+            return pick<0, 1, 2>(mode == 3 ? 0 : stream_geo(c4n), [&](auto GEO) { return go(MODE, EMITG, GEO); });
+        });
+    });
+}
+
 static int bn_backward_impl(const float* dout, const void* msk, int mode, const float* y, const float* mean, const float* invstd,
                             const float* gamma, float* dy, float* gmasked, float* dgamma, float* dbeta, int M, int C, void* ws,
                             size_t ws_bytes, hipStream_t st, PoolSrc ps = PoolSrc{}) {
     OSI_REQUIRE(dout && y && mean && invstd && gamma && (dy || mode == 3) && dgamma && dbeta && ws);
     OSI_REQUIRE(M > 0 && C > 0 && C % 4 == 0);
     int P;
-    int rpb = rows_per_block(M, C, P);
-    // partial sums + the two per-channel coefficient vectors
-    OSI_REQUIRE(ws_bytes >= ((size_t)2 * P * C + 2 * (size_t)C) * sizeof(float));
-    float* pdb = (float*)ws;
-    float* pdg = pdb + (size_t)P * C;
-    float* c1 = pdg + (size_t)P * C;
-    float* c2 = c1 + C;
-    if (mode == 3) hipLaunchKernelGGL(k_bn_bwd_partial<3>, dim3(P), dim3(NT), 0, st, dout, msk, y, mean, invstd, M, C, rpb, pdb, pdg, ps);
-    else if (mode == 2) hipLaunchKernelGGL(k_bn_bwd_partial<2>, dim3(P), dim3(NT), 0, st, dout, msk, y, mean, invstd, M, C, rpb, pdb, pdg, ps);
-    else if (mode == 1) hipLaunchKernelGGL(k_bn_bwd_partial<1>, dim3(P), dim3(NT), 0, st, dout, msk, y, mean, invstd, M, C, rpb, pdb, pdg, ps);
-    else hipLaunchKernelGGL(k_bn_bwd_partial<0>, dim3(P), dim3(NT), 0, st, dout, msk, y, mean, invstd, M, C, rpb, pdb, pdg, ps);
-    OSI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_bn_bwd_final, dim3(osi_cdiv(C, NT / 64)), dim3(NT), 0, st, one_cons(pdb, pdg, nullptr, nullptr, dgamma, dbeta, c1, c2), false, P, M, C);
-    OSI_LAUNCH_CHECK();
+    const int rpb = rows_per_block(M, C, P);
+    OSI_REQUIRE(ws_bytes >= ws_floats(P, C) * sizeof(float));
+    const BwdWs w = carve_ws(ws, P, C);
+    if (int e = launch_bwd_partial(mode, dout, msk, y, mean, invstd, dgamma, dbeta, M, C, rpb, P, w, ps, st)) return e;
     if (!dy) return OSI_OK;     // reductions only (dgamma, dbeta): the caller assembles the consumer's gradient another way
-    const size_t n4 = (size_t)M * C / 4;
-    const int grid = stream_grid(n4, true), c4n = C / 4;
-    auto D = (const f32x4*)dout; auto Y = (const f32x4*)y;
-    auto MU = (const f32x4*)mean; auto IS = (const f32x4*)invstd; auto G = (const f32x4*)gamma;
-    auto C1 = (const f32x4*)c1; auto C2 = (const f32x4*)c2;
-    auto DY = (f32x4*)dy; auto GO = (f32x4*)gmasked;
-    const int geo = stream_geo(c4n);
-#define OSI_BWD_APPLY_G(MODE_, EMIT_, GEO_) hipLaunchKernelGGL((k_bn_bwd_apply<MODE_, EMIT_, GEO_>), dim3(grid), dim3(NT), 0, st, D, msk, Y, MU, IS, G, C1, C2, DY, GO, n4, c4n, ps)
-#define OSI_BWD_APPLY(MODE_, EMIT_) do { if (geo == 1) OSI_BWD_APPLY_G(MODE_, EMIT_, 1); else if (geo == 2) OSI_BWD_APPLY_G(MODE_, EMIT_, 2); else OSI_BWD_APPLY_G(MODE_, EMIT_, 0); } while (0)
-    if (mode == 3) OSI_BWD_APPLY_G(3, false, 0);   // the stem's pool-gather form (one launch per step) keeps the per-element constants
-    else if (mode == 2) { if (gmasked) OSI_BWD_APPLY(2, true); else OSI_BWD_APPLY(2, false); }
-    else if (mode == 1) { if (gmasked) OSI_BWD_APPLY(1, true); else OSI_BWD_APPLY(1, false); }
-    else { if (gmasked) OSI_BWD_APPLY(0, true); else OSI_BWD_APPLY(0, false); }
-#undef OSI_BWD_APPLY
-#undef OSI_BWD_APPLY_G
-    OSI_LAUNCH_CHECK();
-    return OSI_OK;
+    return launch_bwd_apply(mode, dout, msk, y, mean, invstd, gamma, w, dy, gmasked, M, C, ps, st);
 }
 
 // (psum_g, psum_gx)[P][C] from a dgrad epilogue -> dgamma, dbeta and the two apply coefficients of n consumers (the table's pa / pb):
@@ -899,13 +934,6 @@ static int bwd_reduce_partials(const BwdConsTable& t, int n, int P, int M, int C
     OSI_LAUNCH_CHECK();
     return OSI_OK;
 }
-// group geometry of the two-level reduction of P row tiles
-static void bwd_groups(int P, int& S, int& Pc) {
-    S = osi_cdiv(P, 64);
-    if (S > OSI_BN_GROUPS) S = OSI_BN_GROUPS;
-    Pc = osi_cdiv(P, S);
-    S = osi_cdiv(P, Pc);
-}
 
 int osi_bn_backward_fused(const float* g, const float* y, const float* mean, const float* invstd, const float* gamma,
                           const float* psum_g, const float* psum_gx, int P, float* dy, float* dgamma, float* dbeta, int M, int C,
@@ -914,27 +942,16 @@ int osi_bn_backward_fused(const float* g, const float* y, const float* mean, con
     OSI_REQUIRE(M > 0 && C > 0 && C % 4 == 0 && P > 0);
     int S, Pc;
     bwd_groups(P, S, Pc);
-    OSI_REQUIRE(ws_bytes >= ((size_t)2 * S * C + 2 * (size_t)C) * sizeof(float));
+    OSI_REQUIRE(ws_bytes >= ws_floats(S, C) * sizeof(float));
     hipStream_t st = (hipStream_t)stream;
-    float* gb = (float*)ws;               // [C][S] group sums of g
-    float* gg = gb + (size_t)S * C;       // [C][S] group sums of g*xhat
-    float* c1 = gg + (size_t)S * C;
-    float* c2 = c1 + C;
-    if (int e = bwd_reduce_partials(one_cons(psum_g, psum_gx, gb, gg, dgamma, dbeta, c1, c2), 1, P, M, C, S, Pc, st)) return e;
-    const size_t n4 = (size_t)M * C / 4;
-    const int c4n = C / 4;
-#define OSI_FUSED_APPLY(GEO_) hipLaunchKernelGGL((k_bn_bwd_apply<0, false, GEO_>), dim3(stream_grid(n4, true)), dim3(NT), 0, st, (const f32x4*)g, \
-                       (const void*)nullptr, (const f32x4*)y, (const f32x4*)mean, (const f32x4*)invstd, (const f32x4*)gamma, (const f32x4*)c1, \
-                       (const f32x4*)c2, (f32x4*)dy, (f32x4*)nullptr, n4, c4n, PoolSrc{})
-    OSI_BY_GEO(stream_geo(c4n), OSI_FUSED_APPLY);
-#undef OSI_FUSED_APPLY
-    OSI_LAUNCH_CHECK();
-    return OSI_OK;
+    const BwdWs w = carve_ws(ws, S, C);     // [C][S] group sums of g and of g * xhat
+    if (int e = bwd_reduce_partials(one_cons(psum_g, psum_gx, w.a, w.b, dgamma, dbeta, w.c1, w.c2), 1, P, M, C, S, Pc, st)) return e;
+    return launch_bwd_apply(0, g, nullptr, y, mean, invstd, gamma, w, dy, nullptr, M, C, PoolSrc{}, st);
 }
 
 size_t osi_bn_backward_fused2_workspace(int C) {
     if (C <= 0) return 0;
-    return 2 * ((size_t)2 * OSI_BN_GROUPS * C + 2 * (size_t)C) * sizeof(float);
+    return 2 * ws_floats(OSI_BN_GROUPS, C) * sizeof(float);
 }
 
 int osi_bn_backward_fused2(const float* g, const osi_bn_fused_consumer* consumers, const float* psum_g, int P, int M, int C, void* ws,
@@ -949,18 +966,15 @@ int osi_bn_backward_fused2(const float* g, const osi_bn_fused_consumer* consumer
     int S, Pc;
     bwd_groups(P, S, Pc);
     hipStream_t st = (hipStream_t)stream;
-    const size_t per = (size_t)2 * OSI_BN_GROUPS * C + 2 * (size_t)C;     // one consumer's slice of ws: the layout of osi_bn_backward_fused
+    const size_t per = ws_floats(OSI_BN_GROUPS, C);     // one consumer's slice of ws: the layout of osi_bn_backward_fused
     BwdConsTable t{};
     BwdApplyCons a[2];
     for (int k = 0; k < 2; ++k) {
         const osi_bn_fused_consumer& c = consumers[k];
-        float* gb = (float*)ws + k * per;
-        float* gg = gb + (size_t)S * C;
-        float* c1 = gg + (size_t)S * C;
-        float* c2 = c1 + C;
-        t.k[k] = BwdCons{psum_g, c.psum_gx, gb, gg, c.dgamma, c.dbeta, c1, c2};
-        a[k] = BwdApplyCons{(const f32x4*)c.y, (const f32x4*)c.mean, (const f32x4*)c.invstd, (const f32x4*)c.gamma, (const f32x4*)c1,
-                            (const f32x4*)c2, (f32x4*)c.dy};
+        const BwdWs w = carve_ws((float*)ws + k * per, S, C);
+        t.k[k] = BwdCons{psum_g, c.psum_gx, w.a, w.b, c.dgamma, c.dbeta, w.c1, w.c2};
+        a[k] = BwdApplyCons{(const f32x4*)c.y, (const f32x4*)c.mean, (const f32x4*)c.invstd, (const f32x4*)c.gamma, (const f32x4*)w.c1,
+                            (const f32x4*)w.c2, (f32x4*)c.dy};
     }
     if (int e = bwd_reduce_partials(t, 2, P, M, C, S, Pc, st)) return e;
     const size_t n4 = (size_t)M * C / 4;
@@ -968,11 +982,11 @@ int osi_bn_backward_fused2(const float* g, const osi_bn_fused_consumer* consumer
     const int grid = stream_grid(n4, true);
     int geo = stream_geo(c4n);
     if (geo == 2 && (grid & 1) && (size_t)grid < (n4 + NT - 1) / NT) geo = 0;   // an odd grid that loops mixes tile parities in a workgroup
-#define OSI_FUSED_APPLY2(GEO_) hipLaunchKernelGGL((k_bn_bwd_apply2<GEO_>), dim3(grid), dim3(NT), 0, st, (const f32x4*)g, a[0], a[1], n4, c4n)
-    OSI_BY_GEO(geo, OSI_FUSED_APPLY2);
-#undef OSI_FUSED_APPLY2
-    OSI_LAUNCH_CHECK();
-    return OSI_OK;
+    return pick<0, 1, 2>(geo, [&](auto GEO) -> int {
+        hipLaunchKernelGGL((k_bn_bwd_apply2<decltype(GEO)::value>), dim3(grid), dim3(NT), 0, st, (const f32x4*)g, a[0], a[1], n4, c4n);
+        OSI_LAUNCH_CHECK();
+        return OSI_OK;
+    });
 }
 
 int osi_bn_backward_reduce(const float* psum_g, const float* psum_gx, int P, float* dgamma, float* dbeta, int M, int C, void* ws,
@@ -980,14 +994,9 @@ int osi_bn_backward_reduce(const float* psum_g, const float* psum_gx, int P, flo
     OSI_REQUIRE(psum_g && psum_gx && dgamma && dbeta && ws && M > 0 && C > 0 && P > 0);
     int S, Pc;
     bwd_groups(P, S, Pc);
-    OSI_REQUIRE(ws_bytes >= ((size_t)2 * S * C + 2 * (size_t)C) * sizeof(float));
-    hipStream_t st = (hipStream_t)stream;
-    float* gb = (float*)ws;
-    float* gg = gb + (size_t)S * C;
-    float* c1 = gg + (size_t)S * C;
-    float* c2 = c1 + C;
-    if (int e = bwd_reduce_partials(one_cons(psum_g, psum_gx, gb, gg, dgamma, dbeta, c1, c2), 1, P, M, C, S, Pc, st)) return e;
-    return OSI_OK;
+    OSI_REQUIRE(ws_bytes >= ws_floats(S, C) * sizeof(float));
+    const BwdWs w = carve_ws(ws, S, C);
+    return bwd_reduce_partials(one_cons(psum_g, psum_gx, w.a, w.b, dgamma, dbeta, w.c1, w.c2), 1, P, M, C, S, Pc, (hipStream_t)stream);
 }
 
 // mode 0: dout is used as it is (already gated by a dgrad epilogue), 2: gated by the bitmask, 3: gathered through the stem's max-pool
@@ -1000,7 +1009,7 @@ static int bn_frozen_impl(const float* dout, const void* msk, int mode, const os
         if (cs[k].dgamma) {
             int P;
             rows_per_block(M, C, P);
-            OSI_REQUIRE(cs[k].y && cs[k].mean && cs[k].invstd && ws && ws_bytes >= ((size_t)2 * P * C + 2 * (size_t)C) * sizeof(float));
+            OSI_REQUIRE(cs[k].y && cs[k].mean && cs[k].invstd && ws && ws_bytes >= ws_floats(P, C) * sizeof(float));
         }
     }
     OSI_REQUIRE(n == 1 || (cs[1].dy != cs[0].dy && cs[1].dy != dout));
@@ -1010,35 +1019,29 @@ static int bn_frozen_impl(const float* dout, const void* msk, int mode, const os
         if (!cs[k].dgamma) continue;
         int P;
         const int rpb = rows_per_block(M, C, P);
-        float* pdb = (float*)ws;
-        float* pdg = pdb + (size_t)P * C;
-        float* c1 = pdg + (size_t)P * C;
-        if (mode == 3) hipLaunchKernelGGL(k_bn_bwd_partial<3>, dim3(P), dim3(NT), 0, st, dout, msk, cs[k].y, cs[k].mean, cs[k].invstd, M, C, rpb, pdb, pdg, ps);
-        else if (mode == 2) hipLaunchKernelGGL(k_bn_bwd_partial<2>, dim3(P), dim3(NT), 0, st, dout, msk, cs[k].y, cs[k].mean, cs[k].invstd, M, C, rpb, pdb, pdg, ps);
-        else hipLaunchKernelGGL(k_bn_bwd_partial<0>, dim3(P), dim3(NT), 0, st, dout, msk, cs[k].y, cs[k].mean, cs[k].invstd, M, C, rpb, pdb, pdg, ps);
-        OSI_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_bn_bwd_final, dim3(osi_cdiv(C, NT / 64)), dim3(NT), 0, st, one_cons(pdb, pdg, nullptr, nullptr, cs[k].dgamma, cs[k].dbeta, c1, c1 + C), false, P, M, C);
-        OSI_LAUNCH_CHECK();
+        if (int e = launch_bwd_partial(mode, dout, msk, cs[k].y, cs[k].mean, cs[k].invstd, cs[k].dgamma, cs[k].dbeta, M, C, rpb, P, carve_ws(ws, P, C),
+                                       ps, st)) return e;
     }
     const size_t n4 = (size_t)M * C / 4;
     const int grid = stream_grid(n4, true), c4n = C / 4;
     auto D = (const f32x4*)dout; auto S0 = (const f32x4*)cs[0].scale; auto S1 = (const f32x4*)(n == 2 ? cs[1].scale : nullptr);
     auto DY0 = (f32x4*)cs[0].dy; auto DY1 = (f32x4*)(n == 2 ? cs[1].dy : nullptr); auto GO = (f32x4*)gmasked;
-    const int geo = stream_geo(c4n);
-#define OSI_FRZ_APPLY_G(MODE_, EMIT_, TWO_, GEO_) hipLaunchKernelGGL((k_bn_frozen_apply<MODE_, EMIT_, TWO_, GEO_>), dim3(grid), dim3(NT), 0, st, D, msk, S0, S1, DY0, DY1, GO, n4, c4n, ps)
-#define OSI_FRZ_APPLY(MODE_, EMIT_, TWO_) do { if (geo == 1) OSI_FRZ_APPLY_G(MODE_, EMIT_, TWO_, 1); else if (geo == 2) OSI_FRZ_APPLY_G(MODE_, EMIT_, TWO_, 2); else OSI_FRZ_APPLY_G(MODE_, EMIT_, TWO_, 0); } while (0)
-    if (mode == 3) OSI_FRZ_APPLY_G(3, false, false, 0);
-    else if (mode == 2) {
-        if (n == 2) { if (gmasked) OSI_FRZ_APPLY(2, true, true); else OSI_FRZ_APPLY(2, false, true); }
-        else { if (gmasked) OSI_FRZ_APPLY(2, true, false); else OSI_FRZ_APPLY(2, false, false); }
-    } else {
-        if (n == 2) { if (gmasked) OSI_FRZ_APPLY(0, true, true); else OSI_FRZ_APPLY(0, false, true); }
-        else { if (gmasked) OSI_FRZ_APPLY(0, true, false); else OSI_FRZ_APPLY(0, false, false); }
-    }
-#undef OSI_FRZ_APPLY
-#undef OSI_FRZ_APPLY_G
-    OSI_LAUNCH_CHECK();
-    return OSI_OK;
+    auto go = [&](auto MODE, auto EMITG, auto TWO, auto GEO) -> int {
+        constexpr int md = decltype(MODE)::value, geo = decltype(GEO)::value;
+        constexpr bool emit = decltype(EMITG)::value != 0, two = decltype(TWO)::value != 0;
+        if constexpr (md != 3 || (geo == 0 && !emit && !two)) {      // the pool-gather form as in launch_bwd_apply
+            hipLaunchKernelGGL((k_bn_frozen_apply<md, emit, two, geo>), dim3(grid), dim3(NT), 0, st, D, msk, S0, S1, DY0, DY1, GO, n4, c4n, ps);
+            OSI_LAUNCH_CHECK();
+            return OSI_OK;
+        } else return OSI_ERR_ARG;
+    };
+    return pick<0, 2, 3>(mode, [&](auto MODE) {
+        return pick<0, 1>(gmasked != nullptr, [&](auto EMITG) {
+            return pick<0, 1>(n == 2, [&](auto TWO) {
+                return pick<0, 1, 2>(mode == 3 ? 0 : stream_geo(c4n), [&](auto GEO) { return go(MODE, EMITG, TWO, GEO); });
+            });
+        });
+    });
 }
 
 int osi_bn_backward_frozen(const float* dout, const void* relu_mask, const osi_bn_frozen_consumer* consumers, int n, float* gmasked, int M,
@@ -1050,24 +1053,16 @@ int osi_bn_relu_maxpool_bwd_frozen(const float* gpool, const void* idx, const fl
                                    const float* scale, float* dy, float* dgamma, float* dbeta, int B, int H, int W, int C, void* ws,
                                    size_t ws_bytes, osi_stream_t stream) {
     OSI_REQUIRE(idx && B > 0 && H > 0 && W > 0 && (long)B * H * W < (1l << 31));
-    PoolSrc ps;
-    ps.idx = (const uint32_t*)idx;
-    ps.dW = make_fastdiv((uint32_t)W); ps.dH = make_fastdiv((uint32_t)H);
-    ps.H = H; ps.W = W; ps.Ho = (H + 2 - 3) / 2 + 1; ps.Wo = (W + 2 - 3) / 2 + 1;
     const osi_bn_frozen_consumer c{y, mean, invstd, scale, dy, dgamma, dbeta};
-    return bn_frozen_impl(gpool, nullptr, 3, &c, 1, nullptr, B * H * W, C, ws, ws_bytes, (hipStream_t)stream, ps);
+    return bn_frozen_impl(gpool, nullptr, 3, &c, 1, nullptr, B * H * W, C, ws, ws_bytes, (hipStream_t)stream, make_pool_src(idx, H, W));
 }
 
 int osi_bn_relu_maxpool_bwd(const float* gpool, const void* idx, const float* y, const float* mean, const float* invstd,
                             const float* gamma, float* dy, float* dgamma, float* dbeta, int B, int H, int W, int C, void* ws,
                             size_t ws_bytes, osi_stream_t stream) {
     OSI_REQUIRE(idx && B > 0 && H > 0 && W > 0 && (long)B * H * W < (1l << 31));
-    PoolSrc ps;
-    ps.idx = (const uint32_t*)idx;
-    ps.dW = make_fastdiv((uint32_t)W); ps.dH = make_fastdiv((uint32_t)H);
-    ps.H = H; ps.W = W; ps.Ho = (H + 2 - 3) / 2 + 1; ps.Wo = (W + 2 - 3) / 2 + 1;
     return bn_backward_impl(gpool, nullptr, 3, y, mean, invstd, gamma, dy, nullptr, dgamma, dbeta, B * H * W, C, ws, ws_bytes,
-                            (hipStream_t)stream, ps);
+                            (hipStream_t)stream, make_pool_src(idx, H, W));
 }
 
 int osi_bn_backward(const float* dout, const float* act, const float* y, const float* mean, const float* invstd,
@@ -1089,7 +1084,7 @@ size_t osi_bn_backward_workspace(int M, int C) {
     if (M <= 0 || C <= 0) return 0;
     int P;
     rows_per_block(M, C, P);
-    return ((size_t)2 * P * C + 2 * (size_t)C) * sizeof(float);
+    return ws_floats(P, C) * sizeof(float);
 }
 
 }  // extern "C"

@@ -2127,16 +2127,8 @@ static int launch_wgrad3(const ConvP& p, int splits, hipStream_t st) {
     return launch_wgrad3_n<5, XF>(p, splits, st);
 }
 
-// ---- run-time values -> template instances ---------------------------------------------------------------------------------------
-// f(Int<V>{}) for the V of the list that equals v, OSI_ERR_ARG when none does: a chain of compares, nothing indirect on the launch path.
+// ---- run-time values -> template instances (Int<V> and pick<Vs...>(v, f) of osi_common.h) -------------------------------------------
 // The dispatchers below guard every combination with `if constexpr (..._exists(...))`: only the kernels those predicates name are built.
-template <int V> using Int = std::integral_constant<int, V>;
-template <int... Vs, class F>
-static int pick(int v, F&& f) {
-    int r = OSI_ERR_ARG;
-    (void)((v == Vs && ((r = f(Int<Vs>{})), true)) || ...);
-    return r;
-}
 struct TileShape { int wm, wn, nst; };       // workgroup tile in 64-row / 64-column units, LDS stages
 static TileShape tile_shape(int tile) {      // by OSI_TILE_* id (128x128, 128x64, 64x128, 64x64, then their _S1 forms); {0, 0, 0}: no such id
     static const TileShape ids[9] = {{0, 0, 0}, {2, 2, 2}, {2, 1, 2}, {1, 2, 2}, {1, 1, 2}, {1, 1, 1}, {1, 2, 1}, {2, 2, 1}, {2, 1, 1}};
@@ -2164,7 +2156,7 @@ static bool row_window_shape(const osi_conv_desc* d) {
 // floats of the statistics part of the forward workspace (row-tile partials + finalize scratch), rounded to 256 B: the slab of a
 // K-split tail starts behind it
 static size_t fwd_stats_floats(const osi_conv_desc* d) {
-    const size_t n = (size_t)2 * osi_cdiv((long)d->B * d->Ho * d->Wo, 64) * d->Cout + (size_t)2 * 32 * d->Cout;
+    const size_t n = bn_pstats_floats(osi_cdiv((long)d->B * d->Ho * d->Wo, 64), d->Cout);
     return (n + 63) / 64 * 64;
 }
 // K-split plan of the forward (GEMM rows = output pixels, columns Cout, K over Cin) or the stride-1 input gradient (input pixels, Cin, Cout)

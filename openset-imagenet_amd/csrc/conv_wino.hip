@@ -1057,6 +1057,30 @@ void plan_units(WinoP& p, void* slab, size_t slab_bytes, const osi_conv_desc* d,
 
 }  // namespace
 
+// k_wino<XF, EPI, ODD, WIDE> on G workgroups and, when the plan has a stream-K remainder (p.r > 0), its fix-up pass. epi: 0 = forward
+// (xf: fused input activation), 1 = the input gradient's fused epilogue, 2 = inference epilogue (own BatchNorm + ReLU on the output);
+// XF is built with EPI 0 only.
+static int launch_wino(const WinoP& p, int G, bool xf, int epi, bool odd, bool wide, hipStream_t st) {
+    auto go = [&](auto XF, auto EPI, auto ODD, auto WIDE) -> int {
+        constexpr bool xfc = decltype(XF)::value != 0, od = decltype(ODD)::value != 0, wd = decltype(WIDE)::value != 0;
+        constexpr int ep = decltype(EPI)::value;
+        if constexpr (!xfc || ep == 0) {
+            hipLaunchKernelGGL((k_wino<xfc, ep, od, wd>), dim3((unsigned)G), dim3(256), 0, st, p);
+            OSI_LAUNCH_CHECK();
+            if (p.r > 0) {
+                hipLaunchKernelGGL((k_wino_fixup<ep, od, wd>), dim3((unsigned)p.r * 16), dim3(64), 0, st, p, G);
+                OSI_LAUNCH_CHECK();
+            }
+            return OSI_OK;
+        } else return OSI_ERR_ARG;
+    };
+    return pick<0, 1>(xf, [&](auto XF) {
+        return pick<0, 1, 2>(epi, [&](auto EPI) {
+            return pick<0, 1>(odd, [&](auto ODD) { return pick<0, 1>(wide, [&](auto WIDE) { return go(XF, EPI, ODD, WIDE); }); });
+        });
+    });
+}
+
 extern "C" {
 
 /* 1 when the Winograd form takes this convolution (3x3 / stride 1 / pad 1, Cin % 16 == 0 and Cout % 64 == 0 forward — the roles swap for
@@ -1101,44 +1125,8 @@ static int fwd_wino_impl(const osi_conv_desc* d, const float* x, const float* in
     const int G = wino_grid(false);
     OSI_REQUIRE(slab_bytes >= (size_t)G * 2 * SLOT_BYTES);
     plan_units(p, slab, slab_bytes, d, G, false);
-    const dim3 grid((unsigned)G), blk(256);
     const bool wide = wide_units(d->Cout), odd = g.odd || (wide && g.T % 32 != 0);
-    auto launch = [&](auto XFC, auto ODDC, auto WIDEC) {
-        constexpr bool xf = decltype(XFC)::value, od = decltype(ODDC)::value, wd = decltype(WIDEC)::value;
-        hipLaunchKernelGGL((k_wino<xf, 0, od, wd>), grid, blk, 0, st, p);
-        if (hipGetLastError() != hipSuccess) return OSI_ERR_LAUNCH;
-        if (p.r > 0) {
-            hipLaunchKernelGGL((k_wino_fixup<0, od, wd>), dim3((unsigned)p.r * 16), dim3(64), 0, st, p, G);
-            if (hipGetLastError() != hipSuccess) return OSI_ERR_LAUNCH;
-        }
-        return OSI_OK;
-    };
-    auto launch_epi = [&](auto ODDC, auto WIDEC) {       // inference epilogue: plain input, own BatchNorm + ReLU on the output
-        constexpr bool od = decltype(ODDC)::value, wd = decltype(WIDEC)::value;
-        hipLaunchKernelGGL((k_wino<false, 2, od, wd>), grid, blk, 0, st, p);
-        if (hipGetLastError() != hipSuccess) return OSI_ERR_LAUNCH;
-        if (p.r > 0) {
-            hipLaunchKernelGGL((k_wino_fixup<2, od, wd>), dim3((unsigned)p.r * 16), dim3(64), 0, st, p, G);
-            if (hipGetLastError() != hipSuccess) return OSI_ERR_LAUNCH;
-        }
-        return OSI_OK;
-    };
-    using T_ = std::true_type; using F_ = std::false_type;
-    if (epi) {
-        if (odd) return wide ? launch_epi(T_{}, T_{}) : launch_epi(T_{}, F_{});
-        return wide ? launch_epi(F_{}, T_{}) : launch_epi(F_{}, F_{});
-    }
-    const int sel = (in_scale ? 4 : 0) | (odd ? 2 : 0) | (wide ? 1 : 0);
-    switch (sel) {
-        case 0: return launch(F_{}, F_{}, F_{});
-        case 1: return launch(F_{}, F_{}, T_{});
-        case 2: return launch(F_{}, T_{}, F_{});
-        case 3: return launch(F_{}, T_{}, T_{});
-        case 4: return launch(T_{}, F_{}, F_{});
-        case 5: return launch(T_{}, F_{}, T_{});
-        case 6: return launch(T_{}, T_{}, F_{});
-        default: return launch(T_{}, T_{}, T_{});
-    }
+    return launch_wino(p, G, in_scale != nullptr, epi ? 2 : 0, odd, wide, st);
 }
 
 int osi_conv_fwd_wino(const osi_conv_desc* d, const float* x, const float* in_scale, const float* in_shift, const float* w, float* y,
@@ -1197,21 +1185,8 @@ static int dgrad_wino_impl(const osi_conv_desc* d, const float* dy, const float*
     const int G = wino_grid(true);
     OSI_REQUIRE(slab_bytes >= (size_t)G * 2 * SLOT_BYTES);
     plan_units(p, slab, slab_bytes, d, G, true);
-    const dim3 grid((unsigned)G), blk(256);
     const bool wide = wide_units(d->Cin), odd = g.odd || (wide && g.T % 32 != 0);
-    auto launch = [&](auto ODDC, auto WIDEC) {
-        constexpr bool od = decltype(ODDC)::value, wd = decltype(WIDEC)::value;
-        hipLaunchKernelGGL((k_wino<false, 1, od, wd>), grid, blk, 0, st, p);
-        if (hipGetLastError() != hipSuccess) return OSI_ERR_LAUNCH;
-        if (p.r > 0) {
-            hipLaunchKernelGGL((k_wino_fixup<1, od, wd>), dim3((unsigned)p.r * 16), dim3(64), 0, st, p, G);
-            if (hipGetLastError() != hipSuccess) return OSI_ERR_LAUNCH;
-        }
-        return OSI_OK;
-    };
-    using T_ = std::true_type; using F_ = std::false_type;
-    if (odd) return wide ? launch(T_{}, T_{}) : launch(T_{}, F_{});
-    return wide ? launch(F_{}, T_{}) : launch(F_{}, F_{});
+    return launch_wino(p, G, false, 1, odd, wide, st);
 }
 
 int osi_conv_dgrad_fused_wino(const osi_conv_desc* d, const float* dy, const float* w, float* dx, const osi_dgrad_fusion* f, void* ws,

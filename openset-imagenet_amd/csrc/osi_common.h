@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/osi.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -64,6 +65,22 @@ struct OsiTuning {
 extern OsiTuning g_osi_tuning;
 
 static inline int osi_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// ---- run-time values -> template instances ---------------------------------------------------------------------------------------
+// f(Int<V>{}) for the V of the list that equals v, OSI_ERR_ARG when none does: a chain of compares, nothing indirect on the launch path.
+// The dispatchers guard every combination with `if constexpr`: only the kernels those conditions name are built.
+template <int V> using Int = std::integral_constant<int, V>;
+template <int... Vs, class F>
+static int pick(int v, F&& f) {
+    int r = OSI_ERR_ARG;
+    (void)((v == Vs && ((r = f(Int<Vs>{})), true)) || ...);
+    return r;
+}
+
+// BatchNorm statistics partials as a convolution's forward epilogue writes them and osi_bn_finalize_stats (bn.hip) reads them: [P][C]
+// row-tile means, [P][C] M2, then the scratch of the two-level finalisation ([C][S] group means and M2, S <= OSI_BN_GROUPS)
+constexpr int OSI_BN_GROUPS = 32;  // level-1 groups of the two-level statistics finalisation
+static inline size_t bn_pstats_floats(int P, int C) { return (size_t)2 * P * C + (size_t)2 * OSI_BN_GROUPS * C; }
 
 // Unsigned division by a runtime-constant divisor: q = (n * mul) >> (32 + sh), exact for n < 2^31.
 struct FastDiv {

@@ -10,6 +10,32 @@ def S():
     return torch.cuda.current_stream().cuda_stream
 
 
+class pinned_knobs:
+    """`with pinned_knobs(bn_grid=7, ...)`: sets the tuning knobs on entry and restores what they were on exit."""
+
+    def __init__(self, **settings):
+        self.settings, self.prev = settings, []
+
+    def __enter__(self):
+        lib = N.lib()
+        for k in self.settings:
+            v = ctypes.c_int()
+            N.check(lib.osi_get_tuning(k.encode(), ctypes.byref(v)), k)
+            self.prev.append((k, v.value))
+        try:
+            for k, v in self.settings.items():
+                N.check(lib.osi_set_tuning(k.encode(), v), f"{k} = {v}")
+        except Exception:
+            self.__exit__()
+            raise
+        return self
+
+    def __exit__(self, *exc):
+        for k, v in reversed(self.prev):
+            N.check(N.lib().osi_set_tuning(k.encode(), v), k)
+        return False
+
+
 def nhwc(x):          # NCHW tensor -> contiguous NHWC copy
     return x.permute(0, 2, 3, 1).contiguous()
 
