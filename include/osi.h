@@ -14,6 +14,16 @@
  *   - activations are fp32 NHWC ([B][H][W][C], C contiguous); conv weights are fp32 KRSC ([Cout][R][S][Cin]) —
  *     byte-identical to a torch OIHW tensor kept in channels_last strides, which is how the Python module owns them.
  *   - all pointers must be 16-byte aligned; channel counts must be multiples of 4 (64 for conv GEMM dimensions).
+ *   - non-finite values propagate as in torch: given the same NaN / +-Inf inputs, the SET of non-finite output elements of every
+ *     entry point equals that of the torch fp64 reference of the same operation, and every finite output element keeps the accuracy
+ *     it has on finite inputs. Every ReLU, variance clamp, pooling comparison and row maximum keeps a NaN (IEEE-754-2019 maximum,
+ *     not fmaxf): relu(NaN) = NaN, a BatchNorm channel holding one NaN / Inf gets non-finite statistics and a NaN output, a pooling
+ *     window holding a NaN gives NaN and its index names a NaN element. Which non-finite value comes out (NaN or +-Inf) is not
+ *     specified (the Winograd transforms turn Inf - Inf into NaN). Not specified either: (a) a non-finite value multiplied by a
+ *     structural zero (padding taps, rows past M, the fourth stem channel); (b) which NaN of a pooling window the index names when
+ *     it holds several; (c) the backward gate of an element whose forward activation was NaN (mask bit, bit 7 of the pool index,
+ *     recomputed gate: closed here, open in torch; the upstream gradient of a real step is NaN by then). A gate that is closed
+ *     takes its element out by a select: a NaN gradient behind it does not spread.
  */
 #ifndef OSI_H
 #define OSI_H

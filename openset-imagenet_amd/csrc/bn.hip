@@ -206,7 +206,7 @@ __global__ __launch_bounds__(16 * WPL) void k_bn_stats_final_wide(const float* _
     const float S2 = wide_reduce(red, s2a + s2b, pl, cl);
     if (pl == 0 && ok) {
         const float mean = pvv + S1 / (float)M;
-        const float m2 = fmaxf(S2 - S1 * S1 / (float)M, 0.f);
+        const float m2 = osi_relu(S2 - S1 * S1 / (float)M);     // the clamp keeps a NaN (osi_relu)
         bn_finish(c, mean, m2, M, gamma, beta, eps, momentum, running_mean, running_var, mean_out, invstd_out, scale_out, shift_out);
     }
 }
@@ -254,7 +254,7 @@ __global__ __launch_bounds__(NT) void k_bn_stats_group(const float* __restrict__
 #pragma unroll
         for (int k = 0; k < 16; ++k) { S1 += red[0][k][cl]; S2 += red[1][k][cl]; }
         gmean[(size_t)c * S + s] = pv + S1 / ng;
-        gm2[(size_t)c * S + s] = fmaxf(S2 - S1 * S1 / ng, 0.f);
+        gm2[(size_t)c * S + s] = osi_relu(S2 - S1 * S1 / ng);
     }
 }
 __global__ __launch_bounds__(NT) void k_bn_stats_final(const float* __restrict__ pmean, const float* __restrict__ pm2, int P,
@@ -376,7 +376,7 @@ __global__ __launch_bounds__(NT) void k_bn_apply(const f32x4* __restrict__ y, co
                 w[0] = b0; w[1] = b1; w[2] = b2; w[3] = b3;
             }
         }
-        if (RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+        if (RELU) v = osi_relu(v);
         out[i] = v;
     }
 }

@@ -280,7 +280,7 @@ __device__ __forceinline__ void fwd_store64(const ConvP& p, int m0, int n0, bool
             const f32x4 a = rd(rl, c4);
             f32x4 v;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { const float t = __builtin_fmaf(a[e], sc[e], sh[e]) + rv[k][e]; v[e] = p.orelu ? fmaxf(t, 0.f) : t; }
+            for (int e = 0; e < 4; ++e) { const float t = __builtin_fmaf(a[e], sc[e], sh[e]) + rv[k][e]; v[e] = p.orelu ? osi_relu(t) : t; }
             if (m < p.M) *reinterpret_cast<f32x4*>(y + (size_t)m * p.Cout) = v;
         }
     } else {
@@ -559,7 +559,7 @@ __global__ __launch_bounds__(256, XF ? (WM * WN == 1 ? 8 : 5) : (NST == 1 ? (WM 
             for (int e = 0; e < 4; ++e) {
                 float t = __builtin_fmaf(ra[i][e], sc[e], sh[e]);
                 if (XF == 2) t += rr[i][e];      // same two roundings as k_bn_apply<RES = 1>: fma, then add
-                v[e] = fmaxf(t, 0.f);
+                v[e] = osi_relu(t);
             }
             ra[i] = v;
         }
@@ -676,7 +676,7 @@ __global__ __launch_bounds__(256, XF ? (WM * WN == 1 ? 8 : 5) : (NST == 1 ? (WM 
                 for (int rr = 0; rr < 16; ++rr) {
                     const int m = m0 + wm * 32 * WM + i * 32 + acc_row(rr, lane);
                     const float t = __builtin_fmaf(acc[i][n][rr], sc, sh) + rv[rr];
-                    if (m < p.M) p.y[(size_t)m * p.Cout + col] = p.orelu ? fmaxf(t, 0.f) : t;
+                    if (m < p.M) p.y[(size_t)m * p.Cout + col] = p.orelu ? osi_relu(t) : t;
                 }
             } else
 #pragma unroll
@@ -1349,7 +1349,7 @@ __global__ __launch_bounds__(256, NST == 1 ? (WM * WN == 4 ? 4 : (WM * WN == 2 ?
 #pragma unroll
         for (int i = 0; i < BRN; ++i) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) rbv[i][e] = fmaxf(__builtin_fmaf(rbv[i][e], sc[e], sh[e]), 0.f);
+            for (int e = 0; e < 4; ++e) rbv[i][e] = osi_relu(__builtin_fmaf(rbv[i][e], sc[e], sh[e]));
         }
         // A padding tap must read as zero AFTER the activation: select. Pixels past the split's end need nothing: their dY row
         // is zero (range-checked load), so whatever finite value relu(shift) leaves in the X row is multiplied away — the 1x1
@@ -1537,7 +1537,7 @@ __global__ __launch_bounds__(256, 3) void k_conv_wgrad3(ConvP p) {   // 72 accum
 #pragma unroll
             for (int i = 0; i < NWIN; ++i)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) rb[i][e] = fmaxf(__builtin_fmaf(rb[i][e], xsc[e], xsh[e]), 0.f);
+                for (int e = 0; e < 4; ++e) rb[i][e] = osi_relu(__builtin_fmaf(rb[i][e], xsc[e], xsh[e]));
         }
         if (tid < W3_BKP) {                 // tap validity of pixel q: bit (3 r + s) set when (h + r - 1, w + s - 1) is inside the image
             const int q = kbeg + t * W3_BKP + tid;
@@ -1732,7 +1732,7 @@ __global__ __launch_bounds__(256, 4) void k_conv1x1_rows(ConvP p, int walkers) {
                 f32x4 v = ra[kt][i];
                 if (XF) {     // rows past M (last tile only) carry relu(shift): never stored, masked out of the statistics by row index
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(__builtin_fmaf(v[e], sc[e], sh[e]), 0.f);
+                    for (int e = 0; e < 4; ++e) v[e] = osi_relu(__builtin_fmaf(v[e], sc[e], sh[e]));
                 }
                 *reinterpret_cast<f32x4*>(sA + kt * IMG + (lr + 32 * i) * LDR + kq * 4) = v;
             }

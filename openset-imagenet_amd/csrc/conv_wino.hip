@@ -287,7 +287,7 @@ __device__ __forceinline__ void epi2_quad(const WinoP& p, PUT put, int g, const 
     for (int k = 0; k < 4; ++k) {
         f32x4 v;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { const float t = __builtin_fmaf(o[k][e], sc[e], sh[e]); v[e] = p.orelu ? fmaxf(t, 0.f) : t; }
+        for (int e = 0; e < 4; ++e) { const float t = __builtin_fmaf(o[k][e], sc[e], sh[e]); v[e] = p.orelu ? osi_relu(t) : t; }
         put(k, g, v);
     }
 }
@@ -425,7 +425,7 @@ __global__ __launch_bounds__(256, 1) void k_wino(WinoP p) {
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int e = 0; e < NV; ++e)
-                    asm volatile("v_fma_f32 %0, %0, %1, %2\n\tv_max_f32 %0, 0, %0\n\tv_cndmask_b32 %0, 0, %0, %3"
+                    asm volatile("v_fma_f32 %0, %0, %1, %2\n\tv_maximum3_f32 %0, %0, 0, 0\n\tv_cndmask_b32 %0, 0, %0, %3"
                                  : "+v"(xr[i * 4 + j][e]) : "v"(sc4[e]), "v"(sh4[e]), "s"(okm[i * 4 + j]));
         }
         {
@@ -764,8 +764,9 @@ __global__ __launch_bounds__(512) void k_wino_wgrad(WgradP p) {
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
             float v = rx_[set][k];
-            // (asm: fmaxf on a value the compiler did not produce itself gets a canonicalising v_max in front of the real one)
-            if constexpr (XF) asm volatile("v_fma_f32 %0, %1, %2, %3\n\tv_max_f32 %0, 0, %0" : "=v"(v) : "v"(rx_[set][k]), "v"(sc), "v"(sh));
+            // (asm since the ReLU was fmaxf, which got a canonicalising v_max in front of the real one on a loaded value; the
+            // NaN-keeping maximum of osi_relu is written out here the same way)
+            if constexpr (XF) asm volatile("v_fma_f32 %0, %1, %2, %3\n\tv_maximum3_f32 %0, %0, 0, 0" : "=v"(v) : "v"(rx_[set][k]), "v"(sc), "v"(sh));
             tx[k] = ((okx_[set] >> k) & 1u) ? v : 0.f;
         }
 #pragma unroll

@@ -44,7 +44,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_loss(LossP p) {
         const float* zr = p.z + (size_t)i * C;
         const long long yi = p.y[i];
         float mx = -__builtin_inff();
-        for (int c = lane; c < C; c += 64) mx = fmaxf(mx, zr[c]);
+        for (int c = lane; c < C; c += 64) mx = osi_max(mx, zr[c]);
         mx = wave_max(mx);
         float se = 0.f, sz = 0.f;
         for (int c = lane; c < C; c += 64) { float v = zr[c]; se += expf(v - mx); sz += v; }
@@ -68,10 +68,10 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_loss(LossP p) {
             ss = wave_sum(ss);
             const float nrm = sqrtf(ss);
             float r, g;  // residual and d(r^2)/d|f|
-            if (yi >= 0) { r = fmaxf(p.xi - nrm, 0.f); g = -2.f * r; }
+            if (yi >= 0) { r = osi_relu(p.xi - nrm); g = -2.f * r; }
             else { r = nrm; g = 2.f * r; }
             obj += r * r;
-            const float k = nrm > 0.f ? p.alpha / (float)p.B * g / nrm : 0.f;
+            const float k = nrm == 0.f ? 0.f : p.alpha / (float)p.B * g / nrm;     // a NaN norm gives a NaN row, as in torch
             for (int c = lane; c < p.F; c += 64) p.dfeat[(size_t)i * p.F + c] = k * fr[c];
         }
     }
@@ -107,10 +107,13 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_loss(LossP p) {
             const float w = lab_ok ? p.cw[yi] : 0.f;
             coef = w * inv; tval = coef;
         }
+        // a label torch.nn.CrossEntropyLoss would refuse (the row is taken out before the loss): an exact zero row by a select, whatever
+        // the logits hold. A row torch itself ignores (ignore_index, -100) keeps coef = 0 times its softmax: NaN logits give a NaN row there too
+        const bool refused = p.mode == OSI_LOSS_ENTROPIC ? yi >= C : !lab_ok && yi != (p.mode == OSI_LOSS_SOFTMAX ? p.ignore_index : -100);
         for (int c = lane; c < C; c += 64) {
             float g = coef * expf(zr[c] - lse) - tuni;
             if (lab_ok && c == (int)yi) g -= tval;
-            dr[c] = g;
+            dr[c] = refused ? 0.f : g;
         }
     }
 }
@@ -122,7 +125,7 @@ __global__ __launch_bounds__(256) void k_softmax(const float* __restrict__ z, fl
     if (i >= B) return;
     const float* zr = z + (size_t)i * C;
     float mx = -__builtin_inff();
-    for (int c = lane; c < C; c += 64) mx = fmaxf(mx, zr[c]);
+    for (int c = lane; c < C; c += 64) mx = osi_max(mx, zr[c]);
     mx = wave_max(mx);
     float se = 0.f;
     for (int c = lane; c < C; c += 64) se += expf(zr[c] - mx);
@@ -145,7 +148,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_confidence(const float* __rest
         const float* zr = z + (size_t)i * C;
         const long long yi = y[i];
         float mx = -__builtin_inff(), mv = -__builtin_inff();
-        for (int c = lane; c < C; c += 64) { float v = zr[c]; mx = fmaxf(mx, v); if (c < n_valid) mv = fmaxf(mv, v); }
+        for (int c = lane; c < C; c += 64) { float v = zr[c]; mx = osi_max(mx, v); if (c < n_valid) mv = osi_max(mv, v); }
         mx = wave_max(mx); mv = wave_max(mv);
         if (SCORES) {
             if (yi == unknown_class) { ns += (double)(1.0f + offset - mv); nc += 1; }

@@ -115,6 +115,12 @@ __device__ __forceinline__ void chan_merge(float& na, float& ma, float& sa, floa
     na = n;
 }
 
+// NaN-keeping maximum (IEEE-754-2019 maximum, one v_maximum3_f32): fmaxf returns the other operand for a NaN, which would turn a
+// diverged activation into a clean zero at the next ReLU. Non-finite values propagate as in torch (include/osi.h, conventions).
+__device__ __forceinline__ float osi_max(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ float osi_relu(float t) { return __builtin_elementwise_maximum(t, 0.f); }
+__device__ __forceinline__ f32x4 osi_relu(f32x4 t) { return __builtin_elementwise_maximum(t, f32x4{0.f, 0.f, 0.f, 0.f}); }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -122,6 +128,6 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    for (int o = 32; o > 0; o >>= 1) v = osi_max(v, __shfl_xor(v, o, 64));
     return v;
 }

@@ -17,7 +17,8 @@ __global__ __launch_bounds__(256) void k_nchw3_to_nhwc4(const float* __restrict_
 }
 
 // MaxPool 3x3 stride 2 pad 1, NHWC. idx = position (0..8) of the first maximum in row-major window order
-// (torch's tie rule: strictly-greater replaces), stored as one byte per output element.
+// (torch's tie rule: strictly-greater replaces, and so does a NaN: a window holding one gives NaN and names it), stored as one
+// byte per output element.
 __global__ __launch_bounds__(256) void k_maxpool_fwd(const f32x4* __restrict__ x, f32x4* __restrict__ y, uint32_t* __restrict__ idx,
                                                     int B, int H, int W, int C4, int Ho, int Wo) {
     size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -40,8 +41,11 @@ __global__ __launch_bounds__(256) void k_maxpool_fwd(const f32x4* __restrict__ x
             if ((unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W) {
                 f32x4 v = x[((size_t)(b * H + h) * W + w) * C4 + c4];
 #pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (first[k] || v[k] > best[k]) { best[k] = v[k]; bi[k] = r * 3 + s; first[k] = false; }
+                for (int k = 0; k < 4; ++k) {
+                    // bitwise, not short-circuit: one select per value instead of a branch per test
+                    const bool take = first[k] | (v[k] > best[k]) | (v[k] != v[k]);
+                    best[k] = take ? v[k] : best[k]; bi[k] = take ? r * 3 + s : bi[k]; first[k] = false;
+                }
             }
         }
     y[i] = best;
@@ -83,10 +87,12 @@ __global__ __launch_bounds__(256) void k_bn_relu_maxpool_fwd(const f32x4* __rest
 #pragma unroll
     for (int j = 0; j < 9; ++j) {
         f32x4 v = win[j] * sc + sh;      // same expression as k_bn_apply
-        v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+        v = osi_relu(v);
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (ok[j] && (first[k] || v[k] > best[k])) { best[k] = v[k]; bi[k] = j; first[k] = false; }
+        for (int k = 0; k < 4; ++k) {
+            const bool take = ok[j] & (first[k] | (v[k] > best[k]) | (v[k] != v[k]));
+            best[k] = take ? v[k] : best[k]; bi[k] = take ? j : bi[k]; first[k] &= !ok[j];
+        }
     }
     pooled[i] = best;
 #pragma unroll
