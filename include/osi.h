@@ -41,7 +41,7 @@ extern "C" {
 
 typedef void* osi_stream_t; /* hipStream_t */
 
-int osi_abi_version(void);            /* bumped on any signature change; 18 = evaluation histograms (osi_eval_values_*, osi_hist_*); 17 = gradient-norm clipping (osi_grad_clip_scale, osi_*_step_groups_dev); 16 = the ROC-AUC entry points (osi_auc_*) */
+int osi_abi_version(void);            /* bumped on any signature change; 19 = projected attack steps (osi_stem_dgrad_pgd, osi_resnet50_backward_attack); 18 = evaluation histograms (osi_eval_values_*, osi_hist_*); 17 = gradient-norm clipping (osi_grad_clip_scale, osi_*_step_groups_dev); 16 = the ROC-AUC entry points (osi_auc_*) */
 const char* osi_build_arch(void);     /* "gfx950" */
 const char* osi_strerror(int code);
 /* Process-wide development knobs (A/B measurements; every default is the measured optimum). Launch functions only READ them and never
@@ -264,6 +264,19 @@ int osi_stem_dgrad(const float* dy, const float* w_krsc3, float* dx_nchw, int B,
  * launch. */
 int osi_stem_dgrad_fgsm(const float* dy, const float* w_krsc3, const float* x_nhwc4, float* x_adv_nhwc4, float eps, float lo, float hi,
                         int B, int H, int W, osi_stream_t stream);
+/* ABI 19. The same input gradient ending in one step of a projected attack (PGD): dx is never written; with dx as above, per pixel and
+ * per channel c = 0, 1, 2, every operation one fp32 rounding,
+ *   t      = x_cur + alpha * sgn(dx)                  (alpha * sgn is exact)
+ *   t      = min(max(t, a - eps), a + eps)            a = the pixel of x_anchor (the clean batch): projection onto its eps-ball
+ *   x_next = min(hi, max(lo, t));   x_next[b][h][w][3] = 0
+ * = torch.clamp(torch.min(torch.max(x + alpha * torch.sign(g), a - eps), a + eps), lo, hi) on fp32 tensors. All three batches are
+ * NHWC4 [B][H][W][4]; one 16-byte load more than the FGSM form per pixel (the anchor), one 16-byte store, every element written,
+ * deterministic. Argument rules of osi_stem_dgrad_fgsm, plus: x_anchor_nhwc4 non-NULL and 16-byte aligned; alpha finite (negative
+ * descends); eps >= 0, +inf allowed (no projection); x_next overlaps neither x_cur nor x_anchor; x_anchor may be x_cur (step 0 of an
+ * attack). OSI_ERR_ARG before any launch. With x_anchor == x_cur and 0 <= alpha <= eps, and with eps = +inf for any anchor, the result
+ * is the bits of osi_stem_dgrad_fgsm(eps := alpha). Non-finite pixels behave as in osi_stem_dgrad_fgsm. */
+int osi_stem_dgrad_pgd(const float* dy, const float* w_krsc3, const float* x_cur_nhwc4, const float* x_anchor_nhwc4, float* x_next_nhwc4,
+                       float alpha, float eps, float lo, float hi, int B, int H, int W, osi_stream_t stream);
 
 /* ---- BatchNorm2d in training mode + ReLU + residual (torchvision Bottleneck under model.py:37; train() at train.py:125) --- */
 size_t osi_bn_workspace(int M, int C);
@@ -647,6 +660,28 @@ int osi_resnet50_backward_ex(osi_resnet50_t net, const float* params, float* gra
 int osi_resnet50_backward_adv(osi_resnet50_t net, const float* params, float* grads, void* workspace, const float* dlogits,
                               const float* dfeatures, float* x_adv_nhwc4, float eps, float lo, float hi, int stage_lo, int stage_hi,
                               osi_stream_t stream);
+
+/* ABI 19. A backward whose last launch is one step of a projected attack (osi_stem_dgrad_pgd) from the batch the forward read (the
+ * iterate) towards x_next, projected onto the eps-ball around x_anchor:
+ *   x_next = clamp(min(max(x + alpha * sign(dJ/dimage), a - eps), a + eps), lo, hi)     [B][H][W][4] fp32, 4th lane zero.
+ * param_grads = 1: parameter gradients are the bits of osi_resnet50_backward_adv (the same dY-materialising stem tail).
+ * param_grads = 0: the input-only dataflow of osi_resnet50_backward_ex(dimage, 0) — grads may be NULL, no weight-gradient launch, no
+ * fc / logits dw / db, nothing on the side stream, the BatchNorm reductions dY needs go into the workspace — and only its last launch
+ * differs: the attack epilogue instead of osi_stem_dgrad. Valid after osi_resnet50_forward(training = 1) and after
+ * osi_resnet50_forward_frozen; after a forward with an inference-form prefix -> OSI_ERR_STATE, as _adv. x_next: 16-byte aligned,
+ * outside `workspace`, apart from the input the forward read and from x_anchor; x_anchor: 16-byte aligned or NULL; alpha finite,
+ * eps >= 0 (+inf allowed), lo <= hi; param_grads 0 or 1, grads non-NULL when 1: OSI_ERR_ARG otherwise. The request (all six fields and
+ * param_grads) is fixed by the call that runs stage 0; a later stage with another request -> OSI_ERR_STATE.
+ * osi_resnet50_backward_adv(x_adv, eps, lo, hi) = _attack({x_adv, NULL, eps, eps, lo, hi}, 1), the same bits: with the anchor the
+ * iterate itself and alpha = eps the projection changes nothing. */
+typedef struct {
+    float* x_next;          /* [B][H][W][4], 16-byte aligned, outside workspace, apart from the input the forward read and from x_anchor */
+    const float* x_anchor;  /* [B][H][W][4] or NULL = the batch the forward read (NCHW-converted copy, staged uint8 batch or bound NHWC4) */
+    float alpha, eps, lo, hi;
+} osi_attack;
+int osi_resnet50_backward_attack(osi_resnet50_t net, const float* params, float* grads, void* workspace, const float* dlogits,
+                                 const float* dfeatures, const osi_attack* a, int param_grads, int stage_lo, int stage_hi,
+                                 osi_stream_t stream);
 
 /* Data-parallel hand-off (ABI 5). With option "stage_join" = 0 a staged osi_resnet50_backward call (stage_hi < stages) does NOT make
  * `stream` wait for the side stream's weight gradients (the last stage always does); instead the caller makes its COMMUNICATION stream

@@ -6,6 +6,7 @@
 //   torch.ops.osi.resnet50_backward   train.py:138     (j.backward() through the network, stage range for the DP bucket schedule)
 //   torch.ops.osi.resnet50_backward_ex  the same, plus dJ/dimage and the input-only backward (adversarial samples, attribution)
 //   torch.ops.osi.resnet50_backward_adv the same, the last stage writing the FGSM batch; torch.ops.osi.grad_accumulate sums two arenas
+//   torch.ops.osi.resnet50_backward_attack  full or input-only backward ending in a projected attack step (PGD); stem_dgrad_pgd: that kernel
 //   torch.ops.osi.resnet50_grads_ready  config/train.yaml:18,35-39 (hand a finished stage's gradients to the communication stream)
 //   torch.ops.osi.loss_fwd_bwd        losses.py:16-29, train.py:343-347 (the three losses + objectosphere term, value and gradient)
 //   torch.ops.osi.adam_step / sgd_step    train.py:139, 356-359; adam_step_groups / sgd_step_groups: the same with parameter groups;
@@ -188,6 +189,59 @@ void resnet50_backward_adv(int64_t net, const Tensor& params, Tensor grads, Tens
                                  dlogits.data_ptr<float>(), fptr(dfeatures), x_adv.data_ptr<float>(), (float)eps, (float)lo, (float)hi,
                                  (int)stage_lo, (int)stage_hi, stream_of(params)),
        "osi_resnet50_backward_adv");
+}
+
+// ABI 19: a backward whose last launch is one projected attack step (osi_stem_dgrad_pgd) from the batch the forward read towards x_next,
+// projected onto the eps-ball around x_anchor (None: around the forward's own batch). param_grads = false: input-only — `grads` is not
+// touched and may be an empty tensor, nothing runs on the side stream (the inner steps of a PGD attack, attacks inside validate())
+void resnet50_backward_attack(int64_t net, const Tensor& params, Tensor grads, Tensor workspace, const Tensor& dlogits,
+                              const std::optional<Tensor>& dfeatures, Tensor x_next, const std::optional<Tensor>& x_anchor, double alpha,
+                              double eps, double lo, double hi, bool param_grads, int64_t stage_lo, int64_t stage_hi) {
+    need(params, at::kFloat, "params"); need(workspace, at::kByte, "workspace");
+    need(dlogits, at::kFloat, "dlogits", NATURAL); need(x_next, at::kFloat, "x_next");
+    if (dfeatures.has_value() && dfeatures->defined()) need(*dfeatures, at::kFloat, "dfeatures", NATURAL);
+    if (param_grads) {
+        need(grads, at::kFloat, "grads");
+        TORCH_CHECK(grads.numel() == params.numel(), "osi::resnet50_backward_attack: gradient arena size mismatch");
+    }
+    TORCH_CHECK(x_next.device() == params.device(), "osi::resnet50_backward_attack: x_next lives on another device than params");
+    int B = 0, H = 0, W = 0;
+    ok(osi_resnet50_geometry(handle(net), &B, &H, &W), "osi_resnet50_geometry");
+    TORCH_CHECK(x_next.dim() == 4 && x_next.size(0) == B && x_next.size(1) == H && x_next.size(2) == W && x_next.size(3) == 4,
+                "osi::resnet50_backward_attack: x_next must be [", B, ", ", H, ", ", W, ", 4] (NHWC4), got ", x_next.sizes());
+    osi_attack a{x_next.data_ptr<float>(), nullptr, (float)alpha, (float)eps, (float)lo, (float)hi};
+    if (x_anchor.has_value() && x_anchor->defined()) {
+        need(*x_anchor, at::kFloat, "x_anchor");
+        TORCH_CHECK(x_anchor->device() == params.device(), "osi::resnet50_backward_attack: x_anchor lives on another device than params");
+        TORCH_CHECK(x_anchor->sizes() == x_next.sizes(), "osi::resnet50_backward_attack: x_anchor must be [", B, ", ", H, ", ", W,
+                    ", 4] (NHWC4), got ", x_anchor->sizes());
+        a.x_anchor = x_anchor->data_ptr<float>();
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(params.device());
+    ok(osi_resnet50_backward_attack(handle(net), params.data_ptr<float>(), param_grads ? grads.data_ptr<float>() : nullptr,
+                                    workspace.data_ptr(), dlogits.data_ptr<float>(), fptr(dfeatures), &a, param_grads ? 1 : 0, (int)stage_lo,
+                                    (int)stage_hi, stream_of(params)),
+       "osi_resnet50_backward_attack");
+}
+
+// ABI 19: the stem's input gradient ending in one projected attack step, on its own (dy [B, Hs, Ws, 64] NHWC, w [64, 7, 7, 3] storage
+// order, three NHWC4 batches of one shape); returns nothing, x_next is written
+void stem_dgrad_pgd(const Tensor& dy, const Tensor& w_krsc3, const Tensor& x_cur, const Tensor& x_anchor, Tensor x_next, double alpha,
+                    double eps, double lo, double hi) {
+    need(dy, at::kFloat, "dy"); need(w_krsc3, at::kFloat, "w_krsc3", NATURAL);
+    need(x_cur, at::kFloat, "x_cur"); need(x_anchor, at::kFloat, "x_anchor"); need(x_next, at::kFloat, "x_next");
+    TORCH_CHECK(x_cur.dim() == 4 && x_cur.size(3) == 4, "osi::stem_dgrad_pgd: x_cur must be [B, H, W, 4] (NHWC4), got ", x_cur.sizes());
+    TORCH_CHECK(x_anchor.sizes() == x_cur.sizes() && x_next.sizes() == x_cur.sizes(), "osi::stem_dgrad_pgd: the three batches differ in shape");
+    TORCH_CHECK(dy.device() == x_cur.device() && w_krsc3.device() == x_cur.device() && x_anchor.device() == x_cur.device() &&
+                x_next.device() == x_cur.device(), "osi::stem_dgrad_pgd: tensors live on different devices");
+    const int64_t B = x_cur.size(0), H = x_cur.size(1), W = x_cur.size(2);
+    TORCH_CHECK(dy.dim() == 4 && dy.size(0) == B && dy.size(1) == (H - 1) / 2 + 1 && dy.size(2) == (W - 1) / 2 + 1 && dy.size(3) == 64,
+                "osi::stem_dgrad_pgd: dy must be [", B, ", ", (H - 1) / 2 + 1, ", ", (W - 1) / 2 + 1, ", 64] (NHWC), got ", dy.sizes());
+    TORCH_CHECK(w_krsc3.numel() == 64 * 7 * 7 * 3, "osi::stem_dgrad_pgd: w_krsc3 must hold 64 x 7 x 7 x 3 floats");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(x_cur.device());
+    ok(osi_stem_dgrad_pgd(dy.data_ptr<float>(), w_krsc3.data_ptr<float>(), x_cur.data_ptr<float>(), x_anchor.data_ptr<float>(),
+                          x_next.data_ptr<float>(), (float)alpha, (float)eps, (float)lo, (float)hi, (int)B, (int)H, (int)W, stream_of(x_cur)),
+       "osi_stem_dgrad_pgd");
 }
 
 // dst += src over two gradient arenas of the same length
@@ -407,6 +461,10 @@ TORCH_LIBRARY(osi, m) {
           "Tensor(c!)? dimage, bool param_grads, int stage_lo, int stage_hi) -> ()");
     m.def("resnet50_backward_adv(int net, Tensor params, Tensor(a!) grads, Tensor(b!) workspace, Tensor dlogits, Tensor? dfeatures, "
           "Tensor(c!) x_adv, float eps, float lo, float hi, int stage_lo, int stage_hi) -> ()");
+    m.def("resnet50_backward_attack(int net, Tensor params, Tensor(a!) grads, Tensor(b!) workspace, Tensor dlogits, Tensor? dfeatures, "
+          "Tensor(c!) x_next, Tensor? x_anchor, float alpha, float eps, float lo, float hi, bool param_grads, int stage_lo, int stage_hi) -> ()");
+    m.def("stem_dgrad_pgd(Tensor dy, Tensor w_krsc3, Tensor x_cur, Tensor x_anchor, Tensor(a!) x_next, float alpha, float eps, float lo, "
+          "float hi) -> ()");
     m.def("grad_accumulate(Tensor(a!) dst, Tensor src) -> ()");
     m.def("resnet50_grads_ready(int net, Tensor grads, int waiter_stream) -> ()");
     m.def("loss_fwd_bwd(int mode, Tensor logits, Tensor target, float unk_weight, int ignore_index, Tensor? class_weights, "
@@ -434,6 +492,8 @@ TORCH_LIBRARY_IMPL(osi, CUDA, m) {
     m.impl("resnet50_backward", &resnet50_backward);
     m.impl("resnet50_backward_ex", &resnet50_backward_ex);
     m.impl("resnet50_backward_adv", &resnet50_backward_adv);
+    m.impl("resnet50_backward_attack", &resnet50_backward_attack);
+    m.impl("stem_dgrad_pgd", &stem_dgrad_pgd);
     m.impl("grad_accumulate", &grad_accumulate);
     m.impl("resnet50_grads_ready", &resnet50_grads_ready);
     m.impl("loss_fwd_bwd", &loss_fwd_bwd);

@@ -72,17 +72,22 @@ static int device_cus() {   // CUs of the CURRENT device (the launch plans are b
     return v;
 }
 
-// What a backward is asked for (osi_resnet50_backward_ex / _adv). dimage != NULL: the stem tail materialises dY and its input gradient
+// What a backward is asked for (osi_resnet50_backward_ex / _adv / _attack). dimage != NULL: the stem tail materialises dY and its input gradient
 // writes dJ/dimage. param_grads = 0: input-only (no weight gradient, nothing into grads). x_adv != NULL: the stem tail materialises dY as
 // for dJ/dimage and the stem's input gradient ends in the FGSM epilogue (osi_stem_dgrad_fgsm) that writes the adversarial NHWC4 batch;
-// dJ/dimage itself is never written.
+// dJ/dimage itself is never written. x_anchor / alpha (osi_resnet50_backward_attack): the epilogue is the projected step of
+// osi_stem_dgrad_pgd, alpha along the sign and back onto the eps-ball around x_anchor (NULL: around the batch the forward read).
+// osi_resnet50_backward_adv is the request {x_anchor = NULL, alpha = eps}, for which the projection is the identity.
 struct BwRequest {
     float* dimage = nullptr;
     int param_grads = 1;
     float* x_adv = nullptr;
     float eps = 0.f, lo = 0.f, hi = 0.f;
+    const float* x_anchor = nullptr;
+    float alpha = 0.f;
     bool operator==(const BwRequest& o) const {
-        return dimage == o.dimage && param_grads == o.param_grads && x_adv == o.x_adv && eps == o.eps && lo == o.lo && hi == o.hi;
+        return dimage == o.dimage && param_grads == o.param_grads && x_adv == o.x_adv && eps == o.eps && lo == o.lo && hi == o.hi &&
+               x_anchor == o.x_anchor && alpha == o.alpha;
     }
 };
 
@@ -1170,8 +1175,14 @@ static int stem_tail(osi_resnet50* n, const float* params, float* grads, float* 
     if (rq.dimage) {
         OSI_TRY(osi_stem_dgrad(S(t), params + c0.w_off, rq.dimage, n->B, n->H, n->W, st));
         OSI_TRY(n->mark(OSI_PROF_CONV_DGRAD, st));
-    } else if (rq.x_adv) {     // the same input gradient, ending in the FGSM epilogue: x_adv from the batch the forward read
+    } else if (rq.x_adv && !rq.x_anchor && rq.alpha == rq.eps) {
+        // the same input gradient, ending in the FGSM epilogue: x_adv from the batch the forward read (a projected step of alpha = eps
+        // anchored at its own iterate is this one: no second load of the same pixel)
         OSI_TRY(osi_stem_dgrad_fgsm(S(t), params + c0.w_off, x4c, rq.x_adv, rq.eps, rq.lo, rq.hi, n->B, n->H, n->W, st));
+        OSI_TRY(n->mark(OSI_PROF_CONV_DGRAD, st));
+    } else if (rq.x_adv) {     // ending in the projected step: the next iterate from the batch the forward read and the anchor
+        OSI_TRY(osi_stem_dgrad_pgd(S(t), params + c0.w_off, x4c, rq.x_anchor ? rq.x_anchor : x4c, rq.x_adv, rq.alpha, rq.eps, rq.lo, rq.hi,
+                                   n->B, n->H, n->W, st));
         OSI_TRY(n->mark(OSI_PROF_CONV_DGRAD, st));
     }
     n->give(t);
@@ -1222,8 +1233,21 @@ int osi_resnet50_backward_ex(osi_resnet50_t n, const float* params, float* grads
     OSI_REQUIRE(!param_grads || grads);
     OSI_REQUIRE(param_grads || dimage);                 // a backward that produces nothing is a caller error
     OSI_REQUIRE(((uintptr_t)dimage & 3) == 0);
-    return backward_stages(n, params, grads, workspace, dlogits, dfeatures, BwRequest{dimage, param_grads, nullptr, 0.f, 0.f, 0.f}, stage_lo,
+    return backward_stages(n, params, grads, workspace, dlogits, dfeatures, BwRequest{dimage, param_grads, nullptr, 0.f, 0.f, 0.f, nullptr, 0.f}, stage_lo,
                            stage_hi, stream);
+}
+
+// The batch an attack epilogue writes may not touch the batch the forward read (bound in place, or the copy inside the workspace), anything
+// else in the workspace, or the anchor: other workgroups still read those pixels — and conv1's weight gradient on the side stream reads
+// the forward's batch — while the epilogue writes.
+static bool attack_output_apart(const osi_resnet50* n, const void* workspace, const float* x_out, const float* x_anchor) {
+    const size_t img_bytes = (size_t)n->B * n->H * n->W * 4 * sizeof(float);
+    auto apart = [&](const void* p, size_t bytes) {
+        const uintptr_t a = (uintptr_t)x_out, b = (uintptr_t)p;
+        return a + img_bytes <= b || b + bytes <= a;
+    };
+    return apart(workspace, n->ws_floats * sizeof(float)) && (!n->x4_cur || apart(n->x4_cur, img_bytes)) &&
+           (!x_anchor || apart(x_anchor, img_bytes));
 }
 
 int osi_resnet50_backward_adv(osi_resnet50_t n, const float* params, float* grads, void* workspace, const float* dlogits,
@@ -1231,17 +1255,22 @@ int osi_resnet50_backward_adv(osi_resnet50_t n, const float* params, float* grad
                               osi_stream_t stream) {
     OSI_REQUIRE(n && params && grads && workspace && x_adv_nhwc4);
     OSI_REQUIRE(((uintptr_t)x_adv_nhwc4 & 15) == 0 && eps >= 0.f && lo <= hi);
-    // the adversarial batch may not touch the clean one (bound in place, or the copy inside the workspace) nor anything else in the
-    // workspace: conv1's weight gradient on the side stream still reads the clean batch while the FGSM epilogue writes
-    const size_t img_bytes = (size_t)n->B * n->H * n->W * 4 * sizeof(float);
-    auto apart = [&](const void* p, size_t bytes) {
-        const uintptr_t a = (uintptr_t)x_adv_nhwc4, b = (uintptr_t)p;
-        return a + img_bytes <= b || b + bytes <= a;
-    };
-    OSI_REQUIRE(apart(workspace, n->ws_floats * sizeof(float)));
-    OSI_REQUIRE(!n->x4_cur || apart(n->x4_cur, img_bytes));
-    return backward_stages(n, params, grads, workspace, dlogits, dfeatures, BwRequest{nullptr, 1, x_adv_nhwc4, eps, lo, hi}, stage_lo,
-                           stage_hi, stream);
+    OSI_REQUIRE(attack_output_apart(n, workspace, x_adv_nhwc4, nullptr));
+    return backward_stages(n, params, grads, workspace, dlogits, dfeatures, BwRequest{nullptr, 1, x_adv_nhwc4, eps, lo, hi, nullptr, eps},
+                           stage_lo, stage_hi, stream);
+}
+
+int osi_resnet50_backward_attack(osi_resnet50_t n, const float* params, float* grads, void* workspace, const float* dlogits,
+                                 const float* dfeatures, const osi_attack* a, int param_grads, int stage_lo, int stage_hi,
+                                 osi_stream_t stream) {
+    OSI_REQUIRE(n && params && workspace && a && a->x_next);
+    OSI_REQUIRE(param_grads == 0 || param_grads == 1);
+    OSI_REQUIRE(!param_grads || grads);
+    OSI_REQUIRE(((uintptr_t)a->x_next & 15) == 0 && ((uintptr_t)a->x_anchor & 15) == 0);
+    OSI_REQUIRE(a->eps >= 0.f && a->lo <= a->hi && a->alpha - a->alpha == 0.f);
+    OSI_REQUIRE(attack_output_apart(n, workspace, a->x_next, a->x_anchor));
+    return backward_stages(n, params, grads, workspace, dlogits, dfeatures,
+                           BwRequest{nullptr, param_grads, a->x_next, a->eps, a->lo, a->hi, a->x_anchor, a->alpha}, stage_lo, stage_hi, stream);
 }
 
 // Hand the gradients of the stages enqueued so far to another stream WITHOUT stalling the compute stream: `waiter` waits for the

@@ -15,10 +15,14 @@
 //   * every element of dx is written once, out-of-range pixels of the last tiles are masked; out-of-range dY pixels read as zero
 //     through the buffer range check.
 //
-// Second form (FGSM = true, osi_stem_dgrad_fgsm): the same K loop, another epilogue. dx is not written at all; the lane already holds
+// Second form (SG_FGSM, osi_stem_dgrad_fgsm): the same K loop, another epilogue. dx is not written at all; the lane already holds
 // the three channel sums of each of its pixels, so it loads the clean pixel from the NHWC4 batch the forward read (16 bytes), moves
 // each channel by eps along the sign of its gradient, clamps and stores the adversarial pixel into an NHWC4 batch (16 bytes, 4th lane
 // zero): one vector store per pixel where the NCHW form needs three scattered 4-byte stores.
+//
+// Third form (SG_PGD, osi_stem_dgrad_pgd): one step of a projected attack. The lane loads the iterate's pixel AND the anchor's (the clean
+// batch: one more 16-byte load), moves the iterate by alpha along the sign, projects onto the eps-ball around the anchor, clamps and stores
+// the next iterate. The epilogue is a compile-time mode of the one kernel template: the K loop is the same code in all three.
 #include "conv_common.h"
 
 using namespace osi_conv;
@@ -68,10 +72,13 @@ __device__ __forceinline__ void sg_chunk(const f32x2* __restrict__ sd, const flo
     }
 }
 
-template <bool FGSM>
+enum : int { SG_NCHW = 0, SG_FGSM = 1, SG_PGD = 2 };   // epilogue of k_stem_dgrad
+
+template <int MODE>
 __global__ __launch_bounds__(256) void k_stem_dgrad(const float* __restrict__ dy, const float* __restrict__ w, float* __restrict__ dx,
                                                     int H, int W, int Hs, int Ws, int tiles_x, int tiles_y, int dy_bytes,
-                                                    const float* __restrict__ x4, float eps, float lo, float hi) {
+                                                    const float* __restrict__ x4, float eps, float lo, float hi,
+                                                    const float* __restrict__ xa4, float alpha) {
     __shared__ __attribute__((aligned(16))) f32x2 sd[SG_LDS_F2];   // read as 16-byte vectors (ds_read_b128)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -110,22 +117,29 @@ __global__ __launch_bounds__(256) void k_stem_dgrad(const float* __restrict__ dy
     }
     const int h = h0 + ph + 2 * i;
     if (h >= H) return;
-    if constexpr (FGSM) {
-        // dx = the NHWC4 output batch here: x_adv = clamp(x + eps * sign(dJ/dx)), the gradient itself stays in registers
+    if constexpr (MODE != SG_NCHW) {
+        // dx = the NHWC4 output batch here, the gradient itself stays in registers. FGSM: x_adv = clamp(x + eps * sign(dJ/dx)).
+        // PGD: x4 = the iterate, xa4 = the anchor (it may be the iterate itself; both are only read), x_next = clamp(the iterate moved
+        // by alpha along the sign, projected onto [anchor - eps, anchor + eps]); alpha * sign is exact, so every line is one rounding
         const size_t row = ((size_t)b * H + h) * W;
         const f32x4* xin = reinterpret_cast<const f32x4*>(x4) + row;
         f32x4* xout = reinterpret_cast<f32x4*>(dx) + row;
+        const float step = MODE == SG_PGD ? alpha : eps;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int x = w0 + pw + 2 * (8 * q + j);
             if (x < W) {
                 const f32x4 p = xin[x];
+                f32x4 a = p;
+                if constexpr (MODE == SG_PGD) a = (reinterpret_cast<const f32x4*>(xa4) + row)[x];
                 f32x4 o;
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     const float t = acc[j][c][0] + acc[j][c][1];                    // the sum the NCHW form stores
                     const float sg = (float)((t > 0.f) - (t < 0.f));                // torch.sign
-                    o[c] = fminf(hi, fmaxf(lo, p[c] + eps * sg));
+                    float v = p[c] + step * sg;
+                    if constexpr (MODE == SG_PGD) v = fminf(fmaxf(v, a[c] - eps), a[c] + eps);
+                    o[c] = fminf(hi, fmaxf(lo, v));
                 }
                 o[3] = 0.f;
                 xout[x] = o;
@@ -157,8 +171,8 @@ int osi_stem_dgrad(const float* dy, const float* w_krsc3, float* dx_nchw, int B,
     const int tiles_x = osi_cdiv(W, SG_TW), tiles_y = osi_cdiv(H, SG_TH);
     const size_t grid = (size_t)B * tiles_x * tiles_y;
     OSI_REQUIRE(grid < ((size_t)1 << 31));
-    hipLaunchKernelGGL(k_stem_dgrad<false>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, dy, w_krsc3, dx_nchw, H, W, Hs, Ws,
-                       tiles_x, tiles_y, (int)dy_bytes, (const float*)nullptr, 0.f, 0.f, 0.f);
+    hipLaunchKernelGGL(k_stem_dgrad<SG_NCHW>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, dy, w_krsc3, dx_nchw, H, W, Hs, Ws,
+                       tiles_x, tiles_y, (int)dy_bytes, (const float*)nullptr, 0.f, 0.f, 0.f, (const float*)nullptr, 0.f);
     OSI_LAUNCH_CHECK();
     return OSI_OK;
 }
@@ -179,8 +193,34 @@ int osi_stem_dgrad_fgsm(const float* dy, const float* w_krsc3, const float* x_nh
     const int tiles_x = osi_cdiv(W, SG_TW), tiles_y = osi_cdiv(H, SG_TH);
     const size_t grid = (size_t)B * tiles_x * tiles_y;
     OSI_REQUIRE(grid < ((size_t)1 << 31));
-    hipLaunchKernelGGL(k_stem_dgrad<true>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, dy, w_krsc3, x_adv_nhwc4, H, W, Hs, Ws,
-                       tiles_x, tiles_y, (int)dy_bytes, x_nhwc4, eps, lo, hi);
+    hipLaunchKernelGGL(k_stem_dgrad<SG_FGSM>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, dy, w_krsc3, x_adv_nhwc4, H, W, Hs, Ws,
+                       tiles_x, tiles_y, (int)dy_bytes, x_nhwc4, eps, lo, hi, (const float*)nullptr, 0.f);
+    OSI_LAUNCH_CHECK();
+    return OSI_OK;
+}
+
+int osi_stem_dgrad_pgd(const float* dy, const float* w_krsc3, const float* x_cur_nhwc4, const float* x_anchor_nhwc4, float* x_next_nhwc4,
+                       float alpha, float eps, float lo, float hi, int B, int H, int W, osi_stream_t stream) {
+    OSI_REQUIRE(dy && w_krsc3 && x_cur_nhwc4 && x_anchor_nhwc4 && x_next_nhwc4 && B > 0 && H >= 32 && W >= 32);
+    OSI_REQUIRE(((uintptr_t)dy & 15) == 0 && ((uintptr_t)w_krsc3 & 3) == 0);
+    OSI_REQUIRE(((uintptr_t)x_cur_nhwc4 & 15) == 0 && ((uintptr_t)x_anchor_nhwc4 & 15) == 0 && ((uintptr_t)x_next_nhwc4 & 15) == 0);
+    OSI_REQUIRE(eps >= 0.f && lo <= hi);              // (a NaN fails both comparisons; eps = +inf: no projection)
+    OSI_REQUIRE(alpha - alpha == 0.f);                // finite, either sign (negative descends)
+    const int Hs = (H - 1) / 2 + 1, Ws = (W - 1) / 2 + 1;
+    const size_t dy_bytes = (size_t)B * Hs * Ws * 64 * sizeof(float);
+    OSI_REQUIRE(dy_bytes < ((size_t)1 << 31));
+    // the next iterate may overlap neither batch it is made from (the anchor may BE the iterate: step 0 of an attack)
+    const size_t img_bytes = (size_t)B * H * W * 4 * sizeof(float);
+    const uintptr_t xn = (uintptr_t)x_next_nhwc4;
+    for (const float* src : {x_cur_nhwc4, x_anchor_nhwc4}) {
+        const uintptr_t xs = (uintptr_t)src;
+        OSI_REQUIRE(xs + img_bytes <= xn || xn + img_bytes <= xs);
+    }
+    const int tiles_x = osi_cdiv(W, SG_TW), tiles_y = osi_cdiv(H, SG_TH);
+    const size_t grid = (size_t)B * tiles_x * tiles_y;
+    OSI_REQUIRE(grid < ((size_t)1 << 31));
+    hipLaunchKernelGGL(k_stem_dgrad<SG_PGD>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, dy, w_krsc3, x_next_nhwc4, H, W, Hs, Ws,
+                       tiles_x, tiles_y, (int)dy_bytes, x_cur_nhwc4, eps, lo, hi, x_anchor_nhwc4, alpha);
     OSI_LAUNCH_CHECK();
     return OSI_OK;
 }

@@ -79,6 +79,11 @@ class GradSpan(Structure):
     _fields_ = [("begin", ctypes.c_ulonglong), ("numel", ctypes.c_ulonglong)]
 
 
+class Attack(Structure):
+    """osi_attack: one projected attack step (x_anchor = None: around the batch the forward read)"""
+    _fields_ = [("x_next", c_void_p), ("x_anchor", c_void_p), ("alpha", c_float), ("eps", c_float), ("lo", c_float), ("hi", c_float)]
+
+
 OPT_MAX_SEGMENTS, OPT_MAX_GROUPS = 192, 16
 NORM_INF, NORM_L2 = 0, 2
 EVAL_SCORE, EVAL_NORM = 0, 1
@@ -134,6 +139,7 @@ _SIGS = {
     "osi_stem_grad_unpack": (c_int, [P, P, c_int, P]),
     "osi_stem_dgrad": (c_int, [P, P, P, c_int, c_int, c_int, P]),
     "osi_stem_dgrad_fgsm": (c_int, [P, P, P, P, c_float, c_float, c_float, c_int, c_int, c_int, P]),
+    "osi_stem_dgrad_pgd": (c_int, [P, P, P, P, P, c_float, c_float, c_float, c_float, c_int, c_int, c_int, P]),
     "osi_bn_workspace": (c_size_t, [c_int, c_int]),
     "osi_bn_train_stats": (c_int, [P, c_int, c_int, P, P, c_float, c_float, P, P, P, P, P, P, P, c_size_t, P]),
     "osi_bn_eval_coeffs": (c_int, [P, P, P, P, c_float, c_int, P, P, P]),
@@ -220,6 +226,7 @@ _SIGS = {
     "osi_resnet50_backward": (c_int, [c_void_p, P, P, P, P, P, c_int, c_int, P]),
     "osi_resnet50_backward_ex": (c_int, [c_void_p, P, P, P, P, P, P, c_int, c_int, c_int, P]),
     "osi_resnet50_backward_adv": (c_int, [c_void_p, P, P, P, P, P, P, c_float, c_float, c_float, c_int, c_int, P]),
+    "osi_resnet50_backward_attack": (c_int, [c_void_p, P, P, P, P, P, POINTER(Attack), c_int, c_int, c_int, P]),
 }
 
 _lib = None

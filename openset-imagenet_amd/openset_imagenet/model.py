@@ -171,12 +171,16 @@ class ResNet50(nn.Module):
         self._grad_sync = None   # set by dp.DistributedDataParallel
         self._fwd_serial = 0     # number of forward passes run; a backward must belong to the latest one
         self._grads_fresh = False  # a backward has filled the gradient arena since the last optimizer.zero_grad()
-        self._bw_request = None    # next_backward(): (epsilon or None, lo, hi, accumulate) for the one backward that follows
+        self._bw_request = None    # next_backward(): (epsilon or None, lo, hi, accumulate, alpha or None, anchor, input_only) for the one
+                                   # backward that follows; alpha is None for an FGSM request
         self._adv_valid = False    # the latest backward wrote adversarial_batch()
-        self._adv = {}             # (B, H, W) -> the model-owned NHWC4 buffer the FGSM epilogue writes
+        self._adv = {}             # (B, H, W) -> the model-owned PAIR of NHWC4 buffers the attack epilogues write: a backward writes the
+                                   # one its forward did not read, so an attack can feed adversarial_batch() back without a copy
+        self._adv_idx = {}         # (B, H, W) -> which of the pair was written last
         self._flat_grads2 = None   # second gradient arena of an accumulating backward
         self._bn_frozen = False    # freeze_bn(): BatchNorm on the running statistics (read-only) while the model is differentiated
         self._eval_plain = False   # the latest forward was an eval-mode inference forward run with grad enabled (no graph)
+        self._fwd_input_only = False   # the latest forward ran under a pending next_backward(input_only=True)
         self._fwd_prefix = 0       # units the differentiable forward being set up runs in the inference forms (forward())
         self.reset_parameters()
 
@@ -240,7 +244,7 @@ class ResNet50(nn.Module):
                 src = getattr(self, arena)
                 node._buffers[bname] = src[off] if arena == "_nbt" else src[off:off + c]
         self._ws = None
-        self._adv, self._flat_grads2 = {}, None
+        self._adv, self._adv_idx, self._flat_grads2 = {}, {}, None
         return self
 
     # ---- arena access for the optimizer / DP layers -------------------------------------------------------
@@ -355,37 +359,68 @@ class ResNet50(nn.Module):
         """True after freeze_bn() (read-only; eval mode differentiates on the running statistics without it)."""
         return self._bn_frozen
 
-    def next_backward(self, fgsm=None, lo=0.0, hi=1.0, accumulate=False):
+    def next_backward(self, fgsm=None, lo=0.0, hi=1.0, accumulate=False, *, pgd=None, input_only=False):
         """Request for the ONE backward that follows (whatever route it takes: a fused loss's plain backward(), autograd):
           fgsm = epsilon   its last stage also writes the adversarial batch clamp(x + epsilon * sign(dJ/dx), lo, hi) from the input the
                            forward read (NCHW, NHWC4 or uint8-staged alike) into a model-owned NHWC4 buffer: adversarial_batch();
                            dJ/dimage itself is never written (osi_resnet50_backward_adv);
+          pgd = (alpha, epsilon, anchor)   one step of a projected attack instead (osi_resnet50_backward_attack): the input the forward
+                           read is the iterate x, adversarial_batch() receives
+                           clamp(min(max(x + alpha * sign(dJ/dx), a - epsilon), a + epsilon), lo, hi) with a = `anchor`, the clean batch
+                           as NHWC4 fp32 [B, H, W, 4] of the forward's geometry on the model's device (adversary.as_nhwc4), or None: the
+                           forward's own input (step 0). alpha is finite (negative descends), epsilon >= 0 (inf: no projection).
+                           Mutually exclusive with fgsm;
+          input_only       (with fgsm or pgd, not with accumulate) the backward computes NO parameter gradient: the gradient arena,
+                           every p.grad and the optimizers' "fresh gradients" mark stay as they are, nothing runs on the weight-gradient
+                           side stream, and under data parallel no bucket is handed to the gradient sync and no collective runs. The
+                           inner steps of a multi-step attack and attacks inside validate(). This request has to PRECEDE its forward in
+                           every mode: a backward that finds the request but whose forward ran without it raises RuntimeError;
           accumulate       its parameter gradients go into a second arena that is then added into the first (osi_grad_accumulate), so
                            p.grad holds the sum of this backward and the one before it, as autograd's accumulation would leave it.
+        The adversarial buffer is a pair per geometry: a backward writes the one its forward did not read, adversarial_batch() is the
+        one written last, so feeding adversarial_batch() back k times needs no copy (the batch of two steps ago is overwritten).
         In eval mode (without freeze_bn()) the request has to PRECEDE the forward: it is what makes that forward differentiable (a plain
         eval-mode forward builds no graph). A request that arrives after such a forward raises; run plain eval-mode forwards under
         torch.no_grad(), as validate() does, when requests for later forwards follow them."""
+        if fgsm is not None and pgd is not None:
+            raise ValueError("next_backward: fgsm and pgd are mutually exclusive")
+        alpha = anchor = None
+        if pgd is not None:
+            alpha, fgsm, anchor = pgd
+            alpha = float(alpha)
+            if not math.isfinite(alpha):
+                raise ValueError("next_backward: pgd alpha must be finite")
+            if anchor is not None:
+                if not isinstance(anchor, torch.Tensor) or not self._is_nhwc4(anchor) or anchor.device != self._flat_params.device:
+                    raise ValueError("next_backward: the pgd anchor must be None or an NHWC4 fp32 batch [B, H, W, 4] on the model's device "
+                                     "(adversary.as_nhwc4)")
+                anchor = anchor.detach().contiguous()
+        if input_only:
+            if fgsm is None or accumulate:
+                raise ValueError("next_backward(input_only=True) goes with fgsm or pgd and not with accumulate: an input-only backward "
+                                 "produces the adversarial batch and nothing else")
         if fgsm is not None and self._prefix_fwd and getattr(self, "_last", None) is not None and self._last[0].owes_backward:
             raise RuntimeError("next_backward(fgsm=...): the latest forward ran the prefix frozen by freeze_below() in the inference form, which "
                                "keeps nothing to differentiate; call next_backward(fgsm=...) BEFORE the forward it belongs to")
-        if (fgsm is not None or accumulate) and self._eval_plain and not self.training and not self._bn_frozen:
+        if (fgsm is not None or accumulate) and not input_only and self._eval_plain and not self.training and not self._bn_frozen:
             raise RuntimeError("next_backward(): the latest forward was an eval-mode inference forward, which keeps nothing to differentiate; "
                                "in eval mode call next_backward(...) BEFORE the forward it belongs to (or freeze_bn() / requires_grad_ on "
                                "the image), and run plain eval-mode forwards under torch.no_grad()")
         if fgsm is not None and not float(fgsm) >= 0.0:
-            raise ValueError("next_backward: fgsm (epsilon) must be >= 0")
+            raise ValueError("next_backward: epsilon must be >= 0")
         if not float(lo) <= float(hi):
             raise ValueError("next_backward: lo <= hi")
-        self._bw_request = (None if fgsm is None else float(fgsm), float(lo), float(hi), bool(accumulate))
+        self._bw_request = (None if fgsm is None else float(fgsm), float(lo), float(hi), bool(accumulate), alpha, anchor, bool(input_only))
 
     def adversarial_batch(self):
-        """The NHWC4 batch [B, H, W, 4] written by the latest backward that ran under next_backward(fgsm=...). Model-owned and
-        overwritten by the next such backward of the same geometry; feed it to the model as it is."""
+        """The NHWC4 batch [B, H, W, 4] written by the latest backward that ran under next_backward(fgsm=... / pgd=...). Model-owned:
+        one of a pair per geometry, overwritten by the second such backward after this one; feed it to the model as it is."""
         last = getattr(self, "_last", None)
-        x_adv = self._adv.get(net_shape(self, last[0])) if last is not None else None
-        if x_adv is None or not self._adv_valid:
-            raise RuntimeError("adversarial_batch(): the latest backward did not run under next_backward(fgsm=...)")
-        return x_adv
+        shape = net_shape(self, last[0]) if last is not None else None
+        pair = self._adv.get(shape)
+        if pair is None or not self._adv_valid:
+            raise RuntimeError("adversarial_batch(): the latest backward did not run under next_backward(fgsm=... / pgd=...)")
+        return pair[self._adv_idx[shape]]
 
     def mark_gradients_ready(self):
         """Tell the fused optimizers that the gradient arena was filled by hand (tests, custom loops) rather than by backward()."""
@@ -438,6 +473,7 @@ class ResNet50(nn.Module):
             logits, features = N.ops().resnet50_forward(net.h.value, self._flat_params, self._flat_buffers, self._nbt, image, flip,
                                                         self._ws, self._F, self._O, bool(self.training and not self._bn_frozen))
         self._eval_plain = not frozen and not self.training and torch.is_grad_enabled()
+        self._fwd_input_only = bool(want_grad) and self._bw_request is not None and self._bw_request[6]
         # (any forward replaces the executor's backward state; only a differentiable one leaves a backward owed)
         net.owes_backward = bool(want_grad)
         self._prefix_fwd = bool(want_grad) and self._fwd_prefix > 0
@@ -448,7 +484,7 @@ class ResNet50(nn.Module):
     def _run_backward(self, dlogits, dfeatures, want_image=False, param_grads=True):
         """Backward of the latest forward. want_image: also return dJ/dimage (NCHW fp32, the forward's batch geometry);
         param_grads = False: input-only backward (no parameter gradient is computed, the gradient arena is not touched)."""
-        net, _ = self._last
+        net, fwd_image = self._last
         B, H, W = net_shape(self, net)
         if dlogits is None:
             dlogits = torch.zeros(B, self._O, device=self._flat_params.device)
@@ -457,9 +493,17 @@ class ResNet50(nn.Module):
         dimage = torch.empty(B, 3, H, W, device=self._flat_params.device) if want_image else None
         sync = self._grad_sync
         request, self._bw_request = self._bw_request, None
-        eps, clamp_lo, clamp_hi, accumulate = request if request is not None else (None, 0.0, 1.0, False)
+        eps, clamp_lo, clamp_hi, accumulate, alpha, anchor, input_only = request if request is not None else (None, 0.0, 1.0, False, None, None, False)
         self._adv_valid = False
-        if (eps is not None or accumulate) and not param_grads:
+        if input_only:    # the request decides: no parameter gradient, whatever the graph says about the parameters
+            if not self._fwd_input_only:
+                raise RuntimeError("next_backward(input_only=True) has to PRECEDE the forward it belongs to: the latest forward was set "
+                                   "up for a backward with parameter gradients")
+            if want_image:
+                raise ValueError("next_backward(input_only=True) builds the adversarial batch inside the backward: the image batch must "
+                                 "not require grad as well (dJ/dimage is not written on that path)")
+            param_grads = False
+        if (eps is not None or accumulate) and not param_grads and not input_only:
             raise RuntimeError("next_backward(): the requested backward computes parameter gradients, but every parameter is frozen")
         if eps is not None and want_image:
             raise ValueError("next_backward(fgsm=...) builds the adversarial batch inside the backward: the image batch must not require "
@@ -470,11 +514,20 @@ class ResNet50(nn.Module):
         if accumulate and (self._flat_grads2 is None or self._flat_grads2.device != dev):
             self._flat_grads2 = torch.zeros_like(self._flat_grads)   # zeros: the alignment gaps between tensors are never written
         if eps is not None:
-            x_adv = self._adv.get((B, H, W))
-            if x_adv is None or x_adv.device != dev:
-                x_adv = self._adv[(B, H, W)] = torch.empty(B, H, W, 4, device=dev)
-            adv = N.ops().resnet50_backward_adv
-            bwd = lambda *a: adv(*a[:6], x_adv, eps, clamp_lo, clamp_hi, *a[6:])
+            pair = self._adv.get((B, H, W))
+            if pair is None or pair[0].device != dev:
+                pair = self._adv[(B, H, W)] = (torch.empty(B, H, W, 4, device=dev), torch.empty(B, H, W, 4, device=dev))
+            # the buffer the forward did not read (a forward on anything else: the first)
+            out = 1 if fwd_image is not None and fwd_image.data_ptr() == pair[0].data_ptr() else 0
+            x_adv = pair[out]
+            assert fwd_image is None or fwd_image.data_ptr() != x_adv.data_ptr(), "the attack epilogue would overwrite its forward's input"
+            if alpha is None and not input_only:
+                adv = N.ops().resnet50_backward_adv
+                bwd = lambda *a: adv(*a[:6], x_adv, eps, clamp_lo, clamp_hi, *a[6:])
+            else:         # ABI 19: the projected step and / or the input-only form (an FGSM step is alpha = epsilon around the iterate)
+                attack = N.ops().resnet50_backward_attack
+                step = eps if alpha is None else alpha
+                bwd = lambda *a: attack(*a[:6], x_adv, anchor, step, eps, clamp_lo, clamp_hi, bool(param_grads), *a[6:])
         elif dimage is None and param_grads:
             bwd = N.ops().resnet50_backward
         else:             # ABI 8: dJ/dimage written by the last stage, and/or no parameter gradient
@@ -483,7 +536,8 @@ class ResNet50(nn.Module):
         grads = self._flat_grads if param_grads else self._flat_grads[:0]
         if accumulate:    # into the second arena (under data parallel its buckets are averaged on their own), added into the first below
             grads = self._flat_grads2
-        if sync is None:  # single GPU: all stages in one call (one side-stream join at the end)
+        if sync is None or input_only:  # single GPU: all stages in one call (one side-stream join at the end); an input-only attack step
+                                        # under data parallel as well: there is no gradient to average, the sync never hears of it
             bwd(net.h.value, self._flat_params, grads, self._ws, dlogits, dfeatures, 0, self._n_stages)
         else:             # data parallel: stage by stage, each finished slice of the gradient arena goes to the all-reduce
             if not net.staged:   # staged calls no longer join the weight-gradient side stream into the compute stream (only the last does)
@@ -502,6 +556,8 @@ class ResNet50(nn.Module):
         if accumulate:
             N.ops().grad_accumulate(self._flat_grads, grads)
         self._adv_valid = eps is not None
+        if eps is not None:
+            self._adv_idx[(B, H, W)] = out
         if param_grads:
             self._grads_fresh = True
             self.bind_gradients()
@@ -518,7 +574,8 @@ class ResNet50(nn.Module):
         With grad enabled: in training mode the forward is differentiable on batch statistics (which it updates) — unless freeze_bn()
         is on: then, and in eval mode whenever something asks for a gradient (freeze_bn(), an image that requires grad, a pending
         next_backward(...) request), it is differentiable on the running statistics, which it leaves untouched (the frozen route).
-        Every other eval-mode forward is the inference forward without a graph."""
+        Every other eval-mode forward is the inference forward without a graph. Under a pending next_backward(input_only=True) the graph
+        exists for the attack alone: its backward computes no parameter gradient, whatever the parameters' requires_grad flags say."""
         self._check_image(image)
         frozen = self._bn_frozen or not self.training
         differentiable = self.training or self._bn_frozen or image.requires_grad or self._bw_request is not None
@@ -541,9 +598,11 @@ class ResNet50(nn.Module):
                     # frozen route: the full frozen topology, the backward runs to full depth (frozen units get no weight gradient)
                 else:
                     self._fwd_prefix = self._cut
-            if param_grad or image_grad:
-                # no parameter requires grad: a detached anchor, so the backward runs input-only
-                anchor = self._anchor if param_grad else self._anchor.detach()
+            input_only = self._bw_request is not None and self._bw_request[6]
+            if param_grad or image_grad or input_only:
+                # no parameter requires grad: a detached anchor, so the backward runs input-only. A pending input-only attack request
+                # needs a graph even then (the anchor is a stand-in leaf: no parameter is part of the graph either way)
+                anchor = self._anchor if (param_grad or input_only) else self._anchor.detach()
                 return _BackboneFn.apply(image, anchor, self, flip, frozen)
         return self._run_forward(image, False, flip)
 

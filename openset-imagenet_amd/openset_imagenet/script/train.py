@@ -25,8 +25,9 @@ def get_args(command_line_options=None):
     p.add_argument("--gpu", "-g", type=int, nargs="?", default=None, const=0, help="GPU index (bare -g = 0)")
     p.add_argument("--nice", type=int, default=20, help="Select Priority Level")
     p.add_argument("--synthetic", type=int, default=0, help="train on this many synthetic samples instead of the protocol CSV files")
-    p.add_argument("--adversary", choices=("no_adv", "fgsm", "gaussian", "uniform"), default=None,
-                   help="adversarial negatives per step (overrides adv.who of the configuration; strength from its adv block)")
+    p.add_argument("--adversary", choices=("no_adv", "fgsm", "pgd", "gaussian", "uniform"), default=None,
+                   help="adversarial negatives per step (overrides adv.who of the configuration; strength from its adv block; pgd needs "
+                        "adv.steps there: the number of steps has no default)")
     args = p.parse_args(command_line_options)
     os.nice(args.nice)
     return args

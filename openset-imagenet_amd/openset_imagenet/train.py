@@ -159,9 +159,12 @@ def step_options(cfg):
 def train(model, data_loader, optimizer, loss_fn, trackers, cfg, epsilon=None):
     """One epoch of training (reference train.py:104-139).
 
-    With `cfg.adv.who` in {fgsm, gaussian, uniform} (new; absent block or `no_adv`: the loop below is the reference's) every step
+    With `cfg.adv.who` in {fgsm, pgd, gaussian, uniform} (new; absent block or `no_adv`: the loop below is the reference's) every step
     trains on the batch AND on negatives generated from it (adversary.py): clean forward / loss j / backward, negatives, second
     training-mode forward / loss j_adv on the negative label / backward adding to the clean gradients, one optimizer.step().
+    who = pgd (keys adv.steps, integer >= 1, and adv.alpha, default epsilon / steps * 1.25): step 1 of the attack rides on the clean
+    backward as FGSM does, steps 2..K are input-only passes on the running statistics (adversary.pgd_attack's), so the statistics are
+    still updated exactly twice per step; steps: 1 with alpha: epsilon is who = fgsm, bit for bit.
     `epsilon` overrides cfg.adv.epsilon (worker() passes the scheduled value); trackers["j_adv"] receives j_adv like trackers["j"].
 
     Optional keys under `opt:` (new; all absent: the loop is the one above, with its tracker set):
@@ -300,6 +303,13 @@ def validate(model, data_loader, loss_fn, n_classes, trackers, cfg, shard=None):
     """Validation loop with the reference's contract (train.py:142-196): eval-mode forward under no_grad, loss per batch into
     trackers["j"], known / negative confidences into trackers["conf_kn"] / ["conf_unk"].
 
+    Optional block `adv.validate: {who: fgsm | pgd, epsilon, alpha, steps, random_start}` (new; absent: the loop is the one above, with
+    its calls, launches and tracker set): after its clean scoring every batch is attacked — adversary.pgd_attack ascending `loss_fn` on
+    the batch's own labels, input-only steps on the running statistics, fgsm = one step of alpha = epsilon — and the adversarial batch
+    is scored by the same inference forward, loss and confidence kernel into trackers["j_adv"], ["conf_kn_adv"], ["conf_unk_adv"]
+    (created on demand). The adversarial values travel in the same per-batch records and the same single synchronisation at the end.
+    Under the softmax loss negatives (label -1) have no loss term and come back unperturbed.
+
     The reference fills an [N_val, C] softmax matrix on the device and reduces it with metrics.confidence() in Python loops
     (`sum(known)`, metrics.py:27-28). Here softmax + confidence are one kernel per batch that leaves the batch's four sums in a
     double[4] on the device; nothing is synchronised until the end of the loop, where the per-batch values are folded on the host in
@@ -308,10 +318,14 @@ def validate(model, data_loader, loss_fn, n_classes, trackers, cfg, shard=None):
     `shard = (rank, world)` or `(rank, world, process_group)` (new — a departure from the reference's "Validate only on first
     process", train.py:248, which leaves world - 1 GPUs idle for a quarter of every epoch's samples, protocol.py:245-250): the loader
     yields only the batches rank, rank + world, ... of the unsharded, unshuffled batch sequence (ShardedEvalBatches); rank 0's BatchNorm
-    buffers are broadcast first, every rank evaluates its batches, the per-batch (index, loss, count, confidence sums) records are
+    buffers are broadcast first, every rank evaluates its batches, the per-batch (index, count, [(loss, confidence sums)]) records are
     all-gathered and EVERY rank replays them in batch order. The trackers are then bit-identical on all ranks to what a single
     process computes on the whole loader: whole batches, the same kernels, the same order of additions. A rank that fails reports
     its error through the same collective, so that no rank is left waiting: every rank raises."""
+    attack = _adversary.validation_attack(cfg)
+    if attack is not None:
+        for name in ("j_adv", "conf_kn_adv", "conf_unk_adv"):
+            trackers.setdefault(name, _losses.AverageMeter())
     for metric in trackers.values():
         metric.reset()
     if cfg.loss.type == "garbage":
@@ -326,6 +340,18 @@ def validate(model, data_loader, loss_fn, n_classes, trackers, cfg, shard=None):
     model.eval()
     losses, counts, rows, chunks, records = [], [], [], [], []
     error = None
+    suffixes = ("",) if attack is None else ("", "_adv")   # scorings per batch, in order: the clean one, then the adversarial one
+    loss3 = (lambda lg, ft, y: loss_fn(lg, y, ft)) if wants_features else (lambda lg, ft, y: loss_fn(lg, y))
+
+    def score(logits, features, labels):
+        """loss and confidence sums of one scored batch, left on the device"""
+        losses.append(loss3(logits, features, labels))
+        if len(rows) % 256 == 0:
+            chunks.append(torch.zeros(256, 4, dtype=torch.float64, device=logits.device))
+        row = chunks[-1][len(rows) % 256]
+        _confidence_partial(logits, labels, min_unk_score, unknown_class, last_valid, row)
+        rows.append(row)
+
     try:
         if world > 1:
             _broadcast_buffers(model, group)
@@ -334,17 +360,17 @@ def validate(model, data_loader, loss_fn, n_classes, trackers, cfg, shard=None):
             for batch in data_loader:
                 images, labels = device_batch(batch)
                 logits, features = model(images)
-                j = loss_fn(logits, labels, features) if wants_features else loss_fn(logits, labels)
-                losses.append(j)
+                score(logits, features, labels)
                 counts.append(labels.shape[0])
-                if len(rows) % 256 == 0:
-                    chunks.append(torch.zeros(256, 4, dtype=torch.float64, device=logits.device))
-                row = chunks[-1][len(rows) % 256]
-                _confidence_partial(logits, labels, min_unk_score, unknown_class, last_valid, row)
-                rows.append(row)
+                if attack is not None:     # (enables grad for its own steps; the scoring forward below is the inference forward again)
+                    logits, features = model(attack(model, images, labels, loss3))
+                    score(logits, features, labels)
         if losses:                         # the one synchronisation of the loop (an asynchronous device error surfaces here: still inside the try)
             conf = torch.cat(chunks)[:len(rows)].cpu().tolist()
-            records = [(rank + k * world, v, n, c) for k, (v, n, c) in enumerate(zip(torch.stack(losses).cpu().tolist(), counts, conf))]
+            values = torch.stack(losses).cpu().tolist()
+            # (index, count, [(loss, confidence sums) per scoring]) per batch
+            scored, m = list(zip(values, conf)), len(suffixes)
+            records = [(rank + k * world, n, scored[m * k:m * (k + 1)]) for k, n in enumerate(counts)]
     except Exception as e:                 # under data parallel the other ranks wait in the gather below: tell them there
         if world == 1:
             raise
@@ -364,16 +390,18 @@ def validate(model, data_loader, loss_fn, n_classes, trackers, cfg, shard=None):
                                "whole batches (ShardedEvalBatches(rank, world))")
     if not records:
         return
-    acc = [0.0, 0.0, 0.0, 0.0]
-    for _, value, n, c in records:         # batch order: AverageMeter sees the reference's update sequence, the sums its additions
-        trackers["j"].update(value, n)
-        for i in range(4):
-            acc[i] += c[i]
-    kn_sum, kn_count, neg_sum, neg_count = acc
-    if kn_count:
-        trackers["conf_kn"].update(kn_sum / kn_count, int(kn_count))
-    if neg_count:
-        trackers["conf_unk"].update(neg_sum / neg_count, int(neg_count))
+    for which, suffix in enumerate(suffixes):   # batch order: AverageMeter sees the reference's update sequence, the sums its additions
+        acc = [0.0, 0.0, 0.0, 0.0]
+        for _, n, scorings in records:
+            value, c = scorings[which]
+            trackers["j" + suffix].update(value, n)
+            for i in range(4):
+                acc[i] += c[i]
+        kn_sum, kn_count, neg_sum, neg_count = acc
+        if kn_count:
+            trackers["conf_kn" + suffix].update(kn_sum / kn_count, int(kn_count))
+        if neg_count:
+            trackers["conf_unk" + suffix].update(neg_sum / neg_count, int(neg_count))
 
 
 def get_arrays(model, loader):
@@ -579,7 +607,7 @@ def _worker_body(cfg, log, out_dir, rank, world, distributed):
     if adv_on:
         _adversary.Plan(cfg)
         t_metrics["j_adv"] = _losses.AverageMeter()
-        if _adversary.who_of(cfg) != "fgsm" and getattr(cfg.adv, "generator", None) is None:   # the noise stream: seeded per rank
+        if _adversary.who_of(cfg) not in ("fgsm", "pgd") and getattr(cfg.adv, "generator", None) is None:   # the noise stream: seeded per rank
             cfg.adv.generator = torch.Generator(device=tools.get_device()).manual_seed(cfg.seed + rank)
     v_metrics = {"j": _losses.AverageMeter(), "conf_kn": _losses.AverageMeter(), "conf_unk": _losses.AverageMeter()}
     _last_worker_state.update(v_metrics=v_metrics, val_loader=val_loader, loss_fn=loss_fn, n_classes=n_classes)
