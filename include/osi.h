@@ -41,7 +41,7 @@ extern "C" {
 
 typedef void* osi_stream_t; /* hipStream_t */
 
-int osi_abi_version(void);            /* bumped on any signature change; 19 = projected attack steps (osi_stem_dgrad_pgd, osi_resnet50_backward_attack); 18 = evaluation histograms (osi_eval_values_*, osi_hist_*); 17 = gradient-norm clipping (osi_grad_clip_scale, osi_*_step_groups_dev); 16 = the ROC-AUC entry points (osi_auc_*) */
+int osi_abi_version(void);            /* bumped on any signature change; 20 = weight averaging (osi_average_update) and the executor's BatchNorm momentum (osi_resnet50_set_bn_momentum / _get_bn_momentum); 19 =projected attack steps (osi_stem_dgrad_pgd, osi_resnet50_backward_attack); 18 = evaluation histograms (osi_eval_values_*, osi_hist_*); 17 = gradient-norm clipping (osi_grad_clip_scale, osi_*_step_groups_dev); 16 = the ROC-AUC entry points (osi_auc_*) */
 const char* osi_build_arch(void);     /* "gfx950" */
 const char* osi_strerror(int code);
 /* Process-wide development knobs (A/B measurements; every default is the measured optimum). Launch functions only READ them and never
@@ -585,6 +585,25 @@ int osi_scale_f32(float* p, size_t n, float s, osi_stream_t stream);
  * one training step. 16-byte aligned, distinct pointers, n % 4 == 0 (OSI_ERR_ARG otherwise). */
 int osi_grad_accumulate(float* dst, const float* src, size_t n, osi_stream_t stream);
 int osi_i64_add(long long* p, int n, long long inc, osi_stream_t stream);
+/* ABI 20. Weight averaging (EMA / SWA, openset_imagenet/averaging.py): avg = lerp(avg, cur, weight) over up to OSI_AVG_MAX_SPANS pairs
+ * of arenas in ONE launch, with the roundings of torch.lerp on fp32: d = cur - avg (one rounding), then avg = fma(weight, d, avg) for
+ * weight < 0.5 and avg = fma(weight - 1, d, cur) otherwise (weight - 1 rounded once to fp32); the fma is explicit, so no contraction
+ * setting changes the bits. weight = 1 reproduces cur exactly whenever d is finite (the difference does not overflow), weight = 0
+ * leaves finite values unchanged, and NaN / Inf come out where torch.lerp puts them.
+ * A span is n floats of `avg` (read and written) and of `cur` (only read); nothing outside [avg, avg + n) is written. spans is a HOST
+ * table, read during the call (it travels in the kernel arguments) and not needed afterwards. The spans are cut into tiles of 1024
+ * floats (one 16-byte unit per lane of a 256-thread workgroup) that at most 2048 workgroups walk in a grid stride, whichever span a
+ * tile lies in. 16-byte loads and stores, no atomics, nothing allocated, nothing synchronised (graph-capturable).
+ * OSI_ERR_ARG before any launch on: a NULL table or n_spans outside 1..OSI_AVG_MAX_SPANS; a NULL or not 16-byte aligned avg or cur;
+ * n == 0, n % 4 != 0 or n/4 > 2^32 - 512; weight NaN or outside [0, 1]; an avg range that overlaps any cur range (its own included)
+ * or another avg range. */
+#define OSI_AVG_MAX_SPANS 4
+typedef struct {
+    float* avg;
+    const float* cur;
+    size_t n; /* floats; n % 4 == 0, both pointers 16-byte aligned */
+} osi_avg_span;
+int osi_average_update(const osi_avg_span* spans, int n_spans, float weight, osi_stream_t stream);
 
 /* ---- whole-network executor: ResNet50.forward (model.py:28-39) and its autograd backward (train.py:138) ---------------
  * One call enqueues the full forward (or a range of backward stages) on `stream`. The caller owns three flat arenas whose
@@ -718,6 +737,15 @@ int osi_resnet50_tensor_unit(osi_resnet50_t net, int i);
 int osi_resnet50_bn_unit(osi_resnet50_t net, int j);
 int osi_resnet50_set_trainable(osi_resnet50_t net, unsigned unit_mask, int eval_prefix_units);
 int osi_resnet50_get_trainable(osi_resnet50_t net, unsigned* unit_mask, int* eval_prefix_units);
+
+/* ABI 20. The running-statistics update factor of the executor: running = (1 - momentum) * running + momentum * batch for every
+ * BatchNorm a training-mode forward finalises (all of them go through osi_bn_finalize_stats, the stem's included). Default 0.1f: the
+ * launches and bits of every earlier ABI. The value takes effect at the next osi_resnet50_forward(training = 1); inference and frozen
+ * forwards never read it, and no kernel's arithmetic changes. momentum = 1 leaves exactly the batch statistics in the buffers
+ * ((1 - 1) * running is an exact zero for a finite running value); 1 / k before batch k = 1, 2, ... from reset buffers is the
+ * cumulative average of torch's BatchNorm with momentum = None (update_bn). OSI_ERR_ARG: NaN, momentum <= 0 or > 1, a NULL pointer. */
+int osi_resnet50_set_bn_momentum(osi_resnet50_t net, float momentum);
+int osi_resnet50_get_bn_momentum(osi_resnet50_t net, float* momentum);
 
 /* Per-executor switches: "overlap" (default 1: weight gradients on a low-priority side stream, overlapped with dgrad / BatchNorm
  * backward and joined back into `stream` at the end of every backward call unless "stage_join" = 0; 0 serialises everything on the

@@ -4,7 +4,8 @@
 //   Adam: m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
 //   SGD : buf = g (first step) | mu*buf + g ; p -= lr*buf
 // Also: arena utilities used by the loop (zero fill, int64 counter bump for num_batches_tracked, scale for DP averaging, and the
-// sum of two gradient arenas: the clean and the adversarial backward of one step, openset_imagenet/adversary.py).
+// sum of two gradient arenas: the clean and the adversarial backward of one step, openset_imagenet/adversary.py), and the averaged
+// copy of the weights (EMA / SWA, openset_imagenet/averaging.py): avg = lerp(avg, cur, weight) over several arenas in one launch.
 #include "osi_common.h"
 
 #include <cmath>
@@ -212,6 +213,41 @@ __global__ __launch_bounds__(256) void k_accumulate(f32x4* __restrict__ dst, con
 __global__ void k_i64_add(long long* p, int n, long long inc) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] += inc;
+}
+
+// ---- weight averaging (osi_average_update): avg = lerp(avg, cur, weight) over up to OSI_AVG_MAX_SPANS arena pairs, one launch ------
+// The spans are cut into tiles of AVG_TILE floats (one 16-byte unit per lane); tile_end[s] = tiles of spans 0..s, so a workgroup's
+// virtual tile index names a span and a tile in it (a uniform search over at most four bounds), and at most AVG_MAX_GRID workgroups
+// walk the tiles in a grid stride. The table arrives by value in the kernel arguments.
+constexpr uint32_t AVG_TILE = 1024;       // floats per workgroup tile = 256 lanes x one f32x4
+constexpr uint32_t AVG_MAX_GRID = 2048;   // grid cap, as the other arena kernels
+struct AvgTable {
+    f32x4* avg[OSI_AVG_MAX_SPANS];
+    const f32x4* cur[OSI_AVG_MAX_SPANS];
+    uint32_t n4[OSI_AVG_MAX_SPANS];
+    uint32_t tile_end[OSI_AVG_MAX_SPANS];  // <= 4 * 2^24 tiles
+    int n;
+};
+
+// torch.lerp on fp32: d = cur - avg; weight < 0.5 (LOW): fma(w, d, avg) with w = weight; else fma(w, d, cur) with w = weight - 1
+template <bool LOW>
+__global__ __launch_bounds__(256) void k_average(AvgTable tab, float w) {
+    const uint32_t tiles = tab.tile_end[tab.n - 1];
+    const f32x4 w4 = splat4(w);
+    for (uint32_t v = blockIdx.x; v < tiles; v += gridDim.x) {
+        int s = 0;
+        uint32_t first = 0;
+#pragma unroll
+        for (int k = 0; k < OSI_AVG_MAX_SPANS - 1; ++k)
+            if (k + 1 < tab.n && v >= tab.tile_end[k]) { s = k + 1; first = tab.tile_end[k]; }
+        const uint32_t i = (v - first) * 256 + threadIdx.x;    // < n4 + 256 <= 2^32 - 256: cannot wrap
+        if (i < tab.n4[s]) {
+            f32x4* __restrict__ pa = tab.avg[s];
+            const f32x4 a = pa[i], c = tab.cur[s][i];
+            const f32x4 d = c - a;
+            pa[i] = fma4(w4, d, LOW ? a : c);
+        }
+    }
 }
 
 static int sgrid(size_t n4) {
@@ -529,6 +565,36 @@ int osi_grad_accumulate(float* dst, const float* src, size_t n, osi_stream_t str
     OSI_REQUIRE(dst && src && dst != src && n > 0 && n % 4 == 0);
     OSI_REQUIRE(((uintptr_t)dst & 15) == 0 && ((uintptr_t)src & 15) == 0);
     hipLaunchKernelGGL(k_accumulate, dim3(sgrid(n / 4)), dim3(256), 0, (hipStream_t)stream, (f32x4*)dst, (const f32x4*)src, n / 4);
+    OSI_LAUNCH_CHECK();
+    return OSI_OK;
+}
+int osi_average_update(const osi_avg_span* spans, int n_spans, float weight, osi_stream_t stream) {
+    OSI_REQUIRE(spans && n_spans >= 1 && n_spans <= OSI_AVG_MAX_SPANS);
+    OSI_REQUIRE(weight >= 0.0f && weight <= 1.0f);                   // a NaN fails both comparisons
+    AvgTable tab;
+    memset(&tab, 0, sizeof tab);
+    uint32_t tiles = 0;
+    for (int i = 0; i < n_spans; ++i) {
+        const osi_avg_span& s = spans[i];
+        OSI_REQUIRE(s.avg && s.cur && ((uintptr_t)s.avg & 15) == 0 && ((uintptr_t)s.cur & 15) == 0);
+        OSI_REQUIRE(norm_arena_ok(s.n));                             // n > 0, n % 4 == 0, n/4 <= 2^32 - 512
+        const uintptr_t a0 = (uintptr_t)s.avg, a1 = a0 + s.n * sizeof(float);
+        for (int j = 0; j < n_spans; ++j) {                          // an avg range meets no cur range and no other avg range
+            const uintptr_t c0 = (uintptr_t)spans[j].cur, c1 = c0 + spans[j].n * sizeof(float);
+            OSI_REQUIRE(a1 <= c0 || c1 <= a0);
+            const uintptr_t b0 = (uintptr_t)spans[j].avg, b1 = b0 + spans[j].n * sizeof(float);
+            OSI_REQUIRE(j == i || a1 <= b0 || b1 <= a0);
+        }
+        tab.avg[i] = (f32x4*)s.avg; tab.cur[i] = (const f32x4*)s.cur; tab.n4[i] = (uint32_t)(s.n / 4);
+        tiles += (uint32_t)((s.n + AVG_TILE - 1) / AVG_TILE);
+        tab.tile_end[i] = tiles;
+    }
+    tab.n = n_spans;
+    const uint32_t grid = tiles < AVG_MAX_GRID ? tiles : AVG_MAX_GRID;
+    if (weight < 0.5f)
+        hipLaunchKernelGGL(k_average<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, tab, weight);
+    else
+        hipLaunchKernelGGL(k_average<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, tab, weight - 1.0f);
     OSI_LAUNCH_CHECK();
     return OSI_OK;
 }

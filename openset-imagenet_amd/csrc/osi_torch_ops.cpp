@@ -11,6 +11,7 @@
 //   torch.ops.osi.loss_fwd_bwd        losses.py:16-29, train.py:343-347 (the three losses + objectosphere term, value and gradient)
 //   torch.ops.osi.adam_step / sgd_step    train.py:139, 356-359; adam_step_groups / sgd_step_groups: the same with parameter groups;
 //                                         grad_clip_scale + *_step_groups_dev: gradient-norm clipping, the scalar left on the device
+//   torch.ops.osi.average_update      EMA / SWA of the arenas in one launch (averaging.py); resnet50_set_bn_momentum: update_bn's 1 / k
 //   torch.ops.osi.stage_canvas        train.py:259-263 after decode + resize (crop, flip, ToTensor, NHWC4)
 //   torch.ops.osi.softmax / confidence_accumulate    train.py:177, metrics.py:8-42
 //
@@ -252,6 +253,27 @@ void grad_accumulate(Tensor dst, const Tensor& src) {
     ok(osi_grad_accumulate(dst.data_ptr<float>(), src.data_ptr<float>(), (size_t)dst.numel(), stream_of(dst)), "osi_grad_accumulate");
 }
 
+// ABI 20: avg[i] = lerp(avg[i], cur[i], weight) over 1 .. OSI_AVG_MAX_SPANS pairs of contiguous fp32 tensors in ONE launch (EMA / SWA of
+// the parameter and buffer arenas, openset_imagenet/averaging.py); overlaps and the weight are validated by the C ABI
+void average_update(at::TensorList avg, at::TensorList cur, double weight) {
+    TORCH_CHECK(!avg.empty() && avg.size() <= OSI_AVG_MAX_SPANS && cur.size() == avg.size(), "osi::average_update: 1 .. ",
+                OSI_AVG_MAX_SPANS, " tensors in each list, as many current as averaged ones");
+    osi_avg_span spans[OSI_AVG_MAX_SPANS];
+    for (size_t i = 0; i < avg.size(); ++i) {
+        need(avg[i], at::kFloat, "avg"); need(cur[i], at::kFloat, "cur");
+        TORCH_CHECK(avg[i].numel() == cur[i].numel() && avg[i].device() == avg[0].device() && cur[i].device() == avg[0].device(),
+                    "osi::average_update: pair ", i, " differs in size or lives on another device");
+        spans[i] = osi_avg_span{avg[i].data_ptr<float>(), cur[i].data_ptr<float>(), (size_t)avg[i].numel()};
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(avg[0].device());
+    ok(osi_average_update(spans, (int)avg.size(), (float)weight, stream_of(avg[0])), "osi_average_update");
+}
+
+// ABI 20: the executor's running-statistics update factor, in force from its next training-mode forward (no tensor: a host setting)
+void resnet50_set_bn_momentum(int64_t net, double momentum) {
+    ok(osi_resnet50_set_bn_momentum(handle(net), (float)momentum), "osi_resnet50_set_bn_momentum");
+}
+
 // Data parallel: the stream `waiter` (a raw hipStream_t handle: torch.cuda.Stream.cuda_stream of the communication stream) waits for the
 // gradients of the backward stages enqueued so far on the CURRENT stream and on the executor's side stream; the current stream waits for nothing
 void resnet50_grads_ready(int64_t net, const Tensor& grads, int64_t waiter) {
@@ -467,6 +489,8 @@ TORCH_LIBRARY(osi, m) {
           "float hi) -> ()");
     m.def("grad_accumulate(Tensor(a!) dst, Tensor src) -> ()");
     m.def("resnet50_grads_ready(int net, Tensor grads, int waiter_stream) -> ()");
+    m.def("average_update(Tensor(a!)[] avg, Tensor[] cur, float weight) -> ()");
+    m.def("resnet50_set_bn_momentum(int net, float momentum) -> ()", &resnet50_set_bn_momentum);   // no tensor argument: no dispatch key
     m.def("loss_fwd_bwd(int mode, Tensor logits, Tensor target, float unk_weight, int ignore_index, Tensor? class_weights, "
           "Tensor? features, float xi, float alpha, bool need_grad) -> (Tensor, Tensor, Tensor)");
     m.def("adam_step(Tensor(a!) params, Tensor grads, Tensor(b!) exp_avg, Tensor(c!) exp_avg_sq, float lr, float beta1, float beta2, "
@@ -496,6 +520,7 @@ TORCH_LIBRARY_IMPL(osi, CUDA, m) {
     m.impl("stem_dgrad_pgd", &stem_dgrad_pgd);
     m.impl("grad_accumulate", &grad_accumulate);
     m.impl("resnet50_grads_ready", &resnet50_grads_ready);
+    m.impl("average_update", &average_update);
     m.impl("loss_fwd_bwd", &loss_fwd_bwd);
     m.impl("adam_step", &adam_step);
     m.impl("sgd_step", &sgd_step);

@@ -163,6 +163,7 @@ struct osi_resnet50 {
     int cur_unit = 0;                // unit of the tensors being registered (osi_resnet50_create)
     unsigned unit_mask = (1u << NUNITS) - 1;
     int eval_prefix = 0;
+    float bn_momentum = 0.1f;        // running-statistics update factor of a training-mode forward (osi_resnet50_set_bn_momentum)
     bool trainable(int unit) const { return (unit_mask >> unit) & 1u; }
     int cut() const { int c = 0; while (!((unit_mask >> c) & 1u)) ++c; return c; }
     // first unit the backward in flight computes: the cut, unless the image gradient is wanted (then full depth)
@@ -437,6 +438,16 @@ int osi_resnet50_get_trainable(osi_resnet50_t net, unsigned* unit_mask, int* eva
     *eval_prefix_units = net->eval_prefix;
     return OSI_OK;
 }
+int osi_resnet50_set_bn_momentum(osi_resnet50_t net, float momentum) {
+    OSI_REQUIRE(net && momentum > 0.0f && momentum <= 1.0f);   // a NaN fails both comparisons
+    net->bn_momentum = momentum;
+    return OSI_OK;
+}
+int osi_resnet50_get_bn_momentum(osi_resnet50_t net, float* momentum) {
+    OSI_REQUIRE(net && momentum);
+    *momentum = net->bn_momentum;
+    return OSI_OK;
+}
 int osi_resnet50_geometry(osi_resnet50_t net, int* B, int* H, int* W) {
     OSI_REQUIRE(net);
     if (B) *B = net->B;
@@ -540,7 +551,7 @@ static int conv_bn_fwd(osi_resnet50* n, int ci, const float* params, float* buff
     else OSI_TRY(osi_conv_fwd(&c.d, x, w, ws + c.y, OSI_TILE_AUTO, st));
     OSI_TRY(n->mark(OSI_PROF_CONV_FWD, st));
     if (mode == BnMode::Batch)
-        OSI_TRY(osi_bn_finalize_stats(sws, sbytes, P, rows, b.M, b.C, params + b.g_off, params + b.b_off, 1e-5f, 0.1f, buffers + b.rm_off,
+        OSI_TRY(osi_bn_finalize_stats(sws, sbytes, P, rows, b.M, b.C, params + b.g_off, params + b.b_off, 1e-5f, n->bn_momentum, buffers + b.rm_off,
                                       buffers + b.rv_off, ws + b.mean, ws + b.invstd, ws + b.scale, ws + b.shift, st));
     else if (mode == BnMode::Inference)   // (frozen: one launch wrote every layer's coefficients up front)
         OSI_TRY(osi_bn_eval_coeffs(buffers + b.rm_off, buffers + b.rv_off, params + b.g_off, params + b.b_off, 1e-5f, b.C, ws + b.scale,

@@ -8,6 +8,7 @@ scope for this build and is not exported — see INTEGRATION.md.
 """
 from . import tools, util
 from . import dataset, losses, metrics, train
+from . import averaging
 from .losses import (AverageMeter, EarlyStopping, EntropicOpensetLoss, GarbageLoss, ObjectosphereLoss, SoftmaxLoss)
 from .model import ResNet50
 from .dataset import ImagenetDataset

@@ -84,7 +84,13 @@ class Attack(Structure):
     _fields_ = [("x_next", c_void_p), ("x_anchor", c_void_p), ("alpha", c_float), ("eps", c_float), ("lo", c_float), ("hi", c_float)]
 
 
+class AvgSpan(Structure):
+    """osi_avg_span: n floats of the average (read and written) and of the current values (read)"""
+    _fields_ = [("avg", c_void_p), ("cur", c_void_p), ("n", c_size_t)]
+
+
 OPT_MAX_SEGMENTS, OPT_MAX_GROUPS = 192, 16
+AVG_MAX_SPANS = 4
 NORM_INF, NORM_L2 = 0, 2
 EVAL_SCORE, EVAL_NORM = 0, 1
 HIST_MAX_BINS = 4096
@@ -192,6 +198,7 @@ _SIGS = {
     "osi_scale_f32": (c_int, [P, c_size_t, c_float, P]),
     "osi_grad_accumulate": (c_int, [P, P, c_size_t, P]),
     "osi_i64_add": (c_int, [P, c_int, c_longlong, P]),
+    "osi_average_update": (c_int, [POINTER(AvgSpan), c_int, c_float, P]),
     "osi_resnet50_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_int]),
     "osi_resnet50_destroy": (None, [c_void_p]),
     "osi_resnet50_num_tensors": (c_int, [c_void_p]),
@@ -210,7 +217,9 @@ _SIGS = {
     "osi_resnet50_bn_unit": (c_int, [c_void_p, c_int]),
     "osi_resnet50_set_trainable": (c_int, [c_void_p, ctypes.c_uint, c_int]),
     "osi_resnet50_get_trainable": (c_int, [c_void_p, POINTER(ctypes.c_uint), POINTER(c_int)]),
-    "osi_resnet50_set_option": (c_int, [c_void_p, c_char_p, c_int]),
+    "osi_resnet50_set_bn_momentum": (c_int, [c_void_p, c_float]),
+    "osi_resnet50_get_bn_momentum": (c_int, [c_void_p, POINTER(c_float)]),
+    "osi_resnet50_set_option":(c_int, [c_void_p, c_char_p, c_int]),
     "osi_resnet50_profile": (c_int, [c_void_p, c_int]),
     "osi_resnet50_profile_read": (c_int, [c_void_p, POINTER(ctypes.c_double), POINTER(c_int)]),
     "osi_resnet50_timeline_read": (c_int, [c_void_p, POINTER(ctypes.c_double), POINTER(c_int), POINTER(c_int), c_int, POINTER(c_int)]),

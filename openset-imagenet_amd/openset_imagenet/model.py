@@ -182,6 +182,7 @@ class ResNet50(nn.Module):
         self._eval_plain = False   # the latest forward was an eval-mode inference forward run with grad enabled (no graph)
         self._fwd_input_only = False   # the latest forward ran under a pending next_backward(input_only=True)
         self._fwd_prefix = 0       # units the differentiable forward being set up runs in the inference forms (forward())
+        self._bn_momentum = 0.1    # bn_momentum: handed to every executor that is not at the default (osi_resnet50_set_bn_momentum)
         self.reset_parameters()
 
     # ------------------------------------------------------------------------------------------------------
@@ -272,6 +273,8 @@ class ResNet50(nn.Module):
         key = (B, H, W)
         if key not in self._nets:
             self._nets[key] = _Net(B, H, W, self._F, self._O, self._logit_bias)
+            if self._bn_momentum != 0.1:
+                N.ops().resnet50_set_bn_momentum(self._nets[key].h.value, self._bn_momentum)
         net = self._nets[key]
         dev = self._flat_params.device
         if self._ws is None or self._ws.numel() < net.ws_bytes or self._ws.device != dev:
@@ -358,6 +361,23 @@ class ResNet50(nn.Module):
     def bn_frozen(self):
         """True after freeze_bn() (read-only; eval mode differentiates on the running statistics without it)."""
         return self._bn_frozen
+
+    @property
+    def bn_momentum(self):
+        """The running-statistics update factor of every BatchNorm in a training-mode forward: running = (1 - m) * running + m * batch,
+        m in (0, 1], default 0.1 (torch's). Applied to every executor the model has created and will create; it takes effect at the
+        next training-mode forward. Frozen and inference forwards never read it. 1.0 leaves the batch statistics in the buffers; 1 / k
+        before batch k is the cumulative average of averaging.update_bn."""
+        return self._bn_momentum
+
+    @bn_momentum.setter
+    def bn_momentum(self, value):
+        value = float(value)
+        if not 0.0 < value <= 1.0:        # a NaN fails both comparisons
+            raise ValueError(f"bn_momentum must lie in (0, 1], got {value!r}")
+        for net in self._nets.values():
+            N.ops().resnet50_set_bn_momentum(net.h.value, value)
+        self._bn_momentum = value
 
     def next_backward(self, fgsm=None, lo=0.0, hi=1.0, accumulate=False, *, pgd=None, input_only=False):
         """Request for the ONE backward that follows (whatever route it takes: a fused loss's plain backward(), autograd):

@@ -33,6 +33,8 @@ def get_args(command_line_options=None):
     p.add_argument("--auc", action="store_true", help="also compute the binary ROC-AUC of each split (known vs -1, known vs -2) on the GPU")
     p.add_argument("--report", action="store_true", help="also write {loss}_{split}_report{suffix}.json (confidences, CCR at FPR, score and "
                    "norm histograms, all counted on the GPU) next to the .npz and print the row of the reference's table")
+    p.add_argument("--averaged", action="store_true", help="evaluate the averaged weights (EMA / SWA) the checkpoint carries under "
+                   "avg_state_dict (config block avg) instead of the trained ones; the output files get the suffix _avg")
     args = p.parse_args(command_line_options)
     try:
         args.output_directory = str(args.output_directory).format(args.protocol)
@@ -103,6 +105,19 @@ def table_row(report, protocol, label, epoch, unk=-2):
     return row + "".join(" & ---" if v is None else f" & {v:1.3f}" for v in ccr) + "\\\\"
 
 
+def averaged_module(model, checkpoint):
+    """`--averaged`: the module of the checkpoint's "avg_state_dict" (averaging.AveragedModel over `model`'s geometry); exits with a
+    clear message when the checkpoint was written without an `avg` block."""
+    from ..averaging import AveragedModel
+    data = torch.load(checkpoint, map_location="cpu", weights_only=False)
+    if "avg_state_dict" not in data:
+        raise SystemExit(f"--averaged: {checkpoint} holds no averaged weights (no 'avg_state_dict': it was trained without an avg block)")
+    averaged = AveragedModel(model)
+    averaged.load_state_dict(data["avg_state_dict"])
+    print(f"Evaluating the averaged weights ({int(averaged.n_averaged)} updates)")
+    return averaged.module
+
+
 def main(command_line_options=None):
     args = get_args(command_line_options)
     if args.gpu is None:
@@ -117,8 +132,12 @@ def main(command_line_options=None):
     n_classes = n_labels if args.loss == "garbage" else n_labels - 1     # evaluate.py:121-124
     suffix = "_best" if args.use_best else "_curr"
     model = ResNet50(fc_layer_dim=n_classes, out_features=n_classes, logit_bias=False)
-    start_epoch, best_score = load_checkpoint(model, args.output_directory / (args.loss + suffix + ".pth"))
+    checkpoint = args.output_directory / (args.loss + suffix + ".pth")
+    start_epoch, best_score = load_checkpoint(model, checkpoint)
     print(f"Taking model from epoch {start_epoch} that achieved best score {best_score}")
+    if args.averaged:
+        model = averaged_module(model, checkpoint)
+        suffix += "_avg"
     tools.device(model)
     written = {}
     for split, ds in splits.items():

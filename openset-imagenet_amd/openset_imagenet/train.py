@@ -5,6 +5,7 @@ openset_imagenet/train.py, on top of the MI355X executor.
   save_checkpoint(f_name, model, epoch, opt, best_score_, scheduler=None)     train.py:37-60   (same dict schema)
   load_checkpoint(model, checkpoint, opt=None, scheduler=None) -> (start_epoch, best_score)   train.py:63-101
   train(model, data_loader, optimizer, loss_fn, trackers, cfg)                train.py:104-139 (same step order)
+      (new, optional: `averaged=` an averaging.AveragedModel the loop updates, saved and restored under "avg_state_dict")
   build_loss / build_model / build_optimizer                                  train.py:329-369 (cfg.loss.type, cfg.opt.*)
 
 Per-step order is the reference's: model.train(), zero_grad, H2D, forward, loss, tracker update, backward, step.
@@ -20,6 +21,7 @@ import numpy as np
 import torch
 
 from . import adversary as _adversary
+from . import averaging as _averaging
 from . import dp as _dp
 from . import losses as _losses
 from . import optim as _optim
@@ -38,20 +40,25 @@ def _unwrap(model):
     return model.module if isinstance(model, (_dp.DistributedDataParallel, torch.nn.parallel.DistributedDataParallel)) else model
 
 
-def save_checkpoint(f_name, model, epoch, opt, best_score_, scheduler=None):
-    """Write {"epoch": epoch+1, "model_state_dict", "opt_state_dict", "best_score"[, "scheduler"]} (reference train.py:37-60)."""
+def save_checkpoint(f_name, model, epoch, opt, best_score_, scheduler=None, averaged=None):
+    """Write {"epoch": epoch+1, "model_state_dict", "opt_state_dict", "best_score"[, "scheduler"]} (reference train.py:37-60).
+    `averaged` (new; an averaging.AveragedModel): its state_dict() goes under "avg_state_dict"; without it the key set is the one above."""
     data = {"epoch": epoch + 1,
             "model_state_dict": _unwrap(model).state_dict(),
             "opt_state_dict": opt.state_dict(),
             "best_score": best_score_}
     if scheduler is not None:
         data["scheduler"] = scheduler.state_dict()
+    if averaged is not None:
+        data["avg_state_dict"] = averaged.state_dict()
     torch.save(data, f_name)
 
 
-def load_checkpoint(model, checkpoint, opt=None, scheduler=None):
+def load_checkpoint(model, checkpoint, opt=None, scheduler=None, averaged=None):
     """Load a checkpoint written by this package or by the reference; strips a DDP "module." prefix
-    (reference train.py:63-101). Returns (start_epoch, best_score); raises Exception when the file is missing."""
+    (reference train.py:63-101). Returns (start_epoch, best_score); raises Exception when the file is missing.
+    `averaged` (new; an averaging.AveragedModel): restored from the checkpoint's "avg_state_dict"; a checkpoint without the key
+    restarts the average from the loaded weights (AveragedModel.restart)."""
     file_path = pathlib.Path(checkpoint)
     if not file_path.is_file():
         raise Exception(f"Checkpoint file '{checkpoint}' not found")
@@ -64,6 +71,11 @@ def load_checkpoint(model, checkpoint, opt=None, scheduler=None):
         opt.load_state_dict(data["opt_state_dict"])
     if scheduler is not None:
         scheduler.load_state_dict(data["scheduler"])
+    if averaged is not None:
+        if "avg_state_dict" in data:
+            averaged.load_state_dict(data["avg_state_dict"])
+        else:
+            averaged.restart(model)
     return data["epoch"], data["best_score"]
 
 
@@ -156,7 +168,7 @@ def step_options(cfg):
     return k, clip, float(kind)
 
 
-def train(model, data_loader, optimizer, loss_fn, trackers, cfg, epsilon=None):
+def train(model, data_loader, optimizer, loss_fn, trackers, cfg, epsilon=None, averaged=None):
     """One epoch of training (reference train.py:104-139).
 
     With `cfg.adv.who` in {fgsm, pgd, gaussian, uniform} (new; absent block or `no_adv`: the loop below is the reference's) every step
@@ -177,9 +189,18 @@ def train(model, data_loader, optimizer, loss_fn, trackers, cfg, epsilon=None):
     A fused optimizer (optim.Adam / AdamW / SGD) takes both in its launch: step(grad_scale=1 / r, clip_norm=x, norm_type=...), nothing
     read back. Any other optimizer: p.grad.mul_(1 / r) over its parameters when r > 1, torch.nn.utils.clip_grad_norm_ over them, step().
     Under data parallel every micro-backward averages its own buckets (correct by linearity) and the norm is launched on the compute
-    stream after the backward's GradSync.finish(), so every rank derives the same scalar from the same averaged arena."""
+    stream after the backward's GradSync.finish(), so every rank derives the same scalar from the same averaged arena.
+
+    `averaged` (new; an averaging.AveragedModel, None: the loop above): the loop counts every optimizer.step() it makes from the start of
+    the epoch — ragged last groups and the two-pass adversarial step included — and after every `avg.every`-th one (optional config
+    block `avg`, averaging.options; default 1) calls averaged.update_parameters(model): one more launch behind the step, nothing read back."""
     plan = _adversary.Plan(cfg, epsilon) if _adversary.who_of(cfg) != "no_adv" else None
     group, clip, norm_type = step_options(cfg)
+    avg_every = 1
+    if averaged is not None:
+        avg_opts = _averaging.options(cfg)
+        avg_every = 1 if avg_opts is None else avg_opts.every
+    steps = 0                                  # optimizer steps of this epoch
     if plan is not None:
         trackers.setdefault("j_adv", _losses.AverageMeter())
     if clip is not None:
@@ -198,7 +219,14 @@ def train(model, data_loader, optimizer, loss_fn, trackers, cfg, epsilon=None):
     fused = isinstance(optimizer, _optim._FlatOptimizer)
 
     def step(r):
-        """the optimizer step that closes a group of r batches"""
+        """the optimizer step that closes a group of r batches, and the weight average that follows every avg.every-th one"""
+        nonlocal steps
+        _step(r)
+        steps += 1
+        if averaged is not None and steps % avg_every == 0:
+            averaged.update_parameters(model)
+
+    def _step(r):
         if r == 1 and clip is None:
             optimizer.step()
         elif fused:
@@ -582,12 +610,20 @@ def _worker_body(cfg, log, out_dir, rank, world, distributed):
     scheduler = torch.optim.lr_scheduler.StepLR(opt, step_size=cfg.opt.decay, gamma=cfg.opt.gamma) if cfg.opt.decay > 0 else None
 
     best_score, start_epoch = 0.0, 0
+    # optional block `avg` (averaging.options; absent or kind: off = the run without it): an averaged copy of the weights, built on the
+    # un-wrapped model. A resumed run restores it from the checkpoint's "avg_state_dict"; with train_mode finetune, or a checkpoint
+    # without the key, it starts afresh from the loaded weights
+    avg_opts, averaged = _averaging.build(cfg, model)
     if cfg.checkpoint is not None:
         if cfg.train_mode == "finetune":     # weights only; keeps the checkpoint's epoch, resets the best score (train.py:374-380)
             start_epoch, _ = load_checkpoint(model, cfg.checkpoint)
+            if averaged is not None:
+                averaged.restart(model)
         else:
-            start_epoch, best_score = load_checkpoint(model, cfg.checkpoint, opt, scheduler)
+            start_epoch, best_score = load_checkpoint(model, cfg.checkpoint, opt, scheduler, averaged)
         log.info(f"Loaded {cfg.checkpoint} at epoch {start_epoch}")
+    if averaged is not None:
+        log.info(f"Weight averaging: {avg_opts}")
     # top-level `freeze_bn: on` (absent = off): BatchNorm on the running statistics, read-only, while the weights train (model.freeze_bn)
     if _freeze_bn_of(cfg):
         model.freeze_bn()
@@ -610,29 +646,50 @@ def _worker_body(cfg, log, out_dir, rank, world, distributed):
         if _adversary.who_of(cfg) not in ("fgsm", "pgd") and getattr(cfg.adv, "generator", None) is None:   # the noise stream: seeded per rank
             cfg.adv.generator = torch.Generator(device=tools.get_device()).manual_seed(cfg.seed + rank)
     v_metrics = {"j": _losses.AverageMeter(), "conf_kn": _losses.AverageMeter(), "conf_unk": _losses.AverageMeter()}
+    a_metrics = None
+    if averaged is not None:   # validate() of the averaged module fills a tracker set of its own, visible as v_metrics["j_avg"] ...
+        a_metrics = {"j": _losses.AverageMeter(), "conf_kn": _losses.AverageMeter(), "conf_unk": _losses.AverageMeter()}
+        v_metrics.update({k + "_avg": m for k, m in a_metrics.items()})
+        _last_worker_state.update(averaged=averaged)
     _last_worker_state.update(v_metrics=v_metrics, val_loader=val_loader, loss_fn=loss_fn, n_classes=n_classes)
     early = _losses.EarlyStopping(patience=cfg.patience) if cfg.patience > 0 else None
     scalars = None
     if rank == 0:
         scalars = open(out_dir / f"scalars-{cfg.log_name}.csv", "w")
-        scalars.write("epoch,train/loss,val/loss,val/conf_kn,val/conf_unk\n")
+        scalars.write("epoch,train/loss,val/loss,val/conf_kn,val/conf_unk" +
+                      (",val/loss_avg,val/conf_kn_avg,val/conf_unk_avg" if averaged is not None else "") + "\n")
     log.info(f"Training: protocol {cfg.protocol}, loss {cfg.loss.type}, {n_classes} classes, {len(train_ds)} / {len(val_ds)} samples, "
              f"{world} GPU(s) x batch {cfg.batch_size}")
+    shard = (rank, world) if shard_val else None
+
+    def scored(averaging):
+        """validate() of the model and then, while the average runs, of the averaged module with the same loop (sharded or not) into
+        v_metrics["j_avg"], ["conf_kn_avg"], ["conf_unk_avg"]; returns the score that drives _best.pth and early stopping (avg.select)"""
+        validate(model, val_loader, loss_fn, n_classes, v_metrics, cfg, shard=shard)
+        score = v_metrics["conf_kn"].avg + v_metrics["conf_unk"].avg
+        if averaging:
+            validate(averaged.module, val_loader, loss_fn, n_classes, a_metrics, cfg, shard=shard)
+            if avg_opts.select == "averaged":
+                score = a_metrics["conf_kn"].avg + a_metrics["conf_unk"].avg
+        return score
+
+    last_epoch = start_epoch - 1
     for epoch in range(start_epoch, cfg.epochs):
         t0 = time.time()
         if sampler is not None:
             sampler.set_epoch(epoch)
-        train(net, train_loader, opt, loss_fn, t_metrics, cfg, epsilon=_adversary.scheduled_epsilon(cfg.adv, epoch) if adv_on else None)
+        averaging = averaged is not None and epoch >= avg_opts.start_epoch   # nothing is averaged or validated before avg.start_epoch
+        train(net, train_loader, opt, loss_fn, t_metrics, cfg, epsilon=_adversary.scheduled_epsilon(cfg.adv, epoch) if adv_on else None,
+              averaged=averaged if averaging else None)
+        last_epoch = epoch
         t1 = time.time()
         stop, failure = False, None
         curr_score = None
         if shard_val:                                     # every rank scores its share of the batches; all ranks end with the same trackers
-            validate(model, val_loader, loss_fn, n_classes, v_metrics, cfg, shard=(rank, world))
-            curr_score = v_metrics["conf_kn"].avg + v_metrics["conf_unk"].avg
+            curr_score = scored(averaging)
         elif rank == 0:                                   # validate on the first process only (reference train.py:248)
             try:
-                validate(model, val_loader, loss_fn, n_classes, v_metrics, cfg)
-                curr_score = v_metrics["conf_kn"].avg + v_metrics["conf_unk"].avg
+                curr_score = scored(averaging)
             except Exception as e:                        # the other ranks wait in the broadcast below: tell them before re-raising.
                 failure = e                               # (KeyboardInterrupt / SystemExit propagate at once: the launcher ends the ranks)
                 log.exception("rank 0 failed in validate()")   # the original traceback, before any collective can mask it
@@ -643,14 +700,17 @@ def _worker_body(cfg, log, out_dir, rank, world, distributed):
             scheduler.step()
         if rank == 0 and failure is None:
             try:
-                scalars.write(f"{epoch},{t_metrics['j'].avg},{v_metrics['j'].avg},{v_metrics['conf_kn'].avg},{v_metrics['conf_unk'].avg}\n")
+                row = f"{epoch},{t_metrics['j'].avg},{v_metrics['j'].avg},{v_metrics['conf_kn'].avg},{v_metrics['conf_unk'].avg}"
+                if averaged is not None:
+                    row += f",{a_metrics['j'].avg},{a_metrics['conf_kn'].avg},{a_metrics['conf_unk'].avg}"
+                scalars.write(row + "\n")
                 scalars.flush()
                 log.info(f"ep:{epoch} train:{t_metrics} val:{v_metrics} t:{t1 - t0:.1f}s v:{time.time() - t1:.1f}s")
-                save_checkpoint(out_dir / (cfg.name + "_curr.pth"), model, epoch, opt, curr_score, scheduler)
+                save_checkpoint(out_dir / (cfg.name + "_curr.pth"), model, epoch, opt, curr_score, scheduler, averaged)
                 _last_worker_state["checkpoints_written"] += 1
                 if curr_score > best_score:
                     best_score = curr_score
-                    save_checkpoint(out_dir / (cfg.name + "_best.pth"), model, epoch, opt, best_score, scheduler)
+                    save_checkpoint(out_dir / (cfg.name + "_best.pth"), model, epoch, opt, best_score, scheduler, averaged)
                     _last_worker_state["checkpoints_written"] += 1
                 if early is not None:
                     early(metrics=curr_score, loss=False)
@@ -669,6 +729,19 @@ def _worker_body(cfg, log, out_dir, rank, world, distributed):
         if stop:
             log.info("early stop")
             break
+    if averaged is not None and avg_opts.update_bn:
+        # avg.update_bn: on (SWA's last act): the averaged weights get BatchNorm statistics of their own from one pass over the training
+        # loader, are validated once more and written to {name}_avg.pth. Every rank runs the pass on its shard of the loader; validation
+        # scores rank 0's statistics, as it does for the model
+        _averaging.update_bn(train_loader, averaged)
+        final = None
+        if shard_val or rank == 0:
+            validate(averaged.module, val_loader, loss_fn, n_classes, a_metrics, cfg, shard=shard)
+            final = a_metrics["conf_kn"].avg + a_metrics["conf_unk"].avg
+        if rank == 0:
+            log.info(f"update_bn: averaged val:{a_metrics}")
+            save_checkpoint(out_dir / (cfg.name + "_avg.pth"), model, last_epoch, opt, final, scheduler, averaged)
+            _last_worker_state["checkpoints_written"] += 1
     if scalars is not None:
         scalars.close()
     return best_score
