@@ -41,7 +41,7 @@ extern "C" {
 
 typedef void* osi_stream_t; /* hipStream_t */
 
-int osi_abi_version(void);            /* bumped on any signature change; 20 = weight averaging (osi_average_update) and the executor's BatchNorm momentum (osi_resnet50_set_bn_momentum / _get_bn_momentum); 19 =projected attack steps (osi_stem_dgrad_pgd, osi_resnet50_backward_attack); 18 = evaluation histograms (osi_eval_values_*, osi_hist_*); 17 = gradient-norm clipping (osi_grad_clip_scale, osi_*_step_groups_dev); 16 = the ROC-AUC entry points (osi_auc_*) */
+int osi_abi_version(void);            /* bumped on any signature change; 21 = OpenMax (osi_openmax_*); 20 = weight averaging (osi_average_update) and the executor's BatchNorm momentum (osi_resnet50_set_bn_momentum / _get_bn_momentum); 19 =projected attack steps (osi_stem_dgrad_pgd, osi_resnet50_backward_attack); 18 = evaluation histograms (osi_eval_values_*, osi_hist_*); 17 = gradient-norm clipping (osi_grad_clip_scale, osi_*_step_groups_dev); 16 = the ROC-AUC entry points (osi_auc_*) */
 const char* osi_build_arch(void);     /* "gfx950" */
 const char* osi_strerror(int code);
 /* Process-wide development knobs (A/B measurements; every default is the measured optimum). Launch functions only READ them and never
@@ -502,6 +502,57 @@ int osi_hist_f32(const float* val, const unsigned char* side, int side_bit, int 
                  osi_stream_t stream);
 int osi_hist_f64(const double* val, const unsigned char* side, int side_bit, int N, const double* edges, int nb, long long* counts,
                  osi_stream_t stream);
+
+/* ABI 21. OpenMax (Bendale & Boult, CVPR 2016; openset_imagenet/openmax.py): class means of the correctly classified training rows, a
+ * Weibull fit to the largest distances of every class, and test logits recalibrated by the probability of lying in that tail. The
+ * method is not part of the reference snapshot; this block is its definition. Inputs are the device-resident arrays of get_arrays:
+ * features[N][F] and logits[N][C] in fp32, int64 labels; F and C are independent. No floating-point atomics: every output is
+ * bit-identical from run to run. Every output is zeroed or written by the call; no allocation, no host synchronisation; workspace
+ * contents are never assumed (ws: osi_openmax_workspace(N, C, F) bytes, 4-byte aligned, overwritten; 0 for non-positive arguments).
+ * OSI_ERR_ARG before any launch on a null pointer (cls excepted), N, C or F <= 0, a short workspace or a bad enum / range.
+ *
+ * osi_openmax_class_means: row i is correct for class c when gt[i] == c, 0 <= c < C, and the first maximum of logits[i] (lowest index
+ *   on ties) is column c; a row holding a NaN logit is never correct, labels outside [0, C) are ignored. correct[i] = 1 / 0.
+ *   count[c] = the correct rows of class c; mav[c] = the mean of their features: summed in fp64 in ascending row order, divided once
+ *   in fp64, rounded once to fp32; all zeros for a class without a correct row.
+ * osi_openmax_distances: d(f, m) with every sum in fp64 in index order, each product rounded before it is added, one fp64 sqrt /
+ *   divide and one rounding to fp32. OSI_OPENMAX_EUCLIDEAN: sqrt(sum (f_j - m_j)^2). OSI_OPENMAX_COSINE:
+ *   1 - (sum f_j m_j) / sqrt(sum f_j^2 * sum m_j^2), NaN for a zero denominator. cls == NULL: dist[N][C], every row against every
+ *   class mean (C <= 64 * 65535: one grid row per 64 classes). Otherwise dist[N], row i against mav[cls[i]], NaN where cls[i] is
+ *   outside [0, C).
+ * osi_openmax_fit_tails: for class c, D_c = the finite dist[i] over the rows with correct[i] and gt[i] == c (-0 counts as +0). The
+ *   tail is the min(T, |D_c|) largest values (tail_count[c]), 2 <= T <= OSI_OPENMAX_MAX_TAIL; shift[c] = its smallest value; the
+ *   fitted data are x = tail - shift[c] + 1 in fp64 (libMR's FitHigh translation, x >= 1). shape[c] = k is the root of
+ *   g(k) = sum x^k ln x / sum x^k - 1/k - mean(ln x) (the maximum-likelihood equation of the two-parameter Weibull), with x^k taken
+ *   as exp(k ln x - k ln x_max); scale[c] = x_max * (mean exp(k ln x - k ln x_max))^(1/k). A class whose tail has fewer than two
+ *   values, or equal largest and smallest values (in fp32, or x_max == 1 after the translation in fp64: a spread below 2^-53), is
+ *   unfitted: fitted[c] = 0 and shape = scale = shift = 0.
+ *   flags2 = {eligible rows whose distance is not finite (left out), unfitted classes}.
+ *   One workgroup per class: radix select over the float bits (four passes over the rows), bitonic sort of the tail in LDS, sums over
+ *   the sorted tail in a fixed tree, so the fit depends on the multiset of the tail alone (permuting the rows changes no bit).
+ *   The solver doubles / halves from k = 1 to a bracket (at most 1100 steps), then takes Newton steps that fall back to bisection
+ *   whenever they leave the bracket (at most 128 steps): the iteration count is bounded whatever the data.
+ * osi_openmax_wscores: w[i][c] = 1 - exp(-(z / scale[c])^shape[c]) with z = dist[i][c] - shift[c] + 1, in fp64 from the fp32
+ *   distance, rounded once to fp32; 0 when z <= 0 or the class is unfitted; NaN for a NaN distance.
+ * osi_openmax_recalibrate: a = min(alpha, C), alpha >= 1. Per row the logits are ranked descending and stably (lower index first on
+ *   ties); the column of rank r < a gets omega = 1 - w * (a - r) / a, every other column omega = 1 (the authors' released code: rank
+ *   0 gets full weight). v^_c = v_c * omega_c, v^_unk = sum_c v_c * (1 - omega_c), probs[i] = softmax([v^_0 .. v^_{C-1}, v^_unk]) in
+ *   fp64 with the row maximum subtracted, rounded once to fp32: probs is [N][C + 1], the unknown column LAST (the background-class
+ *   convention of this package). A row whose logits hold a NaN is NaN throughout. C above 2048 does not fit the row ranking in LDS:
+ *   OSI_ERR_ARG. */
+enum { OSI_OPENMAX_EUCLIDEAN = 0, OSI_OPENMAX_COSINE = 1 };
+#define OSI_OPENMAX_MAX_TAIL 4096
+size_t osi_openmax_workspace(int N, int C, int F);
+int osi_openmax_class_means(const float* features, const float* logits, const long long* gt, int N, int C, int F, float* mav,
+                            long long* count, unsigned char* correct, void* ws, size_t ws_bytes, osi_stream_t stream);
+int osi_openmax_distances(const float* features, const float* mav, const long long* cls, int N, int C, int F, int metric, float* dist,
+                          osi_stream_t stream);
+int osi_openmax_fit_tails(const float* dist, const long long* gt, const unsigned char* correct, int N, int C, int T, double* shape,
+                          double* scale, double* shift, unsigned char* fitted, long long* tail_count, long long* flags2, void* ws,
+                          size_t ws_bytes, osi_stream_t stream);
+int osi_openmax_wscores(const float* dist, int N, int C, const double* shape, const double* scale, const double* shift,
+                        const unsigned char* fitted, float* w, osi_stream_t stream);
+int osi_openmax_recalibrate(const float* logits, const float* w, int N, int C, int alpha, float* probs, osi_stream_t stream);
 
 /* ---- optimizer + arena utilities (train.py:356-359 construction, train.py:127,139 zero_grad/step) --- */
 int osi_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,

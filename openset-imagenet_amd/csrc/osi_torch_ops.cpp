@@ -14,6 +14,7 @@
 //   torch.ops.osi.average_update      EMA / SWA of the arenas in one launch (averaging.py); resnet50_set_bn_momentum: update_bn's 1 / k
 //   torch.ops.osi.stage_canvas        train.py:259-263 after decode + resize (crop, flip, ToTensor, NHWC4)
 //   torch.ops.osi.softmax / confidence_accumulate    train.py:177, metrics.py:8-42
+//   torch.ops.osi.openmax_class_means / _distances / _fit_tails / _wscores / _recalibrate    OpenMax (openset_imagenet/openmax.py)
 //
 // This file contains no arithmetic: every op validates its tensor arguments (device, dtype, contiguity, sizes), takes the CURRENT
 // HIP stream of the tensors' device inside the op, and forwards raw pointers to the C ABI of libosi_hip.so (include/osi.h), which
@@ -470,9 +471,110 @@ void confidence_accumulate(const Tensor& logits, const Tensor& target, double of
                                  acc4.data_ptr<double>(), stream_of(logits)), "osi_confidence_accumulate");
 }
 
+// ---- OpenMax (include/osi.h, ABI 21): every op allocates its outputs and leaves them on the device
+void openmax_rows(const Tensor& a, const Tensor& b, const char* what) {
+    TORCH_CHECK(a.device() == b.device(), "osi::", what, ": tensors on different devices");
+    TORCH_CHECK(a.size(0) == b.size(0), "osi::", what, ": tensors disagree on the number of rows");
+}
+
+std::tuple<Tensor, Tensor, Tensor> openmax_class_means(const Tensor& features, const Tensor& logits, const Tensor& gt, Tensor workspace) {
+    need(features, at::kFloat, "features", NATURAL); need(logits, at::kFloat, "logits", NATURAL); need(gt, at::kLong, "gt", NATURAL);
+    need(workspace, at::kByte, "workspace", NATURAL);
+    TORCH_CHECK(features.dim() == 2 && logits.dim() == 2 && gt.dim() == 1, "osi::openmax_class_means: features [N,F], logits [N,C], gt [N]");
+    openmax_rows(features, logits, "openmax_class_means"); openmax_rows(features, gt, "openmax_class_means");
+    const int N = (int)features.size(0), F = (int)features.size(1), C = (int)logits.size(1);
+    TORCH_CHECK(workspace.device() == features.device() && (size_t)workspace.numel() >= osi_openmax_workspace(N, C, F),
+                "osi::openmax_class_means: workspace too small");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(features.device());
+    Tensor mav = at::empty({C, F}, features.options());
+    Tensor count = at::empty({C}, features.options().dtype(at::kLong));
+    Tensor correct = at::empty({N}, features.options().dtype(at::kByte));
+    ok(osi_openmax_class_means(features.data_ptr<float>(), logits.data_ptr<float>(), (const long long*)gt.data_ptr<int64_t>(), N, C, F,
+                               mav.data_ptr<float>(), (long long*)count.data_ptr<int64_t>(), correct.data_ptr<unsigned char>(),
+                               workspace.data_ptr(), (size_t)workspace.numel(), stream_of(features)), "osi_openmax_class_means");
+    return {mav, count, correct};
+}
+
+Tensor openmax_distances(const Tensor& features, const Tensor& mav, const std::optional<Tensor>& cls, int64_t metric) {
+    need(features, at::kFloat, "features", NATURAL); need(mav, at::kFloat, "mav", NATURAL);
+    TORCH_CHECK(features.dim() == 2 && mav.dim() == 2 && features.size(1) == mav.size(1) && mav.device() == features.device(),
+                "osi::openmax_distances: features [N,F] and mav [C,F] on one device");
+    const int N = (int)features.size(0), F = (int)features.size(1), C = (int)mav.size(0);
+    const long long* cp = nullptr;
+    if (cls.has_value() && cls->defined()) {
+        need(*cls, at::kLong, "cls", NATURAL);
+        TORCH_CHECK(cls->dim() == 1, "osi::openmax_distances: cls is [N]");
+        openmax_rows(features, *cls, "openmax_distances");
+        cp = (const long long*)cls->data_ptr<int64_t>();
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(features.device());
+    Tensor dist = cp ? at::empty({N}, features.options()) : at::empty({N, C}, features.options());
+    ok(osi_openmax_distances(features.data_ptr<float>(), mav.data_ptr<float>(), cp, N, C, F, (int)metric, dist.data_ptr<float>(),
+                             stream_of(features)), "osi_openmax_distances");
+    return dist;
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> openmax_fit_tails(const Tensor& dist, const Tensor& gt, const Tensor& correct,
+                                                                             int64_t C, int64_t tailsize, Tensor workspace) {
+    need(dist, at::kFloat, "dist", NATURAL); need(gt, at::kLong, "gt", NATURAL); need(correct, at::kByte, "correct", 1);
+    need(workspace, at::kByte, "workspace", NATURAL);
+    TORCH_CHECK(dist.dim() == 1 && gt.dim() == 1 && correct.dim() == 1, "osi::openmax_fit_tails: dist, gt and correct are [N]");
+    openmax_rows(dist, gt, "openmax_fit_tails"); openmax_rows(dist, correct, "openmax_fit_tails");
+    TORCH_CHECK(C > 0 && C <= INT_MAX, "osi::openmax_fit_tails: C out of range");
+    const int N = (int)dist.size(0);
+    TORCH_CHECK(workspace.device() == dist.device() && (size_t)workspace.numel() >= osi_openmax_workspace(N, (int)C, 1),
+                "osi::openmax_fit_tails: workspace too small");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dist.device());
+    const auto f64 = dist.options().dtype(at::kDouble), i64 = dist.options().dtype(at::kLong);
+    Tensor shape = at::empty({C}, f64), scale = at::empty({C}, f64), shift = at::empty({C}, f64);
+    Tensor fitted = at::empty({C}, dist.options().dtype(at::kByte)), tail_count = at::empty({C}, i64), flags2 = at::empty({2}, i64);
+    ok(osi_openmax_fit_tails(dist.data_ptr<float>(), (const long long*)gt.data_ptr<int64_t>(), correct.data_ptr<unsigned char>(), N, (int)C,
+                             (int)tailsize, shape.data_ptr<double>(), scale.data_ptr<double>(), shift.data_ptr<double>(),
+                             fitted.data_ptr<unsigned char>(), (long long*)tail_count.data_ptr<int64_t>(),
+                             (long long*)flags2.data_ptr<int64_t>(), workspace.data_ptr(), (size_t)workspace.numel(), stream_of(dist)),
+       "osi_openmax_fit_tails");
+    return {shape, scale, shift, fitted, tail_count, flags2};
+}
+
+Tensor openmax_wscores(const Tensor& dist, const Tensor& shape, const Tensor& scale, const Tensor& shift, const Tensor& fitted) {
+    need(dist, at::kFloat, "dist", NATURAL); need(shape, at::kDouble, "shape", NATURAL); need(scale, at::kDouble, "scale", NATURAL);
+    need(shift, at::kDouble, "shift", NATURAL); need(fitted, at::kByte, "fitted", 1);
+    TORCH_CHECK(dist.dim() == 2, "osi::openmax_wscores: dist is [N,C]");
+    const int64_t C = dist.size(1);
+    TORCH_CHECK(shape.numel() == C && scale.numel() == C && shift.numel() == C && fitted.numel() == C,
+                "osi::openmax_wscores: shape, scale, shift and fitted hold one entry per column of dist");
+    TORCH_CHECK(shape.device() == dist.device() && scale.device() == dist.device() && shift.device() == dist.device() &&
+                fitted.device() == dist.device(), "osi::openmax_wscores: tensors on different devices");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dist.device());
+    Tensor w = at::empty_like(dist);
+    ok(osi_openmax_wscores(dist.data_ptr<float>(), (int)dist.size(0), (int)C, shape.data_ptr<double>(), scale.data_ptr<double>(),
+                           shift.data_ptr<double>(), fitted.data_ptr<unsigned char>(), w.data_ptr<float>(), stream_of(dist)),
+       "osi_openmax_wscores");
+    return w;
+}
+
+Tensor openmax_recalibrate(const Tensor& logits, const Tensor& w, int64_t alpha) {
+    need(logits, at::kFloat, "logits", NATURAL); need(w, at::kFloat, "w", NATURAL);
+    TORCH_CHECK(logits.dim() == 2 && w.sizes() == logits.sizes() && w.device() == logits.device(),
+                "osi::openmax_recalibrate: logits and w are [N,C] on one device");
+    TORCH_CHECK(alpha >= 1, "osi::openmax_recalibrate: alpha must be >= 1");
+    const int N = (int)logits.size(0), C = (int)logits.size(1);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(logits.device());
+    Tensor probs = at::empty({N, C + 1}, logits.options());
+    ok(osi_openmax_recalibrate(logits.data_ptr<float>(), w.data_ptr<float>(), N, C, (int)std::min<int64_t>(alpha, INT_MAX),
+                               probs.data_ptr<float>(), stream_of(logits)), "osi_openmax_recalibrate");
+    return probs;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(osi, m) {
+    m.def("openmax_class_means(Tensor features, Tensor logits, Tensor gt, Tensor(a!) workspace) -> (Tensor, Tensor, Tensor)");
+    m.def("openmax_distances(Tensor features, Tensor mav, Tensor? cls, int metric) -> Tensor");
+    m.def("openmax_fit_tails(Tensor dist, Tensor gt, Tensor correct, int C, int tailsize, Tensor(a!) workspace) -> "
+          "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("openmax_wscores(Tensor dist, Tensor shape, Tensor scale, Tensor shift, Tensor fitted) -> Tensor");
+    m.def("openmax_recalibrate(Tensor logits, Tensor w, int alpha) -> Tensor");
     m.def("resnet50_forward(int net, Tensor params, Tensor(a!) buffers, Tensor(b!) nbt, Tensor image, Tensor? flip, Tensor(c!) workspace, "
           "int fc_dim, int out_features, bool training) -> (Tensor, Tensor)");
     m.def("resnet50_forward_frozen(int net, Tensor params, Tensor buffers, Tensor image, Tensor? flip, Tensor(a!) workspace, "
@@ -532,4 +634,9 @@ TORCH_LIBRARY_IMPL(osi, CUDA, m) {
     m.impl("stage_canvas", &stage_canvas);
     m.impl("softmax", &softmax);
     m.impl("confidence_accumulate", &confidence_accumulate);
+    m.impl("openmax_class_means", &openmax_class_means);
+    m.impl("openmax_distances", &openmax_distances);
+    m.impl("openmax_fit_tails", &openmax_fit_tails);
+    m.impl("openmax_wscores", &openmax_wscores);
+    m.impl("openmax_recalibrate", &openmax_recalibrate);
 }

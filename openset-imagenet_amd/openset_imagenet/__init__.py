@@ -9,10 +9,12 @@ scope for this build and is not exported — see INTEGRATION.md.
 from . import tools, util
 from . import dataset, losses, metrics, train
 from . import averaging
+from . import openmax
+from .openmax import OpenMax
 from .losses import (AverageMeter, EarlyStopping, EntropicOpensetLoss, GarbageLoss, ObjectosphereLoss, SoftmaxLoss)
 from .model import ResNet50
 from .dataset import ImagenetDataset
 from .pipeline import CanvasDataset
 
 __all__ = ["ResNet50", "ImagenetDataset", "CanvasDataset", "EntropicOpensetLoss", "SoftmaxLoss", "GarbageLoss", "ObjectosphereLoss", "AverageMeter",
-           "EarlyStopping", "tools", "util", "train", "metrics", "losses", "dataset"]
+           "EarlyStopping", "OpenMax", "tools", "util", "train", "metrics", "losses", "dataset"]

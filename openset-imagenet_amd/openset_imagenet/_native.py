@@ -94,6 +94,8 @@ AVG_MAX_SPANS = 4
 NORM_INF, NORM_L2 = 0, 2
 EVAL_SCORE, EVAL_NORM = 0, 1
 HIST_MAX_BINS = 4096
+OPENMAX_EUCLIDEAN, OPENMAX_COSINE = 0, 1
+OPENMAX_MAX_TAIL = 4096
 
 P = c_void_p
 _PD = POINTER(ConvDesc)
@@ -186,6 +188,12 @@ _SIGS = {
     "osi_eval_values_f64": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_longlong, c_int, P, P, P, P, P, P, c_size_t, P]),
     "osi_hist_f32": (c_int, [P, P, c_int, c_int, P, c_int, P, P]),
     "osi_hist_f64": (c_int, [P, P, c_int, c_int, P, c_int, P, P]),
+    "osi_openmax_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "osi_openmax_class_means": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, P, c_size_t, P]),
+    "osi_openmax_distances": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P]),
+    "osi_openmax_fit_tails": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, P, P, P, P, c_size_t, P]),
+    "osi_openmax_wscores": (c_int, [P, c_int, c_int, P, P, P, P, P, P]),
+    "osi_openmax_recalibrate": (c_int, [P, P, c_int, c_int, c_int, P, P]),
     "osi_adam_step": (c_int, [P, P, P, P, c_size_t, c_double, c_double, c_double, c_double, c_longlong, c_float, P]),
     "osi_sgd_step": (c_int, [P, P, P, c_size_t, c_float, c_float, c_int, c_float, P]),
     "osi_adam_step_groups": (c_int, [P, P, P, P, P, c_size_t, POINTER(OptSegment), c_int, POINTER(AdamGroup), c_int, c_float, P]),

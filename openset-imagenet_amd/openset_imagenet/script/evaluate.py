@@ -5,7 +5,10 @@ eval mode (train.get_arrays); there is no CPU evaluation path. `--oscr` (this bu
 of the OSCR curve computed on the GPU (util.calculate_oscr); `--auc` (likewise) prints the binary ROC-AUC of known against negative
 (-1) and against unknown (-2) samples, counted on the GPU (metrics.auc_score_binary); `--report` (likewise) writes `{loss}_{split}_report{suffix}.json` with
 the confidences, the CCR at FPR 1e-3 / 1e-2 / 0.1 / 1 and the 30-bin score and feature-norm histograms (evaluation_report), and
-prints the row of the reference's table (script/plot_all.py:344-385)."""
+prints the row of the reference's table (script/plot_all.py:344-385). `--openmax TAILSIZE` (likewise; softmax and entropic losses)
+fits OpenMax (openmax.OpenMax) on the arrays of the training split, saves it as `{loss}_openmax{suffix}.pth` and writes, next to each
+split's .npz, `{loss}_{split}_arr{suffix}_openmax.npz` with `gt`, `logits`, `features`, `scores` (the recalibrated class
+probabilities) and `unknown` (the probability of the unknown class); with `--oscr` the same OSCR line is printed for those scores."""
 import argparse
 import json
 import pathlib
@@ -35,7 +38,13 @@ def get_args(command_line_options=None):
                    "norm histograms, all counted on the GPU) next to the .npz and print the row of the reference's table")
     p.add_argument("--averaged", action="store_true", help="evaluate the averaged weights (EMA / SWA) the checkpoint carries under "
                    "avg_state_dict (config block avg) instead of the trained ones; the output files get the suffix _avg")
+    p.add_argument("--openmax", type=int, default=None, metavar="TAILSIZE", help="also fit OpenMax with this tail size on the training "
+                   "split (softmax and entropic losses) and write {loss}_{split}_arr{suffix}_openmax.npz with the recalibrated scores")
+    p.add_argument("--openmax-alpha", type=int, default=3, help="OpenMax: how many top-ranked logits are recalibrated")
+    p.add_argument("--openmax-distance", choices=["euclidean", "cosine"], default="euclidean", help="OpenMax: distance to the class means")
     args = p.parse_args(command_line_options)
+    if args.openmax is not None and args.loss == "garbage":
+        p.error("--openmax needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
     try:
         args.output_directory = str(args.output_directory).format(args.protocol)
     except Exception:
@@ -105,6 +114,34 @@ def table_row(report, protocol, label, epoch, unk=-2):
     return row + "".join(" & ---" if v is None else f" & {v:1.3f}" for v in ccr) + "\\\\"
 
 
+def oscr_lines(split, gt, scores, tag=""):
+    """The one-line OSCR summary of `--oscr` for each negative label present in gt."""
+    lines = []
+    for unk in (-1, -2):
+        if (gt == unk).any():
+            ccr, fpr = util.calculate_oscr(gt, scores, unk_label=unk)
+            at = ccr[np.searchsorted(-fpr, -0.1)] if len(ccr) and np.isfinite(fpr).all() and (fpr <= 0.1).any() else float("nan")
+            lines.append(f"{split}: {tag}OSCR vs label {unk}: {len(ccr)} points, CCR@FPR<=0.1 = {at:.4f}")
+    return lines
+
+
+def openmax_arrays(train_arrays, split_arrays, tailsize, alpha, distance):
+    """`--openmax` on arrays: fit OpenMax on the training split's `gt`, `logits`, `features` (mappings as get_arrays' .npz holds them;
+    an already fitted openmax.OpenMax is taken as it is) and recalibrate one split. Returns (om, arrays): arrays holds the numpy
+    `gt`, `logits`, `features` of the split, `scores` = probs[:, :C] and `unknown` = probs[:, C]."""
+    from ..openmax import OpenMax
+    if isinstance(train_arrays, OpenMax):
+        om = train_arrays
+    else:
+        om = OpenMax(tailsize=tailsize, distance=distance, alpha=alpha)
+        om.fit(train_arrays["features"], train_arrays["logits"], train_arrays["gt"])
+    probs = om.predict(split_arrays["logits"], split_arrays["features"]).cpu().numpy()
+    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    c = probs.shape[1] - 1
+    return om, dict(gt=host(split_arrays["gt"]), logits=host(split_arrays["logits"]), features=host(split_arrays["features"]),
+                    scores=probs[:, :c], unknown=probs[:, c])
+
+
 def averaged_module(model, checkpoint):
     """`--averaged`: the module of the checkpoint's "avg_state_dict" (averaging.AveragedModel over `model`'s geometry); exits with a
     clear message when the checkpoint was written without an `avg` block."""
@@ -140,6 +177,20 @@ def main(command_line_options=None):
         suffix += "_avg"
     tools.device(model)
     written = {}
+    om = None
+    if args.openmax is not None:
+        from ..openmax import OpenMax
+        om = OpenMax(tailsize=args.openmax, distance=args.openmax_distance, alpha=args.openmax_alpha)    # refuses bad options first
+        train_ds = _image_loader(args.protocol_directory / f"p{args.protocol}_train.csv", args.imagenet_directory, False, "eval")
+        print(f"train dataset len:{len(train_ds)}, labels:{train_ds.table.label_count}")
+        loader = torch.utils.data.DataLoader(train_ds, batch_size=args.batch_size, num_workers=args.workers)
+        t_gt, t_logits, t_features, _ = get_arrays(model=model, loader=loader)
+        om.fit(t_features, t_logits, t_gt)
+        om_path = args.output_directory / f"{args.loss}_openmax{suffix}.pth"
+        torch.save(om.state_dict(), om_path)
+        left_out, unfitted = om.flags.tolist()
+        print(f"OpenMax (tail {args.openmax}, alpha {args.openmax_alpha}, {args.openmax_distance}) fitted on {int(om.count.sum())} correct "
+              f"training samples, {unfitted} classes unfitted, {left_out} distances not finite; saved in: {om_path}")
     for split, ds in splits.items():
         loader = torch.utils.data.DataLoader(ds, batch_size=args.batch_size, num_workers=args.workers)
         gt, logits, features, scores = get_arrays(model=model, loader=loader)
@@ -149,11 +200,18 @@ def main(command_line_options=None):
         written[split] = file_path
         if args.oscr:
             s = scores[:, :-1] if args.loss == "garbage" else scores           # the background column is not a known class
-            for unk in (-1, -2):
-                if (gt == unk).any():
-                    ccr, fpr = util.calculate_oscr(gt, s, unk_label=unk)
-                    at = ccr[np.searchsorted(-fpr, -0.1)] if len(ccr) and np.isfinite(fpr).all() and (fpr <= 0.1).any() else float("nan")
-                    print(f"{split}: OSCR vs label {unk}: {len(ccr)} points, CCR@FPR<=0.1 = {at:.4f}")
+            for line in oscr_lines(split, gt, s):
+                print(line)
+        if om is not None:
+            _, arrays = openmax_arrays(om, dict(gt=gt, logits=logits, features=features), args.openmax, args.openmax_alpha,
+                                       args.openmax_distance)
+            om_file = args.output_directory / f"{args.loss}_{split}_arr{suffix}_openmax.npz"
+            np.savez(om_file, **arrays)
+            print(f"OpenMax scores saved in: {om_file}")
+            written[split + "_openmax"] = om_file
+            if args.oscr:
+                for line in oscr_lines(split, gt, arrays["scores"], tag="OpenMax "):
+                    print(line)
         if args.auc:
             for unk in (-1, -2):
                 sel = auc_rows(gt, scores, unk, args.loss)
