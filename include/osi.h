@@ -41,7 +41,7 @@ extern "C" {
 
 typedef void* osi_stream_t; /* hipStream_t */
 
-int osi_abi_version(void);            /* bumped on any signature change; 21 = OpenMax (osi_openmax_*); 20 = weight averaging (osi_average_update) and the executor's BatchNorm momentum (osi_resnet50_set_bn_momentum / _get_bn_momentum); 19 =projected attack steps (osi_stem_dgrad_pgd, osi_resnet50_backward_attack); 18 = evaluation histograms (osi_eval_values_*, osi_hist_*); 17 = gradient-norm clipping (osi_grad_clip_scale, osi_*_step_groups_dev); 16 = the ROC-AUC entry points (osi_auc_*) */
+int osi_abi_version(void);            /* bumped on any signature change; 22 = the Extreme Value Machine (osi_evm_*); 21 = OpenMax (osi_openmax_*); 20 = weight averaging (osi_average_update) and the executor's BatchNorm momentum (osi_resnet50_set_bn_momentum / _get_bn_momentum); 19 =projected attack steps (osi_stem_dgrad_pgd, osi_resnet50_backward_attack); 18 = evaluation histograms (osi_eval_values_*, osi_hist_*); 17 = gradient-norm clipping (osi_grad_clip_scale, osi_*_step_groups_dev); 16 = the ROC-AUC entry points (osi_auc_*) */
 const char* osi_build_arch(void);     /* "gfx950" */
 const char* osi_strerror(int code);
 /* Process-wide development knobs (A/B measurements; every default is the measured optimum). Launch functions only READ them and never
@@ -553,6 +553,62 @@ int osi_openmax_fit_tails(const float* dist, const long long* gt, const unsigned
 int osi_openmax_wscores(const float* dist, int N, int C, const double* shape, const double* scale, const double* shift,
                         const unsigned char* fitted, float* w, osi_stream_t stream);
 int osi_openmax_recalibrate(const float* logits, const float* w, int N, int C, int alpha, float* probs, osi_stream_t stream);
+
+/* ABI 22. The Extreme Value Machine (Rudd, Jain, Scheirer, Boult, TPAMI 2018; openset_imagenet/evm.py): one Weibull distribution per
+ * training row, fitted to the row's nearest negatives; a greedy set cover keeps the rows of a class that explain the others (the
+ * extreme vectors); the score of a class for a query is the largest inclusion probability over the class's extreme vectors. The
+ * method is not part of the reference snapshot; this block is its definition, after libMR's FitLow as the authors' code uses it.
+ * Inputs are features[N][F] in fp32 and int64 labels gt[N]. A positive of class c is a row with gt == c; EVERY other row is a negative
+ * of c: other classes, negative labels, labels >= C. No floating-point atomics: every output is bit-identical from run to run. Every
+ * output is zeroed or written by the call; no allocation, no host synchronisation; workspace contents are never assumed (ws:
+ * osi_evm_workspace(R, N, F) bytes cover all five calls, 8-byte aligned, overwritten; 0 for non-positive arguments). OSI_ERR_ARG before
+ * any launch on a null pointer, a non-positive size, a short workspace or a bad enum / range.
+ *
+ * osi_evm_distances: dist[R][N], every row of a[R][F] against every row of b[N][F] (4-byte aligned). dot = the fp32 matrix-core product
+ *   a_i . b_j: a chain of fp32 fused multiply-adds (v_mfma_f32_32x32x2_f32) from 0 over K in steps of 32; inside a step the order is
+ *   k = 8q + e, 8q + 4 + e for q = 0..3, e = 0..3; K is zero-filled past F. The order is fixed: same bits from run to run, and the
+ *   same bits for a pair whatever R, N and the pair's position. naa, nbb = the squared row norms: fp64 sums in index order (every
+ *   product of two fp32 values is exact in fp64), one pre-pass into the workspace.
+ *   OSI_EVM_COSINE: (float)(1 - (double)dot / sqrt(naa * nbb)), the product rounded to fp64 before the root; NaN for a zero denominator.
+ *   OSI_EVM_EUCLIDEAN: t = (naa + nbb) - 2 * (double)dot in fp64, (float)sqrt(t < 0 ? 0 : t): a NaN passes the clamp.
+ *   NaN and Inf in the inputs propagate as these formulas say. R * N * 4, R * F * 4 or N * F * 4 >= 2^31 -> OSI_ERR_ARG (32-bit buffer
+ *   descriptors).
+ * osi_evm_fit_rows: one Weibull per row r of dist[R][ld], ld >= N. The candidates are y_j = -(multiplier * dist[r][j]), the product
+ *   rounded to fp32, over the columns j < N with gt[j] != cls and a finite y_j (a finite distance, and no overflow of the product);
+ *   -0 counts as +0. From here it is exactly the tail fit of osi_openmax_fit_tails applied to y: the min(T, candidates) largest y (the
+ *   nearest negatives; tail_count[r]), shift[r] = the smallest of them, x = y - shift[r] + 1 in fp64, the same likelihood equation with
+ *   x^k as exp(k ln x - k ln x_max), the same solver and step limits; a row with fewer than two candidates or a collapsed tail (equal
+ *   ends in fp32, or x_max == 1 in fp64) is unfitted: fitted[r] = 0, shape = scale = shift = 0. 2 <= T <= OSI_EVM_MAX_TAIL,
+ *   multiplier > 0 and finite (the paper's 0.5 is exact). flags2 = {candidates left out for a non-finite value, summed over the rows;
+ *   unfitted rows}. One workgroup per row; the result depends on the multiset of the row's candidates only (permuting the columns of
+ *   dist and gt together changes no bit). The workspace is not used.
+ * Inclusion probability: Psi_r(d) = 1 - exp(-(z / scale[r])^shape[r]) with y = -(multiplier * d) rounded to fp32 and
+ *   z = (double)y - shift[r] + 1, in fp64, rounded once to fp32; 0 when z <= 0 or row r is unfitted; NaN for a NaN d (fitted or not).
+ * osi_evm_set_cover: dpp[R][R] = the distances among one class's own rows. Row i covers row j when both are fitted and i == j or
+ *   Psi_i(dpp[i][j]) >= cover_threshold (the fp32 value against the fp32 threshold; a NaN covers nothing). U starts as the fitted
+ *   rows; every step picks the not yet picked fitted row that covers most rows of U, the lowest index on ties, and takes what it covers
+ *   out of U; it stops when U is empty. order[k] = the k-th pick, -1 from n_ev[0] on. Unfitted rows are never picked and never need
+ *   covering. R <= OSI_EVM_MAX_COVER_ROWS; the cover is a bit matrix in the workspace (R * ceil(R / 64) words) with one count per row
+ *   that each pick updates from the words it changed: a pick costs at most one pass over the matrix. Integer arithmetic only.
+ *   cover_threshold NaN -> OSI_ERR_ARG.
+ * osi_evm_probs: dist[M][ld] = the queries against the V extreme vectors, ld >= V; the extreme vectors are sorted by class and
+ *   ev_start[C + 1] holds the offsets (values outside [0, V] are clamped). probs[m][c] = the maximum of Psi_v(dist[m][v]) over
+ *   ev_start[c] <= v < ev_start[c + 1]: 0 for a class without any, NaN if any term is NaN (as torch.max). An entry with scale == 0
+ *   counts as unfitted. probs is [M][C] fp32. */
+enum { OSI_EVM_EUCLIDEAN = 0, OSI_EVM_COSINE = 1 };
+#define OSI_EVM_MAX_TAIL 4096
+#define OSI_EVM_MAX_COVER_ROWS 16384
+size_t osi_evm_workspace(int R, int N, int F);
+int osi_evm_distances(const float* a, int R, const float* b, int N, int F, int metric, float* dist, void* ws, size_t ws_bytes,
+                      osi_stream_t stream);
+int osi_evm_fit_rows(const float* dist, int R, int N, long long ld, const long long* gt, long long cls, int T, float multiplier,
+                     double* shape, double* scale, double* shift, unsigned char* fitted, long long* tail_count, long long* flags2,
+                     void* ws, size_t ws_bytes, osi_stream_t stream);
+int osi_evm_set_cover(const float* dpp, int R, const double* shape, const double* scale, const double* shift,
+                      const unsigned char* fitted, float multiplier, float cover_threshold, long long* order, long long* n_ev, void* ws,
+                      size_t ws_bytes, osi_stream_t stream);
+int osi_evm_probs(const float* dist, int M, int V, long long ld, const double* shape, const double* scale, const double* shift,
+                  const long long* ev_start, int C, float multiplier, float* probs, osi_stream_t stream);
 
 /* ---- optimizer + arena utilities (train.py:356-359 construction, train.py:127,139 zero_grad/step) --- */
 int osi_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,

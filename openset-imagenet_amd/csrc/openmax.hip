@@ -10,10 +10,11 @@
 //   tail fit      a row pass turns the eligible distances into order-preserving 32-bit keys; one workgroup per class selects the T
 //                 largest with a four-pass radix select over the key bytes, sorts them in LDS (bitonic), and solves the Weibull
 //                 likelihood equation by Newton steps kept inside a bracket. The sums run over the SORTED tail in a fixed tree, so the
-//                 fit depends on the multiset only.
+//                 fit depends on the multiset only. Select, sort and solver live in tail_fit.h, shared with evm.hip.
 //   w-scores      element-wise Weibull CDF in fp64.
 //   recalibrate   one wave per row: stable descending ranks by counting, the unknown activation, a softmax over C + 1 in fp64.
 #include "osi_common.h"
+#include "tail_fit.h"
 
 #include <limits.h>
 #include <math.h>
@@ -24,31 +25,20 @@ constexpr int NT = 256;
 constexpr int NW = NT / 64;
 constexpr int MAX_BLOCKS = 2048;            // grid cap of the grid-stride passes
 constexpr int RECAL_MAX_C = 2048;           // row ranking in LDS: 4 rows x C x (fp32 logit + 16-bit rank) = 48 KB at the cap
-constexpr int EXPAND_MAX = 1100;            // bracket doublings / halvings: more than the exponent range of fp64
-constexpr int SOLVE_MAX = 128;              // Newton / bisection steps inside a bracket of one binade (53 bisections exhaust it)
 
 inline int stride_blocks(long long n) {
     const long long b = (n + NT - 1) / NT;
     return (int)(b < 1 ? 1 : (b > MAX_BLOCKS ? MAX_BLOCKS : b));
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);      // a + b == b + a: every lane ends with the same bits
-    return v;
-}
+using osi_tail::wave_sum_d;
 __device__ __forceinline__ double wave_max_d(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
     return v;
 }
 
-// order-preserving key of a finite float (larger value = larger unsigned key) and back
-__device__ __forceinline__ unsigned fkey(float d) {
-    const unsigned b = __float_as_uint(d);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float funkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+using osi_tail::fkey;
 
 // ----------------------------------------------------------------------------------------------------------- class means
 // mark[i] = the class row i is correct for, -1 otherwise
@@ -231,172 +221,26 @@ __global__ __launch_bounds__(NT) void k_om_keys(const float* __restrict__ dist, 
     }
 }
 
-struct FitSums {
-    double s0, s1, s2;      // sum e, sum e l, sum e l^2 with e = exp(k (l - lmax))
-};
-
-// Fixed tree: per thread in index order of its strided elements, xor butterfly in the wave, the waves in order. Every thread
-// returns the same bits, so the solver's branches are uniform.
-__device__ __forceinline__ FitSums fit_sums(const double* __restrict__ lnx, int K, double k, double lmax, double (*red)[NW]) {
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-    for (int t = threadIdx.x; t < K; t += NT) {
-        const double l = lnx[t], e = exp(k * (l - lmax));
-        s0 += e;
-        s1 += e * l;
-        s2 += e * l * l;
-    }
-    s0 = wave_sum_d(s0); s1 = wave_sum_d(s1); s2 = wave_sum_d(s2);
-    __syncthreads();                                        // the previous call's readers are done with red
-    if ((threadIdx.x & 63) == 0) {
-        const int w = threadIdx.x >> 6;
-        red[0][w] = s0; red[1][w] = s1; red[2][w] = s2;
-    }
-    __syncthreads();
-    FitSums r = {red[0][0], red[1][0], red[2][0]};
-#pragma unroll
-    for (int w = 1; w < NW; ++w) { r.s0 += red[0][w]; r.s1 += red[1][w]; r.s2 += red[2][w]; }
-    return r;
-}
-
+// One workgroup per class; the select, the sort and the solver are tail_fit.h's, over the rows the key pass marked for the class.
 __global__ __launch_bounds__(NT) void k_om_fit(const unsigned* __restrict__ key, const int* __restrict__ mark, int N, int T,
                                               double* __restrict__ shape, double* __restrict__ scale, double* __restrict__ shift,
                                               unsigned char* __restrict__ fitted, long long* __restrict__ tail_count,
                                               long long* __restrict__ flags2) {
-    __shared__ unsigned keys[OSI_OPENMAX_MAX_TAIL];         // 16 KB
-    __shared__ double lnx[OSI_OPENMAX_MAX_TAIL];            // 32 KB
-    __shared__ unsigned hist[256];
-    __shared__ double red[3][NW];
-    __shared__ unsigned s_prefix, s_rem, s_K, s_cursor, s_bad;
-    const int c = blockIdx.x, tid = threadIdx.x;
-    if (tid == 0) { s_prefix = 0; s_rem = 0; s_K = 0; s_cursor = 0; s_bad = 0; }
-
-    // radix select of the K-th largest key, most significant byte first; the first pass also counts the class
-    unsigned mask = 0;
-    for (int p = 0; p < 4; ++p) {
-        const int sh = 24 - 8 * p;
-        hist[tid] = 0;                                      // NT == 256 bins
-        __syncthreads();
-        const unsigned prefix = s_prefix;
-        unsigned bad = 0;
-        for (long long i = tid; i < N; i += NT) {
-            const int mk = mark[i];
-            if (mk == c) {
-                const unsigned k = key[i];
-                if ((k & mask) == prefix) atomicAdd(&hist[(k >> sh) & 255u], 1u);
-            } else if (p == 0 && mk == -2 - c) {
-                ++bad;
-            }
-        }
-        if (p == 0 && bad) atomicAdd(&s_bad, bad);
-        __syncthreads();
-        if (tid == 0) {
-            unsigned rem = s_rem;
-            if (p == 0) {
-                unsigned n = 0;
-                for (int d = 0; d < 256; ++d) n += hist[d];
-                rem = n < (unsigned)T ? n : (unsigned)T;
-                s_K = rem;
-            }
-            if (rem) {
-                int d = 255;
-                for (; d > 0; --d) {
-                    if (hist[d] >= rem) break;
-                    rem -= hist[d];
-                }
-                s_prefix = prefix | ((unsigned)d << sh);
-            }
-            s_rem = rem;                                    // copies of the digit's keys still to take
-        }
-        mask |= 255u << sh;
-        __syncthreads();
-    }
-    const int K = (int)s_K;
-    const unsigned thr = s_prefix;
-    const int n_thr = (int)s_rem, n_gt = K - n_thr;         // the tail: every key above thr, and n_thr copies of thr
-    bool fit = K >= 2;
-    if (fit) {
-        for (long long i = tid; i < N; i += NT) {
-            if (mark[i] == c) {
-                const unsigned k = key[i];
-                if (k > thr) {
-                    const unsigned pos = atomicAdd(&s_cursor, 1u);
-                    if (pos < (unsigned)n_gt) keys[pos] = k;    // always true: n_gt was counted from the same keys
-                }
-            }
-        }
-        int P = 2;
-        while (P < K) P <<= 1;                              // <= 4096
-        __syncthreads();
-        for (int t = n_gt + tid; t < P; t += NT) keys[t] = t < K ? thr : 0xffffffffu;
-        __syncthreads();
-        for (int k2 = 2; k2 <= P; k2 <<= 1)                 // bitonic sort, ascending; the padding ends up behind the tail
-            for (int j = k2 >> 1; j > 0; j >>= 1) {
-                for (int t = tid; t < P; t += NT) {
-                    const int u = t ^ j;
-                    if (u > t) {
-                        const unsigned a = keys[t], b = keys[u];
-                        if ((a > b) == ((t & k2) == 0)) { keys[t] = b; keys[u] = a; }
-                    }
-                }
-                __syncthreads();
-            }
-        // equal ends, in fp32 or after the translation to x = d - shift + 1 in fp64 (distances below 2^-53): nothing to fit
-        fit = keys[0] != keys[K - 1] && (double)funkey(keys[K - 1]) - (double)funkey(keys[0]) + 1.0 > 1.0;
-    }
-    double k_out = 0.0, lam_out = 0.0, shift_out = 0.0;
-    if (fit) {                                              // uniform: keys[] is shared
-        const float dmin = funkey(keys[0]);
-        for (int t = tid; t < K; t += NT) lnx[t] = log((double)funkey(keys[t]) - (double)dmin + 1.0);
-        __syncthreads();
-        const double xmax = (double)funkey(keys[K - 1]) - (double)dmin + 1.0;
-        const double lmax = lnx[K - 1];
-        double ls = 0.0;
-        for (int t = tid; t < K; t += NT) ls += lnx[t];
-        ls = wave_sum_d(ls);
-        if ((tid & 63) == 0) red[0][tid >> 6] = ls;
-        __syncthreads();
-        double lmean = red[0][0];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) lmean += red[0][w];
-        lmean /= (double)K;
-        // g(k) = s1 / s0 - 1 / k - lmean, increasing; g < 0 near 0 and g -> lmax - lmean > 0
-        auto g_of = [&](double k, double& dg) {
-            const FitSums s = fit_sums(lnx, K, k, lmax, red);
-            const double m1 = s.s1 / s.s0;
-            dg = s.s2 / s.s0 - m1 * m1 + 1.0 / (k * k);
-            return m1 - 1.0 / k - lmean;
-        };
-        double lo = 1.0, hi = 1.0, dg;
-        double g = g_of(1.0, dg);
-        if (g < 0.0) {
-            for (int it = 0; it < EXPAND_MAX && g < 0.0; ++it) { lo = hi; hi *= 2.0; g = g_of(hi, dg); }
-        } else {
-            for (int it = 0; it < EXPAND_MAX && g >= 0.0; ++it) { hi = lo; lo *= 0.5; g = g_of(lo, dg); }
-        }
-        double k = 0.5 * (lo + hi);
-        for (int it = 0; it < SOLVE_MAX; ++it) {
-            g = g_of(k, dg);
-            if (g == 0.0) break;
-            if (g < 0.0) lo = k; else hi = k;
-            double kn = k - g / dg;
-            if (!(kn > lo && kn < hi)) kn = 0.5 * (lo + hi);
-            const double step = fabs(kn - k);
-            k = kn;
-            if (step <= 4.0e-16 * kn || !(hi > lo)) break;
-        }
-        const FitSums s = fit_sums(lnx, K, k, lmax, red);
-        k_out = k;
-        lam_out = xmax * exp(log(s.s0 / (double)K) / k);
-        shift_out = (double)dmin;
-    }
-    if (tid == 0) {
-        shape[c] = k_out;
-        scale[c] = lam_out;
-        shift[c] = shift_out;
-        fitted[c] = fit ? 1 : 0;
-        tail_count[c] = K;
-        if (s_bad) atomicAdd((unsigned long long*)&flags2[0], (unsigned long long)s_bad);     // integer atomics: order-free
-        if (!fit) atomicAdd((unsigned long long*)&flags2[1], 1ull);
+    __shared__ osi_tail::Shared sm;
+    const int c = blockIdx.x;
+    const osi_tail::Result r = osi_tail::tail_fit(sm, N, T, [&](long long i, unsigned& k) {
+        const int mk = mark[i];
+        if (mk == c) { k = key[i]; return 1; }
+        return mk == -2 - c ? 2 : 0;
+    });
+    if (threadIdx.x == 0) {
+        shape[c] = r.shape;
+        scale[c] = r.scale;
+        shift[c] = r.shift;
+        fitted[c] = r.fit ? 1 : 0;
+        tail_count[c] = r.K;
+        if (r.bad) atomicAdd((unsigned long long*)&flags2[0], (unsigned long long)r.bad);     // integer atomics: order-free
+        if (!r.fit) atomicAdd((unsigned long long*)&flags2[1], 1ull);
     }
 }
 

@@ -15,6 +15,7 @@
 //   torch.ops.osi.stage_canvas        train.py:259-263 after decode + resize (crop, flip, ToTensor, NHWC4)
 //   torch.ops.osi.softmax / confidence_accumulate    train.py:177, metrics.py:8-42
 //   torch.ops.osi.openmax_class_means / _distances / _fit_tails / _wscores / _recalibrate    OpenMax (openset_imagenet/openmax.py)
+//   torch.ops.osi.evm_distances / _fit_rows / _set_cover / _probs                            the Extreme Value Machine (openset_imagenet/evm.py)
 //
 // This file contains no arithmetic: every op validates its tensor arguments (device, dtype, contiguity, sizes), takes the CURRENT
 // HIP stream of the tensors' device inside the op, and forwards raw pointers to the C ABI of libosi_hip.so (include/osi.h), which
@@ -566,9 +567,89 @@ Tensor openmax_recalibrate(const Tensor& logits, const Tensor& w, int64_t alpha)
     return probs;
 }
 
+// ---- Extreme Value Machine (include/osi.h, ABI 22): every op allocates its outputs and leaves them on the device
+Tensor evm_distances(const Tensor& a, const Tensor& b, int64_t metric, Tensor workspace) {
+    need(a, at::kFloat, "a", NATURAL); need(b, at::kFloat, "b", NATURAL); need(workspace, at::kByte, "workspace", 8);
+    TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && a.size(1) == b.size(1) && a.device() == b.device() && workspace.device() == a.device(),
+                "osi::evm_distances: a [R,F] and b [N,F] on one device");
+    TORCH_CHECK(a.size(0) <= INT_MAX && b.size(0) <= INT_MAX && a.size(1) <= INT_MAX, "osi::evm_distances: sizes out of range");
+    const int R = (int)a.size(0), N = (int)b.size(0), F = (int)a.size(1);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(a.device());
+    Tensor dist = at::empty({R, N}, a.options());
+    ok(osi_evm_distances(a.data_ptr<float>(), R, b.data_ptr<float>(), N, F, (int)metric, dist.data_ptr<float>(), workspace.data_ptr(),
+                         (size_t)workspace.numel(), stream_of(a)), "osi_evm_distances");
+    return dist;
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> evm_fit_rows(const Tensor& dist, const Tensor& gt, int64_t cls, int64_t tailsize,
+                                                                        double multiplier, Tensor workspace) {
+    need(dist, at::kFloat, "dist", NATURAL); need(gt, at::kLong, "gt", NATURAL); need(workspace, at::kByte, "workspace", 8);
+    TORCH_CHECK(dist.dim() == 2 && gt.dim() == 1 && gt.size(0) <= dist.size(1) && gt.device() == dist.device() &&
+                workspace.device() == dist.device(), "osi::evm_fit_rows: dist [R,ld] and gt [N], N <= ld, on one device");
+    TORCH_CHECK(dist.size(0) <= INT_MAX && gt.size(0) <= INT_MAX, "osi::evm_fit_rows: sizes out of range");
+    const int64_t R = dist.size(0);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dist.device());
+    const auto f64 = dist.options().dtype(at::kDouble), i64 = dist.options().dtype(at::kLong);
+    Tensor shape = at::empty({R}, f64), scale = at::empty({R}, f64), shift = at::empty({R}, f64);
+    Tensor fitted = at::empty({R}, dist.options().dtype(at::kByte)), tail_count = at::empty({R}, i64), flags2 = at::empty({2}, i64);
+    ok(osi_evm_fit_rows(dist.data_ptr<float>(), (int)R, (int)gt.size(0), (long long)dist.size(1), (const long long*)gt.data_ptr<int64_t>(),
+                        (long long)cls, (int)std::min<int64_t>(tailsize, INT_MAX), (float)multiplier, shape.data_ptr<double>(),
+                        scale.data_ptr<double>(), shift.data_ptr<double>(), fitted.data_ptr<unsigned char>(),
+                        (long long*)tail_count.data_ptr<int64_t>(), (long long*)flags2.data_ptr<int64_t>(), workspace.data_ptr(),
+                        (size_t)workspace.numel(), stream_of(dist)), "osi_evm_fit_rows");
+    return {shape, scale, shift, fitted, tail_count, flags2};
+}
+
+void evm_params(const Tensor& ref, const Tensor& shape, const Tensor& scale, const Tensor& shift, int64_t n, const char* what) {
+    need(shape, at::kDouble, "shape", NATURAL); need(scale, at::kDouble, "scale", NATURAL); need(shift, at::kDouble, "shift", NATURAL);
+    TORCH_CHECK(shape.numel() == n && scale.numel() == n && shift.numel() == n, "osi::", what, ": shape, scale and shift hold ", n, " entries");
+    TORCH_CHECK(shape.device() == ref.device() && scale.device() == ref.device() && shift.device() == ref.device(), "osi::", what,
+                ": tensors on different devices");
+}
+
+std::tuple<Tensor, Tensor> evm_set_cover(const Tensor& dpp, const Tensor& shape, const Tensor& scale, const Tensor& shift,
+                                         const Tensor& fitted, double multiplier, double cover_threshold, Tensor workspace) {
+    need(dpp, at::kFloat, "dpp", NATURAL); need(fitted, at::kByte, "fitted", 1); need(workspace, at::kByte, "workspace", 8);
+    TORCH_CHECK(dpp.dim() == 2 && dpp.size(0) == dpp.size(1) && dpp.size(0) <= INT_MAX, "osi::evm_set_cover: dpp is [R,R]");
+    const int64_t R = dpp.size(0);
+    evm_params(dpp, shape, scale, shift, R, "evm_set_cover");
+    TORCH_CHECK(fitted.numel() == R && fitted.device() == dpp.device() && workspace.device() == dpp.device(),
+                "osi::evm_set_cover: fitted holds one entry per row, on the device of dpp");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dpp.device());
+    const auto i64 = dpp.options().dtype(at::kLong);
+    Tensor order = at::empty({R}, i64), n_ev = at::empty({1}, i64);
+    ok(osi_evm_set_cover(dpp.data_ptr<float>(), (int)R, shape.data_ptr<double>(), scale.data_ptr<double>(), shift.data_ptr<double>(),
+                         fitted.data_ptr<unsigned char>(), (float)multiplier, (float)cover_threshold, (long long*)order.data_ptr<int64_t>(),
+                         (long long*)n_ev.data_ptr<int64_t>(), workspace.data_ptr(), (size_t)workspace.numel(), stream_of(dpp)),
+       "osi_evm_set_cover");
+    return {order, n_ev};
+}
+
+Tensor evm_probs(const Tensor& dist, const Tensor& shape, const Tensor& scale, const Tensor& shift, const Tensor& ev_start,
+                 double multiplier) {
+    need(dist, at::kFloat, "dist", NATURAL); need(ev_start, at::kLong, "ev_start", NATURAL);
+    TORCH_CHECK(dist.dim() == 2 && ev_start.dim() == 1 && ev_start.numel() >= 2 && ev_start.device() == dist.device(),
+                "osi::evm_probs: dist is [M,ld], ev_start [C+1] on its device");
+    const int64_t V = shape.numel(), C = ev_start.numel() - 1;
+    evm_params(dist, shape, scale, shift, V, "evm_probs");
+    TORCH_CHECK(V <= dist.size(1) && dist.size(0) <= INT_MAX && V <= INT_MAX && C <= INT_MAX, "osi::evm_probs: V <= ld, sizes in range");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dist.device());
+    Tensor probs = at::empty({dist.size(0), C}, dist.options());
+    ok(osi_evm_probs(dist.data_ptr<float>(), (int)dist.size(0), (int)V, (long long)dist.size(1), shape.data_ptr<double>(),
+                     scale.data_ptr<double>(), shift.data_ptr<double>(), (const long long*)ev_start.data_ptr<int64_t>(), (int)C,
+                     (float)multiplier, probs.data_ptr<float>(), stream_of(dist)), "osi_evm_probs");
+    return probs;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(osi, m) {
+    m.def("evm_distances(Tensor a, Tensor b, int metric, Tensor(a!) workspace) -> Tensor");
+    m.def("evm_fit_rows(Tensor dist, Tensor gt, int cls, int tailsize, float multiplier, Tensor(a!) workspace) -> "
+          "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("evm_set_cover(Tensor dpp, Tensor shape, Tensor scale, Tensor shift, Tensor fitted, float multiplier, float cover_threshold, "
+          "Tensor(a!) workspace) -> (Tensor, Tensor)");
+    m.def("evm_probs(Tensor dist, Tensor shape, Tensor scale, Tensor shift, Tensor ev_start, float multiplier) -> Tensor");
     m.def("openmax_class_means(Tensor features, Tensor logits, Tensor gt, Tensor(a!) workspace) -> (Tensor, Tensor, Tensor)");
     m.def("openmax_distances(Tensor features, Tensor mav, Tensor? cls, int metric) -> Tensor");
     m.def("openmax_fit_tails(Tensor dist, Tensor gt, Tensor correct, int C, int tailsize, Tensor(a!) workspace) -> "
@@ -639,4 +720,8 @@ TORCH_LIBRARY_IMPL(osi, CUDA, m) {
     m.impl("openmax_fit_tails", &openmax_fit_tails);
     m.impl("openmax_wscores", &openmax_wscores);
     m.impl("openmax_recalibrate", &openmax_recalibrate);
+    m.impl("evm_distances", &evm_distances);
+    m.impl("evm_fit_rows", &evm_fit_rows);
+    m.impl("evm_set_cover", &evm_set_cover);
+    m.impl("evm_probs", &evm_probs);
 }

@@ -11,10 +11,12 @@ from . import dataset, losses, metrics, train
 from . import averaging
 from . import openmax
 from .openmax import OpenMax
+from . import evm
+from .evm import EVM
 from .losses import (AverageMeter, EarlyStopping, EntropicOpensetLoss, GarbageLoss, ObjectosphereLoss, SoftmaxLoss)
 from .model import ResNet50
 from .dataset import ImagenetDataset
 from .pipeline import CanvasDataset
 
 __all__ = ["ResNet50", "ImagenetDataset", "CanvasDataset", "EntropicOpensetLoss", "SoftmaxLoss", "GarbageLoss", "ObjectosphereLoss", "AverageMeter",
-           "EarlyStopping", "OpenMax", "tools", "util", "train", "metrics", "losses", "dataset"]
+           "EarlyStopping", "OpenMax", "EVM", "tools", "util", "train", "metrics", "losses", "dataset"]

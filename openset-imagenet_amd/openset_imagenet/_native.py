@@ -96,6 +96,9 @@ EVAL_SCORE, EVAL_NORM = 0, 1
 HIST_MAX_BINS = 4096
 OPENMAX_EUCLIDEAN, OPENMAX_COSINE = 0, 1
 OPENMAX_MAX_TAIL = 4096
+EVM_EUCLIDEAN, EVM_COSINE = 0, 1
+EVM_MAX_TAIL = 4096
+EVM_MAX_COVER_ROWS = 16384
 
 P = c_void_p
 _PD = POINTER(ConvDesc)
@@ -194,6 +197,11 @@ _SIGS = {
     "osi_openmax_fit_tails": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, P, P, P, P, c_size_t, P]),
     "osi_openmax_wscores": (c_int, [P, c_int, c_int, P, P, P, P, P, P]),
     "osi_openmax_recalibrate": (c_int, [P, P, c_int, c_int, c_int, P, P]),
+    "osi_evm_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "osi_evm_distances": (c_int, [P, c_int, P, c_int, c_int, c_int, P, P, c_size_t, P]),
+    "osi_evm_fit_rows": (c_int, [P, c_int, c_int, c_longlong, P, c_longlong, c_int, c_float, P, P, P, P, P, P, P, c_size_t, P]),
+    "osi_evm_set_cover": (c_int, [P, c_int, P, P, P, P, c_float, c_float, P, P, P, c_size_t, P]),
+    "osi_evm_probs": (c_int, [P, c_int, c_int, c_longlong, P, P, P, P, c_int, c_float, P, P]),
     "osi_adam_step": (c_int, [P, P, P, P, c_size_t, c_double, c_double, c_double, c_double, c_longlong, c_float, P]),
     "osi_sgd_step": (c_int, [P, P, P, c_size_t, c_float, c_float, c_int, c_float, P]),
     "osi_adam_step_groups": (c_int, [P, P, P, P, P, c_size_t, POINTER(OptSegment), c_int, POINTER(AdamGroup), c_int, c_float, P]),

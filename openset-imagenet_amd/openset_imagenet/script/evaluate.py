@@ -8,7 +8,10 @@ the confidences, the CCR at FPR 1e-3 / 1e-2 / 0.1 / 1 and the 30-bin score and f
 prints the row of the reference's table (script/plot_all.py:344-385). `--openmax TAILSIZE` (likewise; softmax and entropic losses)
 fits OpenMax (openmax.OpenMax) on the arrays of the training split, saves it as `{loss}_openmax{suffix}.pth` and writes, next to each
 split's .npz, `{loss}_{split}_arr{suffix}_openmax.npz` with `gt`, `logits`, `features`, `scores` (the recalibrated class
-probabilities) and `unknown` (the probability of the unknown class); with `--oscr` the same OSCR line is printed for those scores."""
+probabilities) and `unknown` (the probability of the unknown class); with `--oscr` the same OSCR line is printed for those scores.
+`--evm TAILSIZE` (likewise; softmax and entropic losses) fits the Extreme Value Machine (evm.EVM; `--evm-cover`, `--evm-multiplier`,
+`--evm-distance`) on the features of the training split, saves it as `{loss}_evm{suffix}.pth` and writes
+`{loss}_{split}_arr{suffix}_evm.npz` with `gt`, `logits`, `features` and `scores` (the per-class inclusion probabilities)."""
 import argparse
 import json
 import pathlib
@@ -42,9 +45,17 @@ def get_args(command_line_options=None):
                    "split (softmax and entropic losses) and write {loss}_{split}_arr{suffix}_openmax.npz with the recalibrated scores")
     p.add_argument("--openmax-alpha", type=int, default=3, help="OpenMax: how many top-ranked logits are recalibrated")
     p.add_argument("--openmax-distance", choices=["euclidean", "cosine"], default="euclidean", help="OpenMax: distance to the class means")
+    p.add_argument("--evm", type=int, default=None, metavar="TAILSIZE", help="also fit the Extreme Value Machine with this tail size on the "
+                   "training split (softmax and entropic losses) and write {loss}_{split}_arr{suffix}_evm.npz with its class scores")
+    p.add_argument("--evm-cover", type=float, default=None, metavar="THRESHOLD", help="EVM: reduce every class to the extreme vectors of a "
+                   "greedy set cover at this inclusion probability (default: keep every fitted row)")
+    p.add_argument("--evm-multiplier", type=float, default=0.5, help="EVM: the factor on the distances before the Weibull fit")
+    p.add_argument("--evm-distance", choices=["euclidean", "cosine"], default="cosine", help="EVM: distance between feature rows")
     args = p.parse_args(command_line_options)
     if args.openmax is not None and args.loss == "garbage":
         p.error("--openmax needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
+    if args.evm is not None and args.loss == "garbage":
+        p.error("--evm needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
     try:
         args.output_directory = str(args.output_directory).format(args.protocol)
     except Exception:
@@ -142,6 +153,22 @@ def openmax_arrays(train_arrays, split_arrays, tailsize, alpha, distance):
                     scores=probs[:, :c], unknown=probs[:, c])
 
 
+def evm_arrays(train_arrays, split_arrays, tailsize, cover_threshold=None, multiplier=0.5, distance="cosine"):
+    """`--evm` on arrays: fit the Extreme Value Machine on the training split's `gt` and `features` (mappings as get_arrays' .npz holds
+    them; an already fitted evm.EVM is taken as it is) and score one split. Returns (evm, arrays): arrays holds the numpy `gt`,
+    `logits`, `features` of the split and `scores` = the [M, C] inclusion probabilities."""
+    from ..evm import EVM
+    if isinstance(train_arrays, EVM):
+        evm = train_arrays
+    else:
+        evm = EVM(tailsize=tailsize, cover_threshold=cover_threshold, distance_multiplier=multiplier, distance=distance)
+        evm.fit(train_arrays["features"], train_arrays["gt"])
+    scores = evm.predict(split_arrays["features"]).cpu().numpy()
+    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    return evm, dict(gt=host(split_arrays["gt"]), logits=host(split_arrays["logits"]), features=host(split_arrays["features"]),
+                     scores=scores)
+
+
 def averaged_module(model, checkpoint):
     """`--averaged`: the module of the checkpoint's "avg_state_dict" (averaging.AveragedModel over `model`'s geometry); exits with a
     clear message when the checkpoint was written without an `avg` block."""
@@ -177,14 +204,26 @@ def main(command_line_options=None):
         suffix += "_avg"
     tools.device(model)
     written = {}
-    om = None
+    om = evm = None
     if args.openmax is not None:
         from ..openmax import OpenMax
         om = OpenMax(tailsize=args.openmax, distance=args.openmax_distance, alpha=args.openmax_alpha)    # refuses bad options first
+    if args.evm is not None:
+        from ..evm import EVM
+        evm = EVM(tailsize=args.evm, cover_threshold=args.evm_cover, distance_multiplier=args.evm_multiplier, distance=args.evm_distance)
+    if om is not None or evm is not None:
         train_ds = _image_loader(args.protocol_directory / f"p{args.protocol}_train.csv", args.imagenet_directory, False, "eval")
         print(f"train dataset len:{len(train_ds)}, labels:{train_ds.table.label_count}")
         loader = torch.utils.data.DataLoader(train_ds, batch_size=args.batch_size, num_workers=args.workers)
         t_gt, t_logits, t_features, _ = get_arrays(model=model, loader=loader)
+    if evm is not None:
+        evm.fit(t_features, t_gt)
+        evm_path = args.output_directory / f"{args.loss}_evm{suffix}.pth"
+        torch.save(evm.state_dict(), evm_path)
+        left_out, unfitted = evm.flags.tolist()
+        print(f"EVM (tail {args.evm}, cover {args.evm_cover}, multiplier {args.evm_multiplier}, {args.evm_distance}) keeps "
+              f"{evm.ev_features.shape[0]} extreme vectors, {unfitted} rows unfitted, {left_out} distances not finite; saved in: {evm_path}")
+    if om is not None:
         om.fit(t_features, t_logits, t_gt)
         om_path = args.output_directory / f"{args.loss}_openmax{suffix}.pth"
         torch.save(om.state_dict(), om_path)
@@ -211,6 +250,15 @@ def main(command_line_options=None):
             written[split + "_openmax"] = om_file
             if args.oscr:
                 for line in oscr_lines(split, gt, arrays["scores"], tag="OpenMax "):
+                    print(line)
+        if evm is not None:
+            _, arrays = evm_arrays(evm, dict(gt=gt, logits=logits, features=features), args.evm)
+            evm_file = args.output_directory / f"{args.loss}_{split}_arr{suffix}_evm.npz"
+            np.savez(evm_file, **arrays)
+            print(f"EVM scores saved in: {evm_file}")
+            written[split + "_evm"] = evm_file
+            if args.oscr:
+                for line in oscr_lines(split, gt, arrays["scores"], tag="EVM "):
                     print(line)
         if args.auc:
             for unk in (-1, -2):
