@@ -610,6 +610,47 @@ int osi_evm_set_cover(const float* dpp, int R, const double* shape, const double
 int osi_evm_probs(const float* dist, int M, int V, long long ld, const double* shape, const double* scale, const double* shift,
                   const long long* ev_start, int C, float multiplier, float* probs, osi_stream_t stream);
 
+/* ABI 23. PROSER (Zhou, Ye, Zhan, "Learning Placeholders for Open-Set Recognition", CVPR 2021; openset_imagenet/proser.py): a short
+ * fine-tuning stage from a closed-set checkpoint that mixes activations in the middle of the network (manifold mixup), adds a small
+ * "dummy" classifier on the deep features and trains both with a three-term cross-entropy. The method is not part of the reference
+ * snapshot; this block is its definition, tests/proser_oracle.py its fp64 restatement. No floating-point atomics, fixed summation
+ * orders: every output is bit-identical from run to run. Nothing is allocated or synchronised (graph-capturable).
+ *
+ * osi_mix_rows_pairs: x is [B][L] fp32, mixed IN PLACE; partner and weight are device arrays of B entries. Row i with j = partner[i]:
+ *   j == i, j < 0 or j >= B: the row is neither read nor written (every bit stays, NaN payloads included), and no access leaves the
+ *   buffer whatever the arrays hold. j > i: row i OWNS the pair and its workgroups write both rows,
+ *     x_i' = fmaf(w_i, x_i, (1 - w_i) * x_j)      x_j' = fmaf(w_j, x_j, (1 - w_j) * x_i)
+ *   both from the old values of both rows; 1 - w is rounded once to fp32, its product is rounded once, then the fma (explicit: no
+ *   contraction setting changes the bits). w = 1 gives the row back and w = 0 gives the partner's row, both exactly for finite
+ *   values. j < i: the row is written by its owner. The callers pass an involution (partner[partner[i]] == i), for which this is the
+ *   pairwise mix; the launch serves the first floor(B / 2) owners in row order, which is every pair of an involution (another table
+ *   stays in range, but its rows may be written from values another pair has already replaced). One lane reads its 16-byte unit of
+ *   both rows and writes both: each element is read once and written once, no staging buffer. The grid is sized to the pairs: a
+ *   pair's workgroups walk the row in tiles of 1024 units, at most 8192 workgroups in all; the row decisions are wave-uniform.
+ *   OSI_ERR_ARG before any launch: a null pointer, B <= 0, L == 0, L % 4 != 0, x not 16-byte aligned.
+ * osi_proser_loss_fwd_bwd: logits[B][C], dummy[B][D] (D >= 1), int64 target[B]; rows [0, n_mixed) are the mixed rows. Per row a = the
+ *   first index of the largest dummy logit (a NaN counts as largest, as torch.max), m = dummy[a], e = [logits, m] with C + 1 columns.
+ *     mixed row (whatever its label):        t1 = lse(e) - m
+ *     clean row (i >= n_mixed), 0 <= y < C:  t2 = lse(e) - e_y,  t3 = lse(e without column y) - m
+ *   (the published implementations set e_y = -1e9 for t3; leaving the column out is the same in fp32 and is the definition here). A
+ *   clean row with a label outside [0, C) has no term, is not counted and gets exact zero gradient rows.
+ *   J = l0 * mean(t1) + l1 * mean(t2) + l2 * mean(t3), each mean over its n1 = n_mixed / n2 counting rows; a term without rows is
+ *   exactly 0 and so are its gradients. loss4 = {J, mean t1, mean t2, mean t3}. With s = softmax(e) and s' = the softmax without
+ *   column y (s'_y = 0): g = l0 / n1 * (s - onehot(C)) for a mixed row, g = l1 / n2 * (s - onehot(y)) + l2 / n2 * (s' - onehot(C))
+ *   for a clean one; dlogits = g[:C], ddummy[a] = g[C], the other D - 1 entries of the ddummy row exact zeros. dlogits and ddummy may
+ *   both be NULL (loss only; one of them NULL: OSI_ERR_ARG). One launch in the form of osi_loss_fwd_bwd: one workgroup for the batch,
+ *   a wave per row; a first sweep over the labels alone gives n2, one sweep over the rows gives every term and finished gradient
+ *   row. A row's term is evaluated as (max - v) + log(sum exp(e - max)) and its softmax as exp(e - max) / sum, so a large common
+ *   magnitude of the logits costs no digits. Sums: fp32 in a row (lanes stride the columns, the butterfly of the wave, then the
+ *   dummy column), double over the rows (per wave in row order, then the waves in index order). A NaN logit in a counting row gives a NaN loss and a NaN gradient row, as in
+ *   torch. B <= 15360, 0 <= n_mixed <= B, C >= 1: OSI_ERR_ARG otherwise.
+ * osi_proser_scores: probs[B][C + 1] = softmax([logits, max_d dummy + bias]) per row, the unknown class in the LAST column (the layout
+ *   of osi_openmax_recalibrate); a NaN propagates through the maximum. */
+int osi_mix_rows_pairs(float* x, const int* partner, const float* weight, int B, size_t L, osi_stream_t stream);
+int osi_proser_loss_fwd_bwd(const float* logits, const float* dummy, const long long* target, int B, int C, int D, int n_mixed, float l0,
+                            float l1, float l2, float* loss4, float* dlogits, float* ddummy, osi_stream_t stream);
+int osi_proser_scores(const float* logits, const float* dummy, float bias, int B, int C, int D, float* probs, osi_stream_t stream);
+
 /* ---- optimizer + arena utilities (train.py:356-359 construction, train.py:127,139 zero_grad/step) --- */
 int osi_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,
                   double beta2, double eps, long long step, float grad_scale, osi_stream_t stream);
@@ -854,6 +895,20 @@ int osi_resnet50_get_trainable(osi_resnet50_t net, unsigned* unit_mask, int* eva
 int osi_resnet50_set_bn_momentum(osi_resnet50_t net, float momentum);
 int osi_resnet50_get_bn_momentum(osi_resnet50_t net, float* momentum);
 
+/* ABI 23. Manifold mixup at the frozen cut (PROSER). osi_resnet50_set_mix is a ONE-SHOT request for the next differentiable forward
+ * (osi_resnet50_forward(training = 1) or osi_resnet50_forward_frozen): partner / weight are device arrays of B entries as
+ * osi_mix_rows_pairs takes them and must stay valid until that forward's launches are enqueued; both NULL clears the request (one
+ * NULL: OSI_ERR_ARG). With the request pending and eval_prefix_units = p in 1 .. 16 (osi_resnet50_set_trainable) the forward launches
+ * osi_mix_rows_pairs on the input of unit p — [B][H * W * C] in the workspace, written by unit p - 1 (the stem's pool for p = 1) —
+ * after unit p - 1 has written it and before anything of unit p reads it: conv1, the projection shortcut (the side stream forks
+ * after the launch) and the residual add of an identity block. The weight gradients of conv1 and the shortcut in the backward read
+ * the same tensor and therefore see the mixed input, which is the correct gradient. The prefix below the cut is frozen, the backward
+ * ends at the cut, no gradient ever crosses the mix: it has no backward. p outside 1 .. 16: the forward returns OSI_ERR_STATE, launches
+ * nothing and leaves the request pending. An inference forward ignores the request and leaves it pending; the differentiable forward
+ * that runs it consumes it. After a forward with a mix a backward with dimage / x_adv returns OSI_ERR_STATE (the rule of every forward
+ * with an inference-form prefix). Without a request every entry point issues the launches of ABI 22. */
+int osi_resnet50_set_mix(osi_resnet50_t net, const int* partner, const float* weight);
+
 /* Per-executor switches: "overlap" (default 1: weight gradients on a low-priority side stream, overlapped with dgrad / BatchNorm
  * backward and joined back into `stream` at the end of every backward call unless "stage_join" = 0; 0 serialises everything on the
  * caller's stream), "fwd_fork" (projection shortcut of the forward pass on the side stream, default 1), "side_priority_normal" (side
@@ -891,6 +946,11 @@ int osi_resnet50_debug_num_gates(osi_resnet50_t net);
 int osi_resnet50_debug_gate_shape(osi_resnet50_t net, int i, int* C, int* H, int* W);
 int osi_resnet50_debug_gate(osi_resnet50_t net, void* workspace, int i, unsigned char* gate_nchw, int* pool_argmax_nchw,
                             osi_stream_t stream);
+/* ABI 23. The input tensor of block unit 1 .. 16 as the latest forward of any kind left it in `workspace` (what that unit's conv1
+ * consumed: the mixed tensor after a forward with osi_resnet50_set_mix): [B][H][W][C] fp32, copied to out_nhwc (device memory) on
+ * `stream`; *floats = B * H * W * C. out_nhwc = NULL only reports the size (workspace may then be NULL too). OSI_ERR_ARG on a unit
+ * outside 1 .. 16 or floats == NULL; OSI_ERR_STATE for a copy before any forward. */
+int osi_resnet50_debug_unit_input(osi_resnet50_t net, void* workspace, int unit, float* out_nhwc, size_t* floats, osi_stream_t stream);
 
 #ifdef __cplusplus
 }

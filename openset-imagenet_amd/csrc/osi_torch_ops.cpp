@@ -16,6 +16,7 @@
 //   torch.ops.osi.softmax / confidence_accumulate    train.py:177, metrics.py:8-42
 //   torch.ops.osi.openmax_class_means / _distances / _fit_tails / _wscores / _recalibrate    OpenMax (openset_imagenet/openmax.py)
 //   torch.ops.osi.evm_distances / _fit_rows / _set_cover / _probs                            the Extreme Value Machine (openset_imagenet/evm.py)
+//   torch.ops.osi.mix_rows_pairs / resnet50_set_mix / proser_loss_fwd_bwd / proser_scores / linear_fwd / linear_bwd    PROSER (openset_imagenet/proser.py)
 //
 // This file contains no arithmetic: every op validates its tensor arguments (device, dtype, contiguity, sizes), takes the CURRENT
 // HIP stream of the tensors' device inside the op, and forwards raw pointers to the C ABI of libosi_hip.so (include/osi.h), which
@@ -641,9 +642,111 @@ Tensor evm_probs(const Tensor& dist, const Tensor& shape, const Tensor& scale, c
     return probs;
 }
 
+// ---- PROSER (include/osi.h, ABI 23)
+void need_pairs(const Tensor& ref, const Tensor& partner, const Tensor& weight, int64_t B, const char* what) {
+    need(partner, at::kInt, "partner", NATURAL); need(weight, at::kFloat, "weight", NATURAL);
+    TORCH_CHECK(partner.numel() == B && weight.numel() == B, "osi::", what, ": partner and weight hold one entry per row (", B, ")");
+    TORCH_CHECK(partner.device() == ref.device() && weight.device() == ref.device(), "osi::", what, ": tensors on different devices");
+}
+
+void mix_rows_pairs(Tensor x, const Tensor& partner, const Tensor& weight) {
+    need(x, at::kFloat, "x");
+    TORCH_CHECK(x.dim() >= 2 && x.size(0) <= INT_MAX && x.numel() > 0, "osi::mix_rows_pairs: x is [B, ...] with at least one element");
+    const int64_t B = x.size(0), L = x.numel() / B;
+    TORCH_CHECK(L % 4 == 0, "osi::mix_rows_pairs: the row length must be a multiple of 4, got ", L);
+    need_pairs(x, partner, weight, B, "mix_rows_pairs");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+    ok(osi_mix_rows_pairs(x.data_ptr<float>(), partner.data_ptr<int>(), weight.data_ptr<float>(), (int)B, (size_t)L, stream_of(x)),
+       "osi_mix_rows_pairs");
+}
+
+// the one-shot request of the executor's next differentiable forward; both tensors absent clears it. The caller keeps them alive until
+// that forward has been enqueued (model.py holds them)
+void resnet50_set_mix(int64_t net, const std::optional<Tensor>& partner, const std::optional<Tensor>& weight) {
+    osi_resnet50_t h = handle(net);
+    const bool hp = partner.has_value() && partner->defined(), hw = weight.has_value() && weight->defined();
+    TORCH_CHECK(hp == hw, "osi::resnet50_set_mix: partner and weight go together");
+    if (!hp) { ok(osi_resnet50_set_mix(h, nullptr, nullptr), "osi_resnet50_set_mix"); return; }
+    int B = 0;
+    ok(osi_resnet50_geometry(h, &B, nullptr, nullptr), "osi_resnet50_geometry");
+    need_pairs(*partner, *partner, *weight, B, "resnet50_set_mix");
+    ok(osi_resnet50_set_mix(h, partner->data_ptr<int>(), weight->data_ptr<float>()), "osi_resnet50_set_mix");
+}
+
+// returns (loss4 [4] = {J, mean t1, mean t2, mean t3}, dlogits [B,C] or empty, ddummy [B,D] or empty)
+std::tuple<Tensor, Tensor, Tensor> proser_loss_fwd_bwd(const Tensor& logits, const Tensor& dummy, const Tensor& target, int64_t n_mixed,
+                                                       double l0, double l1, double l2, bool need_grad) {
+    need(logits, at::kFloat, "logits", NATURAL); need(dummy, at::kFloat, "dummy", NATURAL); need(target, at::kLong, "target", NATURAL);
+    TORCH_CHECK(logits.dim() == 2 && dummy.dim() == 2 && target.dim() == 1 && dummy.size(0) == logits.size(0) &&
+                target.size(0) == logits.size(0), "osi::proser_loss_fwd_bwd: expected logits [B, C], dummy [B, D] and target [B]");
+    TORCH_CHECK(dummy.device() == logits.device() && target.device() == logits.device(), "osi::proser_loss_fwd_bwd: tensors on different devices");
+    TORCH_CHECK(logits.size(0) <= INT_MAX && logits.size(1) <= INT_MAX && dummy.size(1) <= INT_MAX && n_mixed >= 0 && n_mixed <= logits.size(0),
+                "osi::proser_loss_fwd_bwd: sizes out of range or n_mixed outside [0, B]");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(logits.device());
+    Tensor loss4 = at::empty({4}, logits.options());
+    Tensor dlogits = need_grad ? at::empty_like(logits) : at::empty({0}, logits.options());
+    Tensor ddummy = need_grad ? at::empty_like(dummy) : at::empty({0}, logits.options());
+    ok(osi_proser_loss_fwd_bwd(logits.data_ptr<float>(), dummy.data_ptr<float>(), (const long long*)target.data_ptr<int64_t>(),
+                               (int)logits.size(0), (int)logits.size(1), (int)dummy.size(1), (int)n_mixed, (float)l0, (float)l1, (float)l2,
+                               loss4.data_ptr<float>(), need_grad ? dlogits.data_ptr<float>() : nullptr,
+                               need_grad ? ddummy.data_ptr<float>() : nullptr, stream_of(logits)), "osi_proser_loss_fwd_bwd");
+    return {loss4, dlogits, ddummy};
+}
+
+Tensor proser_scores(const Tensor& logits, const Tensor& dummy, double bias) {
+    need(logits, at::kFloat, "logits", NATURAL); need(dummy, at::kFloat, "dummy", NATURAL);
+    TORCH_CHECK(logits.dim() == 2 && dummy.dim() == 2 && dummy.size(0) == logits.size(0) && dummy.device() == logits.device(),
+                "osi::proser_scores: expected logits [B, C] and dummy [B, D] on one device");
+    TORCH_CHECK(logits.size(0) <= INT_MAX && logits.size(1) < INT_MAX && dummy.size(1) <= INT_MAX, "osi::proser_scores: sizes out of range");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(logits.device());
+    Tensor probs = at::empty({logits.size(0), logits.size(1) + 1}, logits.options());
+    ok(osi_proser_scores(logits.data_ptr<float>(), dummy.data_ptr<float>(), (float)bias, (int)logits.size(0), (int)logits.size(1),
+                         (int)dummy.size(1), probs.data_ptr<float>(), stream_of(logits)), "osi_proser_scores");
+    return probs;
+}
+
+// the small dense layer of the package's own kernels (csrc/linear.hip) for layers outside the executor: y = x w^T + bias
+Tensor linear_fwd(const Tensor& x, const Tensor& w, const std::optional<Tensor>& bias) {
+    need(x, at::kFloat, "x", NATURAL); need(w, at::kFloat, "w", NATURAL);
+    TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1) && w.device() == x.device(), "osi::linear_fwd: x [B, K] and w [O, K] on one device");
+    const bool hb = bias.has_value() && bias->defined();
+    if (hb) { need(*bias, at::kFloat, "bias", NATURAL); TORCH_CHECK(bias->numel() == w.size(0) && bias->device() == x.device(), "osi::linear_fwd: bias holds O entries"); }
+    TORCH_CHECK(x.size(1) <= INT_MAX, "osi::linear_fwd: sizes out of range");
+    // the 16-byte loads of the K % 4 == 0 form need aligned rows
+    TORCH_CHECK(x.size(1) % 4 != 0 || ((reinterpret_cast<uintptr_t>(x.data_ptr()) | reinterpret_cast<uintptr_t>(w.data_ptr())) & 15) == 0,
+                "osi::linear_fwd: x and w must be 16-byte aligned when K is a multiple of 4");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+    Tensor y = at::empty({x.size(0), w.size(0)}, x.options());
+    ok(osi_linear_fwd(x.data_ptr<float>(), w.data_ptr<float>(), fptr(bias), y.data_ptr<float>(), (int)x.size(0), (int)x.size(1), (int)w.size(0),
+                      stream_of(x)), "osi_linear_fwd");
+    return y;
+}
+
+// returns (dx [B,K] or empty, dw [O,K], db [O])
+std::tuple<Tensor, Tensor, Tensor> linear_bwd(const Tensor& dy, const Tensor& x, const Tensor& w, bool need_dx) {
+    need(dy, at::kFloat, "dy", NATURAL); need(x, at::kFloat, "x", NATURAL); need(w, at::kFloat, "w", NATURAL);
+    TORCH_CHECK(dy.dim() == 2 && x.dim() == 2 && w.dim() == 2 && dy.size(0) == x.size(0) && dy.size(1) == w.size(0) && x.size(1) == w.size(1) &&
+                x.device() == dy.device() && w.device() == dy.device(), "osi::linear_bwd: dy [B, O], x [B, K] and w [O, K] on one device");
+    TORCH_CHECK(x.size(1) <= INT_MAX, "osi::linear_bwd: sizes out of range");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dy.device());
+    Tensor dx = need_dx ? at::empty_like(x) : at::empty({0}, x.options());
+    Tensor dw = at::empty_like(w), db = at::empty({w.size(0)}, w.options());
+    ok(osi_linear_bwd(dy.data_ptr<float>(), x.data_ptr<float>(), w.data_ptr<float>(), need_dx ? dx.data_ptr<float>() : nullptr, 0,
+                      dw.data_ptr<float>(), db.data_ptr<float>(), (int)dy.size(0), (int)x.size(1), (int)w.size(0), stream_of(dy)),
+       "osi_linear_bwd");
+    return {dx, dw, db};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(osi, m) {
+    m.def("mix_rows_pairs(Tensor(a!) x, Tensor partner, Tensor weight) -> ()");
+    m.def("resnet50_set_mix(int net, Tensor? partner, Tensor? weight) -> ()", &resnet50_set_mix);   // both absent clears: no dispatch key
+    m.def("proser_loss_fwd_bwd(Tensor logits, Tensor dummy, Tensor target, int n_mixed, float l0, float l1, float l2, bool need_grad) -> "
+          "(Tensor, Tensor, Tensor)");
+    m.def("proser_scores(Tensor logits, Tensor dummy, float bias) -> Tensor");
+    m.def("linear_fwd(Tensor x, Tensor w, Tensor? bias) -> Tensor");
+    m.def("linear_bwd(Tensor dy, Tensor x, Tensor w, bool need_dx) -> (Tensor, Tensor, Tensor)");
     m.def("evm_distances(Tensor a, Tensor b, int metric, Tensor(a!) workspace) -> Tensor");
     m.def("evm_fit_rows(Tensor dist, Tensor gt, int cls, int tailsize, float multiplier, Tensor(a!) workspace) -> "
           "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
@@ -724,4 +827,9 @@ TORCH_LIBRARY_IMPL(osi, CUDA, m) {
     m.impl("evm_fit_rows", &evm_fit_rows);
     m.impl("evm_set_cover", &evm_set_cover);
     m.impl("evm_probs", &evm_probs);
+    m.impl("mix_rows_pairs", &mix_rows_pairs);
+    m.impl("proser_loss_fwd_bwd", &proser_loss_fwd_bwd);
+    m.impl("proser_scores", &proser_scores);
+    m.impl("linear_fwd", &linear_fwd);
+    m.impl("linear_bwd", &linear_bwd);
 }

@@ -125,6 +125,9 @@ struct osi_resnet50 {
                                      // the backward that follows takes the frozen dataflow (dy = scale * g; the fused stem tail and the Winograd
                                      // input gradients are training-only)
     int fw_prefix = 0;               // eval_prefix of the latest differentiable forward: the gates of those units do not exist
+    bool ran_fwd = false;            // a forward of any kind has run: the block inputs exist (osi_resnet50_debug_unit_input)
+    const int* mix_partner = nullptr;    // osi_resnet50_set_mix: the one-shot request of the next differentiable forward (device arrays of
+    const float* mix_weight = nullptr;   // B entries); that forward mixes the rows of the first trainable unit's input and clears it
     const float* x4_cur = nullptr;   // input of the step in flight (forward sets it, the stem weight gradient reads it)
     int next_stage = 0;
     BwRequest rq;                    // request of the backward in flight, fixed by the call that runs stage 0 (block 0's dgrad form depends on it)
@@ -443,6 +446,11 @@ int osi_resnet50_set_bn_momentum(osi_resnet50_t net, float momentum) {
     net->bn_momentum = momentum;
     return OSI_OK;
 }
+int osi_resnet50_set_mix(osi_resnet50_t net, const int* partner, const float* weight) {
+    OSI_REQUIRE(net && (partner == nullptr) == (weight == nullptr));
+    net->mix_partner = partner; net->mix_weight = weight;
+    return OSI_OK;
+}
 int osi_resnet50_get_bn_momentum(osi_resnet50_t net, float* momentum) {
     OSI_REQUIRE(net && momentum);
     *momentum = net->bn_momentum;
@@ -750,6 +758,9 @@ static int block_fwd_train(osi_resnet50* n, Block& k, const float* params, float
 static int forward_impl(osi_resnet50_t n, const float* params, float* buffers, long long* nbt, const float* image, void* workspace,
                         float* logits, float* features, BnMode mode, osi_stream_t stream) {
     if (!n->plan_unchanged()) return OSI_ERR_STATE;   // a plan-relevant knob changed after create: the workspace no longer fits the plans
+    // a pending mix (osi_resnet50_set_mix) belongs to the input of the first trainable block: it needs a block cut, and nothing runs without one
+    const bool mix = mode != BnMode::Inference && n->mix_partner;
+    if (mix && (n->eval_prefix < 1 || n->eval_prefix > (int)n->blocks.size())) return OSI_ERR_STATE;
     // input binding
     const float* ext = n->x4_ext;
     n->x4_ext = nullptr;
@@ -778,12 +789,19 @@ static int forward_impl(osi_resnet50_t n, const float* params, float* buffers, l
     OSI_TRY(stem_fwd(n, params, buffers, ws, x4, mode, ev > 0, st));
     // bottleneck blocks
     for (Block& k : n->blocks) {
+        if (mix && n->convs[k.c1].unit == p) {   // unit p - 1 has written this tensor, nothing of unit p has read it; the shortcut's fork comes later
+            const osi_conv_desc& d = n->convs[k.c1].d;
+            OSI_TRY(osi_mix_rows_pairs(ws + k.x_in, n->mix_partner, n->mix_weight, n->B, (size_t)d.H * d.W * d.Cin, st));
+            OSI_TRY(n->mark(OSI_PROF_OTHER, st));
+        }
         if (n->convs[k.c1].unit < ev) OSI_TRY(block_fwd_eval(n, k, params, ws, st));
         else OSI_TRY(block_fwd_train(n, k, params, buffers, ws, mode, st));
     }
     OSI_TRY(head_fwd(n, params, ws, logits, features, st));
     // state. An all-inference-form forward leaves no pre-BN tensors, bitmasks or arg-max decisions of a training forward (osi_resnet50_debug_gate)
     n->any_fwd = ev < osi_resnet50::NUNITS;
+    n->ran_fwd = true;
+    if (mix) { n->mix_partner = nullptr; n->mix_weight = nullptr; }   // one-shot
     if (mode == BnMode::Batch) {      // the BatchNorms that ran on batch statistics: those of units >= p, the tail of the forward-ordered table
         int j0 = 0;
         while (j0 < (int)n->bns.size() && n->bns[j0].unit < p) ++j0;
@@ -1387,6 +1405,20 @@ int osi_resnet50_debug_gate(osi_resnet50_t n, void* workspace, int i, unsigned c
         hipLaunchKernelGGL(k_dbg_gate_fma, dim3((unsigned)((e + 255) / 256)), dim3(256), 0, st, ws + c.y, ws + b.scale, ws + b.shift,
                            gate_nchw, e, HW, b.C);
     OSI_LAUNCH_CHECK();
+    return OSI_OK;
+}
+
+int osi_resnet50_debug_unit_input(osi_resnet50_t n, void* workspace, int unit, float* out_nhwc, size_t* floats, osi_stream_t stream) {
+    OSI_REQUIRE(n && floats && unit >= 1 && unit <= (int)n->blocks.size());
+    const Block& k = n->blocks[unit - 1];
+    const osi_conv_desc& d = n->convs[k.c1].d;
+    *floats = (size_t)n->B * d.H * d.W * d.Cin;
+    if (!out_nhwc) return OSI_OK;
+    OSI_REQUIRE(workspace);
+    if (!n->ran_fwd) return OSI_ERR_STATE;
+    if (hipMemcpyAsync(out_nhwc, (const float*)workspace + k.x_in, *floats * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) !=
+        hipSuccess)
+        return OSI_ERR_LAUNCH;
     return OSI_OK;
 }
 

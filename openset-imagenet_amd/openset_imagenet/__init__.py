@@ -13,10 +13,12 @@ from . import openmax
 from .openmax import OpenMax
 from . import evm
 from .evm import EVM
+from . import proser
+from .proser import PROSER
 from .losses import (AverageMeter, EarlyStopping, EntropicOpensetLoss, GarbageLoss, ObjectosphereLoss, SoftmaxLoss)
 from .model import ResNet50
 from .dataset import ImagenetDataset
 from .pipeline import CanvasDataset
 
 __all__ = ["ResNet50", "ImagenetDataset", "CanvasDataset", "EntropicOpensetLoss", "SoftmaxLoss", "GarbageLoss", "ObjectosphereLoss", "AverageMeter",
-           "EarlyStopping", "OpenMax", "EVM", "tools", "util", "train", "metrics", "losses", "dataset"]
+           "EarlyStopping", "OpenMax", "EVM", "PROSER", "tools", "util", "train", "metrics", "losses", "dataset"]

@@ -202,6 +202,11 @@ _SIGS = {
     "osi_evm_fit_rows": (c_int, [P, c_int, c_int, c_longlong, P, c_longlong, c_int, c_float, P, P, P, P, P, P, P, c_size_t, P]),
     "osi_evm_set_cover": (c_int, [P, c_int, P, P, P, P, c_float, c_float, P, P, P, c_size_t, P]),
     "osi_evm_probs": (c_int, [P, c_int, c_int, c_longlong, P, P, P, P, c_int, c_float, P, P]),
+    "osi_mix_rows_pairs": (c_int, [P, P, P, c_int, c_size_t, P]),
+    "osi_proser_loss_fwd_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, P, P, P, P]),
+    "osi_proser_scores": (c_int, [P, P, c_float, c_int, c_int, c_int, P, P]),
+    "osi_resnet50_set_mix": (c_int, [c_void_p, P, P]),
+    "osi_resnet50_debug_unit_input": (c_int, [c_void_p, P, c_int, P, POINTER(c_size_t), P]),
     "osi_adam_step": (c_int, [P, P, P, P, c_size_t, c_double, c_double, c_double, c_double, c_longlong, c_float, P]),
     "osi_sgd_step": (c_int, [P, P, P, c_size_t, c_float, c_float, c_int, c_float, P]),
     "osi_adam_step_groups": (c_int, [P, P, P, P, P, c_size_t, POINTER(OptSegment), c_int, POINTER(AdamGroup), c_int, c_float, P]),

@@ -173,6 +173,7 @@ class ResNet50(nn.Module):
         self._grads_fresh = False  # a backward has filled the gradient arena since the last optimizer.zero_grad()
         self._bw_request = None    # next_backward(): (epsilon or None, lo, hi, accumulate, alpha or None, anchor, input_only) for the one
                                    # backward that follows; alpha is None for an FGSM request
+        self._fw_request = None    # next_forward(): (partner, weight) of the mix the next differentiable forward applies at the cut
         self._adv_valid = False    # the latest backward wrote adversarial_batch()
         self._adv = {}             # (B, H, W) -> the model-owned PAIR of NHWC4 buffers the attack epilogues write: a backward writes the
                                    # one its forward did not read, so an attack can feed adversarial_batch() back without a copy
@@ -432,6 +433,39 @@ class ResNet50(nn.Module):
             raise ValueError("next_backward: lo <= hi")
         self._bw_request = (None if fgsm is None else float(fgsm), float(lo), float(hi), bool(accumulate), alpha, anchor, bool(input_only))
 
+    def next_forward(self, mix=None):
+        """Request for the ONE differentiable forward that follows (beside next_backward):
+          mix = (partner, weight)   manifold mixup at the cut declared with freeze_below(): after the frozen prefix has written the input
+                           of the first trainable block and before that block reads it, the rows of that tensor are mixed pairwise in
+                           place (osi_mix_rows_pairs): row i becomes weight[i] * x_i + (1 - weight[i]) * x_partner[i], a row that is its own
+                           partner stays as it is. partner: int32, weight: fp32, device tensors of B entries (the batch of that forward);
+                           partner is an involution (partner[partner[i]] == i). The suffix trains on the mixed activations; the prefix is
+                           frozen, so no gradient crosses the mix. None clears a pending request.
+        Raises ValueError when no block cut is declared (frozen_below is None or "fc"). The forward raises RuntimeError when it would not
+        run the prefix in the inference form — an image that requires grad, a pending attack request, no trainable parameter — and the
+        request stays pending (next_forward(mix=None) clears it). A no-grad or inference forward ignores the request and leaves it pending."""
+        if mix is None:
+            self._fw_request = None
+            return
+        if not 0 < self._cut < self._n_units - 1:
+            raise ValueError(f"next_forward(mix=...): the mix lives at the input of the first trainable block, but frozen_below is "
+                             f"{self.frozen_below!r}; declare a block cut with freeze_below('layer1' .. 'layer4' or 'layerN.K') first")
+        try:
+            partner, weight = mix
+        except (TypeError, ValueError):
+            raise TypeError("next_forward: mix must be a pair (partner, weight) of device tensors") from None
+        if not isinstance(partner, torch.Tensor) or not isinstance(weight, torch.Tensor):
+            raise TypeError("next_forward: mix must be a pair (partner, weight) of device tensors")
+        if partner.dtype != torch.int32 or weight.dtype != torch.float32:
+            raise TypeError(f"next_forward: mix partner must be int32 and weight float32, got {partner.dtype} and {weight.dtype}")
+        if partner.dim() != 1 or weight.dim() != 1 or partner.shape != weight.shape:
+            raise ValueError(f"next_forward: mix partner and weight must be vectors of one length (the batch), got shapes "
+                             f"{tuple(partner.shape)} and {tuple(weight.shape)}")
+        dev = self._flat_params.device
+        if not partner.is_cuda or partner.device != dev or weight.device != dev:
+            raise ValueError("next_forward: mix partner and weight must live on the model's device (the MI355X build has no CPU path)")
+        self._fw_request = (partner.detach().contiguous(), weight.detach().contiguous())
+
     def adversarial_batch(self):
         """The NHWC4 batch [B, H, W, 4] written by the latest backward that ran under next_backward(fgsm=... / pgd=...). Model-owned:
         one of a pair per geometry, overwritten by the second such backward after this one; feed it to the model as it is."""
@@ -478,6 +512,9 @@ class ResNet50(nn.Module):
         net = self._net(B, H, W)
         if want_grad:    # the executor learns which units are trainable, and how much of the frozen prefix runs the inference forms
             self._set_trainable(net, self._trainable_plan()[0], self._fwd_prefix)
+        mix = self._fw_request if want_grad else None
+        if mix is not None and mix[0].numel() != B:
+            raise ValueError(f"next_forward: mix partner and weight hold {mix[0].numel()} entries, the batch has {B} rows")
         if staged and flip is not None:   # ToTensor + horizontal flip + NHWC4 staging in one pass on the device (osi_u8hwc3_to_nhwc4)
             flip = torch.as_tensor(flip).to(device=image.device, dtype=torch.uint8).contiguous()
             if flip.numel() != B:
@@ -486,12 +523,20 @@ class ResNet50(nn.Module):
             raise ValueError("flip flags are only meaningful with a uint8 [B,H,W,3] batch")
         # one custom op = the whole network on the current HIP stream: uint8 batches are staged, NHWC4 batches bound in place
         # (conv1 forward now, conv1 weight gradient at the end of this step's backward), NCHW batches converted on the way in
-        if frozen:   # the training topology on the running statistics (read-only), differentiable: osi_resnet50_forward_frozen
-            logits, features = N.ops().resnet50_forward_frozen(net.h.value, self._flat_params, self._flat_buffers, image, flip, self._ws,
-                                                               self._F, self._O)
-        else:
-            logits, features = N.ops().resnet50_forward(net.h.value, self._flat_params, self._flat_buffers, self._nbt, image, flip,
-                                                        self._ws, self._F, self._O, bool(self.training and not self._bn_frozen))
+        if mix is not None:   # one-shot: the executor mixes the input of the first trainable block in this forward (osi_resnet50_set_mix)
+            N.ops().resnet50_set_mix(net.h.value, mix[0], mix[1])
+            self._fw_request = None
+        try:
+            if frozen:   # the training topology on the running statistics (read-only), differentiable: osi_resnet50_forward_frozen
+                logits, features = N.ops().resnet50_forward_frozen(net.h.value, self._flat_params, self._flat_buffers, image, flip, self._ws,
+                                                                   self._F, self._O)
+            else:
+                logits, features = N.ops().resnet50_forward(net.h.value, self._flat_params, self._flat_buffers, self._nbt, image, flip,
+                                                            self._ws, self._F, self._O, bool(self.training and not self._bn_frozen))
+        except Exception:
+            if mix is not None:   # a forward that failed before it ran leaves the executor's request pending: take it back
+                N.ops().resnet50_set_mix(net.h.value, None, None)
+            raise
         self._eval_plain = not frozen and not self.training and torch.is_grad_enabled()
         self._fwd_input_only = bool(want_grad) and self._bw_request is not None and self._bw_request[6]
         # (any forward replaces the executor's backward state; only a differentiable one leaves a backward owed)
@@ -619,6 +664,10 @@ class ResNet50(nn.Module):
                 else:
                     self._fwd_prefix = self._cut
             input_only = self._bw_request is not None and self._bw_request[6]
+            if self._fw_request is not None and not 0 < self._fwd_prefix < self._n_units - 1:
+                raise RuntimeError("next_forward(mix=...) is pending, but this forward does not run a frozen prefix below a block cut (an image "
+                                   "that requires grad, a pending attack request, no trainable parameter, or the cut was moved): the mix has "
+                                   "no place in it; next_forward(mix=None) clears the request")
             if param_grad or image_grad or input_only:
                 # no parameter requires grad: a detached anchor, so the backward runs input-only. A pending input-only attack request
                 # needs a graph even then (the anchor is a stand-in leaf: no parameter is part of the graph either way)

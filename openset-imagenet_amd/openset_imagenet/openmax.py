@@ -15,7 +15,7 @@ not part of the reference snapshot: include/osi.h (ABI 21) is its definition, te
 All arithmetic runs in the kernels of csrc/openmax.hip (torch.ops.osi.openmax_*); there is no CPU path. Inputs may be numpy arrays
 or torch tensors, on the host or on the device. Nothing is read back: `mav`, `shape`, `scale`, `shift`, `fitted`, `count`,
 `tail_count` and `flags` ({eligible rows left out for a non-finite distance, unfitted classes}) are device tensors the caller may
-read. Out of scope: PROSER, per-class tail sizes, multi-GPU fitting.
+read. PROSER is openset_imagenet.proser. Out of scope: per-class tail sizes, multi-GPU fitting.
 """
 import torch
 

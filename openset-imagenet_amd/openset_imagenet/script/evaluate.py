@@ -11,7 +11,11 @@ split's .npz, `{loss}_{split}_arr{suffix}_openmax.npz` with `gt`, `logits`, `fea
 probabilities) and `unknown` (the probability of the unknown class); with `--oscr` the same OSCR line is printed for those scores.
 `--evm TAILSIZE` (likewise; softmax and entropic losses) fits the Extreme Value Machine (evm.EVM; `--evm-cover`, `--evm-multiplier`,
 `--evm-distance`) on the features of the training split, saves it as `{loss}_evm{suffix}.pth` and writes
-`{loss}_{split}_arr{suffix}_evm.npz` with `gt`, `logits`, `features` and `scores` (the per-class inclusion probabilities)."""
+`{loss}_{split}_arr{suffix}_evm.npz` with `gt`, `logits`, `features` and `scores` (the per-class inclusion probabilities).
+`--proser` (likewise; softmax and entropic losses) loads the fine-tuned network, dummy classifier and calibrated bias that
+`python -m openset_imagenet.script.proser` saved as `{loss}_proser{suffix}.pth` (proser.PROSER) and writes
+`{loss}_{split}_arr{suffix}_proser.npz` with `gt`, `logits`, `features` of THAT network, `scores` = probs[:, :C] and `unknown` =
+probs[:, C]; with `--oscr` the same OSCR line is printed for those scores."""
 import argparse
 import json
 import pathlib
@@ -51,7 +55,11 @@ def get_args(command_line_options=None):
                    "greedy set cover at this inclusion probability (default: keep every fitted row)")
     p.add_argument("--evm-multiplier", type=float, default=0.5, help="EVM: the factor on the distances before the Weibull fit")
     p.add_argument("--evm-distance", choices=["euclidean", "cosine"], default="cosine", help="EVM: distance between feature rows")
+    p.add_argument("--proser", action="store_true", help="also evaluate the PROSER stage saved as {loss}_proser{suffix}.pth (softmax and "
+                   "entropic losses) and write {loss}_{split}_arr{suffix}_proser.npz with its scores and the probability of the unknown class")
     args = p.parse_args(command_line_options)
+    if args.proser and args.loss == "garbage":
+        p.error("--proser needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
     if args.openmax is not None and args.loss == "garbage":
         p.error("--openmax needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
     if args.evm is not None and args.loss == "garbage":
@@ -169,6 +177,27 @@ def evm_arrays(train_arrays, split_arrays, tailsize, cover_threshold=None, multi
                      scores=scores)
 
 
+def proser_arrays(proser, split_arrays):
+    """`--proser` on arrays: `gt`, `logits`, `features` of one split as the fine-tuned network of `proser` (proser.PROSER) gave them
+    (mappings as get_arrays' .npz holds them). Returns the numpy `gt`, `logits`, `features`, `scores` = probs[:, :C] and `unknown` =
+    probs[:, C] of PROSER.predict over the dummy classifier's logits."""
+    probs = proser.predict(split_arrays["logits"], proser.dummy_logits(split_arrays["features"])).cpu().numpy()
+    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    c = probs.shape[1] - 1
+    return dict(gt=host(split_arrays["gt"]), logits=host(split_arrays["logits"]), features=host(split_arrays["features"]),
+                scores=probs[:, :c], unknown=probs[:, c])
+
+
+def load_proser(path, n_classes):
+    """The PROSER module of a file written by script/proser.py, on the device, with a network of its own."""
+    from ..proser import PROSER
+    sd = torch.load(path, map_location="cpu", weights_only=False)
+    net = ResNet50(fc_layer_dim=n_classes, out_features=n_classes, logit_bias=False)
+    proser = PROSER(net, dummy_count=int(sd["dummy_count"]), mix_at=sd["mix_at"], lambdas=tuple(sd["lambdas"]), alpha=float(sd["alpha"]))
+    proser.load_state_dict(sd)
+    return tools.device(proser)
+
+
 def averaged_module(model, checkpoint):
     """`--averaged`: the module of the checkpoint's "avg_state_dict" (averaging.AveragedModel over `model`'s geometry); exits with a
     clear message when the checkpoint was written without an `avg` block."""
@@ -204,7 +233,13 @@ def main(command_line_options=None):
         suffix += "_avg"
     tools.device(model)
     written = {}
-    om = evm = None
+    om = evm = proser = None
+    if args.proser:
+        proser_path = args.output_directory / f"{args.loss}_proser{suffix}.pth"
+        if not proser_path.is_file():
+            raise SystemExit(f"--proser: {proser_path} not found; run python -m openset_imagenet.script.proser {args.loss} {args.protocol} first")
+        proser = load_proser(proser_path, n_classes)
+        print(f"PROSER stage loaded from: {proser_path} (dummy {proser.dummy_count}, mix at {proser.mix_at}, bias {float(proser.bias):.6f})")
     if args.openmax is not None:
         from ..openmax import OpenMax
         om = OpenMax(tailsize=args.openmax, distance=args.openmax_distance, alpha=args.openmax_alpha)    # refuses bad options first
@@ -259,6 +294,16 @@ def main(command_line_options=None):
             written[split + "_evm"] = evm_file
             if args.oscr:
                 for line in oscr_lines(split, gt, arrays["scores"], tag="EVM "):
+                    print(line)
+        if proser is not None:
+            p_gt, p_logits, p_features, _ = get_arrays(model=proser.model, loader=loader)
+            arrays = proser_arrays(proser, dict(gt=p_gt, logits=p_logits, features=p_features))
+            proser_file = args.output_directory / f"{args.loss}_{split}_arr{suffix}_proser.npz"
+            np.savez(proser_file, **arrays)
+            print(f"PROSER scores saved in: {proser_file}")
+            written[split + "_proser"] = proser_file
+            if args.oscr:
+                for line in oscr_lines(split, p_gt, arrays["scores"], tag="PROSER "):
                     print(line)
         if args.auc:
             for unk in (-1, -2):
