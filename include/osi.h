@@ -651,6 +651,40 @@ int osi_proser_loss_fwd_bwd(const float* logits, const float* dummy, const long 
                             float l1, float l2, float* loss4, float* dlogits, float* ddummy, osi_stream_t stream);
 int osi_proser_scores(const float* logits, const float* dummy, float bias, int B, int C, int D, float* probs, osi_stream_t stream);
 
+/* ABI 24. Deep nearest neighbours (Sun, Ming, Zhu, Li, "Out-of-Distribution Detection with Deep Nearest Neighbors", ICML 2022;
+ * openset_imagenet/knn.py): ordered selection over the rows of a distance matrix dist[M][ld] (ld >= N columns used) as
+ * osi_evm_distances writes it. The method is not part of the reference snapshot; this block is its definition, tests/knn_oracle.py
+ * its numpy restatement. There is no floating-point arithmetic on the selection path: every output is an element of the input (its
+ * canonical value, below) or an index, bit-identical from run to run and independent of the grid. Nothing is allocated or
+ * synchronised; every output element is written by the call; workspace contents are never assumed (ws: osi_knn_workspace(M, N, K)
+ * bytes, 8-byte aligned; 0 for non-positive arguments; the kernels stage nothing in it and the size is a small constant). OSI_ERR_ARG
+ * before any launch on a null required pointer (skip may be NULL), a non-positive size, ld < N, K outside [1, OSI_KNN_MAX_K], a short
+ * workspace or a bad enum. The matrix is read with plain 64-bit addressing: no 2 GiB limit of its own.
+ *
+ * Order, shared by both calls. A distance is read as d + 0.0f (-0 becomes +0): that canonical value is compared and returned. Values
+ *   rank by IEEE order, every NaN after +Inf (a NaN's payload is not part of the definition); equal values, and NaNs among themselves,
+ *   rank by ascending column. skip[m] (int64) names one column of row m that does not take part (leave-one-out on the bank); a value
+ *   outside [0, N) skips nothing.
+ * osi_knn_topk: per row the first min(K, n) columns in that order, n = N minus a skipped column: out_dist[M][K] the canonical values,
+ *   out_idx[M][K] (int64) their columns, ascending by (value, column); the remaining entries hold +Inf and -1.
+ * osi_knn_class_kth: the columns are sorted by class, class c owns start[c] .. start[c + 1] - 1 (start[C + 1] int64; values are clamped
+ *   to [0, N], a descending pair is an empty class). out[m][c] = the min(K, n_c)-th element of the segment in that order, n_c = the
+ *   segment length minus a skipped column inside it; +Inf for n_c = 0. `transform` says what is stored for that value v:
+ *   OSI_KNN_RAW v; OSI_KNN_SIM_COSINE fminf(fmaxf(1 - 0.5f * v, 0), 1) in fp32 (the product, then one rounded subtraction);
+ *   OSI_KNN_SIM_INVERSE 1.0f / (1.0f + v), each operation rounded to fp32. Under both similarities a NaN v stores NaN and +Inf stores 0.
+ * One workgroup per row / per (row, class): the segment is read once in tiles of 2048 columns; columns below the running threshold are
+ * appended IN COLUMN ORDER (wave ballots) to a buffer in LDS; a four-pass radix select over the buffer and an ordered in-place
+ * compaction cut it back to K, which resolves threshold ties by the lowest column. Segments of any length, no staging limit. A class
+ * segment of at most 2048 columns is one wave's work instead: keys in registers, a bitwise select on wave ballots (the k-th VALUE
+ * needs no tie rule). Two launches for osi_knn_class_kth, one for osi_knn_topk. */
+enum { OSI_KNN_RAW = 0, OSI_KNN_SIM_COSINE = 1, OSI_KNN_SIM_INVERSE = 2 };
+#define OSI_KNN_MAX_K 1024
+size_t osi_knn_workspace(int M, int N, int K);
+int osi_knn_topk(const float* dist, int M, int N, long long ld, int K, const long long* skip, float* out_dist, long long* out_idx,
+                 void* ws, size_t ws_bytes, osi_stream_t stream);
+int osi_knn_class_kth(const float* dist, int M, int N, long long ld, const long long* start, int C, int K, const long long* skip,
+                      int transform, float* out, void* ws, size_t ws_bytes, osi_stream_t stream);
+
 /* ---- optimizer + arena utilities (train.py:356-359 construction, train.py:127,139 zero_grad/step) --- */
 int osi_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,
                   double beta2, double eps, long long step, float grad_scale, osi_stream_t stream);

@@ -16,6 +16,7 @@
 //   torch.ops.osi.softmax / confidence_accumulate    train.py:177, metrics.py:8-42
 //   torch.ops.osi.openmax_class_means / _distances / _fit_tails / _wscores / _recalibrate    OpenMax (openset_imagenet/openmax.py)
 //   torch.ops.osi.evm_distances / _fit_rows / _set_cover / _probs                            the Extreme Value Machine (openset_imagenet/evm.py)
+//   torch.ops.osi.knn_topk / knn_class_kth                                                   deep nearest neighbours (openset_imagenet/knn.py)
 //   torch.ops.osi.mix_rows_pairs / resnet50_set_mix / proser_loss_fwd_bwd / proser_scores / linear_fwd / linear_bwd    PROSER (openset_imagenet/proser.py)
 //
 // This file contains no arithmetic: every op validates its tensor arguments (device, dtype, contiguity, sizes), takes the CURRENT
@@ -642,6 +643,44 @@ Tensor evm_probs(const Tensor& dist, const Tensor& shape, const Tensor& scale, c
     return probs;
 }
 
+// ---- deep nearest neighbours (include/osi.h, ABI 24): dist is [M,ld], every column of it takes part (N = ld)
+const long long* knn_skip(const Tensor& dist, const c10::optional<Tensor>& skip, const char* what) {
+    if (!skip.has_value() || !skip->defined()) return nullptr;
+    need(*skip, at::kLong, "skip", NATURAL);
+    TORCH_CHECK(skip->numel() == dist.size(0) && skip->device() == dist.device(), "osi::", what, ": skip holds one column per row, on the device of dist");
+    return (const long long*)skip->data_ptr<int64_t>();
+}
+
+std::tuple<Tensor, Tensor> knn_topk(const Tensor& dist, int64_t k, const c10::optional<Tensor>& skip, Tensor workspace) {
+    need(dist, at::kFloat, "dist", NATURAL); need(workspace, at::kByte, "workspace", 8);
+    TORCH_CHECK(dist.dim() == 2 && dist.size(0) <= INT_MAX && dist.size(1) <= INT_MAX && workspace.device() == dist.device(),
+                "osi::knn_topk: dist is [M,N], sizes in range, workspace on its device");
+    TORCH_CHECK(k >= 1 && k <= OSI_KNN_MAX_K, "osi::knn_topk: k must lie in [1, ", OSI_KNN_MAX_K, "]");
+    const int64_t M = dist.size(0);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dist.device());
+    Tensor out_dist = at::empty({M, k}, dist.options()), out_idx = at::empty({M, k}, dist.options().dtype(at::kLong));
+    ok(osi_knn_topk(dist.data_ptr<float>(), (int)M, (int)dist.size(1), (long long)dist.size(1), (int)k, knn_skip(dist, skip, "knn_topk"),
+                    out_dist.data_ptr<float>(), (long long*)out_idx.data_ptr<int64_t>(), workspace.data_ptr(), (size_t)workspace.numel(),
+                    stream_of(dist)), "osi_knn_topk");
+    return {out_dist, out_idx};
+}
+
+Tensor knn_class_kth(const Tensor& dist, const Tensor& start, int64_t k, const c10::optional<Tensor>& skip, int64_t transform,
+                     Tensor workspace) {
+    need(dist, at::kFloat, "dist", NATURAL); need(start, at::kLong, "start", NATURAL); need(workspace, at::kByte, "workspace", 8);
+    TORCH_CHECK(dist.dim() == 2 && start.dim() == 1 && start.numel() >= 2 && start.device() == dist.device() &&
+                workspace.device() == dist.device(), "osi::knn_class_kth: dist is [M,N], start [C+1] on its device");
+    TORCH_CHECK(dist.size(0) <= INT_MAX && dist.size(1) <= INT_MAX && start.numel() - 1 <= INT_MAX, "osi::knn_class_kth: sizes out of range");
+    TORCH_CHECK(k >= 1 && k <= OSI_KNN_MAX_K, "osi::knn_class_kth: k must lie in [1, ", OSI_KNN_MAX_K, "]");
+    const int64_t M = dist.size(0), C = start.numel() - 1;
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dist.device());
+    Tensor out = at::empty({M, C}, dist.options());
+    ok(osi_knn_class_kth(dist.data_ptr<float>(), (int)M, (int)dist.size(1), (long long)dist.size(1), (const long long*)start.data_ptr<int64_t>(),
+                         (int)C, (int)k, knn_skip(dist, skip, "knn_class_kth"), (int)std::min<int64_t>(std::max<int64_t>(transform, -1), INT_MAX),
+                         out.data_ptr<float>(), workspace.data_ptr(), (size_t)workspace.numel(), stream_of(dist)), "osi_knn_class_kth");
+    return out;
+}
+
 // ---- PROSER (include/osi.h, ABI 23)
 void need_pairs(const Tensor& ref, const Tensor& partner, const Tensor& weight, int64_t B, const char* what) {
     need(partner, at::kInt, "partner", NATURAL); need(weight, at::kFloat, "weight", NATURAL);
@@ -753,6 +792,8 @@ TORCH_LIBRARY(osi, m) {
     m.def("evm_set_cover(Tensor dpp, Tensor shape, Tensor scale, Tensor shift, Tensor fitted, float multiplier, float cover_threshold, "
           "Tensor(a!) workspace) -> (Tensor, Tensor)");
     m.def("evm_probs(Tensor dist, Tensor shape, Tensor scale, Tensor shift, Tensor ev_start, float multiplier) -> Tensor");
+    m.def("knn_topk(Tensor dist, int k, Tensor? skip, Tensor(a!) workspace) -> (Tensor, Tensor)");
+    m.def("knn_class_kth(Tensor dist, Tensor start, int k, Tensor? skip, int transform, Tensor(a!) workspace) -> Tensor");
     m.def("openmax_class_means(Tensor features, Tensor logits, Tensor gt, Tensor(a!) workspace) -> (Tensor, Tensor, Tensor)");
     m.def("openmax_distances(Tensor features, Tensor mav, Tensor? cls, int metric) -> Tensor");
     m.def("openmax_fit_tails(Tensor dist, Tensor gt, Tensor correct, int C, int tailsize, Tensor(a!) workspace) -> "
@@ -827,6 +868,8 @@ TORCH_LIBRARY_IMPL(osi, CUDA, m) {
     m.impl("evm_fit_rows", &evm_fit_rows);
     m.impl("evm_set_cover", &evm_set_cover);
     m.impl("evm_probs", &evm_probs);
+    m.impl("knn_topk", &knn_topk);
+    m.impl("knn_class_kth", &knn_class_kth);
     m.impl("mix_rows_pairs", &mix_rows_pairs);
     m.impl("proser_loss_fwd_bwd", &proser_loss_fwd_bwd);
     m.impl("proser_scores", &proser_scores);

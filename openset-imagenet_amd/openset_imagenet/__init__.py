@@ -13,6 +13,8 @@ from . import openmax
 from .openmax import OpenMax
 from . import evm
 from .evm import EVM
+from . import knn
+from .knn import KNN
 from . import proser
 from .proser import PROSER
 from .losses import (AverageMeter, EarlyStopping, EntropicOpensetLoss, GarbageLoss, ObjectosphereLoss, SoftmaxLoss)
@@ -21,4 +23,4 @@ from .dataset import ImagenetDataset
 from .pipeline import CanvasDataset
 
 __all__ = ["ResNet50", "ImagenetDataset", "CanvasDataset", "EntropicOpensetLoss", "SoftmaxLoss", "GarbageLoss", "ObjectosphereLoss", "AverageMeter",
-           "EarlyStopping", "OpenMax", "EVM", "PROSER", "tools", "util", "train", "metrics", "losses", "dataset"]
+           "EarlyStopping", "OpenMax", "EVM", "KNN", "PROSER", "tools", "util", "train", "metrics", "losses", "dataset"]

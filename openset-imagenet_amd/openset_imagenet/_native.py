@@ -99,6 +99,8 @@ OPENMAX_MAX_TAIL = 4096
 EVM_EUCLIDEAN, EVM_COSINE = 0, 1
 EVM_MAX_TAIL = 4096
 EVM_MAX_COVER_ROWS = 16384
+KNN_RAW, KNN_SIM_COSINE, KNN_SIM_INVERSE = 0, 1, 2
+KNN_MAX_K = 1024
 
 P = c_void_p
 _PD = POINTER(ConvDesc)
@@ -202,6 +204,9 @@ _SIGS = {
     "osi_evm_fit_rows": (c_int, [P, c_int, c_int, c_longlong, P, c_longlong, c_int, c_float, P, P, P, P, P, P, P, c_size_t, P]),
     "osi_evm_set_cover": (c_int, [P, c_int, P, P, P, P, c_float, c_float, P, P, P, c_size_t, P]),
     "osi_evm_probs": (c_int, [P, c_int, c_int, c_longlong, P, P, P, P, c_int, c_float, P, P]),
+    "osi_knn_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "osi_knn_topk": (c_int, [P, c_int, c_int, c_longlong, c_int, P, P, P, P, c_size_t, P]),
+    "osi_knn_class_kth": (c_int, [P, c_int, c_int, c_longlong, P, c_int, c_int, P, c_int, P, P, c_size_t, P]),
     "osi_mix_rows_pairs": (c_int, [P, P, P, c_int, c_size_t, P]),
     "osi_proser_loss_fwd_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, P, P, P, P]),
     "osi_proser_scores": (c_int, [P, P, c_float, c_int, c_int, c_int, P, P]),

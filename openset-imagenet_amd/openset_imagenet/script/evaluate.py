@@ -12,6 +12,10 @@ probabilities) and `unknown` (the probability of the unknown class); with `--osc
 `--evm TAILSIZE` (likewise; softmax and entropic losses) fits the Extreme Value Machine (evm.EVM; `--evm-cover`, `--evm-multiplier`,
 `--evm-distance`) on the features of the training split, saves it as `{loss}_evm{suffix}.pth` and writes
 `{loss}_{split}_arr{suffix}_evm.npz` with `gt`, `logits`, `features` and `scores` (the per-class inclusion probabilities).
+`--knn K` (likewise; softmax and entropic losses) keeps the features of the training split as the bank of deep nearest neighbours
+(knn.KNN; `--knn-distance`, `--knn-fraction`), saves it as `{loss}_knn{suffix}.pth` and writes `{loss}_{split}_arr{suffix}_knn.npz`
+with `gt`, `logits`, `features`, `scores` (per class the similarity of the K-th nearest bank row of that class) and `unknown` (the
+distance to the K-th nearest bank row overall).
 `--proser` (likewise; softmax and entropic losses) loads the fine-tuned network, dummy classifier and calibrated bias that
 `python -m openset_imagenet.script.proser` saved as `{loss}_proser{suffix}.pth` (proser.PROSER) and writes
 `{loss}_{split}_arr{suffix}_proser.npz` with `gt`, `logits`, `features` of THAT network, `scores` = probs[:, :C] and `unknown` =
@@ -55,6 +59,10 @@ def get_args(command_line_options=None):
                    "greedy set cover at this inclusion probability (default: keep every fitted row)")
     p.add_argument("--evm-multiplier", type=float, default=0.5, help="EVM: the factor on the distances before the Weibull fit")
     p.add_argument("--evm-distance", choices=["euclidean", "cosine"], default="cosine", help="EVM: distance between feature rows")
+    p.add_argument("--knn", type=int, default=None, metavar="K", help="also score with deep nearest neighbours: the K-th nearest row of the "
+                   "training split's features (softmax and entropic losses); writes {loss}_{split}_arr{suffix}_knn.npz")
+    p.add_argument("--knn-distance", choices=["euclidean", "cosine"], default="cosine", help="KNN: distance between feature rows")
+    p.add_argument("--knn-fraction", type=float, default=1.0, metavar="F", help="KNN: the share of every class's training rows kept as the bank")
     p.add_argument("--proser", action="store_true", help="also evaluate the PROSER stage saved as {loss}_proser{suffix}.pth (softmax and "
                    "entropic losses) and write {loss}_{split}_arr{suffix}_proser.npz with its scores and the probability of the unknown class")
     args = p.parse_args(command_line_options)
@@ -64,6 +72,8 @@ def get_args(command_line_options=None):
         p.error("--openmax needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
     if args.evm is not None and args.loss == "garbage":
         p.error("--evm needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
+    if args.knn is not None and args.loss == "garbage":
+        p.error("--knn needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
     try:
         args.output_directory = str(args.output_directory).format(args.protocol)
     except Exception:
@@ -177,6 +187,24 @@ def evm_arrays(train_arrays, split_arrays, tailsize, cover_threshold=None, multi
                      scores=scores)
 
 
+def knn_arrays(train_arrays, split_arrays, k, distance="cosine", fraction=1.0, seed=0):
+    """`--knn` on arrays: keep the training split's `gt` and `features` as the bank of deep nearest neighbours (mappings as get_arrays'
+    .npz holds them; an already fitted knn.KNN is taken as it is) and score one split. Returns (knn, arrays): arrays holds the numpy
+    `gt`, `logits`, `features` of the split, `scores` = the [M, C] class similarities and `unknown` = the [M] distances to the k-th
+    nearest bank row."""
+    from ..knn import KNN
+    if isinstance(train_arrays, KNN):
+        knn = train_arrays
+    else:
+        knn = KNN(k=k, distance=distance, bank_fraction=fraction, seed=seed)
+        knn.fit(train_arrays["features"], train_arrays["gt"])
+    scores = knn.predict(split_arrays["features"]).cpu().numpy()
+    unknown = knn.unknown_score(split_arrays["features"]).cpu().numpy()
+    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    return knn, dict(gt=host(split_arrays["gt"]), logits=host(split_arrays["logits"]), features=host(split_arrays["features"]),
+                     scores=scores, unknown=unknown)
+
+
 def proser_arrays(proser, split_arrays):
     """`--proser` on arrays: `gt`, `logits`, `features` of one split as the fine-tuned network of `proser` (proser.PROSER) gave them
     (mappings as get_arrays' .npz holds them). Returns the numpy `gt`, `logits`, `features`, `scores` = probs[:, :C] and `unknown` =
@@ -233,7 +261,7 @@ def main(command_line_options=None):
         suffix += "_avg"
     tools.device(model)
     written = {}
-    om = evm = proser = None
+    om = evm = knn = proser = None
     if args.proser:
         proser_path = args.output_directory / f"{args.loss}_proser{suffix}.pth"
         if not proser_path.is_file():
@@ -246,7 +274,10 @@ def main(command_line_options=None):
     if args.evm is not None:
         from ..evm import EVM
         evm = EVM(tailsize=args.evm, cover_threshold=args.evm_cover, distance_multiplier=args.evm_multiplier, distance=args.evm_distance)
-    if om is not None or evm is not None:
+    if args.knn is not None:
+        from ..knn import KNN
+        knn = KNN(k=args.knn, distance=args.knn_distance, bank_fraction=args.knn_fraction)               # refuses bad options first
+    if om is not None or evm is not None or knn is not None:
         train_ds = _image_loader(args.protocol_directory / f"p{args.protocol}_train.csv", args.imagenet_directory, False, "eval")
         print(f"train dataset len:{len(train_ds)}, labels:{train_ds.table.label_count}")
         loader = torch.utils.data.DataLoader(train_ds, batch_size=args.batch_size, num_workers=args.workers)
@@ -258,6 +289,12 @@ def main(command_line_options=None):
         left_out, unfitted = evm.flags.tolist()
         print(f"EVM (tail {args.evm}, cover {args.evm_cover}, multiplier {args.evm_multiplier}, {args.evm_distance}) keeps "
               f"{evm.ev_features.shape[0]} extreme vectors, {unfitted} rows unfitted, {left_out} distances not finite; saved in: {evm_path}")
+    if knn is not None:
+        knn.fit(t_features, t_gt)
+        knn_path = args.output_directory / f"{args.loss}_knn{suffix}.pth"
+        torch.save(knn.state_dict(), knn_path)
+        print(f"KNN (k {args.knn}, {args.knn_distance}, fraction {args.knn_fraction}) keeps a bank of {knn.bank_features.shape[0]} rows; "
+              f"saved in: {knn_path}")
     if om is not None:
         om.fit(t_features, t_logits, t_gt)
         om_path = args.output_directory / f"{args.loss}_openmax{suffix}.pth"
@@ -294,6 +331,15 @@ def main(command_line_options=None):
             written[split + "_evm"] = evm_file
             if args.oscr:
                 for line in oscr_lines(split, gt, arrays["scores"], tag="EVM "):
+                    print(line)
+        if knn is not None:
+            _, arrays = knn_arrays(knn, dict(gt=gt, logits=logits, features=features), args.knn)
+            knn_file = args.output_directory / f"{args.loss}_{split}_arr{suffix}_knn.npz"
+            np.savez(knn_file, **arrays)
+            print(f"KNN scores saved in: {knn_file}")
+            written[split + "_knn"] = knn_file
+            if args.oscr:
+                for line in oscr_lines(split, gt, arrays["scores"], tag="KNN "):
                     print(line)
         if proser is not None:
             p_gt, p_logits, p_features, _ = get_arrays(model=proser.model, loader=loader)
