@@ -685,6 +685,51 @@ int osi_knn_topk(const float* dist, int M, int N, long long ld, int K, const lon
 int osi_knn_class_kth(const float* dist, int M, int N, long long ld, const long long* start, int C, int K, const long long* skip,
                       int transform, float* out, void* ws, size_t ws_bytes, osi_stream_t stream);
 
+/* ABI 25. Mahalanobis and Relative Mahalanobis open-set scores (Lee, Lee, Lee, Shin, "A Simple Unified Framework for Detecting
+ * Out-of-Distribution Samples and Adversarial Attacks", NeurIPS 2018; Ren et al., "A Simple Fix to Mahalanobis Distance for Improving
+ * Near-OOD Detection", 2021; openset_imagenet/mahalanobis.py): class-conditional Gaussians with ONE tied covariance on features
+ * [N][F] fp32 with labels gt[N] int64; every fitted quantity is fp64. The method is not part of the reference snapshot; this block is
+ * its definition, tests/mahalanobis_oracle.py its numpy restatement. The products run on the fp64 matrix instruction of gfx950
+ * (v_mfma_f64_16x16x4_f64), 64 x 64 tiles staged through LDS. No floating-point atomics: every sum has a fixed order that depends on
+ * the sizes alone, so every output is bit-identical from run to run. Nothing is allocated or synchronised; every output element is
+ * written by the call; workspace contents are never assumed (ws: osi_maha_workspace(N, C, F) bytes, 8-byte aligned, 0 for a
+ * non-positive argument or F > OSI_MAHA_MAX_F; the scatter alone needs more than its first 64 bytes, and for it N is the rows of the
+ * call). OSI_ERR_ARG before any launch on a null required pointer, a non-positive size, a short or misaligned workspace, a bad enum, a
+ * scalar that is not finite or out of range, and on sizes past the limit: addressing is 64-bit, and a call takes F <= OSI_MAHA_MAX_F
+ * and fewer than 2^31 ELEMENTS in each of its matrices (N * F, (C + 1) * F, M * F, M * C); longer inputs go in row chunks.
+ *
+ * A row is COUNTED when 0 <= gt[i] < C; every other row is ignored everywhere.
+ * osi_maha_class_means: mean[C + 1][F], count[C + 1] (int64). Row c < C = the mean of the counted rows of class c, row C = the mean of
+ *   all counted rows; fp64 sums divided once; an empty class gives zeros and count 0.
+ * osi_maha_scatter: S[F][F] = the sum over the counted rows of a a^T, a = (double)x - m in one rounded subtraction per element, m =
+ *   mean[gt[i]] (OSI_MAHA_WITHIN) or mean[C] (OSI_MAHA_TOTAL); `mean` is an input like any other. accumulate = 1 adds the sum to what
+ *   S holds (row chunks), 0 overwrites. The lower triangle is computed and mirrored: S is bitwise symmetric. The rows are cut into a
+ *   number of splits fixed by (N, F); partial tiles go to the workspace and are added in split order.
+ * osi_maha_factor: Sigma = (1 - a) scale S + a (scale tr S / F) I with a = shrinkage in [0, 1], scale > 0 finite. L = the lower
+ *   Cholesky factor of Sigma, W = L^-1, logdet[0] = 2 sum ln L_ii; strict upper triangles are exact zeros. info[0] = 0 on success,
+ *   else the 1-based index of the first pivot p with !(p > 0) or p = +Inf: L and W are then all zeros and logdet NaN. Right-looking,
+ *   panels of 64 columns: the diagonal block in LDS by one workgroup, the panel by substitution (true divisions), the trailing update
+ *   on the matrix cores; W by rows from the last panel to the first (W L = I is the small residual). 5 ceil(F / 64) launches, a
+ *   function of F alone; after a failed pivot the remaining launches read info and leave. S is read only.
+ * osi_maha_whiten_f32 / _f64: z[M][F] (fp64), z[i] = W x[i] with W lower triangular: tiles above the diagonal are skipped.
+ * osi_maha_sqdist: v[i][c] = sum_j (z[i][j] - zm[c][j])^2 in the difference form, minus[i] (fp64, may be NULL) subtracted, then
+ *   OSI_MAHA_RAW v; OSI_MAHA_SIM_GAUSS exp(-max(v, 0) / (2 F)); OSI_MAHA_SIM_LOGISTIC 1 / (1 + exp(v / (2 F))), in fp64; a NaN
+ *   propagates. Exactly one of out_f32[M][C] (rounded once from fp64) and out_f64[M][C] is non-null. */
+enum { OSI_MAHA_WITHIN = 0, OSI_MAHA_TOTAL = 1 };
+enum { OSI_MAHA_RAW = 0, OSI_MAHA_SIM_GAUSS = 1, OSI_MAHA_SIM_LOGISTIC = 2 };
+#define OSI_MAHA_MAX_F 32768
+size_t osi_maha_workspace(int N, int C, int F);
+int osi_maha_class_means(const float* features, const long long* gt, int N, int C, int F, double* mean, long long* count, void* ws,
+                         size_t ws_bytes, osi_stream_t stream);
+int osi_maha_scatter(const float* features, const long long* gt, const double* mean, int N, int C, int F, int mode, int accumulate,
+                     double* S, void* ws, size_t ws_bytes, osi_stream_t stream);
+int osi_maha_factor(const double* S, int F, double scale, double shrinkage, double* L, double* W, double* logdet, int* info, void* ws,
+                    size_t ws_bytes, osi_stream_t stream);
+int osi_maha_whiten_f32(const float* x, int M, int F, const double* W, double* z, void* ws, size_t ws_bytes, osi_stream_t stream);
+int osi_maha_whiten_f64(const double* x, int M, int F, const double* W, double* z, void* ws, size_t ws_bytes, osi_stream_t stream);
+int osi_maha_sqdist(const double* z, int M, const double* zm, int C, int F, const double* minus, int transform, float* out_f32,
+                    double* out_f64, void* ws, size_t ws_bytes, osi_stream_t stream);
+
 /* ---- optimizer + arena utilities (train.py:356-359 construction, train.py:127,139 zero_grad/step) --- */
 int osi_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,
                   double beta2, double eps, long long step, float grad_scale, osi_stream_t stream);

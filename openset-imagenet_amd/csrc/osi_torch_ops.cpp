@@ -17,6 +17,7 @@
 //   torch.ops.osi.openmax_class_means / _distances / _fit_tails / _wscores / _recalibrate    OpenMax (openset_imagenet/openmax.py)
 //   torch.ops.osi.evm_distances / _fit_rows / _set_cover / _probs                            the Extreme Value Machine (openset_imagenet/evm.py)
 //   torch.ops.osi.knn_topk / knn_class_kth                                                   deep nearest neighbours (openset_imagenet/knn.py)
+//   torch.ops.osi.maha_class_means / _scatter / _factor / _whiten / _sqdist                  Mahalanobis scores (openset_imagenet/mahalanobis.py)
 //   torch.ops.osi.mix_rows_pairs / resnet50_set_mix / proser_loss_fwd_bwd / proser_scores / linear_fwd / linear_bwd    PROSER (openset_imagenet/proser.py)
 //
 // This file contains no arithmetic: every op validates its tensor arguments (device, dtype, contiguity, sizes), takes the CURRENT
@@ -681,6 +682,92 @@ Tensor knn_class_kth(const Tensor& dist, const Tensor& start, int64_t k, const c
     return out;
 }
 
+// ---- Mahalanobis / Relative Mahalanobis (include/osi.h, ABI 25): fp32 features, int64 labels, every fitted tensor fp64
+int maha_dim(int64_t v, const char* what) {
+    TORCH_CHECK(v >= 1 && v <= INT_MAX, "osi::", what, ": sizes out of range");
+    return (int)v;
+}
+
+std::tuple<Tensor, Tensor> maha_class_means(const Tensor& features, const Tensor& gt, int64_t C, Tensor workspace) {
+    need(features, at::kFloat, "features", NATURAL); need(gt, at::kLong, "gt", NATURAL); need(workspace, at::kByte, "workspace", 8);
+    TORCH_CHECK(features.dim() == 2 && gt.dim() == 1 && gt.numel() == features.size(0) && gt.device() == features.device() &&
+                workspace.device() == features.device(), "osi::maha_class_means: features [N,F], gt [N] on one device");
+    const int N = maha_dim(features.size(0), "maha_class_means"), F = maha_dim(features.size(1), "maha_class_means");
+    const int c = maha_dim(C, "maha_class_means");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(features.device());
+    Tensor mean = at::empty({C + 1, (int64_t)F}, features.options().dtype(at::kDouble));
+    Tensor count = at::empty({C + 1}, features.options().dtype(at::kLong));
+    ok(osi_maha_class_means(features.data_ptr<float>(), (const long long*)gt.data_ptr<int64_t>(), N, c, F, mean.data_ptr<double>(),
+                            (long long*)count.data_ptr<int64_t>(), workspace.data_ptr(), (size_t)workspace.numel(), stream_of(features)),
+       "osi_maha_class_means");
+    return {mean, count};
+}
+
+void maha_scatter(const Tensor& features, const Tensor& gt, const Tensor& mean, int64_t mode, bool accumulate, Tensor S, Tensor workspace) {
+    need(features, at::kFloat, "features", NATURAL); need(gt, at::kLong, "gt", NATURAL); need(mean, at::kDouble, "mean", 8);
+    need(S, at::kDouble, "S", 8); need(workspace, at::kByte, "workspace", 8);
+    TORCH_CHECK(features.dim() == 2 && gt.dim() == 1 && gt.numel() == features.size(0) && mean.dim() == 2 && mean.size(0) >= 2 &&
+                mean.size(1) == features.size(1) && S.dim() == 2 && S.size(0) == features.size(1) && S.size(1) == features.size(1),
+                "osi::maha_scatter: features [N,F], gt [N], mean [C+1,F], S [F,F]");
+    TORCH_CHECK(gt.device() == features.device() && mean.device() == features.device() && S.device() == features.device() &&
+                workspace.device() == features.device(), "osi::maha_scatter: tensors on different devices");
+    const int N = maha_dim(features.size(0), "maha_scatter"), F = maha_dim(features.size(1), "maha_scatter");
+    const int C = maha_dim(mean.size(0) - 1, "maha_scatter");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(features.device());
+    ok(osi_maha_scatter(features.data_ptr<float>(), (const long long*)gt.data_ptr<int64_t>(), mean.data_ptr<double>(), N, C, F,
+                        (int)std::min<int64_t>(std::max<int64_t>(mode, -1), INT_MAX), accumulate ? 1 : 0, S.data_ptr<double>(),
+                        workspace.data_ptr(), (size_t)workspace.numel(), stream_of(features)), "osi_maha_scatter");
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> maha_factor(const Tensor& S, double scale, double shrinkage, Tensor workspace) {
+    need(S, at::kDouble, "S", 8); need(workspace, at::kByte, "workspace", 8);
+    TORCH_CHECK(S.dim() == 2 && S.size(0) == S.size(1) && workspace.device() == S.device(), "osi::maha_factor: S is [F,F], workspace on its device");
+    const int F = maha_dim(S.size(0), "maha_factor");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(S.device());
+    Tensor L = at::empty_like(S), W = at::empty_like(S);
+    Tensor logdet = at::empty({1}, S.options()), info = at::empty({1}, S.options().dtype(at::kInt));
+    ok(osi_maha_factor(S.data_ptr<double>(), F, scale, shrinkage, L.data_ptr<double>(), W.data_ptr<double>(), logdet.data_ptr<double>(),
+                       info.data_ptr<int>(), workspace.data_ptr(), (size_t)workspace.numel(), stream_of(S)), "osi_maha_factor");
+    return {L, W, logdet, info};
+}
+
+Tensor maha_whiten(const Tensor& x, const Tensor& W, Tensor workspace) {
+    need(W, at::kDouble, "W", 8); need(workspace, at::kByte, "workspace", 8);
+    TORCH_CHECK(x.defined() && (x.scalar_type() == at::kFloat || x.scalar_type() == at::kDouble), "osi::maha_whiten: x is fp32 or fp64");
+    need(x, x.scalar_type(), "x", NATURAL);
+    TORCH_CHECK(x.dim() == 2 && W.dim() == 2 && W.size(0) == x.size(1) && W.size(1) == x.size(1) && W.device() == x.device() &&
+                workspace.device() == x.device(), "osi::maha_whiten: x [M,F], W [F,F] on one device");
+    const int M = maha_dim(x.size(0), "maha_whiten"), F = maha_dim(x.size(1), "maha_whiten");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+    Tensor z = at::empty({(int64_t)M, (int64_t)F}, W.options());
+    if (x.scalar_type() == at::kFloat)
+        ok(osi_maha_whiten_f32(x.data_ptr<float>(), M, F, W.data_ptr<double>(), z.data_ptr<double>(), workspace.data_ptr(),
+                               (size_t)workspace.numel(), stream_of(x)), "osi_maha_whiten_f32");
+    else
+        ok(osi_maha_whiten_f64(x.data_ptr<double>(), M, F, W.data_ptr<double>(), z.data_ptr<double>(), workspace.data_ptr(),
+                               (size_t)workspace.numel(), stream_of(x)), "osi_maha_whiten_f64");
+    return z;
+}
+
+Tensor maha_sqdist(const Tensor& z, const Tensor& zm, const c10::optional<Tensor>& minus, int64_t transform, bool f64_out, Tensor workspace) {
+    need(z, at::kDouble, "z", 8); need(zm, at::kDouble, "zm", 8); need(workspace, at::kByte, "workspace", 8);
+    TORCH_CHECK(z.dim() == 2 && zm.dim() == 2 && zm.size(1) == z.size(1) && zm.device() == z.device() && workspace.device() == z.device(),
+                "osi::maha_sqdist: z [M,F], zm [C,F] on one device");
+    const double* mp = nullptr;
+    if (minus.has_value() && minus->defined()) {
+        need(*minus, at::kDouble, "minus", 8);
+        TORCH_CHECK(minus->numel() == z.size(0) && minus->device() == z.device(), "osi::maha_sqdist: minus holds one value per row, on the device of z");
+        mp = minus->data_ptr<double>();
+    }
+    const int M = maha_dim(z.size(0), "maha_sqdist"), F = maha_dim(z.size(1), "maha_sqdist"), C = maha_dim(zm.size(0), "maha_sqdist");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(z.device());
+    Tensor out = at::empty({(int64_t)M, (int64_t)C}, z.options().dtype(f64_out ? at::kDouble : at::kFloat));
+    ok(osi_maha_sqdist(z.data_ptr<double>(), M, zm.data_ptr<double>(), C, F, mp, (int)std::min<int64_t>(std::max<int64_t>(transform, -1), INT_MAX),
+                       f64_out ? nullptr : out.data_ptr<float>(), f64_out ? out.data_ptr<double>() : nullptr, workspace.data_ptr(),
+                       (size_t)workspace.numel(), stream_of(z)), "osi_maha_sqdist");
+    return out;
+}
+
 // ---- PROSER (include/osi.h, ABI 23)
 void need_pairs(const Tensor& ref, const Tensor& partner, const Tensor& weight, int64_t B, const char* what) {
     need(partner, at::kInt, "partner", NATURAL); need(weight, at::kFloat, "weight", NATURAL);
@@ -794,6 +881,11 @@ TORCH_LIBRARY(osi, m) {
     m.def("evm_probs(Tensor dist, Tensor shape, Tensor scale, Tensor shift, Tensor ev_start, float multiplier) -> Tensor");
     m.def("knn_topk(Tensor dist, int k, Tensor? skip, Tensor(a!) workspace) -> (Tensor, Tensor)");
     m.def("knn_class_kth(Tensor dist, Tensor start, int k, Tensor? skip, int transform, Tensor(a!) workspace) -> Tensor");
+    m.def("maha_class_means(Tensor features, Tensor gt, int C, Tensor(a!) workspace) -> (Tensor, Tensor)");
+    m.def("maha_scatter(Tensor features, Tensor gt, Tensor mean, int mode, bool accumulate, Tensor(a!) S, Tensor(b!) workspace) -> ()");
+    m.def("maha_factor(Tensor S, float scale, float shrinkage, Tensor(a!) workspace) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("maha_whiten(Tensor x, Tensor W, Tensor(a!) workspace) -> Tensor");
+    m.def("maha_sqdist(Tensor z, Tensor zm, Tensor? minus, int transform, bool f64_out, Tensor(a!) workspace) -> Tensor");
     m.def("openmax_class_means(Tensor features, Tensor logits, Tensor gt, Tensor(a!) workspace) -> (Tensor, Tensor, Tensor)");
     m.def("openmax_distances(Tensor features, Tensor mav, Tensor? cls, int metric) -> Tensor");
     m.def("openmax_fit_tails(Tensor dist, Tensor gt, Tensor correct, int C, int tailsize, Tensor(a!) workspace) -> "
@@ -870,6 +962,11 @@ TORCH_LIBRARY_IMPL(osi, CUDA, m) {
     m.impl("evm_probs", &evm_probs);
     m.impl("knn_topk", &knn_topk);
     m.impl("knn_class_kth", &knn_class_kth);
+    m.impl("maha_class_means", &maha_class_means);
+    m.impl("maha_scatter", &maha_scatter);
+    m.impl("maha_factor", &maha_factor);
+    m.impl("maha_whiten", &maha_whiten);
+    m.impl("maha_sqdist", &maha_sqdist);
     m.impl("mix_rows_pairs", &mix_rows_pairs);
     m.impl("proser_loss_fwd_bwd", &proser_loss_fwd_bwd);
     m.impl("proser_scores", &proser_scores);

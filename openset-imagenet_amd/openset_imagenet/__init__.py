@@ -15,6 +15,8 @@ from . import evm
 from .evm import EVM
 from . import knn
 from .knn import KNN
+from . import mahalanobis
+from .mahalanobis import Mahalanobis
 from . import proser
 from .proser import PROSER
 from .losses import (AverageMeter, EarlyStopping, EntropicOpensetLoss, GarbageLoss, ObjectosphereLoss, SoftmaxLoss)
@@ -23,4 +25,4 @@ from .dataset import ImagenetDataset
 from .pipeline import CanvasDataset
 
 __all__ = ["ResNet50", "ImagenetDataset", "CanvasDataset", "EntropicOpensetLoss", "SoftmaxLoss", "GarbageLoss", "ObjectosphereLoss", "AverageMeter",
-           "EarlyStopping", "OpenMax", "EVM", "KNN", "PROSER", "tools", "util", "train", "metrics", "losses", "dataset"]
+           "EarlyStopping", "OpenMax", "EVM", "KNN", "Mahalanobis", "PROSER", "tools", "util", "train", "metrics", "losses", "dataset"]

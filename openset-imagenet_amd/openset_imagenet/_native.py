@@ -101,6 +101,9 @@ EVM_MAX_TAIL = 4096
 EVM_MAX_COVER_ROWS = 16384
 KNN_RAW, KNN_SIM_COSINE, KNN_SIM_INVERSE = 0, 1, 2
 KNN_MAX_K = 1024
+MAHA_WITHIN, MAHA_TOTAL = 0, 1
+MAHA_RAW, MAHA_SIM_GAUSS, MAHA_SIM_LOGISTIC = 0, 1, 2
+MAHA_MAX_F = 32768
 
 P = c_void_p
 _PD = POINTER(ConvDesc)
@@ -207,6 +210,13 @@ _SIGS = {
     "osi_knn_workspace": (c_size_t, [c_int, c_int, c_int]),
     "osi_knn_topk": (c_int, [P, c_int, c_int, c_longlong, c_int, P, P, P, P, c_size_t, P]),
     "osi_knn_class_kth": (c_int, [P, c_int, c_int, c_longlong, P, c_int, c_int, P, c_int, P, P, c_size_t, P]),
+    "osi_maha_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "osi_maha_class_means": (c_int, [P, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
+    "osi_maha_scatter": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_size_t, P]),
+    "osi_maha_factor": (c_int, [P, c_int, c_double, c_double, P, P, P, P, P, c_size_t, P]),
+    "osi_maha_whiten_f32": (c_int, [P, c_int, c_int, P, P, P, c_size_t, P]),
+    "osi_maha_whiten_f64": (c_int, [P, c_int, c_int, P, P, P, c_size_t, P]),
+    "osi_maha_sqdist": (c_int, [P, c_int, P, c_int, c_int, P, c_int, P, P, P, c_size_t, P]),
     "osi_mix_rows_pairs": (c_int, [P, P, P, c_int, c_size_t, P]),
     "osi_proser_loss_fwd_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, P, P, P, P]),
     "osi_proser_scores": (c_int, [P, P, c_float, c_int, c_int, c_int, P, P]),

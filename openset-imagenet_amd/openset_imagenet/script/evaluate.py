@@ -16,6 +16,10 @@ probabilities) and `unknown` (the probability of the unknown class); with `--osc
 (knn.KNN; `--knn-distance`, `--knn-fraction`), saves it as `{loss}_knn{suffix}.pth` and writes `{loss}_{split}_arr{suffix}_knn.npz`
 with `gt`, `logits`, `features`, `scores` (per class the similarity of the K-th nearest bank row of that class) and `unknown` (the
 distance to the K-th nearest bank row overall).
+`--mahalanobis` (likewise; softmax and entropic losses) fits the Mahalanobis detector (mahalanobis.Mahalanobis: class means and one tied
+covariance in fp64; `--mahalanobis-shrinkage`, `--mahalanobis-relative`) on the features of the training split, saves it as
+`{loss}_mahalanobis{suffix}.pth` and writes `{loss}_{split}_arr{suffix}_mahalanobis.npz` with `gt`, `logits`, `features`, `scores`
+(per class the similarity of the squared distance) and `unknown` (the smallest squared distance of the row).
 `--proser` (likewise; softmax and entropic losses) loads the fine-tuned network, dummy classifier and calibrated bias that
 `python -m openset_imagenet.script.proser` saved as `{loss}_proser{suffix}.pth` (proser.PROSER) and writes
 `{loss}_{split}_arr{suffix}_proser.npz` with `gt`, `logits`, `features` of THAT network, `scores` = probs[:, :C] and `unknown` =
@@ -63,6 +67,12 @@ def get_args(command_line_options=None):
                    "training split's features (softmax and entropic losses); writes {loss}_{split}_arr{suffix}_knn.npz")
     p.add_argument("--knn-distance", choices=["euclidean", "cosine"], default="cosine", help="KNN: distance between feature rows")
     p.add_argument("--knn-fraction", type=float, default=1.0, metavar="F", help="KNN: the share of every class's training rows kept as the bank")
+    p.add_argument("--mahalanobis", action="store_true", help="also score with the Mahalanobis detector fitted on the training split's "
+                   "features (softmax and entropic losses); writes {loss}_{split}_arr{suffix}_mahalanobis.npz")
+    p.add_argument("--mahalanobis-shrinkage", type=float, default=0.0, metavar="A", help="Mahalanobis: shrink the covariance towards a scaled "
+                   "identity by this share in [0, 1] (needed when it is not positive definite)")
+    p.add_argument("--mahalanobis-relative", action="store_true", help="Mahalanobis: subtract the distance under one background Gaussian "
+                   "(Relative Mahalanobis)")
     p.add_argument("--proser", action="store_true", help="also evaluate the PROSER stage saved as {loss}_proser{suffix}.pth (softmax and "
                    "entropic losses) and write {loss}_{split}_arr{suffix}_proser.npz with its scores and the probability of the unknown class")
     args = p.parse_args(command_line_options)
@@ -74,6 +84,10 @@ def get_args(command_line_options=None):
         p.error("--evm needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
     if args.knn is not None and args.loss == "garbage":
         p.error("--knn needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
+    if args.mahalanobis and args.loss == "garbage":
+        p.error("--mahalanobis needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
+    if not 0.0 <= args.mahalanobis_shrinkage <= 1.0:
+        p.error(f"--mahalanobis-shrinkage must lie in [0, 1], got {args.mahalanobis_shrinkage}")
     try:
         args.output_directory = str(args.output_directory).format(args.protocol)
     except Exception:
@@ -205,6 +219,24 @@ def knn_arrays(train_arrays, split_arrays, k, distance="cosine", fraction=1.0, s
                      scores=scores, unknown=unknown)
 
 
+def mahalanobis_arrays(train_arrays, split_arrays, shrinkage=0.0, relative=False):
+    """`--mahalanobis` on arrays: fit the class means and the tied covariance on the training split's `gt` and `features` (mappings as
+    get_arrays' .npz holds them; an already fitted mahalanobis.Mahalanobis is taken as it is) and score one split. Returns (maha,
+    arrays): arrays holds the numpy `gt`, `logits`, `features` of the split, `scores` = the [M, C] class similarities and `unknown` =
+    the [M] smallest squared distances."""
+    from ..mahalanobis import Mahalanobis
+    if isinstance(train_arrays, Mahalanobis):
+        maha = train_arrays
+    else:
+        maha = Mahalanobis(shrinkage=shrinkage, relative=relative)
+        maha.fit(train_arrays["features"], train_arrays["gt"])
+    scores = maha.predict(split_arrays["features"]).cpu().numpy()
+    unknown = maha.unknown_score(split_arrays["features"]).cpu().numpy()
+    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    return maha, dict(gt=host(split_arrays["gt"]), logits=host(split_arrays["logits"]), features=host(split_arrays["features"]),
+                      scores=scores, unknown=unknown)
+
+
 def proser_arrays(proser, split_arrays):
     """`--proser` on arrays: `gt`, `logits`, `features` of one split as the fine-tuned network of `proser` (proser.PROSER) gave them
     (mappings as get_arrays' .npz holds them). Returns the numpy `gt`, `logits`, `features`, `scores` = probs[:, :C] and `unknown` =
@@ -261,7 +293,7 @@ def main(command_line_options=None):
         suffix += "_avg"
     tools.device(model)
     written = {}
-    om = evm = knn = proser = None
+    om = evm = knn = maha = proser = None
     if args.proser:
         proser_path = args.output_directory / f"{args.loss}_proser{suffix}.pth"
         if not proser_path.is_file():
@@ -277,7 +309,10 @@ def main(command_line_options=None):
     if args.knn is not None:
         from ..knn import KNN
         knn = KNN(k=args.knn, distance=args.knn_distance, bank_fraction=args.knn_fraction)               # refuses bad options first
-    if om is not None or evm is not None or knn is not None:
+    if args.mahalanobis:
+        from ..mahalanobis import Mahalanobis
+        maha = Mahalanobis(shrinkage=args.mahalanobis_shrinkage, relative=args.mahalanobis_relative)     # refuses bad options first
+    if om is not None or evm is not None or knn is not None or maha is not None:
         train_ds = _image_loader(args.protocol_directory / f"p{args.protocol}_train.csv", args.imagenet_directory, False, "eval")
         print(f"train dataset len:{len(train_ds)}, labels:{train_ds.table.label_count}")
         loader = torch.utils.data.DataLoader(train_ds, batch_size=args.batch_size, num_workers=args.workers)
@@ -295,6 +330,12 @@ def main(command_line_options=None):
         torch.save(knn.state_dict(), knn_path)
         print(f"KNN (k {args.knn}, {args.knn_distance}, fraction {args.knn_fraction}) keeps a bank of {knn.bank_features.shape[0]} rows; "
               f"saved in: {knn_path}")
+    if maha is not None:
+        maha.fit(t_features, t_gt)
+        maha_path = args.output_directory / f"{args.loss}_mahalanobis{suffix}.pth"
+        torch.save(maha.state_dict(), maha_path)
+        print(f"Mahalanobis (shrinkage {args.mahalanobis_shrinkage}, relative {args.mahalanobis_relative}) fitted on "
+              f"{int(maha.counts[-1])} training samples, log-determinant {float(maha.logdet):.6f}; saved in: {maha_path}")
     if om is not None:
         om.fit(t_features, t_logits, t_gt)
         om_path = args.output_directory / f"{args.loss}_openmax{suffix}.pth"
@@ -340,6 +381,15 @@ def main(command_line_options=None):
             written[split + "_knn"] = knn_file
             if args.oscr:
                 for line in oscr_lines(split, gt, arrays["scores"], tag="KNN "):
+                    print(line)
+        if maha is not None:
+            _, arrays = mahalanobis_arrays(maha, dict(gt=gt, logits=logits, features=features))
+            maha_file = args.output_directory / f"{args.loss}_{split}_arr{suffix}_mahalanobis.npz"
+            np.savez(maha_file, **arrays)
+            print(f"Mahalanobis scores saved in: {maha_file}")
+            written[split + "_mahalanobis"] = maha_file
+            if args.oscr:
+                for line in oscr_lines(split, gt, arrays["scores"], tag="Mahalanobis "):
                     print(line)
         if proser is not None:
             p_gt, p_logits, p_features, _ = get_arrays(model=proser.model, loader=loader)
