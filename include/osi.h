@@ -730,6 +730,54 @@ int osi_maha_whiten_f64(const double* x, int M, int F, const double* W, double* 
 int osi_maha_sqdist(const double* z, int M, const double* zm, int C, int F, const double* minus, int transform, float* out_f32,
                     double* out_f64, void* ws, size_t ws_bytes, osi_stream_t stream);
 
+/* ABI 26. ViM open-set scores (Wang, Li, Feng, Zhang, "ViM: Out-Of-Distribution with Virtual-logit Matching", CVPR 2022;
+ * openset_imagenet/vim.py) and the symmetric eigensolver they need. The method is not part of the reference snapshot; this block is its
+ * definition, tests/vim_oracle.py its numpy restatement. Everything is fp64 except the features and logits (fp32). No floating-point
+ * atomics: every sum has a fixed order that depends on the sizes alone, so every output is bit-identical from run to run. Nothing is
+ * allocated or synchronised; every output element is written by the call; workspace contents are never assumed (ws:
+ * osi_vim_workspace(M, K, F) bytes, 8-byte aligned, 0 for a non-positive argument or F or K > OSI_EIGH_MAX_F; the eigensolver alone
+ * needs more than its first 64 bytes, and for it M and K are anything positive). OSI_ERR_ARG before any launch on a null required
+ * pointer, a non-positive size, a short or misaligned workspace, a bad enum, an alpha that is not finite, F or K > OSI_EIGH_MAX_F and
+ * 2^31 or more ELEMENTS in a matrix (M * F, M * K, M * (C + 1)); longer inputs go in row chunks.
+ *
+ * The eigensolver is parallel cyclic Jacobi on S[F][F], symmetric, of the kind osi_maha_scatter writes (the second moment
+ * sum (x - o)(x - o)^T is osi_maha_scatter with C = 1, OSI_MAHA_TOTAL, mean = [anything; o] and labels 0). The caller owns A[F][F],
+ * Vt[F][F], head[2], info[1] and hands the same ones to the three calls; two rows of OSI_EIGH_MAX_F doubles are the 64 KB of LDS of
+ * one workgroup.
+ * osi_eigh_begin: A <- S, Vt <- I, head[0] = ||S||_F (sum of squares in a fixed order: an entry above 1e154 overflows it),
+ *   head[1] = tau = 2^-52 ||S||_F, info[0] = 1 when the norm is not finite, else 0.
+ * osi_eigh_sweep: one sweep of the round-robin ordering over n = F rounded up to even players: n - 1 rounds (F - 1 for an even F, F
+ *   with one bye each for an odd F) of floor(F / 2) disjoint pairs p < q; round r pairs the fixed player n - 1 with r and
+ *   (r + m) mod (n - 1) with (r - m) mod (n - 1), m = 1 .. n / 2 - 1: a function of F and r alone. Every round takes its angles from the
+ *   matrix as the previous round left it: the pair is rotated iff |a_pq| > tau, with theta = (a_qq - a_pp) / (2 a_pq),
+ *   t = sign(theta) / (|theta| + sqrt(theta^2 + 1)) (sign(0) = 1), c = 1 / sqrt(t^2 + 1), s = t c; A <- J^T A J with a_pq = a_qp = 0
+ *   set exactly, Vt <- J^T Vt (rows of Vt are the vectors). rotations[0] (int64) = the rotations of this sweep. Two launches a round,
+ *   a function of F alone; with info[0] != 0 they leave at once and rotations[0] = 0. Only a_pq with p < q is tested: the two
+ *   triangles of A are kept by different workgroups and may differ in their last bits.
+ * osi_eigh_finish: evals[F] = the diagonal of A, descending, ties by index (a NaN last); evecs[k] = the matching row of Vt, signed so
+ *   that its entry of largest magnitude (the first of equals) is positive. info[0] != 0: NaN values and zero vectors.
+ *   Convergence is the caller's loop: begin, sweep until a sweep reports 0 rotations (one read-back per sweep), finish.
+ * osi_vim_project_f32: z[M][K] (fp64), z[i][k] = sum_j ((double)x[i][j] - origin[j]) R[k][j] for R[K][F], one rounded fp64 subtraction
+ *   per element, the products on the fp64 matrix instruction (the tile routine of ABI 25).
+ * osi_vim_scores: from z[M][K] and logits[M][C] (fp32; not read by OSI_VIM_NORM, which takes NULL and any C), in fp64, row sums in an
+ *   order fixed by K and C: OSI_VIM_NORM n_i = sqrt(sum_k z_ik^2), [M]; OSI_VIM_UNKNOWN alpha n_i - logsumexp(logits_i), [M];
+ *   OSI_VIM_PROBS the max-subtracted softmax of [logits_i, alpha n_i], [M][C + 1], the virtual class last. An infinite maximum is not
+ *   subtracted; a NaN in z or in the logits of a row propagates to every output of the row. Exactly one of out_f32 (rounded once from
+ *   fp64) and out_f64 is non-null. */
+enum { OSI_VIM_NORM = 0, OSI_VIM_UNKNOWN = 1, OSI_VIM_PROBS = 2 };
+#define OSI_EIGH_MAX_F 4096
+size_t osi_vim_workspace(int M, int K, int F);
+int osi_eigh_begin(const double* S, int F, double* A, double* Vt, double* head, int* info, void* ws, size_t ws_bytes,
+                   osi_stream_t stream);
+int osi_eigh_sweep(double* A, double* Vt, int F, const double* head, const int* info, long long* rotations, void* ws, size_t ws_bytes,
+                   osi_stream_t stream);
+int osi_eigh_finish(const double* A, const double* Vt, int F, const int* info, double* evals, double* evecs, void* ws, size_t ws_bytes,
+                    osi_stream_t stream);
+int osi_vim_project_f32(const float* x, const double* origin, int M, int F, const double* R, int K, double* z, void* ws, size_t ws_bytes,
+                        osi_stream_t stream);
+int osi_vim_scores(const double* z, int M, int K, const float* logits, int C, double alpha, int mode, float* out_f32, double* out_f64,
+                   void* ws, size_t ws_bytes, osi_stream_t stream);
+
 /* ---- optimizer + arena utilities (train.py:356-359 construction, train.py:127,139 zero_grad/step) --- */
 int osi_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,
                   double beta2, double eps, long long step, float grad_scale, osi_stream_t stream);

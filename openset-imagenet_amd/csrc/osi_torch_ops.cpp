@@ -18,6 +18,7 @@
 //   torch.ops.osi.evm_distances / _fit_rows / _set_cover / _probs                            the Extreme Value Machine (openset_imagenet/evm.py)
 //   torch.ops.osi.knn_topk / knn_class_kth                                                   deep nearest neighbours (openset_imagenet/knn.py)
 //   torch.ops.osi.maha_class_means / _scatter / _factor / _whiten / _sqdist                  Mahalanobis scores (openset_imagenet/mahalanobis.py)
+//   torch.ops.osi.eigh_begin / eigh_sweep / eigh_finish / vim_project / vim_scores           ViM scores, symmetric eigensolver (openset_imagenet/vim.py)
 //   torch.ops.osi.mix_rows_pairs / resnet50_set_mix / proser_loss_fwd_bwd / proser_scores / linear_fwd / linear_bwd    PROSER (openset_imagenet/proser.py)
 //
 // This file contains no arithmetic: every op validates its tensor arguments (device, dtype, contiguity, sizes), takes the CURRENT
@@ -768,6 +769,80 @@ Tensor maha_sqdist(const Tensor& z, const Tensor& zm, const c10::optional<Tensor
     return out;
 }
 
+// ---- ViM and the symmetric eigensolver (include/osi.h, ABI 26): fp32 features and logits, every fitted tensor fp64
+std::tuple<Tensor, Tensor, Tensor, Tensor> eigh_begin(const Tensor& S, Tensor workspace) {
+    need(S, at::kDouble, "S", 8); need(workspace, at::kByte, "workspace", 8);
+    TORCH_CHECK(S.dim() == 2 && S.size(0) == S.size(1) && workspace.device() == S.device(), "osi::eigh_begin: S is [F,F], workspace on its device");
+    const int F = maha_dim(S.size(0), "eigh_begin");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(S.device());
+    Tensor A = at::empty_like(S), Vt = at::empty_like(S);
+    Tensor head = at::empty({2}, S.options()), info = at::empty({1}, S.options().dtype(at::kInt));
+    ok(osi_eigh_begin(S.data_ptr<double>(), F, A.data_ptr<double>(), Vt.data_ptr<double>(), head.data_ptr<double>(), info.data_ptr<int>(),
+                      workspace.data_ptr(), (size_t)workspace.numel(), stream_of(S)), "osi_eigh_begin");
+    return {A, Vt, head, info};
+}
+
+Tensor eigh_sweep(Tensor A, Tensor Vt, const Tensor& head, const Tensor& info, Tensor workspace) {
+    need(A, at::kDouble, "A", 8); need(Vt, at::kDouble, "Vt", 8); need(head, at::kDouble, "head", 8); need(info, at::kInt, "info", NATURAL);
+    need(workspace, at::kByte, "workspace", 8);
+    TORCH_CHECK(A.dim() == 2 && A.size(0) == A.size(1) && Vt.sizes() == A.sizes() && head.numel() == 2 && info.numel() == 1,
+                "osi::eigh_sweep: A and Vt are [F,F], head holds 2 values, info 1");
+    TORCH_CHECK(Vt.device() == A.device() && head.device() == A.device() && info.device() == A.device() && workspace.device() == A.device(),
+                "osi::eigh_sweep: tensors on different devices");
+    const int F = maha_dim(A.size(0), "eigh_sweep");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
+    Tensor rotations = at::empty({1}, A.options().dtype(at::kLong));
+    ok(osi_eigh_sweep(A.data_ptr<double>(), Vt.data_ptr<double>(), F, head.data_ptr<double>(), info.data_ptr<int>(),
+                      (long long*)rotations.data_ptr<int64_t>(), workspace.data_ptr(), (size_t)workspace.numel(), stream_of(A)), "osi_eigh_sweep");
+    return rotations;
+}
+
+std::tuple<Tensor, Tensor> eigh_finish(const Tensor& A, const Tensor& Vt, const Tensor& info, Tensor workspace) {
+    need(A, at::kDouble, "A", 8); need(Vt, at::kDouble, "Vt", 8); need(info, at::kInt, "info", NATURAL); need(workspace, at::kByte, "workspace", 8);
+    TORCH_CHECK(A.dim() == 2 && A.size(0) == A.size(1) && Vt.sizes() == A.sizes() && info.numel() == 1 && Vt.device() == A.device() &&
+                info.device() == A.device() && workspace.device() == A.device(), "osi::eigh_finish: A and Vt are [F,F], info 1 value, on one device");
+    const int F = maha_dim(A.size(0), "eigh_finish");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
+    Tensor evals = at::empty({(int64_t)F}, A.options()), evecs = at::empty_like(A);
+    ok(osi_eigh_finish(A.data_ptr<double>(), Vt.data_ptr<double>(), F, info.data_ptr<int>(), evals.data_ptr<double>(), evecs.data_ptr<double>(),
+                       workspace.data_ptr(), (size_t)workspace.numel(), stream_of(A)), "osi_eigh_finish");
+    return {evals, evecs};
+}
+
+Tensor vim_project(const Tensor& x, const Tensor& origin, const Tensor& R, Tensor workspace) {
+    need(x, at::kFloat, "x", NATURAL); need(origin, at::kDouble, "origin", 8); need(R, at::kDouble, "R", 8); need(workspace, at::kByte, "workspace", 8);
+    TORCH_CHECK(x.dim() == 2 && R.dim() == 2 && R.size(1) == x.size(1) && origin.numel() == x.size(1) && origin.device() == x.device() &&
+                R.device() == x.device() && workspace.device() == x.device(), "osi::vim_project: x [M,F], origin [F], R [K,F] on one device");
+    const int M = maha_dim(x.size(0), "vim_project"), F = maha_dim(x.size(1), "vim_project"), K = maha_dim(R.size(0), "vim_project");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+    Tensor z = at::empty({(int64_t)M, (int64_t)K}, R.options());
+    ok(osi_vim_project_f32(x.data_ptr<float>(), origin.data_ptr<double>(), M, F, R.data_ptr<double>(), K, z.data_ptr<double>(),
+                           workspace.data_ptr(), (size_t)workspace.numel(), stream_of(x)), "osi_vim_project_f32");
+    return z;
+}
+
+Tensor vim_scores(const Tensor& z, const c10::optional<Tensor>& logits, double alpha, int64_t mode, bool f64_out, Tensor workspace) {
+    need(z, at::kDouble, "z", 8); need(workspace, at::kByte, "workspace", 8);
+    TORCH_CHECK(z.dim() == 2 && workspace.device() == z.device(), "osi::vim_scores: z [M,K], workspace on its device");
+    const int M = maha_dim(z.size(0), "vim_scores"), K = maha_dim(z.size(1), "vim_scores");
+    const float* lp = nullptr;
+    int C = 1;
+    if (logits.has_value() && logits->defined()) {
+        need(*logits, at::kFloat, "logits", NATURAL);
+        TORCH_CHECK(logits->dim() == 2 && logits->size(0) == z.size(0) && logits->device() == z.device(),
+                    "osi::vim_scores: logits [M,C] on the device of z");
+        C = maha_dim(logits->size(1), "vim_scores");
+        lp = logits->data_ptr<float>();
+    }
+    const int md = (int)std::min<int64_t>(std::max<int64_t>(mode, -1), INT_MAX);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(z.device());
+    Tensor out = md == OSI_VIM_PROBS ? at::empty({(int64_t)M, (int64_t)C + 1}, z.options().dtype(f64_out ? at::kDouble : at::kFloat))
+                                     : at::empty({(int64_t)M}, z.options().dtype(f64_out ? at::kDouble : at::kFloat));
+    ok(osi_vim_scores(z.data_ptr<double>(), M, K, lp, C, alpha, md, f64_out ? nullptr : out.data_ptr<float>(),
+                      f64_out ? out.data_ptr<double>() : nullptr, workspace.data_ptr(), (size_t)workspace.numel(), stream_of(z)), "osi_vim_scores");
+    return out;
+}
+
 // ---- PROSER (include/osi.h, ABI 23)
 void need_pairs(const Tensor& ref, const Tensor& partner, const Tensor& weight, int64_t B, const char* what) {
     need(partner, at::kInt, "partner", NATURAL); need(weight, at::kFloat, "weight", NATURAL);
@@ -886,6 +961,11 @@ TORCH_LIBRARY(osi, m) {
     m.def("maha_factor(Tensor S, float scale, float shrinkage, Tensor(a!) workspace) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("maha_whiten(Tensor x, Tensor W, Tensor(a!) workspace) -> Tensor");
     m.def("maha_sqdist(Tensor z, Tensor zm, Tensor? minus, int transform, bool f64_out, Tensor(a!) workspace) -> Tensor");
+    m.def("eigh_begin(Tensor S, Tensor(a!) workspace) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("eigh_sweep(Tensor(a!) A, Tensor(b!) Vt, Tensor head, Tensor info, Tensor(c!) workspace) -> Tensor");
+    m.def("eigh_finish(Tensor A, Tensor Vt, Tensor info, Tensor(a!) workspace) -> (Tensor, Tensor)");
+    m.def("vim_project(Tensor x, Tensor origin, Tensor R, Tensor(a!) workspace) -> Tensor");
+    m.def("vim_scores(Tensor z, Tensor? logits, float alpha, int mode, bool f64_out, Tensor(a!) workspace) -> Tensor");
     m.def("openmax_class_means(Tensor features, Tensor logits, Tensor gt, Tensor(a!) workspace) -> (Tensor, Tensor, Tensor)");
     m.def("openmax_distances(Tensor features, Tensor mav, Tensor? cls, int metric) -> Tensor");
     m.def("openmax_fit_tails(Tensor dist, Tensor gt, Tensor correct, int C, int tailsize, Tensor(a!) workspace) -> "
@@ -967,6 +1047,11 @@ TORCH_LIBRARY_IMPL(osi, CUDA, m) {
     m.impl("maha_factor", &maha_factor);
     m.impl("maha_whiten", &maha_whiten);
     m.impl("maha_sqdist", &maha_sqdist);
+    m.impl("eigh_begin", &eigh_begin);
+    m.impl("eigh_sweep", &eigh_sweep);
+    m.impl("eigh_finish", &eigh_finish);
+    m.impl("vim_project", &vim_project);
+    m.impl("vim_scores", &vim_scores);
     m.impl("mix_rows_pairs", &mix_rows_pairs);
     m.impl("proser_loss_fwd_bwd", &proser_loss_fwd_bwd);
     m.impl("proser_scores", &proser_scores);

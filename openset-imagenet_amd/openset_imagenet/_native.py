@@ -104,6 +104,8 @@ KNN_MAX_K = 1024
 MAHA_WITHIN, MAHA_TOTAL = 0, 1
 MAHA_RAW, MAHA_SIM_GAUSS, MAHA_SIM_LOGISTIC = 0, 1, 2
 MAHA_MAX_F = 32768
+VIM_NORM, VIM_UNKNOWN, VIM_PROBS = 0, 1, 2
+EIGH_MAX_F = 4096
 
 P = c_void_p
 _PD = POINTER(ConvDesc)
@@ -217,6 +219,12 @@ _SIGS = {
     "osi_maha_whiten_f32": (c_int, [P, c_int, c_int, P, P, P, c_size_t, P]),
     "osi_maha_whiten_f64": (c_int, [P, c_int, c_int, P, P, P, c_size_t, P]),
     "osi_maha_sqdist": (c_int, [P, c_int, P, c_int, c_int, P, c_int, P, P, P, c_size_t, P]),
+    "osi_vim_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "osi_eigh_begin": (c_int, [P, c_int, P, P, P, P, P, c_size_t, P]),
+    "osi_eigh_sweep": (c_int, [P, P, c_int, P, P, P, P, c_size_t, P]),
+    "osi_eigh_finish": (c_int, [P, P, c_int, P, P, P, P, c_size_t, P]),
+    "osi_vim_project_f32": (c_int, [P, P, c_int, c_int, P, c_int, P, P, c_size_t, P]),
+    "osi_vim_scores": (c_int, [P, c_int, c_int, P, c_int, c_double, c_int, P, P, P, c_size_t, P]),
     "osi_mix_rows_pairs": (c_int, [P, P, P, c_int, c_size_t, P]),
     "osi_proser_loss_fwd_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, P, P, P, P]),
     "osi_proser_scores": (c_int, [P, P, c_float, c_int, c_int, c_int, P, P]),

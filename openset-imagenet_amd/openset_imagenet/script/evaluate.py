@@ -20,6 +20,10 @@ distance to the K-th nearest bank row overall).
 covariance in fp64; `--mahalanobis-shrinkage`, `--mahalanobis-relative`) on the features of the training split, saves it as
 `{loss}_mahalanobis{suffix}.pth` and writes `{loss}_{split}_arr{suffix}_mahalanobis.npz` with `gt`, `logits`, `features`, `scores`
 (per class the similarity of the squared distance) and `unknown` (the smallest squared distance of the row).
+`--vim` (likewise; softmax and entropic losses) fits ViM (vim.ViM: the principal subspace of the training split's features from the
+device eigensolver, `--vim-dim`; the evaluation network has no logit bias, so the origin is zero), saves it as `{loss}_vim{suffix}.pth`
+and writes `{loss}_{split}_arr{suffix}_vim.npz` with `gt`, `logits`, `features`, `scores` (the known classes' softmax with the virtual
+logit) and `unknown` (alpha * residual norm - logsumexp of the logits).
 `--proser` (likewise; softmax and entropic losses) loads the fine-tuned network, dummy classifier and calibrated bias that
 `python -m openset_imagenet.script.proser` saved as `{loss}_proser{suffix}.pth` (proser.PROSER) and writes
 `{loss}_{split}_arr{suffix}_proser.npz` with `gt`, `logits`, `features` of THAT network, `scores` = probs[:, :C] and `unknown` =
@@ -73,6 +77,11 @@ def get_args(command_line_options=None):
                    "identity by this share in [0, 1] (needed when it is not positive definite)")
     p.add_argument("--mahalanobis-relative", action="store_true", help="Mahalanobis: subtract the distance under one background Gaussian "
                    "(Relative Mahalanobis)")
+    p.add_argument("--vim", action="store_true", help="also score with ViM (virtual-logit matching) fitted on the training split's features "
+                   "and logits (softmax and entropic losses); writes {loss}_{split}_arr{suffix}_vim.npz. The evaluation network has "
+                   "logit_bias=False, so ViM's origin is zero")
+    p.add_argument("--vim-dim", type=int, default=None, metavar="D", help="ViM: the dimension of the principal subspace (default: the "
+                   "paper's rule, 1000 for 2048 or more feature columns, 512 for 768 or more, else half of them)")
     p.add_argument("--proser", action="store_true", help="also evaluate the PROSER stage saved as {loss}_proser{suffix}.pth (softmax and "
                    "entropic losses) and write {loss}_{split}_arr{suffix}_proser.npz with its scores and the probability of the unknown class")
     args = p.parse_args(command_line_options)
@@ -86,6 +95,10 @@ def get_args(command_line_options=None):
         p.error("--knn needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
     if args.mahalanobis and args.loss == "garbage":
         p.error("--mahalanobis needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
+    if args.vim and args.loss == "garbage":
+        p.error("--vim needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
+    if args.vim_dim is not None and args.vim_dim < 1:
+        p.error(f"--vim-dim must be positive, got {args.vim_dim}")
     if not 0.0 <= args.mahalanobis_shrinkage <= 1.0:
         p.error(f"--mahalanobis-shrinkage must lie in [0, 1], got {args.mahalanobis_shrinkage}")
     try:
@@ -237,6 +250,24 @@ def mahalanobis_arrays(train_arrays, split_arrays, shrinkage=0.0, relative=False
                       scores=scores, unknown=unknown)
 
 
+def vim_arrays(train_arrays, split_arrays, dim=None):
+    """`--vim` on arrays: fit ViM on the training split's `gt`, `logits` and `features` (mappings as get_arrays' .npz holds them; an
+    already fitted vim.ViM is taken as it is; the origin is zero, as for a network without a logit bias) and score one split. Returns
+    (vim, arrays): arrays holds the numpy `gt`, `logits`, `features` of the split, `scores` = the [M, C] known columns of the softmax
+    with the virtual logit and `unknown` = the [M] values alpha * residual norm - logsumexp(logits)."""
+    from ..vim import ViM
+    if isinstance(train_arrays, ViM):
+        vim = train_arrays
+    else:
+        vim = ViM(dim=dim)
+        vim.fit(train_arrays["features"], train_arrays["logits"], train_arrays["gt"])
+    scores = vim.predict(split_arrays["features"], split_arrays["logits"]).cpu().numpy()
+    unknown = vim.unknown_score(split_arrays["features"], split_arrays["logits"]).cpu().numpy()
+    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    return vim, dict(gt=host(split_arrays["gt"]), logits=host(split_arrays["logits"]), features=host(split_arrays["features"]),
+                     scores=scores, unknown=unknown)
+
+
 def proser_arrays(proser, split_arrays):
     """`--proser` on arrays: `gt`, `logits`, `features` of one split as the fine-tuned network of `proser` (proser.PROSER) gave them
     (mappings as get_arrays' .npz holds them). Returns the numpy `gt`, `logits`, `features`, `scores` = probs[:, :C] and `unknown` =
@@ -293,7 +324,7 @@ def main(command_line_options=None):
         suffix += "_avg"
     tools.device(model)
     written = {}
-    om = evm = knn = maha = proser = None
+    om = evm = knn = maha = vim = proser = None
     if args.proser:
         proser_path = args.output_directory / f"{args.loss}_proser{suffix}.pth"
         if not proser_path.is_file():
@@ -312,7 +343,10 @@ def main(command_line_options=None):
     if args.mahalanobis:
         from ..mahalanobis import Mahalanobis
         maha = Mahalanobis(shrinkage=args.mahalanobis_shrinkage, relative=args.mahalanobis_relative)     # refuses bad options first
-    if om is not None or evm is not None or knn is not None or maha is not None:
+    if args.vim:
+        from ..vim import ViM
+        vim = ViM(dim=args.vim_dim)                                                                     # refuses bad options first
+    if om is not None or evm is not None or knn is not None or maha is not None or vim is not None:
         train_ds = _image_loader(args.protocol_directory / f"p{args.protocol}_train.csv", args.imagenet_directory, False, "eval")
         print(f"train dataset len:{len(train_ds)}, labels:{train_ds.table.label_count}")
         loader = torch.utils.data.DataLoader(train_ds, batch_size=args.batch_size, num_workers=args.workers)
@@ -336,6 +370,12 @@ def main(command_line_options=None):
         torch.save(maha.state_dict(), maha_path)
         print(f"Mahalanobis (shrinkage {args.mahalanobis_shrinkage}, relative {args.mahalanobis_relative}) fitted on "
               f"{int(maha.counts[-1])} training samples, log-determinant {float(maha.logdet):.6f}; saved in: {maha_path}")
+    if vim is not None:
+        vim.fit(t_features, t_logits, t_gt)                 # logit_bias=False above: the origin is zero
+        vim_path = args.output_directory / f"{args.loss}_vim{suffix}.pth"
+        torch.save(vim.state_dict(), vim_path)
+        print(f"ViM (dim {vim.dim} of {vim.components.shape[0]}) fitted on {vim.count} training samples in {vim.sweeps} Jacobi sweeps, "
+              f"alpha {vim.alpha:.6f}; saved in: {vim_path}")
     if om is not None:
         om.fit(t_features, t_logits, t_gt)
         om_path = args.output_directory / f"{args.loss}_openmax{suffix}.pth"
@@ -390,6 +430,15 @@ def main(command_line_options=None):
             written[split + "_mahalanobis"] = maha_file
             if args.oscr:
                 for line in oscr_lines(split, gt, arrays["scores"], tag="Mahalanobis "):
+                    print(line)
+        if vim is not None:
+            _, arrays = vim_arrays(vim, dict(gt=gt, logits=logits, features=features))
+            vim_file = args.output_directory / f"{args.loss}_{split}_arr{suffix}_vim.npz"
+            np.savez(vim_file, **arrays)
+            print(f"ViM scores saved in: {vim_file}")
+            written[split + "_vim"] = vim_file
+            if args.oscr:
+                for line in oscr_lines(split, gt, arrays["scores"], tag="ViM "):
                     print(line)
         if proser is not None:
             p_gt, p_logits, p_features, _ = get_arrays(model=proser.model, loader=loader)
