@@ -27,12 +27,6 @@ constexpr int OVR_MAX_C = 2048;         // widest row the LDS tiling takes: 16 K
 constexpr int OVR_BLOCKS = 2048;        // workgroups a one-vs-rest launch aims for (8 per CU)
 constexpr int OVR_MAX_CHUNK = 1 << 23;  // most j rows per workgroup: 256 threads x 2^23 stays inside its 32-bit LDS class counters
 
-__device__ __forceinline__ unsigned wave_sum_u(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // lanes that share one row in the row passes: the largest power of two <= min(C, 64), so that a wave reads whole rows side by side
 inline int row_lanes(int C) {
     int l = 1;
@@ -124,8 +118,8 @@ __global__ __launch_bounds__(NT) void k_auc_bin_pairs(const T* __restrict__ vals
         }
         __syncthreads();
     }
-    g = wave_sum_u(g);
-    e = wave_sum_u(e);
+    g = wave_sum(g);
+    e = wave_sum(e);
     if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = g; red[1][threadIdx.x >> 6] = e; }
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -2,7 +2,8 @@
 // 64 x 64 tile of C = A B^T, a wave a 32 x 32 quarter of it (2 x 2 MFMA tiles, 16 accumulator doubles per lane). Both operands are
 // staged through LDS K-major, 16 values of the summed index per stage, the next stage's global loads in flight in registers while this
 // one multiplies. What differs between the callers is only where an operand element comes from (a loader) and where a result element
-// goes (the kernel's epilogue). Everything lives in the including file's anonymous namespace.
+// goes (the kernel's epilogue). The two files' workgroup sum (block_sum) and element limit are here too. Everything lives in the
+// including file's anonymous namespace.
 #pragma once
 #include "osi_common.h"
 
@@ -15,6 +16,20 @@ constexpr int TM = 64;                      // tile edge of gemm_tile
 constexpr int KT = 16;                      // summed indices per LDS stage
 constexpr int LDT = TM + 4;                 // LDS row stride in doubles
 constexpr int EPT = KT * TM / NT;           // operand elements per thread and stage (4)
+constexpr long long MAX_ELEMS = 1ll << 31;  // a call takes fewer elements than this in each of its matrices (include/osi.h)
+
+template <class T>
+__device__ __forceinline__ T block_sum(T v, T* sh) {                   // a fixed tree over the 256 threads; every thread gets the sum
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = NT / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    const T r = sh[0];
+    __syncthreads();
+    return r;
+}
 
 struct Tile {
     double a[KT][LDT];

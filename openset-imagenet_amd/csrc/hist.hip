@@ -28,22 +28,6 @@ inline int row_lanes(int C) {
     return l;
 }
 
-__device__ __forceinline__ double wave_min_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ unsigned wave_sum_u(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ------------------------------------------------------------------------------------------------------------ row values
 // L lanes per row (L = 1 for the norm: its fp64 sum runs in index order in one thread). Rows are walked grid-stride; every lane of a
 // wave runs every shuffle. The workgroup leaves {kn_min, kn_max, unk_min, unk_max} in part[blockIdx.x] and adds its five counters.
@@ -117,10 +101,10 @@ __global__ __launch_bounds__(NT) void k_eval_rows(const T* __restrict__ scores, 
         }
     }
     const int wave = threadIdx.x >> 6;
-    const double v4[4] = {wave_min_d(mn[0]), wave_max_d(mx[0]), wave_min_d(mn[1]), wave_max_d(mx[1])};
+    const double v4[4] = {wave_fmin(mn[0]), wave_fmax(mx[0]), wave_fmin(mn[1]), wave_fmax(mx[1])};
     unsigned u5[5];
 #pragma unroll
-    for (int k = 0; k < 5; ++k) u5[k] = wave_sum_u(cnt[k]);
+    for (int k = 0; k < 5; ++k) u5[k] = wave_sum(cnt[k]);
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) red_d[k][wave] = v4[k];
@@ -151,7 +135,7 @@ __global__ __launch_bounds__(NT) void k_eval_range(const double* __restrict__ pa
         o[0] = fmin(o[0], part[(size_t)p * 4 + 0]); o[1] = fmax(o[1], part[(size_t)p * 4 + 1]);
         o[2] = fmin(o[2], part[(size_t)p * 4 + 2]); o[3] = fmax(o[3], part[(size_t)p * 4 + 3]);
     }
-    o[0] = wave_min_d(o[0]); o[1] = wave_max_d(o[1]); o[2] = wave_min_d(o[2]); o[3] = wave_max_d(o[3]);
+    o[0] = wave_fmin(o[0]); o[1] = wave_fmax(o[1]); o[2] = wave_fmin(o[2]); o[3] = wave_fmax(o[3]);
     if ((threadIdx.x & 63) == 0)
         for (int k = 0; k < 4; ++k) red_d[k][threadIdx.x >> 6] = o[k];
     __syncthreads();

@@ -14,7 +14,7 @@
 // class_kth gives segments of up to 2048 columns to ONE WAVE each instead (k_knn_class_kth_wave: keys in registers, a bitwise select on
 // wave ballots, no LDS and no barrier); the workgroup form above takes the longer ones. Both launches walk all units and pick their own.
 // No floating-point arithmetic but d + 0.0f and the stored transform; no atomics on the tie path; unit choices depend on blockIdx only.
-#include "osi_common.h"
+#include "tail_fit.h"                       // fkey / funkey
 
 #include <math.h>
 
@@ -31,14 +31,12 @@ constexpr unsigned NAN_KEY = 0xffffffffu;
 static_assert(OSI_KNN_MAX_K <= KEEP && OSI_KNN_MAX_K <= 1024, "the sort stage holds 1024 pairs");
 static_assert(E * NW <= 64, "one wave scans the table of wave counts");
 
-// ascending order-preserving key of the canonical value: -Inf < ... < -0 = +0 < ... < +Inf < every NaN
+// ascending order-preserving key (osi_tail::fkey, undone by osi_tail::funkey) of the canonical value:
+// -Inf < ... < -0 = +0 < ... < +Inf < every NaN
 __device__ __forceinline__ unsigned knn_key(float d) {
     const float v = __fadd_rn(d, 0.0f);     // -0 -> +0
-    if (v != v) return NAN_KEY;
-    const unsigned b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    return v != v ? NAN_KEY : osi_tail::fkey(v);
 }
-__device__ __forceinline__ float knn_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
 struct Shared {
     __attribute__((aligned(16))) unsigned key[CAP];
@@ -235,7 +233,7 @@ __global__ __launch_bounds__(NT) void k_knn_topk(const float* __restrict__ dist,
             }
         for (int t = tid; t < K; t += NT) {
             const unsigned long long p = t < count ? pairs[t] : 0ull;
-            out_dist[(size_t)m * K + t] = t < count ? knn_unkey((unsigned)(p >> 32)) : INFINITY;
+            out_dist[(size_t)m * K + t] = t < count ? osi_tail::funkey((unsigned)(p >> 32)) : INFINITY;
             out_idx[(size_t)m * K + t] = t < count ? (long long)(unsigned)p : -1ll;
         }
         __syncthreads();                                    // the next row rewrites the buffer
@@ -329,7 +327,7 @@ __global__ __launch_bounds__(NT) void k_knn_class_kth_wave(const float* __restri
             else if (n <= 512) k = wave_select<8>(row, un.c0, un.c1, sk, rank);
             else if (n <= 1024) k = wave_select<16>(row, un.c0, un.c1, sk, rank);
             else k = wave_select<WE>(row, un.c0, un.c1, sk, rank);
-            v = knn_unkey(k);
+            v = osi_tail::funkey(k);
         }
         if ((threadIdx.x & 63) == 0) out[u] = knn_transform(v, transform);
     }
@@ -349,7 +347,7 @@ __global__ __launch_bounds__(NT) void k_knn_class_kth(const float* __restrict__ 
         float v = INFINITY;
         if (count > 0) {                                    // uniform
             int r;
-            v = knn_unkey(select_rank(sm, count, count < K ? count : K, r));
+            v = osi_tail::funkey(select_rank(sm, count, count < K ? count : K, r));
         }
         if (threadIdx.x == 0) out[u] = knn_transform(v, transform);
         __syncthreads();                                    // the next unit rewrites the buffer and the histograms

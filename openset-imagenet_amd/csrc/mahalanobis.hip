@@ -26,7 +26,6 @@ namespace {
 constexpr int NB = 64;                      // panel width of the factorisation
 constexpr int LDB = NB + 1;
 constexpr int MAX_F = OSI_MAHA_MAX_F;
-constexpr long long MAX_ELEMS = 1ll << 31;
 constexpr size_t WS_HEAD = 64;              // bytes in front of the scatter partials: [0] the trace
 constexpr int MAX_SPLITS = 64;
 static_assert(NB == TM, "panel offsets are tile offsets");
@@ -38,19 +37,6 @@ __device__ __forceinline__ void tri_tile(int t, int& bi, int& bj) {
     while ((long long)b * (b + 1) / 2 > t) --b;
     bi = b;
     bj = t - (int)((long long)b * (b + 1) / 2);
-}
-
-template <class T>
-__device__ __forceinline__ T block_sum_ordered(T v, T* sh) {          // a fixed tree over the 256 threads; every thread gets the sum
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = NT / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    const T r = sh[0];
-    __syncthreads();
-    return r;
 }
 
 // ------------------------------------------------------------------------------------------------------------------- means
@@ -153,7 +139,7 @@ __global__ __launch_bounds__(NT) void k_trace(const double* __restrict__ S, int 
     __shared__ double sh[NT];
     double s = 0.0;
     for (int i = threadIdx.x; i < F; i += NT) s += S[(size_t)i * (size_t)F + (size_t)i];
-    s = block_sum_ordered(s, sh);
+    s = block_sum(s, sh);
     if (threadIdx.x == 0) {
         head[0] = s;
         info[0] = 0;
@@ -304,7 +290,7 @@ __global__ __launch_bounds__(NT) void k_finish(double* __restrict__ L, double* _
     if (blockIdx.x != 0) return;
     double s = 0.0;
     for (int i = threadIdx.x; i < F; i += NT) s += log(L[(size_t)i * (size_t)F + (size_t)i]);
-    s = block_sum_ordered(s, sh);
+    s = block_sum(s, sh);
     if (threadIdx.x == 0) logdet[0] = 2.0 * s;
 }
 
@@ -330,11 +316,6 @@ __global__ __launch_bounds__(NT) void k_whiten(const T* __restrict__ x, int M, i
 
 // ------------------------------------------------------------------------------------------------------------------ sqdist
 constexpr int SQ_R = 4;                     // rows a wave scores against one class at a time
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __global__ __launch_bounds__(NT) void k_maha_sqdist(const double* __restrict__ z, int M, const double* __restrict__ zm, int C, int F,
                                                    const double* __restrict__ minus, int transform, float* __restrict__ o32,
                                                    double* __restrict__ o64) {
@@ -357,7 +338,7 @@ __global__ __launch_bounds__(NT) void k_maha_sqdist(const double* __restrict__ z
             }
         }
 #pragma unroll
-        for (int r = 0; r < SQ_R; ++r) acc[r] = wave_sum_f64(acc[r]);
+        for (int r = 0; r < SQ_R; ++r) acc[r] = wave_sum(acc[r]);
         double v = acc[0];
 #pragma unroll
         for (int r = 1; r < SQ_R; ++r) v = lane == r ? acc[r] : v;

@@ -31,13 +31,6 @@ inline int stride_blocks(long long n) {
     return (int)(b < 1 ? 1 : (b > MAX_BLOCKS ? MAX_BLOCKS : b));
 }
 
-using osi_tail::wave_sum_d;
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 using osi_tail::fkey;
 
 // ----------------------------------------------------------------------------------------------------------- class means
@@ -302,8 +295,8 @@ __global__ __launch_bounds__(NT) void k_om_recal(const float* __restrict__ logit
                     unk += (double)vc * (1.0 - om);
                     mx = fmax(mx, (double)vc * om);
                 }
-                unk = wave_sum_d(unk);
-                mx = fmax(wave_max_d(mx), unk);
+                unk = wave_sum(unk);
+                mx = fmax(wave_fmax(mx), unk);
                 double s = 0.0;
                 for (int c = lane; c < C; c += 64) {
                     const int r = rk[c];
@@ -311,7 +304,7 @@ __global__ __launch_bounds__(NT) void k_om_recal(const float* __restrict__ logit
                     s += exp((double)v[c] * om - mx);
                 }
                 const double eu = exp(unk - mx);
-                s = wave_sum_d(s) + eu;
+                s = wave_sum(s) + eu;
                 for (int c = lane; c < C; c += 64) {
                     const int r = rk[c];
                     const double om = r < a ? 1.0 - (double)wr[c] * (double)(a - r) / (double)a : 1.0;

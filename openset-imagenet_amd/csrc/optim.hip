@@ -298,10 +298,7 @@ template <> struct NormAcc<OSI_NORM_L2> {
     double v = 0.0;
     __device__ __forceinline__ void add(float x, bool on) { const double d = (double)x; v += on ? d * d : 0.0; }
     __device__ __forceinline__ void merge(unsigned long long bits) { v += __longlong_as_double((long long)bits); }
-    __device__ __forceinline__ void wave() {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    }
+    __device__ __forceinline__ void wave() { v = wave_sum(v); }
     __device__ __forceinline__ unsigned long long bits() const { return (unsigned long long)__double_as_longlong(v); }
     __device__ __forceinline__ double norm() const { return sqrt(v); }
 };

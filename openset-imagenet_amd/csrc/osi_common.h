@@ -121,13 +121,37 @@ __device__ __forceinline__ float osi_max(float a, float b) { return __builtin_el
 __device__ __forceinline__ float osi_relu(float t) { return __builtin_elementwise_maximum(t, 0.f); }
 __device__ __forceinline__ f32x4 osi_relu(f32x4 t) { return __builtin_elementwise_maximum(t, f32x4{0.f, 0.f, 0.f, 0.f}); }
 
+// Xor butterflies over the 64 lanes of a wave. a + b == b + a, so every lane ends with the same bits.
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ unsigned wave_sum(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// Two behaviours towards a NaN, both relied on, hence two names. wave_max KEEPS one (osi_max): a diverged logit reaches the loss as
+// a NaN. wave_fmax / wave_fmin SKIP one (fmax / fmin): their callers want the range of the finite values, or find the NaN again in
+// the sums that follow.
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = osi_max(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ double wave_fmax(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ double wave_fmin(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
     return v;
 }

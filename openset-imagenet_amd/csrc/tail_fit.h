@@ -17,12 +17,6 @@ constexpr int EXPAND_MAX = 1100;            // bracket doublings / halvings: mor
 constexpr int SOLVE_MAX = 128;              // Newton / bisection steps inside a bracket of one binade (53 bisections exhaust it)
 static_assert(MAX_TAIL == OSI_OPENMAX_MAX_TAIL && MAX_TAIL == OSI_EVM_MAX_TAIL, "one tail capacity");
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);      // a + b == b + a: every lane ends with the same bits
-    return v;
-}
-
 // order-preserving key of a finite float (larger value = larger unsigned key) and back
 __device__ __forceinline__ unsigned fkey(float d) {
     const unsigned b = __float_as_uint(d);
@@ -59,7 +53,7 @@ __device__ __forceinline__ FitSums fit_sums(const double* __restrict__ lnx, int 
         s1 += e * l;
         s2 += e * l * l;
     }
-    s0 = wave_sum_d(s0); s1 = wave_sum_d(s1); s2 = wave_sum_d(s2);
+    s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2);
     __syncthreads();                                        // the previous call's readers are done with red
     if ((threadIdx.x & 63) == 0) {
         const int w = threadIdx.x >> 6;
@@ -163,7 +157,7 @@ __device__ __forceinline__ Result tail_fit(Shared& sm, long long N, int T, Cand 
         const double lmax = lnx[K - 1];
         double ls = 0.0;
         for (int t = tid; t < K; t += NT) ls += lnx[t];
-        ls = wave_sum_d(ls);
+        ls = wave_sum(ls);
         if ((tid & 63) == 0) sm.red[0][tid >> 6] = ls;
         __syncthreads();
         double lmean = sm.red[0][0];

@@ -19,23 +19,9 @@
 namespace {
 
 constexpr int MAX_F = OSI_EIGH_MAX_F;
-constexpr long long MAX_ELEMS = 1ll << 31;
 constexpr size_t WS_HEAD = 64;              // bytes every call asks for
 constexpr int NORM_BLOCKS = 1024;           // most partial sums of the Frobenius norm
 static_assert(2 * MAX_F * sizeof(double) <= 65536, "two rows of the widest matrix fit the LDS of one workgroup");
-
-template <class T>
-__device__ __forceinline__ T block_sum(T v, T* sh) {                   // a fixed tree over the 256 threads; every thread gets the sum
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = NT / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    const T r = sh[0];
-    __syncthreads();
-    return r;
-}
 
 // ---- the round-robin ordering: n players (n even), n - 1 rounds; player n - 1 stays, the others turn. Pair m of round r -------------
 __device__ __forceinline__ void pair_of(int n, int r, int m, int& p, int& q) {
@@ -277,16 +263,7 @@ __global__ __launch_bounds__(NT) void k_vim_project(const float* __restrict__ x,
 }
 
 // ------------------------------------------------------------------------------------------------------------------- scores
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_max_f64(double v) {            // fmax: a NaN is skipped here and comes back through the sums
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
+// the maximum of the logits is taken with wave_fmax: a NaN is skipped there and comes back through the sums
 __global__ __launch_bounds__(NT) void k_vim_scores(const double* __restrict__ z, int M, int K, const float* __restrict__ logits, int C,
                                                   double alpha, int mode, float* __restrict__ o32, double* __restrict__ o64) {
     const int lane = threadIdx.x & 63;
@@ -294,7 +271,7 @@ __global__ __launch_bounds__(NT) void k_vim_scores(const double* __restrict__ z,
         const double* zr = z + (size_t)i * (size_t)K;
         double sq = 0.0;
         for (int k = lane; k < K; k += 64) sq = fma(zr[k], zr[k], sq);
-        const double norm = sqrt(wave_sum_f64(sq));
+        const double norm = sqrt(wave_sum(sq));
         if (mode == OSI_VIM_NORM) {
             if (lane == 0) {
                 if (o32) o32[i] = (float)norm;
@@ -306,12 +283,12 @@ __global__ __launch_bounds__(NT) void k_vim_scores(const double* __restrict__ z,
         const float* lr = logits + (size_t)i * (size_t)C;
         double mx = -INFINITY;
         for (int c = lane; c < C; c += 64) mx = fmax(mx, (double)lr[c]);
-        mx = wave_max_f64(mx);
+        mx = wave_fmax(mx);
         if (mode == OSI_VIM_PROBS) mx = fmax(mx, v);
         const double shift = (mx - mx == 0.0) ? mx : 0.0;   // an infinite maximum is not subtracted
         double se = 0.0;
         for (int c = lane; c < C; c += 64) se += exp((double)lr[c] - shift);
-        se = wave_sum_f64(se);
+        se = wave_sum(se);
         if (mode == OSI_VIM_UNKNOWN) {
             const double u = v - (shift + log(se));
             if (lane == 0) {

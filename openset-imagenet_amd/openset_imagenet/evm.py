@@ -23,22 +23,18 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .openmax import _matrix
+from ._detector import _DESC_LIMIT, Detector, _check_chunk, _chunk_rows, _fit_shapes, _host_labels, _launch_rows, _matrix
 from .util import _labels_on_device, _need_gpu
 
 _METRICS = {"euclidean": N.EVM_EUCLIDEAN, "cosine": N.EVM_COSINE}
-_STATE = ("ev_features", "ev_shape", "ev_scale", "ev_shift", "ev_start", "flags")
-_SETTINGS = ("tailsize", "cover_threshold", "distance_multiplier", "distance", "use_negatives")
-_DESC_LIMIT = 1 << 31           # the kernels' buffer descriptors are 32-bit (include/osi.h)
-_CHUNK_BYTES = 1 << 29          # distance matrices are produced in row chunks of at most this size
 
 
-def _chunk_rows(columns):
-    """Rows of a [rows, columns] fp32 distance chunk: under the descriptor limit and under _CHUNK_BYTES."""
-    return max(1, min(_CHUNK_BYTES, _DESC_LIMIT - 1) // (4 * columns))
+class EVM(Detector):
+    _STATE = ("ev_features", "ev_shape", "ev_scale", "ev_shift", "ev_start", "flags")
+    _SETTINGS = ("tailsize", "cover_threshold", "distance_multiplier", "distance", "use_negatives")
+    _DTYPES = dict(ev_features=torch.float32, ev_shape=torch.float64, ev_scale=torch.float64, ev_shift=torch.float64,
+                   ev_start=torch.int64, flags=torch.int64)
 
-
-class EVM:
     def __init__(self, tailsize=1000, cover_threshold=None, distance_multiplier=0.5, distance="cosine", use_negatives=True):
         if isinstance(tailsize, bool) or not isinstance(tailsize, int):
             raise TypeError(f"tailsize must be an int, got {type(tailsize).__name__}")
@@ -60,48 +56,17 @@ class EVM:
             raise ValueError(f"distance must be one of {sorted(_METRICS)}, got {distance!r}")
         self.tailsize, self.cover_threshold, self.distance_multiplier = tailsize, cover_threshold, float(distance_multiplier)
         self.distance, self.use_negatives = distance, bool(use_negatives)
-        for name in _STATE:
+        for name in self._STATE:
             setattr(self, name, None)
         self._ws = None
-
-    # ------------------------------------------------------------------------------------------------------------ helpers
-    @property
-    def is_fitted(self):
-        return self.ev_features is not None
-
-    def _workspace(self, r, n, f, dev):
-        need = N.lib().osi_evm_workspace(r, n, f)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        return self._ws
-
-    def _require_fit(self, what):
-        if not self.is_fitted:
-            raise ValueError(f"EVM.{what} before fit: call fit(features, gt) or load_state_dict first")
-
-    def _on(self, dev):
-        """The fitted tensors on `dev` (a state dict loads on the host; the first computing call moves them)."""
-        if self.ev_features.device != dev:
-            for name in _STATE:
-                setattr(self, name, getattr(self, name).to(dev))
 
     # ---------------------------------------------------------------------------------------------------------------- fit
     def fit(self, features, gt):
         """One Weibull per row of a known class from features [N, F] and labels [N] of the training split; the extreme vectors of
         every class 0 .. max(gt). Rows with labels below 0 are negatives of every class (dropped when use_negatives is False).
         Returns self."""
-        f_shape = tuple(torch.as_tensor(features).shape)
-        if len(f_shape) != 2:
-            raise ValueError(f"features must be a matrix [N_samples, N_columns], got shape {f_shape}")
-        if len(gt) != f_shape[0]:
-            raise ValueError(f"features and gt disagree on the number of samples: {f_shape[0]}, {len(gt)}")
-        if f_shape[0] == 0 or f_shape[1] == 0:
-            raise ValueError(f"features must not be empty, got shape {f_shape}")
-        y_host = (gt.detach().cpu().numpy() if isinstance(gt, torch.Tensor) else np.asarray(gt)).astype(np.int64)
-        if y_host.ndim != 1:
-            raise ValueError(f"gt must be a vector [N_samples], got shape {y_host.shape}")
-        if y_host.max() < 0:
-            raise ValueError("gt holds no known class (every label is negative)")
+        f_shape = _fit_shapes(features, gt)
+        y_host = _host_labels(gt)
         c = int(y_host.max()) + 1
         keep = None
         if not self.use_negatives and (y_host < 0).any():
@@ -124,7 +89,7 @@ class EVM:
         y = _labels_on_device(y_host, dev)
         metric, mult = _METRICS[self.distance], self.distance_multiplier
         step = _chunk_rows(n)
-        ws = self._workspace(max(len(i) for i in rows), n, f_dim, dev)
+        ws = self._workspace(N.lib().osi_evm_workspace(max(len(i) for i in rows), n, f_dim), dev)
         per_class, flags = [], torch.zeros(2, dtype=torch.int64, device=dev)
         for k, idx in enumerate(rows):                          # nothing is read back in here
             if len(idx) == 0:
@@ -173,21 +138,16 @@ class EVM:
         c = self.ev_start.numel() - 1
         if len(f_shape) != 2 or f_shape[1] != f_dim:
             raise ValueError(f"features must be [M, {f_dim}] (the width fit saw), got shape {f_shape}")
-        if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1):
-            raise ValueError(f"chunk must be a positive int or None, got {chunk!r}")
+        _check_chunk(chunk)
         dev = _need_gpu("EVM.predict")
         self._on(dev)
         m = f_shape[0]
         if m == 0 or v == 0:
             return torch.zeros(m, c, dtype=torch.float32, device=dev)
-        if m * f_dim * 4 >= _DESC_LIMIT:
-            step_f = max(1, (_DESC_LIMIT - 1) // (4 * f_dim))
-        else:
-            step_f = m
-        step = min(_chunk_rows(v), step_f, chunk or m)
+        step = min(_chunk_rows(v), _launch_rows(m, f_dim), chunk or m)
         ops = N.ops()
         q = _matrix(features, dev, "features")
-        ws = self._workspace(min(step, m), v, f_dim, dev)
+        ws = self._workspace(N.lib().osi_evm_workspace(min(step, m), v, f_dim), dev)
         out = torch.empty(m, c, dtype=torch.float32, device=dev)
         for r0 in range(0, m, step):
             dist = ops.evm_distances(q[r0:r0 + step], self.ev_features, _METRICS[self.distance], ws)
@@ -195,23 +155,10 @@ class EVM:
         return out
 
     # -------------------------------------------------------------------------------------------------------------- state
-    def state_dict(self):
-        """Plain CPU tensors and the five settings; torch.save-able."""
-        self._require_fit("state_dict")
-        sd = {name: getattr(self, name).detach().cpu().clone() for name in _STATE}
-        sd.update({k: getattr(self, k) for k in _SETTINGS})
-        return sd
-
-    def load_state_dict(self, sd):
-        missing = [k for k in _STATE + _SETTINGS if k not in sd]
-        if missing:
-            raise ValueError(f"state dict lacks {missing}")
+    def _restore(self, sd, tensors):
         cover = sd["cover_threshold"]
         EVM.__init__(self, int(sd["tailsize"]), None if cover is None else float(cover), float(sd["distance_multiplier"]), sd["distance"],
                      bool(sd["use_negatives"]))
-        dtypes = dict(ev_features=torch.float32, ev_shape=torch.float64, ev_scale=torch.float64, ev_shift=torch.float64,
-                      ev_start=torch.int64, flags=torch.int64)
-        tensors = {k: torch.as_tensor(sd[k]).detach().to(dtypes[k]).contiguous().clone() for k in _STATE}
         if tensors["ev_features"].dim() != 2:
             raise ValueError(f"state dict: ev_features must be [V, F], got shape {tuple(tensors['ev_features'].shape)}")
         v = tensors["ev_features"].shape[0]
@@ -223,6 +170,3 @@ class EVM:
             raise ValueError(f"state dict: ev_start must be [C + 1] offsets rising from 0 to {v}, got {start.tolist()}")
         if tuple(tensors["flags"].shape) != (2,):
             raise ValueError(f"state dict: flags must hold two entries, got shape {tuple(tensors['flags'].shape)}")
-        for k, t in tensors.items():
-            setattr(self, k, t)
-        return self

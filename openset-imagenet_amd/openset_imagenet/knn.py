@@ -28,15 +28,11 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .evm import _chunk_rows
-from .openmax import _matrix
+from ._detector import _DESC_LIMIT, Detector, _check_chunk, _chunk_rows, _fit_shapes, _host_labels, _launch_rows, _matrix
 from .util import _labels_on_device, _need_gpu
 
 _METRICS = {"euclidean": N.EVM_EUCLIDEAN, "cosine": N.EVM_COSINE}
 _TRANSFORMS = {"euclidean": N.KNN_SIM_INVERSE, "cosine": N.KNN_SIM_COSINE}
-_STATE = ("bank_features", "bank_start", "bank_rows", "bank_labels")
-_SETTINGS = ("k", "distance", "bank_fraction", "seed")
-_DESC_LIMIT = 1 << 31           # the distance kernel's buffer descriptors are 32-bit (include/osi.h)
 
 
 def bank_selection(gt, bank_fraction=1.0, seed=0):
@@ -63,7 +59,13 @@ def bank_selection(gt, bank_fraction=1.0, seed=0):
     return order.astype(np.int64), start
 
 
-class KNN:
+class KNN(Detector):
+    _STATE = ("bank_features", "bank_start", "bank_rows", "bank_labels")
+    _OPTIONAL = ("threshold",)
+    _SETTINGS = ("k", "distance", "bank_fraction", "seed")
+    _DTYPES = dict(bank_features=torch.float32, bank_start=torch.int64, bank_rows=torch.int64, bank_labels=torch.int64,
+                   threshold=torch.float32)
+
     def __init__(self, k=10, distance="cosine", bank_fraction=1.0, seed=0):
         if isinstance(k, bool) or not isinstance(k, int):
             raise TypeError(f"k must be an int, got {type(k).__name__}")
@@ -78,35 +80,11 @@ class KNN:
         if isinstance(seed, bool) or not isinstance(seed, int):
             raise TypeError(f"seed must be an int, got {type(seed).__name__}")
         self.k, self.distance, self.bank_fraction, self.seed = k, distance, float(bank_fraction), seed
-        for name in _STATE:
+        for name in self._STATE + self._OPTIONAL:
             setattr(self, name, None)
-        self.threshold = None
         self._ws = None
 
     # ------------------------------------------------------------------------------------------------------------ helpers
-    @property
-    def is_fitted(self):
-        return self.bank_features is not None
-
-    def _workspace(self, m, n, f, dev):
-        lib = N.lib()
-        need = max(lib.osi_evm_workspace(m, n, f), lib.osi_knn_workspace(m, n, self.k))
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        return self._ws
-
-    def _require_fit(self, what):
-        if not self.is_fitted:
-            raise ValueError(f"KNN.{what} before fit: call fit(features, gt) or load_state_dict first")
-
-    def _on(self, dev):
-        """The fitted tensors on `dev` (a state dict loads on the host; the first computing call moves them)."""
-        if self.bank_features.device != dev:
-            for name in _STATE:
-                setattr(self, name, getattr(self, name).to(dev))
-            if self.threshold is not None:
-                self.threshold = self.threshold.to(dev)
-
     def _queries(self, features, chunk, what, exclude_self=False):
         """Checks of every scoring call, before any GPU work: (shape of the queries, device, rows per launch)."""
         self._require_fit(what)
@@ -114,20 +92,19 @@ class KNN:
         n, f_dim = self.bank_features.shape
         if len(f_shape) != 2 or f_shape[1] != f_dim:
             raise ValueError(f"features must be [M, {f_dim}] (the width fit saw), got shape {f_shape}")
-        if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1):
-            raise ValueError(f"chunk must be a positive int or None, got {chunk!r}")
+        _check_chunk(chunk)
         if exclude_self and f_shape[0] != n:
             raise ValueError(f"exclude_self=True takes the bank itself as queries ({n} rows, in bank order), got {f_shape[0]} rows")
         dev = _need_gpu(f"KNN.{what}")
         self._on(dev)
         m = f_shape[0]
-        step_f = max(1, (_DESC_LIMIT - 1) // (4 * f_dim)) if m * f_dim * 4 >= _DESC_LIMIT else max(m, 1)
-        return m, dev, min(_chunk_rows(n), step_f, chunk or max(m, 1))
+        return m, dev, min(_chunk_rows(n), _launch_rows(m, f_dim), chunk or max(m, 1))
 
     def _chunks(self, q, m, step, dev):
         """(first row, distance chunk [rows, N]) over the query rows; the workspace is shared by all of them."""
         n, f_dim = self.bank_features.shape
-        ws = self._workspace(min(step, m), n, f_dim, dev)
+        lib, rows = N.lib(), min(step, m)
+        ws = self._workspace(max(lib.osi_evm_workspace(rows, n, f_dim), lib.osi_knn_workspace(rows, n, self.k)), dev)
         for r0 in range(0, m, step):
             yield r0, N.ops().evm_distances(q[r0:r0 + step], self.bank_features, _METRICS[self.distance], ws), ws
 
@@ -135,18 +112,8 @@ class KNN:
     def fit(self, features, gt):
         """The bank from features [N, F] and labels [N] of the training split: the rows of the classes 0 .. max(gt), sorted by class.
         Rows with labels below 0 (negatives) are dropped. Forgets an earlier calibration. Returns self."""
-        f_shape = tuple(torch.as_tensor(features).shape)
-        if len(f_shape) != 2:
-            raise ValueError(f"features must be a matrix [N_samples, N_columns], got shape {f_shape}")
-        if len(gt) != f_shape[0]:
-            raise ValueError(f"features and gt disagree on the number of samples: {f_shape[0]}, {len(gt)}")
-        if f_shape[0] == 0 or f_shape[1] == 0:
-            raise ValueError(f"features must not be empty, got shape {f_shape}")
-        y_host = (gt.detach().cpu().numpy() if isinstance(gt, torch.Tensor) else np.asarray(gt)).astype(np.int64)   # the one readback
-        if y_host.ndim != 1:
-            raise ValueError(f"gt must be a vector [N_samples], got shape {y_host.shape}")
-        if y_host.max() < 0:
-            raise ValueError("gt holds no known class (every label is negative)")
+        f_shape = _fit_shapes(features, gt)
+        y_host = _host_labels(gt)                           # the one readback
         rows, start = bank_selection(y_host, self.bank_fraction, self.seed)
         n, f_dim = len(rows), f_shape[1]
         if n * f_dim * 4 >= _DESC_LIMIT:
@@ -222,21 +189,9 @@ class KNN:
         return self
 
     # -------------------------------------------------------------------------------------------------------------- state
-    def state_dict(self):
-        """Plain CPU tensors, the four settings and the threshold (a 0-d tensor or None); torch.save-able."""
-        self._require_fit("state_dict")
-        sd = {name: getattr(self, name).detach().cpu().clone() for name in _STATE}
-        sd.update({k: getattr(self, k) for k in _SETTINGS})
-        sd["threshold"] = None if self.threshold is None else self.threshold.detach().cpu().clone()
-        return sd
-
-    def load_state_dict(self, sd):
-        missing = [k for k in _STATE + _SETTINGS + ("threshold",) if k not in sd]
-        if missing:
-            raise ValueError(f"state dict lacks {missing}")
+    def _restore(self, sd, tensors):
+        """The threshold of the state dict is a 0-d tensor, or None before `calibrate`."""
         KNN.__init__(self, int(sd["k"]), sd["distance"], float(sd["bank_fraction"]), int(sd["seed"]))
-        dtypes = dict(bank_features=torch.float32, bank_start=torch.int64, bank_rows=torch.int64, bank_labels=torch.int64)
-        tensors = {k: torch.as_tensor(sd[k]).detach().to(dtypes[k]).contiguous().clone() for k in _STATE}
         if tensors["bank_features"].dim() != 2:
             raise ValueError(f"state dict: bank_features must be [N, F], got shape {tuple(tensors['bank_features'].shape)}")
         n = tensors["bank_features"].shape[0]
@@ -246,12 +201,6 @@ class KNN:
         start = tensors["bank_start"]
         if start.dim() != 1 or start.numel() < 2 or int(start[0]) != 0 or int(start[-1]) != n or bool((start[1:] < start[:-1]).any()):
             raise ValueError(f"state dict: bank_start must be [C + 1] offsets rising from 0 to {n}, got {start.tolist()}")
-        threshold = sd["threshold"]
-        if threshold is not None:
-            threshold = torch.as_tensor(threshold).detach().to(torch.float32).clone()
-            if threshold.dim() != 0:
-                raise ValueError(f"state dict: threshold must be a scalar or None, got shape {tuple(threshold.shape)}")
-        for k, t in tensors.items():
-            setattr(self, k, t)
-        self.threshold = threshold
-        return self
+        threshold = tensors["threshold"]
+        if threshold is not None and threshold.dim() != 0:
+            raise ValueError(f"state dict: threshold must be a scalar or None, got shape {tuple(threshold.shape)}")

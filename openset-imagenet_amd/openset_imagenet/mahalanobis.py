@@ -21,23 +21,22 @@ is no CPU path. Inputs may be numpy arrays or torch tensors, on the host or on t
 and the factorisation's status, the scoring calls read nothing back. The fitted state - `means [C + 1, F]` (row C the background mean),
 `counts [C + 1]`, `L`, `W` `[F, F]`, `logdet [1]`, `whitened_means [C, F]` and, when relative, `L0`, `W0`, `logdet0`,
 `whitened_mean0 [1, F]` - are fp64 device tensors the caller may read. Rows go through the kernels in chunks: scoring in the chunks of
-evm._chunk_rows (the fp64 whitened rows of a chunk are twice its size), fit in chunks under the ABI's limit of 2^31 elements per
+_detector._chunk_rows (the fp64 whitened rows of a chunk are twice its size), fit in chunks under the ABI's limit of 2^31 elements per
 matrix (a million rows at F = 2048; past it the scatter accumulates over the chunks and the means are put together from the chunks'
 means and counts). Out of scope: per-class covariances, low-rank variants, input pre-processing, multi-GPU fits."""
 import torch
 
 from . import _native as N
-from .evm import _chunk_rows
-from .openmax import _matrix
+from ._detector import _MAX_ELEMS, Detector, _check_chunk, _chunk_rows, _fit_shapes, _matrix
 from .util import _labels_on_device, _need_gpu
 
-_STATE = ("means", "counts", "L", "W", "logdet", "whitened_means")
-_BACKGROUND = ("L0", "W0", "logdet0", "whitened_mean0")
-_SETTINGS = ("shrinkage", "relative")
-_MAX_ELEMS = 1 << 31            # a call takes fewer elements than this in each of its matrices (include/osi.h)
 
+class Mahalanobis(Detector):
+    _STATE = ("means", "counts", "L", "W", "logdet", "whitened_means")
+    _OPTIONAL = ("L0", "W0", "logdet0", "whitened_mean0")                   # the background Gaussian of relative=True
+    _SETTINGS = ("shrinkage", "relative")
+    _DTYPES = dict({k: torch.float64 for k in _STATE + _OPTIONAL}, counts=torch.int64)
 
-class Mahalanobis:
     def __init__(self, shrinkage=0.0, relative=False):
         if isinstance(shrinkage, bool) or not isinstance(shrinkage, (int, float)):
             raise TypeError(f"shrinkage must be a number, got {type(shrinkage).__name__}")
@@ -46,38 +45,9 @@ class Mahalanobis:
         if not isinstance(relative, bool):
             raise TypeError(f"relative must be a bool, got {type(relative).__name__}")
         self.shrinkage, self.relative = float(shrinkage), relative
-        for name in _STATE + _BACKGROUND:
+        for name in self._STATE + self._OPTIONAL:
             setattr(self, name, None)
         self._ws = None
-
-    # ------------------------------------------------------------------------------------------------------------ helpers
-    @property
-    def is_fitted(self):
-        return self.W is not None
-
-    def _names(self):
-        return _STATE + (_BACKGROUND if self.relative else ())
-
-    def _workspace(self, n, c, f, dev):
-        need = N.lib().osi_maha_workspace(n, c, f)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        return self._ws
-
-    def _require_fit(self, what):
-        if not self.is_fitted:
-            raise ValueError(f"Mahalanobis.{what} before fit: call fit(features, gt) or load_state_dict first")
-
-    def _on(self, dev):
-        """The fitted tensors on `dev` (a state dict loads on the host; the first computing call moves them)."""
-        if self.W.device != dev:
-            for name in self._names():
-                setattr(self, name, getattr(self, name).to(dev))
-
-    @staticmethod
-    def _check_chunk(chunk):
-        if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1):
-            raise ValueError(f"chunk must be a positive int or None, got {chunk!r}")
 
     # ---------------------------------------------------------------------------------------------------------------- fit
     def _factor(self, s, n, ws, what):
@@ -91,16 +61,10 @@ class Mahalanobis:
     def fit(self, features, gt, chunk=None):
         """Means, tied covariance, its Cholesky factor and inverse and the whitened means from features [N, F] and labels [N] of the
         training split; C = max(gt) + 1, rows with a negative label are ignored. `chunk`: rows per scatter launch. Returns self."""
-        f_shape = tuple(torch.as_tensor(features).shape)
-        if len(f_shape) != 2:
-            raise ValueError(f"features must be a matrix [N_samples, N_columns], got shape {f_shape}")
-        if len(gt) != f_shape[0]:
-            raise ValueError(f"features and gt disagree on the number of samples: {f_shape[0]}, {len(gt)}")
-        if f_shape[0] == 0 or f_shape[1] == 0:
-            raise ValueError(f"features must not be empty, got shape {f_shape}")
+        f_shape = _fit_shapes(features, gt)
         if f_shape[1] > N.MAHA_MAX_F:
             raise ValueError(f"features are {f_shape[1]} columns wide; the kernels take at most {N.MAHA_MAX_F}")
-        self._check_chunk(chunk)
+        _check_chunk(chunk)
         dev = _need_gpu("Mahalanobis.fit")
         y = _labels_on_device(gt, dev)
         if y.dim() != 1:
@@ -111,7 +75,7 @@ class Mahalanobis:
         x = _matrix(features, dev, "features")
         rows, f_dim = x.shape
         step = min((_MAX_ELEMS - 1) // f_dim, chunk or rows)                # fit writes nothing per row: only the ABI's limit cuts it
-        ws = self._workspace(min(step, rows), c, f_dim, dev)
+        ws = self._workspace(N.lib().osi_maha_workspace(min(step, rows), c, f_dim), dev)
         ops = N.ops()
         if step >= rows:
             means, counts = ops.maha_class_means(x, y, c, ws)
@@ -148,7 +112,7 @@ class Mahalanobis:
         c, f_dim = self.whitened_means.shape
         if len(f_shape) != 2 or f_shape[1] != f_dim:
             raise ValueError(f"features must be [M, {f_dim}] (the width fit saw), got shape {f_shape}")
-        self._check_chunk(chunk)
+        _check_chunk(chunk)
         dev = _need_gpu(f"Mahalanobis.{what}")
         self._on(dev)
         m = f_shape[0]
@@ -157,7 +121,7 @@ class Mahalanobis:
             return out
         q = _matrix(features, dev, "features")
         step = min(_chunk_rows(max(f_dim, c)), chunk or m)
-        ws = self._workspace(1, c, f_dim, dev)
+        ws = self._workspace(N.lib().osi_maha_workspace(1, c, f_dim), dev)
         ops = N.ops()
         for r0 in range(0, m, step):
             rows = q[r0:r0 + step]
@@ -181,23 +145,17 @@ class Mahalanobis:
         return self._score(features, chunk, "unknown_score", N.MAHA_RAW).min(dim=1).values
 
     # -------------------------------------------------------------------------------------------------------------- state
-    def state_dict(self):
-        """Plain CPU tensors and the two settings; the background entries are None when not relative; torch.save-able."""
-        self._require_fit("state_dict")
-        sd = {name: (None if getattr(self, name) is None else getattr(self, name).detach().cpu().clone()) for name in _STATE + _BACKGROUND}
-        sd.update({k: getattr(self, k) for k in _SETTINGS})
-        return sd
-
-    def load_state_dict(self, sd):
-        missing = [k for k in _STATE + _BACKGROUND + _SETTINGS if k not in sd]
-        if missing:
-            raise ValueError(f"state dict lacks {missing}")
+    def _restore(self, sd, t):
+        """The background entries of the state dict are None when not relative, and are not read then."""
         Mahalanobis.__init__(self, float(sd["shrinkage"]), bool(sd["relative"]))
-        names = self._names()
-        absent = [k for k in names if sd[k] is None]
-        if absent:
-            raise ValueError(f"state dict holds no tensor for {absent}")
-        t = {k: torch.as_tensor(sd[k]).detach().to(torch.int64 if k == "counts" else torch.float64).contiguous().clone() for k in names}
+        names = self._STATE
+        if self.relative:
+            names += self._OPTIONAL
+            absent = [k for k in self._OPTIONAL if t[k] is None]
+            if absent:
+                raise ValueError(f"state dict holds no tensor for {absent}")
+        else:
+            t.update(dict.fromkeys(self._OPTIONAL))
         if t["whitened_means"].dim() != 2:
             raise ValueError(f"state dict: whitened_means must be [C, F], got shape {tuple(t['whitened_means'].shape)}")
         c, f_dim = t["whitened_means"].shape
@@ -206,6 +164,3 @@ class Mahalanobis:
         for k in names:
             if k in shapes and tuple(t[k].shape) != shapes[k]:
                 raise ValueError(f"state dict: {k} must have shape {shapes[k]}, got {tuple(t[k].shape)}")
-        for k in names:
-            setattr(self, k, t[k])
-        return self

@@ -20,21 +20,19 @@ read. PROSER is openset_imagenet.proser. Out of scope: per-class tail sizes, mul
 import torch
 
 from . import _native as N
+from ._detector import Detector, _fit_shapes, _matrix
 from .util import _labels_on_device, _need_gpu
 
 _METRICS = {"euclidean": N.OPENMAX_EUCLIDEAN, "cosine": N.OPENMAX_COSINE}
-_STATE = ("mav", "shape", "scale", "shift", "fitted", "count", "tail_count", "flags")
 
 
-def _matrix(x, dev, name):
-    """[rows, columns] fp32 on the device."""
-    t = torch.as_tensor(x).detach()
-    if t.dim() != 2:
-        raise ValueError(f"{name} must be a matrix [N_samples, N_columns], got shape {tuple(t.shape)}")
-    return t.to(device=dev, dtype=torch.float32).contiguous()
+class OpenMax(Detector):
+    _STATE = ("mav", "shape", "scale", "shift", "fitted", "count", "tail_count", "flags")
+    _SETTINGS = ("tailsize", "distance", "alpha")
+    _DTYPES = dict(mav=torch.float32, shape=torch.float64, scale=torch.float64, shift=torch.float64, fitted=torch.uint8,
+                   count=torch.int64, tail_count=torch.int64, flags=torch.int64)
+    _FIT = "fit(features, logits, gt)"
 
-
-class OpenMax:
     def __init__(self, tailsize=1000, distance="euclidean", alpha=3):
         if isinstance(tailsize, bool) or not isinstance(tailsize, int):
             raise TypeError(f"tailsize must be an int, got {type(tailsize).__name__}")
@@ -47,48 +45,20 @@ class OpenMax:
         if distance not in _METRICS:
             raise ValueError(f"distance must be one of {sorted(_METRICS)}, got {distance!r}")
         self.tailsize, self.distance, self.alpha = tailsize, distance, alpha
-        for name in _STATE:
+        for name in self._STATE:
             setattr(self, name, None)
         self._ws = None
-
-    # ------------------------------------------------------------------------------------------------------------ helpers
-    @property
-    def is_fitted(self):
-        return self.mav is not None
-
-    def _workspace(self, n, c, f, dev):
-        need = N.lib().osi_openmax_workspace(n, c, f)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        return self._ws
-
-    def _require_fit(self, what):
-        if not self.is_fitted:
-            raise ValueError(f"OpenMax.{what} before fit: call fit(features, logits, gt) or load_state_dict first")
-
-    def _on(self, dev):
-        """The fitted tensors on `dev` (a state dict loads on the host; the first computing call moves them)."""
-        if self.mav.device != dev:
-            for name in _STATE:
-                setattr(self, name, getattr(self, name).to(dev))
 
     # ---------------------------------------------------------------------------------------------------------------- fit
     def fit(self, features, logits, gt):
         """Class means and Weibull tails from features [N, F], logits [N, C] and labels [N] of the training split. Rows whose label
         lies outside [0, C) (negatives, unknowns) and rows the network classifies wrongly take no part. Returns self."""
-        f_shape, l_shape = tuple(torch.as_tensor(features).shape), tuple(torch.as_tensor(logits).shape)
-        if len(f_shape) != 2 or len(l_shape) != 2:
-            raise ValueError(f"features and logits must be matrices, got shapes {f_shape} and {l_shape}")
-        n_gt = len(gt)
-        if f_shape[0] != l_shape[0] or n_gt != l_shape[0]:
-            raise ValueError(f"features, logits and gt disagree on the number of samples: {f_shape[0]}, {l_shape[0]}, {n_gt}")
-        if l_shape[0] == 0 or l_shape[1] == 0 or f_shape[1] == 0:
-            raise ValueError(f"features and logits must not be empty, got shapes {f_shape} and {l_shape}")
+        _fit_shapes(features, gt, logits)
         dev = _need_gpu("OpenMax.fit")
         ops = N.ops()
         f, lg, y = _matrix(features, dev, "features"), _matrix(logits, dev, "logits"), _labels_on_device(gt, dev)
         n, c = lg.shape
-        ws = self._workspace(n, c, f.shape[1], dev)
+        ws = self._workspace(N.lib().osi_openmax_workspace(n, c, f.shape[1]), dev)
         self.mav, self.count, correct = ops.openmax_class_means(f, lg, y, ws)
         dist = ops.openmax_distances(f, self.mav, y, _METRICS[self.distance])
         self.shape, self.scale, self.shift, self.fitted, self.tail_count, self.flags = ops.openmax_fit_tails(
@@ -125,21 +95,8 @@ class OpenMax:
         return N.ops().openmax_recalibrate(_matrix(logits, w.device, "logits"), w, self.alpha)
 
     # -------------------------------------------------------------------------------------------------------------- state
-    def state_dict(self):
-        """Plain CPU tensors and the three settings; torch.save-able."""
-        self._require_fit("state_dict")
-        sd = {name: getattr(self, name).detach().cpu().clone() for name in _STATE}
-        sd.update(tailsize=self.tailsize, distance=self.distance, alpha=self.alpha)
-        return sd
-
-    def load_state_dict(self, sd):
-        missing = [k for k in _STATE + ("tailsize", "distance", "alpha") if k not in sd]
-        if missing:
-            raise ValueError(f"state dict lacks {missing}")
+    def _restore(self, sd, tensors):
         OpenMax.__init__(self, int(sd["tailsize"]), sd["distance"], int(sd["alpha"]))
-        dtypes = dict(mav=torch.float32, shape=torch.float64, scale=torch.float64, shift=torch.float64, fitted=torch.uint8,
-                      count=torch.int64, tail_count=torch.int64, flags=torch.int64)
-        tensors = {k: torch.as_tensor(sd[k]).detach().to(dtypes[k]).contiguous().clone() for k in _STATE}
         if tensors["mav"].dim() != 2:
             raise ValueError(f"state dict: mav must be [C, F], got shape {tuple(tensors['mav'].shape)}")
         c = tensors["mav"].shape[0]
@@ -148,6 +105,3 @@ class OpenMax:
                 raise ValueError(f"state dict: {k} must hold one entry per class ({c}), got shape {tuple(tensors[k].shape)}")
         if tuple(tensors["flags"].shape) != (2,):
             raise ValueError(f"state dict: flags must hold two entries, got shape {tuple(tensors['flags'].shape)}")
-        for k, t in tensors.items():
-            setattr(self, k, t)
-        return self

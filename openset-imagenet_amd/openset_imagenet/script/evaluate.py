@@ -36,8 +36,65 @@ import numpy as np
 import torch
 
 from .. import metrics, tools, util
+from ..evm import EVM
+from ..knn import KNN
+from ..mahalanobis import Mahalanobis
 from ..model import ResNet50
+from ..openmax import OpenMax
 from ..train import _image_loader, get_arrays, load_checkpoint
+from ..vim import ViM
+
+
+def _known_and_unknown(probs):
+    """[M, C + 1] device probabilities with the unknown class last -> numpy `scores` [M, C] and `unknown` [M]."""
+    probs = probs.cpu().numpy()
+    c = probs.shape[1] - 1
+    return dict(scores=probs[:, :c], unknown=probs[:, c])
+
+
+# One record per post-hoc detector, in the order main() fits, scores and prints them:
+#   name      in the option (--name), the file names and the keys of main()'s `written`
+#   tag       of the OSCR line
+#   cls       the detector
+#   on        args -> whether the option asks for it
+#   options   args -> the keyword arguments of cls
+#   fit       (detector, the `features`, `logits`, `gt` of the training split as a mapping)
+#   score     (detector, arrays of a split) -> numpy `scores` [M, C] and, where the method has one, `unknown` [M]
+#   summary   (detector, args) -> the line printed after the fit, up to "; saved in: ..."
+DETECTORS = (
+    dict(name="openmax", tag="OpenMax ", cls=OpenMax, on=lambda args: args.openmax is not None,
+         options=lambda args: dict(tailsize=args.openmax, distance=args.openmax_distance, alpha=args.openmax_alpha),
+         fit=lambda om, t: om.fit(t["features"], t["logits"], t["gt"]),
+         score=lambda om, a: _known_and_unknown(om.predict(a["logits"], a["features"])),
+         summary=lambda om, args: f"OpenMax (tail {args.openmax}, alpha {args.openmax_alpha}, {args.openmax_distance}) fitted on "
+         f"{int(om.count.sum())} correct training samples, " + "{1} classes unfitted, {0} distances not finite".format(*om.flags.tolist())),
+    dict(name="evm", tag="EVM ", cls=EVM, on=lambda args: args.evm is not None,
+         options=lambda args: dict(tailsize=args.evm, cover_threshold=args.evm_cover, distance_multiplier=args.evm_multiplier,
+                                   distance=args.evm_distance),
+         fit=lambda evm, t: evm.fit(t["features"], t["gt"]),
+         score=lambda evm, a: dict(scores=evm.predict(a["features"]).cpu().numpy()),
+         summary=lambda evm, args: f"EVM (tail {args.evm}, cover {args.evm_cover}, multiplier {args.evm_multiplier}, {args.evm_distance}) keeps "
+         f"{evm.ev_features.shape[0]} extreme vectors, " + "{1} rows unfitted, {0} distances not finite".format(*evm.flags.tolist())),
+    dict(name="knn", tag="KNN ", cls=KNN, on=lambda args: args.knn is not None,
+         options=lambda args: dict(k=args.knn, distance=args.knn_distance, bank_fraction=args.knn_fraction),
+         fit=lambda knn, t: knn.fit(t["features"], t["gt"]),
+         score=lambda knn, a: dict(scores=knn.predict(a["features"]).cpu().numpy(), unknown=knn.unknown_score(a["features"]).cpu().numpy()),
+         summary=lambda knn, args: f"KNN (k {args.knn}, {args.knn_distance}, fraction {args.knn_fraction}) keeps a bank of "
+         f"{knn.bank_features.shape[0]} rows"),
+    dict(name="mahalanobis", tag="Mahalanobis ", cls=Mahalanobis, on=lambda args: args.mahalanobis,
+         options=lambda args: dict(shrinkage=args.mahalanobis_shrinkage, relative=args.mahalanobis_relative),
+         fit=lambda maha, t: maha.fit(t["features"], t["gt"]),
+         score=lambda maha, a: dict(scores=maha.predict(a["features"]).cpu().numpy(), unknown=maha.unknown_score(a["features"]).cpu().numpy()),
+         summary=lambda maha, args: f"Mahalanobis (shrinkage {args.mahalanobis_shrinkage}, relative {args.mahalanobis_relative}) fitted on "
+         f"{int(maha.counts[-1])} training samples, log-determinant {float(maha.logdet):.6f}"),
+    dict(name="vim", tag="ViM ", cls=ViM, on=lambda args: args.vim,
+         options=lambda args: dict(dim=args.vim_dim),
+         fit=lambda vim, t: vim.fit(t["features"], t["logits"], t["gt"]),       # no weight or bias: the origin is zero
+         score=lambda vim, a: dict(scores=vim.predict(a["features"], a["logits"]).cpu().numpy(),
+                                   unknown=vim.unknown_score(a["features"], a["logits"]).cpu().numpy()),
+         summary=lambda vim, args: f"ViM (dim {vim.dim} of {vim.components.shape[0]}) fitted on {vim.count} training samples in "
+         f"{vim.sweeps} Jacobi sweeps, alpha {vim.alpha:.6f}"),
+)
 
 
 def get_args(command_line_options=None):
@@ -85,18 +142,9 @@ def get_args(command_line_options=None):
     p.add_argument("--proser", action="store_true", help="also evaluate the PROSER stage saved as {loss}_proser{suffix}.pth (softmax and "
                    "entropic losses) and write {loss}_{split}_arr{suffix}_proser.npz with its scores and the probability of the unknown class")
     args = p.parse_args(command_line_options)
-    if args.proser and args.loss == "garbage":
-        p.error("--proser needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
-    if args.openmax is not None and args.loss == "garbage":
-        p.error("--openmax needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
-    if args.evm is not None and args.loss == "garbage":
-        p.error("--evm needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
-    if args.knn is not None and args.loss == "garbage":
-        p.error("--knn needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
-    if args.mahalanobis and args.loss == "garbage":
-        p.error("--mahalanobis needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
-    if args.vim and args.loss == "garbage":
-        p.error("--vim needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
+    post_hoc = ["proser"] * args.proser + [row["name"] for row in DETECTORS if row["on"](args)]
+    if post_hoc and args.loss == "garbage":
+        p.error(f"--{post_hoc[0]} needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
     if args.vim_dim is not None and args.vim_dim < 1:
         p.error(f"--vim-dim must be positive, got {args.vim_dim}")
     if not 0.0 <= args.mahalanobis_shrinkage <= 1.0:
@@ -181,102 +229,63 @@ def oscr_lines(split, gt, scores, tag=""):
     return lines
 
 
-def openmax_arrays(train_arrays, split_arrays, tailsize, alpha, distance):
-    """`--openmax` on arrays: fit OpenMax on the training split's `gt`, `logits`, `features` (mappings as get_arrays' .npz holds them;
-    an already fitted openmax.OpenMax is taken as it is) and recalibrate one split. Returns (om, arrays): arrays holds the numpy
-    `gt`, `logits`, `features` of the split, `scores` = probs[:, :C] and `unknown` = probs[:, C]."""
-    from ..openmax import OpenMax
-    if isinstance(train_arrays, OpenMax):
-        om = train_arrays
-    else:
-        om = OpenMax(tailsize=tailsize, distance=distance, alpha=alpha)
-        om.fit(train_arrays["features"], train_arrays["logits"], train_arrays["gt"])
-    probs = om.predict(split_arrays["logits"], split_arrays["features"]).cpu().numpy()
+def scored_arrays(score, detector, split_arrays):
+    """The numpy `gt`, `logits`, `features` of one split (a mapping as get_arrays' .npz holds them) and, after them, what
+    `score(detector, split_arrays)` gives: `scores` and perhaps `unknown`. This is what main() writes next to the split's .npz."""
     host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
-    c = probs.shape[1] - 1
-    return om, dict(gt=host(split_arrays["gt"]), logits=host(split_arrays["logits"]), features=host(split_arrays["features"]),
-                    scores=probs[:, :c], unknown=probs[:, c])
+    scored = score(detector, split_arrays)
+    return dict({key: host(split_arrays[key]) for key in ("gt", "logits", "features")}, **scored)
+
+
+def _detector_arrays(name, train_arrays, split_arrays, **options):
+    """Behind the *_arrays helpers below: the detector `name` of DETECTORS, built with `options` and fitted on the training split's
+    arrays (a mapping as get_arrays' .npz holds them) unless `train_arrays` is that detector, already fitted and then taken as it is;
+    one split scored with it. Returns (detector, arrays of scored_arrays)."""
+    row = next(row for row in DETECTORS if row["name"] == name)
+    detector = train_arrays
+    if not isinstance(detector, row["cls"]):
+        detector = row["cls"](**options)
+        row["fit"](detector, train_arrays)
+    return detector, scored_arrays(row["score"], detector, split_arrays)
+
+
+def openmax_arrays(train_arrays, split_arrays, tailsize, alpha, distance):
+    """`--openmax` on arrays: OpenMax fitted on the training split's `gt`, `logits`, `features`. Returns (om, arrays) with `scores` =
+    probs[:, :C] and `unknown` = probs[:, C]."""
+    return _detector_arrays("openmax", train_arrays, split_arrays, tailsize=tailsize, distance=distance, alpha=alpha)
 
 
 def evm_arrays(train_arrays, split_arrays, tailsize, cover_threshold=None, multiplier=0.5, distance="cosine"):
-    """`--evm` on arrays: fit the Extreme Value Machine on the training split's `gt` and `features` (mappings as get_arrays' .npz holds
-    them; an already fitted evm.EVM is taken as it is) and score one split. Returns (evm, arrays): arrays holds the numpy `gt`,
-    `logits`, `features` of the split and `scores` = the [M, C] inclusion probabilities."""
-    from ..evm import EVM
-    if isinstance(train_arrays, EVM):
-        evm = train_arrays
-    else:
-        evm = EVM(tailsize=tailsize, cover_threshold=cover_threshold, distance_multiplier=multiplier, distance=distance)
-        evm.fit(train_arrays["features"], train_arrays["gt"])
-    scores = evm.predict(split_arrays["features"]).cpu().numpy()
-    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
-    return evm, dict(gt=host(split_arrays["gt"]), logits=host(split_arrays["logits"]), features=host(split_arrays["features"]),
-                     scores=scores)
+    """`--evm` on arrays: the Extreme Value Machine fitted on the training split's `gt` and `features`. Returns (evm, arrays) with
+    `scores` = the [M, C] inclusion probabilities."""
+    return _detector_arrays("evm", train_arrays, split_arrays, tailsize=tailsize, cover_threshold=cover_threshold,
+                            distance_multiplier=multiplier, distance=distance)
 
 
 def knn_arrays(train_arrays, split_arrays, k, distance="cosine", fraction=1.0, seed=0):
-    """`--knn` on arrays: keep the training split's `gt` and `features` as the bank of deep nearest neighbours (mappings as get_arrays'
-    .npz holds them; an already fitted knn.KNN is taken as it is) and score one split. Returns (knn, arrays): arrays holds the numpy
-    `gt`, `logits`, `features` of the split, `scores` = the [M, C] class similarities and `unknown` = the [M] distances to the k-th
-    nearest bank row."""
-    from ..knn import KNN
-    if isinstance(train_arrays, KNN):
-        knn = train_arrays
-    else:
-        knn = KNN(k=k, distance=distance, bank_fraction=fraction, seed=seed)
-        knn.fit(train_arrays["features"], train_arrays["gt"])
-    scores = knn.predict(split_arrays["features"]).cpu().numpy()
-    unknown = knn.unknown_score(split_arrays["features"]).cpu().numpy()
-    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
-    return knn, dict(gt=host(split_arrays["gt"]), logits=host(split_arrays["logits"]), features=host(split_arrays["features"]),
-                     scores=scores, unknown=unknown)
+    """`--knn` on arrays: the training split's `gt` and `features` kept as the bank of deep nearest neighbours. Returns (knn, arrays)
+    with `scores` = the [M, C] class similarities and `unknown` = the [M] distances to the k-th nearest bank row."""
+    return _detector_arrays("knn", train_arrays, split_arrays, k=k, distance=distance, bank_fraction=fraction, seed=seed)
 
 
 def mahalanobis_arrays(train_arrays, split_arrays, shrinkage=0.0, relative=False):
-    """`--mahalanobis` on arrays: fit the class means and the tied covariance on the training split's `gt` and `features` (mappings as
-    get_arrays' .npz holds them; an already fitted mahalanobis.Mahalanobis is taken as it is) and score one split. Returns (maha,
-    arrays): arrays holds the numpy `gt`, `logits`, `features` of the split, `scores` = the [M, C] class similarities and `unknown` =
-    the [M] smallest squared distances."""
-    from ..mahalanobis import Mahalanobis
-    if isinstance(train_arrays, Mahalanobis):
-        maha = train_arrays
-    else:
-        maha = Mahalanobis(shrinkage=shrinkage, relative=relative)
-        maha.fit(train_arrays["features"], train_arrays["gt"])
-    scores = maha.predict(split_arrays["features"]).cpu().numpy()
-    unknown = maha.unknown_score(split_arrays["features"]).cpu().numpy()
-    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
-    return maha, dict(gt=host(split_arrays["gt"]), logits=host(split_arrays["logits"]), features=host(split_arrays["features"]),
-                      scores=scores, unknown=unknown)
+    """`--mahalanobis` on arrays: the class means and the tied covariance fitted on the training split's `gt` and `features`. Returns
+    (maha, arrays) with `scores` = the [M, C] class similarities and `unknown` = the [M] smallest squared distances."""
+    return _detector_arrays("mahalanobis", train_arrays, split_arrays, shrinkage=shrinkage, relative=relative)
 
 
 def vim_arrays(train_arrays, split_arrays, dim=None):
-    """`--vim` on arrays: fit ViM on the training split's `gt`, `logits` and `features` (mappings as get_arrays' .npz holds them; an
-    already fitted vim.ViM is taken as it is; the origin is zero, as for a network without a logit bias) and score one split. Returns
-    (vim, arrays): arrays holds the numpy `gt`, `logits`, `features` of the split, `scores` = the [M, C] known columns of the softmax
-    with the virtual logit and `unknown` = the [M] values alpha * residual norm - logsumexp(logits)."""
-    from ..vim import ViM
-    if isinstance(train_arrays, ViM):
-        vim = train_arrays
-    else:
-        vim = ViM(dim=dim)
-        vim.fit(train_arrays["features"], train_arrays["logits"], train_arrays["gt"])
-    scores = vim.predict(split_arrays["features"], split_arrays["logits"]).cpu().numpy()
-    unknown = vim.unknown_score(split_arrays["features"], split_arrays["logits"]).cpu().numpy()
-    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
-    return vim, dict(gt=host(split_arrays["gt"]), logits=host(split_arrays["logits"]), features=host(split_arrays["features"]),
-                     scores=scores, unknown=unknown)
+    """`--vim` on arrays: ViM fitted on the training split's `gt`, `logits` and `features` (the origin is zero, as for a network without
+    a logit bias). Returns (vim, arrays) with `scores` = the [M, C] known columns of the softmax with the virtual logit and `unknown` =
+    the [M] values alpha * residual norm - logsumexp(logits)."""
+    return _detector_arrays("vim", train_arrays, split_arrays, dim=dim)
 
 
 def proser_arrays(proser, split_arrays):
     """`--proser` on arrays: `gt`, `logits`, `features` of one split as the fine-tuned network of `proser` (proser.PROSER) gave them
     (mappings as get_arrays' .npz holds them). Returns the numpy `gt`, `logits`, `features`, `scores` = probs[:, :C] and `unknown` =
     probs[:, C] of PROSER.predict over the dummy classifier's logits."""
-    probs = proser.predict(split_arrays["logits"], proser.dummy_logits(split_arrays["features"])).cpu().numpy()
-    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
-    c = probs.shape[1] - 1
-    return dict(gt=host(split_arrays["gt"]), logits=host(split_arrays["logits"]), features=host(split_arrays["features"]),
-                scores=probs[:, :c], unknown=probs[:, c])
+    return scored_arrays(lambda p, a: _known_and_unknown(p.predict(a["logits"], p.dummy_logits(a["features"]))), proser, split_arrays)
 
 
 def load_proser(path, n_classes):
@@ -324,65 +333,35 @@ def main(command_line_options=None):
         suffix += "_avg"
     tools.device(model)
     written = {}
-    om = evm = knn = maha = vim = proser = None
+    proser = None
     if args.proser:
         proser_path = args.output_directory / f"{args.loss}_proser{suffix}.pth"
         if not proser_path.is_file():
             raise SystemExit(f"--proser: {proser_path} not found; run python -m openset_imagenet.script.proser {args.loss} {args.protocol} first")
         proser = load_proser(proser_path, n_classes)
         print(f"PROSER stage loaded from: {proser_path} (dummy {proser.dummy_count}, mix at {proser.mix_at}, bias {float(proser.bias):.6f})")
-    if args.openmax is not None:
-        from ..openmax import OpenMax
-        om = OpenMax(tailsize=args.openmax, distance=args.openmax_distance, alpha=args.openmax_alpha)    # refuses bad options first
-    if args.evm is not None:
-        from ..evm import EVM
-        evm = EVM(tailsize=args.evm, cover_threshold=args.evm_cover, distance_multiplier=args.evm_multiplier, distance=args.evm_distance)
-    if args.knn is not None:
-        from ..knn import KNN
-        knn = KNN(k=args.knn, distance=args.knn_distance, bank_fraction=args.knn_fraction)               # refuses bad options first
-    if args.mahalanobis:
-        from ..mahalanobis import Mahalanobis
-        maha = Mahalanobis(shrinkage=args.mahalanobis_shrinkage, relative=args.mahalanobis_relative)     # refuses bad options first
-    if args.vim:
-        from ..vim import ViM
-        vim = ViM(dim=args.vim_dim)                                                                     # refuses bad options first
-    if om is not None or evm is not None or knn is not None or maha is not None or vim is not None:
+    fitted = [(row, row["cls"](**row["options"](args))) for row in DETECTORS if row["on"](args)]      # refuses bad options first
+    if fitted:
         train_ds = _image_loader(args.protocol_directory / f"p{args.protocol}_train.csv", args.imagenet_directory, False, "eval")
         print(f"train dataset len:{len(train_ds)}, labels:{train_ds.table.label_count}")
         loader = torch.utils.data.DataLoader(train_ds, batch_size=args.batch_size, num_workers=args.workers)
         t_gt, t_logits, t_features, _ = get_arrays(model=model, loader=loader)
-    if evm is not None:
-        evm.fit(t_features, t_gt)
-        evm_path = args.output_directory / f"{args.loss}_evm{suffix}.pth"
-        torch.save(evm.state_dict(), evm_path)
-        left_out, unfitted = evm.flags.tolist()
-        print(f"EVM (tail {args.evm}, cover {args.evm_cover}, multiplier {args.evm_multiplier}, {args.evm_distance}) keeps "
-              f"{evm.ev_features.shape[0]} extreme vectors, {unfitted} rows unfitted, {left_out} distances not finite; saved in: {evm_path}")
-    if knn is not None:
-        knn.fit(t_features, t_gt)
-        knn_path = args.output_directory / f"{args.loss}_knn{suffix}.pth"
-        torch.save(knn.state_dict(), knn_path)
-        print(f"KNN (k {args.knn}, {args.knn_distance}, fraction {args.knn_fraction}) keeps a bank of {knn.bank_features.shape[0]} rows; "
-              f"saved in: {knn_path}")
-    if maha is not None:
-        maha.fit(t_features, t_gt)
-        maha_path = args.output_directory / f"{args.loss}_mahalanobis{suffix}.pth"
-        torch.save(maha.state_dict(), maha_path)
-        print(f"Mahalanobis (shrinkage {args.mahalanobis_shrinkage}, relative {args.mahalanobis_relative}) fitted on "
-              f"{int(maha.counts[-1])} training samples, log-determinant {float(maha.logdet):.6f}; saved in: {maha_path}")
-    if vim is not None:
-        vim.fit(t_features, t_logits, t_gt)                 # logit_bias=False above: the origin is zero
-        vim_path = args.output_directory / f"{args.loss}_vim{suffix}.pth"
-        torch.save(vim.state_dict(), vim_path)
-        print(f"ViM (dim {vim.dim} of {vim.components.shape[0]}) fitted on {vim.count} training samples in {vim.sweeps} Jacobi sweeps, "
-              f"alpha {vim.alpha:.6f}; saved in: {vim_path}")
-    if om is not None:
-        om.fit(t_features, t_logits, t_gt)
-        om_path = args.output_directory / f"{args.loss}_openmax{suffix}.pth"
-        torch.save(om.state_dict(), om_path)
-        left_out, unfitted = om.flags.tolist()
-        print(f"OpenMax (tail {args.openmax}, alpha {args.openmax_alpha}, {args.openmax_distance}) fitted on {int(om.count.sum())} correct "
-              f"training samples, {unfitted} classes unfitted, {left_out} distances not finite; saved in: {om_path}")
+    for row, detector in fitted:
+        row["fit"](detector, dict(gt=t_gt, logits=t_logits, features=t_features))
+        path = args.output_directory / f"{args.loss}_{row['name']}{suffix}.pth"
+        torch.save(detector.state_dict(), path)
+        print(f"{row['summary'](detector, args)}; saved in: {path}")
+
+    def write(split, name, tag, gt, arrays):
+        """One detector's arrays of a split next to the split's .npz, and its OSCR line."""
+        file_path = args.output_directory / f"{args.loss}_{split}_arr{suffix}_{name}.npz"
+        np.savez(file_path, **arrays)
+        print(f"{tag}scores saved in: {file_path}")
+        written[f"{split}_{name}"] = file_path
+        if args.oscr:
+            for line in oscr_lines(split, gt, arrays["scores"], tag=tag):
+                print(line)
+
     for split, ds in splits.items():
         loader = torch.utils.data.DataLoader(ds, batch_size=args.batch_size, num_workers=args.workers)
         gt, logits, features, scores = get_arrays(model=model, loader=loader)
@@ -394,62 +373,11 @@ def main(command_line_options=None):
             s = scores[:, :-1] if args.loss == "garbage" else scores           # the background column is not a known class
             for line in oscr_lines(split, gt, s):
                 print(line)
-        if om is not None:
-            _, arrays = openmax_arrays(om, dict(gt=gt, logits=logits, features=features), args.openmax, args.openmax_alpha,
-                                       args.openmax_distance)
-            om_file = args.output_directory / f"{args.loss}_{split}_arr{suffix}_openmax.npz"
-            np.savez(om_file, **arrays)
-            print(f"OpenMax scores saved in: {om_file}")
-            written[split + "_openmax"] = om_file
-            if args.oscr:
-                for line in oscr_lines(split, gt, arrays["scores"], tag="OpenMax "):
-                    print(line)
-        if evm is not None:
-            _, arrays = evm_arrays(evm, dict(gt=gt, logits=logits, features=features), args.evm)
-            evm_file = args.output_directory / f"{args.loss}_{split}_arr{suffix}_evm.npz"
-            np.savez(evm_file, **arrays)
-            print(f"EVM scores saved in: {evm_file}")
-            written[split + "_evm"] = evm_file
-            if args.oscr:
-                for line in oscr_lines(split, gt, arrays["scores"], tag="EVM "):
-                    print(line)
-        if knn is not None:
-            _, arrays = knn_arrays(knn, dict(gt=gt, logits=logits, features=features), args.knn)
-            knn_file = args.output_directory / f"{args.loss}_{split}_arr{suffix}_knn.npz"
-            np.savez(knn_file, **arrays)
-            print(f"KNN scores saved in: {knn_file}")
-            written[split + "_knn"] = knn_file
-            if args.oscr:
-                for line in oscr_lines(split, gt, arrays["scores"], tag="KNN "):
-                    print(line)
-        if maha is not None:
-            _, arrays = mahalanobis_arrays(maha, dict(gt=gt, logits=logits, features=features))
-            maha_file = args.output_directory / f"{args.loss}_{split}_arr{suffix}_mahalanobis.npz"
-            np.savez(maha_file, **arrays)
-            print(f"Mahalanobis scores saved in: {maha_file}")
-            written[split + "_mahalanobis"] = maha_file
-            if args.oscr:
-                for line in oscr_lines(split, gt, arrays["scores"], tag="Mahalanobis "):
-                    print(line)
-        if vim is not None:
-            _, arrays = vim_arrays(vim, dict(gt=gt, logits=logits, features=features))
-            vim_file = args.output_directory / f"{args.loss}_{split}_arr{suffix}_vim.npz"
-            np.savez(vim_file, **arrays)
-            print(f"ViM scores saved in: {vim_file}")
-            written[split + "_vim"] = vim_file
-            if args.oscr:
-                for line in oscr_lines(split, gt, arrays["scores"], tag="ViM "):
-                    print(line)
+        for row, detector in fitted:
+            write(split, row["name"], row["tag"], gt, scored_arrays(row["score"], detector, dict(gt=gt, logits=logits, features=features)))
         if proser is not None:
             p_gt, p_logits, p_features, _ = get_arrays(model=proser.model, loader=loader)
-            arrays = proser_arrays(proser, dict(gt=p_gt, logits=p_logits, features=p_features))
-            proser_file = args.output_directory / f"{args.loss}_{split}_arr{suffix}_proser.npz"
-            np.savez(proser_file, **arrays)
-            print(f"PROSER scores saved in: {proser_file}")
-            written[split + "_proser"] = proser_file
-            if args.oscr:
-                for line in oscr_lines(split, p_gt, arrays["scores"], tag="PROSER "):
-                    print(line)
+            write(split, "proser", "PROSER ", p_gt, proser_arrays(proser, dict(gt=p_gt, logits=p_logits, features=p_features)))
         if args.auc:
             for unk in (-1, -2):
                 sel = auc_rows(gt, scores, unk, args.loss)

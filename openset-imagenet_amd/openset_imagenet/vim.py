@@ -23,18 +23,13 @@ part of the reference snapshot: include/osi.h (ABI 26) is its definition, tests/
 
 Everything runs in fp64 in the kernels of csrc/vim.hip, the projection on the fp64 matrix cores; there is no CPU path. Inputs may be
 numpy arrays or torch tensors, on the host or on the device. The fitted tensors are fp64 device tensors the caller may read. Rows go
-through the kernels in the chunks of evm._chunk_rows, or of `chunk=` rows. Out of scope: per-class subspaces, F > 4096, multi-GPU fits."""
+through the kernels in the chunks of _detector._chunk_rows, or of `chunk=` rows. Out of scope: per-class subspaces, F > 4096, multi-GPU fits."""
 import numpy as np
 import torch
 
 from . import _native as N
-from .evm import _chunk_rows
-from .openmax import _matrix
+from ._detector import _MAX_ELEMS, Detector, _check_chunk, _chunk_rows, _fit_shapes, _matrix
 from .util import _labels_on_device, _need_gpu
-
-_STATE = ("origin", "eigenvalues", "components")
-_SETTINGS = ("dim", "alpha", "count", "classes")
-_MAX_ELEMS = 1 << 31            # a call takes fewer elements than this in each of its matrices (include/osi.h)
 
 
 def default_dim(f_dim):
@@ -69,7 +64,11 @@ def eigh(S, max_sweeps=30):
     return values, vectors, sweep
 
 
-class ViM:
+class ViM(Detector):
+    _STATE = ("origin", "eigenvalues", "components")
+    _SETTINGS = ("dim", "alpha", "count", "classes")    # what the fit found, not what the constructor takes
+    _DTYPES = dict.fromkeys(_STATE, torch.float64)
+    _FIT = "fit(features, logits)"
     max_sweeps = 30             # of the eigensolver in fit
 
     def __init__(self, dim=None, origin="logit"):
@@ -88,37 +87,16 @@ class ViM:
             if origin.dim() != 1 or origin.numel() == 0:
                 raise ValueError(f"origin must be 'logit' or a vector [F], got shape {tuple(origin.shape)}")
         self.requested_dim, self.requested_origin = dim, origin
-        for name in _STATE + _SETTINGS:
+        for name in self._STATE + self._SETTINGS:
             setattr(self, name, None)
         self.sweeps = None
         self._ws = None
 
     # ------------------------------------------------------------------------------------------------------------ helpers
-    @property
-    def is_fitted(self):
-        return self.components is not None
-
-    def _workspace(self, n, f, dev):
+    def _scratch(self, n, f, dev):
+        """The workspace of a scatter over n rows, of the eigensolver and of the scoring calls."""
         lib = N.lib()
-        need = max(lib.osi_maha_workspace(n, 1, f), lib.osi_vim_workspace(1, 1, f))
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        return self._ws
-
-    def _require_fit(self, what):
-        if not self.is_fitted:
-            raise ValueError(f"ViM.{what} before fit: call fit(features, logits) or load_state_dict first")
-
-    def _on(self, dev):
-        """The fitted tensors on `dev` (a state dict loads on the host; the first computing call moves them)."""
-        if self.components.device != dev:
-            for name in _STATE:
-                setattr(self, name, getattr(self, name).to(dev))
-
-    @staticmethod
-    def _check_chunk(chunk):
-        if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1):
-            raise ValueError(f"chunk must be a positive int or None, got {chunk!r}")
+        return self._workspace(max(lib.osi_maha_workspace(n, 1, f), lib.osi_vim_workspace(1, 1, f)), dev)
 
     def _origin_of(self, f_dim, c, weight, bias):
         """The origin [F] as a host fp64 tensor: the explicit one, or -pinv(weight) bias (fp64 numpy, the one host solve)."""
@@ -146,22 +124,14 @@ class ViM:
         gt < 0 are ignored (gt=None counts every row). `weight [C, F]` / `bias [C]`: the last layer, for origin="logit"; the origin is
         -pinv(weight) bias, computed once in fp64 numpy on the host (a C x F solve), and zero without a bias. `chunk`: rows per
         launch. Returns self."""
-        f_shape, l_shape = tuple(torch.as_tensor(features).shape), tuple(torch.as_tensor(logits).shape)
-        if len(f_shape) != 2:
-            raise ValueError(f"features must be a matrix [N_samples, N_columns], got shape {f_shape}")
-        if len(l_shape) != 2 or l_shape[0] != f_shape[0]:
-            raise ValueError(f"logits must be a matrix [N_samples, N_classes] with the rows of features ({f_shape[0]}), got shape {l_shape}")
-        if gt is not None and len(gt) != f_shape[0]:
-            raise ValueError(f"features and gt disagree on the number of samples: {f_shape[0]}, {len(gt)}")
-        if f_shape[0] == 0 or f_shape[1] == 0 or l_shape[1] == 0:
-            raise ValueError(f"features and logits must not be empty, got shapes {f_shape}, {l_shape}")
+        f_shape, l_shape = _fit_shapes(features, gt, logits, gt_optional=True)
         rows, f_dim, c = f_shape[0], f_shape[1], l_shape[1]
         if f_dim > N.EIGH_MAX_F:
             raise ValueError(f"features are {f_dim} columns wide; the eigensolver takes at most {N.EIGH_MAX_F}")
         dim = default_dim(f_dim) if self.requested_dim is None else self.requested_dim
         if not 0 < dim < f_dim:
             raise ValueError(f"dim must satisfy 0 < dim < F, got dim {dim} for F = {f_dim}")
-        self._check_chunk(chunk)
+        _check_chunk(chunk)
         origin = self._origin_of(f_dim, c, weight, bias)
         dev = _need_gpu("ViM.fit")
         x, lg = _matrix(features, dev, "features"), _matrix(logits, dev, "logits")
@@ -176,7 +146,7 @@ class ViM:
         origin = origin.to(dev)
         mean = torch.stack([torch.zeros_like(origin), origin])          # [anything; origin]: OSI_MAHA_TOTAL reads row C = 1
         step = min((_MAX_ELEMS - 1) // f_dim, chunk or rows)
-        ws = self._workspace(min(step, rows), f_dim, dev)
+        ws = self._scratch(min(step, rows), f_dim, dev)
         ops = N.ops()
         s = torch.empty(f_dim, f_dim, dtype=torch.float64, device=dev)
         for r0 in range(0, rows, step):
@@ -216,7 +186,7 @@ class ViM:
             l_shape = tuple(torch.as_tensor(logits).shape)
             if l_shape != (f_shape[0], self.classes):
                 raise ValueError(f"logits must be [{f_shape[0]}, {self.classes}] (the rows of features, the classes fit saw), got shape {l_shape}")
-        self._check_chunk(chunk)
+        _check_chunk(chunk)
         dev = _need_gpu(f"ViM.{what}")
         self._on(dev)
         m = f_shape[0]
@@ -226,7 +196,7 @@ class ViM:
         q = _matrix(features, dev, "features")
         lg = None if mode == N.VIM_NORM else _matrix(logits, dev, "logits")
         step = min(_chunk_rows(max(f_dim, self.classes + 1)), chunk or m)
-        ws = self._workspace(1, f_dim, dev)
+        ws = self._scratch(1, f_dim, dev)
         ops = N.ops()
         residual = self.components[self.dim:]
         for r0 in range(0, m, step):
@@ -251,18 +221,7 @@ class ViM:
         return self._score(features, logits, chunk, "predict", N.VIM_PROBS)[:, :self.classes]
 
     # -------------------------------------------------------------------------------------------------------------- state
-    def state_dict(self):
-        """Plain CPU tensors and the settings; torch.save-able."""
-        self._require_fit("state_dict")
-        sd = {name: getattr(self, name).detach().cpu().clone() for name in _STATE}
-        sd.update({k: getattr(self, k) for k in _SETTINGS})
-        return sd
-
-    def load_state_dict(self, sd):
-        missing = [k for k in _STATE + _SETTINGS if k not in sd]
-        if missing:
-            raise ValueError(f"state dict lacks {missing}")
-        t = {k: torch.as_tensor(sd[k]).detach().to(torch.float64).contiguous().clone() for k in _STATE}
+    def _restore(self, sd, t):
         if t["components"].dim() != 2 or t["components"].shape[0] != t["components"].shape[1]:
             raise ValueError(f"state dict: components must be [F, F], got shape {tuple(t['components'].shape)}")
         f_dim = t["components"].shape[0]
@@ -277,7 +236,4 @@ class ViM:
         if classes < 1:
             raise ValueError(f"state dict: classes must be positive, got {classes}")
         ViM.__init__(self, dim, t["origin"])
-        for k in _STATE:
-            setattr(self, k, t[k])
         self.dim, self.alpha, self.count, self.classes = dim, alpha, count, classes
-        return self

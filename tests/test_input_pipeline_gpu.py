@@ -106,6 +106,34 @@ def test_worker_on_jpeg_files(cuda, tmp_path, u8, workers):
             ccr, fpr = calculate_oscr(a["gt"], a["scores"])
             occr, ofpr = oracle_oscr(a["gt"], a["scores"])
             assert np.array_equal(ccr, occr, equal_nan=True) and np.array_equal(fpr, ofpr, equal_nan=True)
+        # every post-hoc detector through main(): one more .npz per split and detector, over the same gt / logits / features, and a
+        # saved state that, restored into a fresh detector, gives the very scores main() wrote
+        from openset_imagenet.evm import EVM
+        from openset_imagenet.knn import KNN
+        from openset_imagenet.mahalanobis import Mahalanobis
+        from openset_imagenet.openmax import OpenMax
+        from openset_imagenet.vim import ViM
+        more = evaluate.main(["entropic", "2", "-g", "0", "--imagenet-directory", str(img_dir), "--protocol-directory", str(proto),
+                              "--output-directory", str(tmp_path / "out"), "--batch-size", "4", "--workers", "0", "--oscr",
+                              "--openmax", "2", "--evm", "2", "--knn", "1", "--mahalanobis", "--mahalanobis-shrinkage", "0.5",
+                              "--vim", "--vim-dim", "1"])
+        detectors = {"openmax": (OpenMax, lambda d, a: evaluate.openmax_arrays(d, a, 2, 3, "euclidean"), True),
+                     "evm": (EVM, lambda d, a: evaluate.evm_arrays(d, a, 2), False),
+                     "knn": (KNN, lambda d, a: evaluate.knn_arrays(d, a, 1), True),
+                     "mahalanobis": (Mahalanobis, lambda d, a: evaluate.mahalanobis_arrays(d, a), True),
+                     "vim": (ViM, lambda d, a: evaluate.vim_arrays(d, a), True)}
+        for name, (cls, arrays_of, has_unknown) in detectors.items():
+            restored = cls().load_state_dict(torch.load(tmp_path / "out" / f"entropic_{name}_curr.pth", weights_only=False))
+            for split, n in (("val", 6), ("test", 7)):
+                plain, a = np.load(more[split]), np.load(more[f"{split}_{name}"])
+                assert sorted(a.files) == sorted(["gt", "logits", "features", "scores"] + ["unknown"] * has_unknown), (name, split)
+                assert a["scores"].shape == (n, 3), (name, split)
+                for key in ("gt", "logits", "features"):
+                    assert np.array_equal(a[key], plain[key]), (name, split, key)
+                back, again = arrays_of(restored, {key: plain[key] for key in ("gt", "logits", "features")})
+                assert back is restored and np.array_equal(again["scores"], a["scores"]), (name, split)
+                if has_unknown:
+                    assert a["unknown"].shape == (n,) and np.array_equal(again["unknown"], a["unknown"]), (name, split)
 
 
 def test_device_crop_flip_equals_pil(cuda):

@@ -47,7 +47,7 @@ print("fit", ts, "sweeps", vim.sweeps, flush=True)
 
 # the parts: second moment, eigensolver
 ops = N.ops()
-ws = vim._workspace(NROWS, F, dev)
+ws = vim._ws                                  # the fit above sized it for NROWS rows
 y = torch.zeros(NROWS, dtype=torch.int64, device=dev)
 mean = torch.zeros(2, F, dtype=torch.float64, device=dev)
 s = torch.empty(F, F, dtype=torch.float64, device=dev)
