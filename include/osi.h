@@ -778,6 +778,53 @@ int osi_vim_project_f32(const float* x, const double* origin, int M, int F, cons
 int osi_vim_scores(const double* z, int M, int K, const float* logits, int C, double alpha, int mode, float* out_f32, double* out_f64,
                    void* ws, size_t ws_bytes, osi_stream_t stream);
 
+/* ABI 27. Activation shaping on the pooled layer, scored with the energy of the re-computed logits (Sun, Guo, Li, "ReAct: Out-of-
+ * distribution Detection With Rectified Activations", NeurIPS 2021; Djurisic, Bozanic, Ashok, Liu, "Extremely Simple Activation Shaping
+ * for Out-of-Distribution Detection", ICLR 2023; Xu, Chen, Fang, Wang, Pan, "Scaling for Training Time and Post-hoc Out-of-distribution
+ * Detection Enhancement", ICLR 2024; Liu, Wang, Owens, Li, "Energy-based Out-of-distribution Detection", NeurIPS 2020;
+ * openset_imagenet/shaping.py). The methods are not part of the reference snapshot; this block is their definition,
+ * tests/shaping_oracle.py its numpy restatement. They shape the network's penultimate activation (osi_resnet50_pooled, below, beside
+ * the executor's other read-outs) and push it through the two head layers again (osi_linear_fwd). Nothing is allocated or
+ * synchronised; every output element is written by the call; workspace contents are never assumed (8-byte aligned; the *_workspace
+ * queries return 0 for arguments the call refuses). Every result is bit-identical from run to run and independent of the grid: the
+ * only atomics count integers, every floating-point sum has a fixed order. OSI_ERR_ARG before any launch on a null required pointer, a
+ * non-positive size, a size past its limit, a bad enum, a bad rank or keep, a short or misaligned workspace.
+ *
+ * The order, that of ABI 24: a value is read as v + 0.0f (-0 becomes +0), that canonical value is compared; values rank by IEEE order,
+ *   every NaN after +Inf ascending, hence before +Inf descending (a NaN's payload is not part of the definition).
+ * osi_order_stats_f32: out[r] (device, [R]) = the canonical value of the ranks[r]-th element, 0-based and ascending, of the n values
+ *   v[0 .. n); a NaN is returned as the quiet NaN 0x7fc00000. ranks is a HOST array of R entries in [0, n), read during the call; they
+ *   may repeat and come in any order. 1 <= R <= OSI_ORDER_STATS_MAX_R. n is 64-bit and v is read with plain 64-bit addressing: no
+ *   2 GiB limit. No floating-point arithmetic but v + 0.0f: every output is an element of the input. Four radix passes of 8 bits over
+ *   all n values, two launches a pass and one before them: 9 launches, a function of nothing; no host read-back between passes.
+ *   ws: osi_order_stats_workspace(n, R) bytes.
+ * osi_shape_rows: out[M][F] from x[M][F], 1 <= F <= OSI_SHAPE_MAX_F; out and x may not overlap. ws: osi_shape_rows_workspace(M, F)
+ *   bytes (the kernels stage nothing in it and the size is a small constant).
+ *   OSI_SHAPE_REACT: out = x > clip ? clip : x, so a NaN stays a NaN (and a NaN clip changes nothing); keep must be 0.
+ *   Every other mode: 1 <= keep <= F, clip is ignored. The KEPT SET of a row is its first `keep` columns in descending order of the
+ *   canonical values, NaN first; equal values, and NaNs among themselves, rank by ascending column. s1 = the sum of the whole row,
+ *   s2 = the sum over the kept set, both of x as stored, in fp64 in an order fixed by F alone.
+ *   OSI_SHAPE_ASH_P: x on the kept set (its bits), +0 elsewhere. OSI_SHAPE_ASH_B: (float)(s1 / keep) on the kept set, +0 elsewhere.
+ *   OSI_SHAPE_ASH_S: x * (float)exp(s1 / s2) on the kept set, +0 elsewhere; the quotient and the exponential in fp64, rounded once to
+ *   fp32, one fp32 product. OSI_SHAPE_SCALE: that product in every column. An all-zero row is not a special case: s1 / s2 = 0 / 0 is
+ *   a NaN and so is every product with it (ASH_S: the kept columns, SCALE: all of them). A NaN or an Inf in a row reaches the sums
+ *   as it is.
+ * osi_logit_scores: out[M] from logits[M][C], computed in fp64 and rounded once, row sums in an order fixed by C. With m the row's
+ *   maximum and m' = m when finite, else 0 (an infinite maximum is not subtracted), s = sum exp(l - m'): OSI_SCORE_ENERGY m' + ln s (the
+ *   log-sum-exp); OSI_SCORE_MAXLOGIT m; OSI_SCORE_MSP exp(m - m') / s (the largest softmax probability). A row of -Inf gives -Inf,
+ *   -Inf and NaN; a NaN in a row gives NaN under every mode. */
+enum { OSI_SHAPE_REACT = 0, OSI_SHAPE_ASH_P = 1, OSI_SHAPE_ASH_B = 2, OSI_SHAPE_ASH_S = 3, OSI_SHAPE_SCALE = 4 };
+enum { OSI_SCORE_ENERGY = 0, OSI_SCORE_MAXLOGIT = 1, OSI_SCORE_MSP = 2 };
+#define OSI_ORDER_STATS_MAX_R 8
+#define OSI_SHAPE_MAX_F 4096
+size_t osi_order_stats_workspace(long long n, int R);
+int osi_order_stats_f32(const float* v, long long n, const long long* ranks, int R, float* out, void* ws, size_t ws_bytes,
+                        osi_stream_t stream);
+size_t osi_shape_rows_workspace(int M, int F);
+int osi_shape_rows(const float* x, int M, int F, int mode, int keep, float clip, float* out, void* ws, size_t ws_bytes,
+                   osi_stream_t stream);
+int osi_logit_scores(const float* logits, int M, int C, int mode, float* out, osi_stream_t stream);
+
 /* ---- optimizer + arena utilities (train.py:356-359 construction, train.py:127,139 zero_grad/step) --- */
 int osi_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,
                   double beta2, double eps, long long step, float grad_scale, osi_stream_t stream);
@@ -1035,6 +1082,15 @@ int osi_resnet50_get_bn_momentum(osi_resnet50_t net, float* momentum);
  * that runs it consumes it. After a forward with a mix a backward with dimage / x_adv returns OSI_ERR_STATE (the rule of every forward
  * with an inference-form prefix). Without a request every entry point issues the launches of ABI 22. */
 int osi_resnet50_set_mix(osi_resnet50_t net, const int* partner, const float* weight);
+
+/* ABI 27. The penultimate activation of the latest forward: the [B][2048] average-pooled output of layer4 (non-negative: the mean of
+ * a block-output ReLU) as it lies in `workspace`, copied to `out` (device memory) on `stream`; *floats = B * 2048. out = NULL only
+ * reports the size (workspace may then be NULL too). Read-only: no executor state changes. Valid after a forward of ANY kind -
+ * training, inference (fused or not) and frozen: every entry point runs the one head (average pool -> fc -> logits) that writes the
+ * tensor, and no backward overwrites it (the head's backward reads it). This is the activation ReAct, ASH and SCALE shape (above,
+ * osi_shape_rows); features = fc(pooled) and logits = logits(features) are osi_linear_fwd on it, bit for bit.
+ * OSI_ERR_ARG on a NULL net or floats, or a NULL workspace with out; OSI_ERR_STATE for a copy before any forward. */
+int osi_resnet50_pooled(osi_resnet50_t net, void* workspace, float* out, size_t* floats, osi_stream_t stream);
 
 /* Per-executor switches: "overlap" (default 1: weight gradients on a low-priority side stream, overlapped with dgrad / BatchNorm
  * backward and joined back into `stream` at the end of every backward call unless "stage_join" = 0; 0 serialises everything on the

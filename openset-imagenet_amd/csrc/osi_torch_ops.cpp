@@ -19,6 +19,7 @@
 //   torch.ops.osi.knn_topk / knn_class_kth                                                   deep nearest neighbours (openset_imagenet/knn.py)
 //   torch.ops.osi.maha_class_means / _scatter / _factor / _whiten / _sqdist                  Mahalanobis scores (openset_imagenet/mahalanobis.py)
 //   torch.ops.osi.eigh_begin / eigh_sweep / eigh_finish / vim_project / vim_scores           ViM scores, symmetric eigensolver (openset_imagenet/vim.py)
+//   torch.ops.osi.resnet50_pooled / order_stats / shape_rows / logit_scores                  activation shaping: ReAct, ASH, SCALE (openset_imagenet/shaping.py)
 //   torch.ops.osi.mix_rows_pairs / resnet50_set_mix / proser_loss_fwd_bwd / proser_scores / linear_fwd / linear_bwd    PROSER (openset_imagenet/proser.py)
 //
 // This file contains no arithmetic: every op validates its tensor arguments (device, dtype, contiguity, sizes), takes the CURRENT
@@ -843,6 +844,58 @@ Tensor vim_scores(const Tensor& z, const c10::optional<Tensor>& logits, double a
     return out;
 }
 
+// ---- activation shaping (include/osi.h, ABI 27): the pooled activation, exact order statistics, shaped rows, logit scores
+Tensor resnet50_pooled(int64_t net, const Tensor& workspace) {
+    need(workspace, at::kByte, "workspace");
+    osi_resnet50_t h = handle(net);
+    TORCH_CHECK((size_t)workspace.numel() >= osi_resnet50_workspace_bytes(h), "osi::resnet50_pooled: workspace too small");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(workspace.device());
+    size_t floats = 0;
+    ok(osi_resnet50_pooled(h, nullptr, nullptr, &floats, nullptr), "osi_resnet50_pooled");
+    Tensor out = at::empty({(int64_t)(floats / 2048), 2048}, workspace.options().dtype(at::kFloat));
+    ok(osi_resnet50_pooled(h, workspace.data_ptr(), out.data_ptr<float>(), &floats, stream_of(workspace)), "osi_resnet50_pooled");
+    return out;
+}
+
+Tensor order_stats(const Tensor& v, at::IntArrayRef ranks, Tensor workspace) {
+    need(v, at::kFloat, "v", NATURAL); need(workspace, at::kByte, "workspace", 8);
+    TORCH_CHECK(v.numel() >= 1 && workspace.device() == v.device(), "osi::order_stats: v is not empty, workspace on its device");
+    TORCH_CHECK(ranks.size() >= 1 && ranks.size() <= OSI_ORDER_STATS_MAX_R, "osi::order_stats: 1 .. ", OSI_ORDER_STATS_MAX_R, " ranks");
+    long long rk[OSI_ORDER_STATS_MAX_R];
+    for (size_t r = 0; r < ranks.size(); ++r) {
+        TORCH_CHECK(ranks[r] >= 0 && ranks[r] < v.numel(), "osi::order_stats: rank ", ranks[r], " outside [0, ", v.numel(), ")");
+        rk[r] = (long long)ranks[r];
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(v.device());
+    Tensor out = at::empty({(int64_t)ranks.size()}, v.options());
+    ok(osi_order_stats_f32(v.data_ptr<float>(), (long long)v.numel(), rk, (int)ranks.size(), out.data_ptr<float>(), workspace.data_ptr(),
+                           (size_t)workspace.numel(), stream_of(v)), "osi_order_stats_f32");
+    return out;
+}
+
+Tensor shape_rows(const Tensor& x, int64_t mode, int64_t keep, double clip, Tensor workspace) {
+    need(x, at::kFloat, "x", NATURAL); need(workspace, at::kByte, "workspace", 8);
+    TORCH_CHECK(x.dim() == 2 && workspace.device() == x.device(), "osi::shape_rows: x [M,F], workspace on its device");
+    const int M = maha_dim(x.size(0), "shape_rows"), F = maha_dim(x.size(1), "shape_rows");
+    const auto clamp = [](int64_t a) { return (int)std::min<int64_t>(std::max<int64_t>(a, -1), INT_MAX); };
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+    Tensor out = at::empty_like(x);
+    ok(osi_shape_rows(x.data_ptr<float>(), M, F, clamp(mode), clamp(keep), (float)clip, out.data_ptr<float>(), workspace.data_ptr(),
+                      (size_t)workspace.numel(), stream_of(x)), "osi_shape_rows");
+    return out;
+}
+
+Tensor logit_scores(const Tensor& logits, int64_t mode) {
+    need(logits, at::kFloat, "logits", NATURAL);
+    TORCH_CHECK(logits.dim() == 2, "osi::logit_scores: logits [M,C]");
+    const int M = maha_dim(logits.size(0), "logit_scores"), C = maha_dim(logits.size(1), "logit_scores");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(logits.device());
+    Tensor out = at::empty({(int64_t)M}, logits.options());
+    ok(osi_logit_scores(logits.data_ptr<float>(), M, C, (int)std::min<int64_t>(std::max<int64_t>(mode, -1), INT_MAX), out.data_ptr<float>(),
+                        stream_of(logits)), "osi_logit_scores");
+    return out;
+}
+
 // ---- PROSER (include/osi.h, ABI 23)
 void need_pairs(const Tensor& ref, const Tensor& partner, const Tensor& weight, int64_t B, const char* what) {
     need(partner, at::kInt, "partner", NATURAL); need(weight, at::kFloat, "weight", NATURAL);
@@ -966,6 +1019,10 @@ TORCH_LIBRARY(osi, m) {
     m.def("eigh_finish(Tensor A, Tensor Vt, Tensor info, Tensor(a!) workspace) -> (Tensor, Tensor)");
     m.def("vim_project(Tensor x, Tensor origin, Tensor R, Tensor(a!) workspace) -> Tensor");
     m.def("vim_scores(Tensor z, Tensor? logits, float alpha, int mode, bool f64_out, Tensor(a!) workspace) -> Tensor");
+    m.def("resnet50_pooled(int net, Tensor workspace) -> Tensor");
+    m.def("order_stats(Tensor v, int[] ranks, Tensor(a!) workspace) -> Tensor");
+    m.def("shape_rows(Tensor x, int mode, int keep, float clip, Tensor(a!) workspace) -> Tensor");
+    m.def("logit_scores(Tensor logits, int mode) -> Tensor");
     m.def("openmax_class_means(Tensor features, Tensor logits, Tensor gt, Tensor(a!) workspace) -> (Tensor, Tensor, Tensor)");
     m.def("openmax_distances(Tensor features, Tensor mav, Tensor? cls, int metric) -> Tensor");
     m.def("openmax_fit_tails(Tensor dist, Tensor gt, Tensor correct, int C, int tailsize, Tensor(a!) workspace) -> "
@@ -1052,6 +1109,10 @@ TORCH_LIBRARY_IMPL(osi, CUDA, m) {
     m.impl("eigh_finish", &eigh_finish);
     m.impl("vim_project", &vim_project);
     m.impl("vim_scores", &vim_scores);
+    m.impl("resnet50_pooled", &resnet50_pooled);
+    m.impl("order_stats", &order_stats);
+    m.impl("shape_rows", &shape_rows);
+    m.impl("logit_scores", &logit_scores);
     m.impl("mix_rows_pairs", &mix_rows_pairs);
     m.impl("proser_loss_fwd_bwd", &proser_loss_fwd_bwd);
     m.impl("proser_scores", &proser_scores);

@@ -1422,6 +1422,20 @@ int osi_resnet50_debug_unit_input(osi_resnet50_t n, void* workspace, int unit, f
     return OSI_OK;
 }
 
+// The head's input as the latest forward left it: forward_impl is the one body of osi_resnet50_forward (training or not, eval_fused or
+// not) and osi_resnet50_forward_frozen, and it always ends in head_fwd, which writes ws + pooled. Nothing else writes that tensor.
+int osi_resnet50_pooled(osi_resnet50_t n, void* workspace, float* out, size_t* floats, osi_stream_t stream) {
+    OSI_REQUIRE(n && floats);
+    *floats = (size_t)n->B * 2048;
+    if (!out) return OSI_OK;
+    OSI_REQUIRE(workspace);
+    if (!n->ran_fwd) return OSI_ERR_STATE;
+    if (hipMemcpyAsync(out, (const float*)workspace + n->pooled, *floats * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) !=
+        hipSuccess)
+        return OSI_ERR_LAUNCH;
+    return OSI_OK;
+}
+
 int osi_resnet50_set_option(osi_resnet50_t n, const char* name, int value) {
     OSI_REQUIRE(n && name);
     if (!strcmp(name, "overlap")) n->overlap = value != 0;

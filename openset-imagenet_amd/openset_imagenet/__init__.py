@@ -19,6 +19,8 @@ from . import mahalanobis
 from .mahalanobis import Mahalanobis
 from . import vim
 from .vim import ViM
+from . import shaping
+from .shaping import ActivationShaping
 from . import proser
 from .proser import PROSER
 from .losses import (AverageMeter, EarlyStopping, EntropicOpensetLoss, GarbageLoss, ObjectosphereLoss, SoftmaxLoss)
@@ -27,4 +29,4 @@ from .dataset import ImagenetDataset
 from .pipeline import CanvasDataset
 
 __all__ = ["ResNet50", "ImagenetDataset", "CanvasDataset", "EntropicOpensetLoss", "SoftmaxLoss", "GarbageLoss", "ObjectosphereLoss", "AverageMeter",
-           "EarlyStopping", "OpenMax", "EVM", "KNN", "Mahalanobis", "ViM", "PROSER", "tools", "util", "train", "metrics", "losses", "dataset"]
+           "EarlyStopping", "OpenMax", "EVM", "KNN", "Mahalanobis", "ViM", "ActivationShaping", "PROSER", "tools", "util", "train", "metrics", "losses", "dataset"]

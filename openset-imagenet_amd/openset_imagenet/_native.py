@@ -106,6 +106,10 @@ MAHA_RAW, MAHA_SIM_GAUSS, MAHA_SIM_LOGISTIC = 0, 1, 2
 MAHA_MAX_F = 32768
 VIM_NORM, VIM_UNKNOWN, VIM_PROBS = 0, 1, 2
 EIGH_MAX_F = 4096
+SHAPE_REACT, SHAPE_ASH_P, SHAPE_ASH_B, SHAPE_ASH_S, SHAPE_SCALE = 0, 1, 2, 3, 4
+SCORE_ENERGY, SCORE_MAXLOGIT, SCORE_MSP = 0, 1, 2
+ORDER_STATS_MAX_R = 8
+SHAPE_MAX_F = 4096
 
 P = c_void_p
 _PD = POINTER(ConvDesc)
@@ -225,6 +229,12 @@ _SIGS = {
     "osi_eigh_finish": (c_int, [P, P, c_int, P, P, P, P, c_size_t, P]),
     "osi_vim_project_f32": (c_int, [P, P, c_int, c_int, P, c_int, P, P, c_size_t, P]),
     "osi_vim_scores": (c_int, [P, c_int, c_int, P, c_int, c_double, c_int, P, P, P, c_size_t, P]),
+    "osi_order_stats_workspace": (c_size_t, [c_longlong, c_int]),
+    "osi_order_stats_f32": (c_int, [P, c_longlong, POINTER(c_longlong), c_int, P, P, c_size_t, P]),
+    "osi_shape_rows_workspace": (c_size_t, [c_int, c_int]),
+    "osi_shape_rows": (c_int, [P, c_int, c_int, c_int, c_int, c_float, P, P, c_size_t, P]),
+    "osi_logit_scores": (c_int, [P, c_int, c_int, c_int, P, P]),
+    "osi_resnet50_pooled": (c_int, [c_void_p, P, P, POINTER(c_size_t), P]),
     "osi_mix_rows_pairs": (c_int, [P, P, P, c_int, c_size_t, P]),
     "osi_proser_loss_fwd_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, P, P, P, P]),
     "osi_proser_scores": (c_int, [P, P, c_float, c_int, c_int, c_int, P, P]),

@@ -476,6 +476,15 @@ class ResNet50(nn.Module):
             raise RuntimeError("adversarial_batch(): the latest backward did not run under next_backward(fgsm=... / pgd=...)")
         return pair[self._adv_idx[shape]]
 
+    def pooled(self):
+        """The penultimate activation of this module's latest forward: the [B, 2048] average-pooled output of layer4 (non-negative),
+        a new device tensor copied out of the executor's workspace (osi_resnet50_pooled). features = fc(pooled), bit for bit. Valid
+        after a forward of any kind (train, eval, frozen) until the next one; ValueError before any forward."""
+        last = getattr(self, "_last", None)
+        if last is None or self._ws is None:
+            raise ValueError("pooled(): this module has not run a forward yet")
+        return N.ops().resnet50_pooled(last[0].h.value, self._ws)
+
     def mark_gradients_ready(self):
         """Tell the fused optimizers that the gradient arena was filled by hand (tests, custom loops) rather than by backward()."""
         self._grads_fresh = True

@@ -24,6 +24,11 @@ covariance in fp64; `--mahalanobis-shrinkage`, `--mahalanobis-relative`) on the 
 device eigensolver, `--vim-dim`; the evaluation network has no logit bias, so the origin is zero), saves it as `{loss}_vim{suffix}.pth`
 and writes `{loss}_{split}_arr{suffix}_vim.npz` with `gt`, `logits`, `features`, `scores` (the known classes' softmax with the virtual
 logit) and `unknown` (alpha * residual norm - logsumexp of the logits).
+`--shaping METHOD` (likewise; softmax and entropic losses; react, ash_p, ash_b, ash_s or scale, `--shaping-percentile`) shapes the
+network's pooled activation (shaping.ActivationShaping; get_arrays(pooled=True) gathers it, react takes its clip from the training
+split), saves the detector as `{loss}_shaping{suffix}.pth` and writes `{loss}_{split}_arr{suffix}_shaping.npz` with `gt`, `logits`,
+`features` (the network's own), `scores` (the softmax of the logits re-computed from the shaped activation) and `unknown` (minus their
+logsumexp).
 `--proser` (likewise; softmax and entropic losses) loads the fine-tuned network, dummy classifier and calibrated bias that
 `python -m openset_imagenet.script.proser` saved as `{loss}_proser{suffix}.pth` (proser.PROSER) and writes
 `{loss}_{split}_arr{suffix}_proser.npz` with `gt`, `logits`, `features` of THAT network, `scores` = probs[:, :C] and `unknown` =
@@ -41,6 +46,7 @@ from ..knn import KNN
 from ..mahalanobis import Mahalanobis
 from ..model import ResNet50
 from ..openmax import OpenMax
+from ..shaping import METHODS as SHAPING_METHODS, ActivationShaping, head_of
 from ..train import _image_loader, get_arrays, load_checkpoint
 from ..vim import ViM
 
@@ -58,7 +64,8 @@ def _known_and_unknown(probs):
 #   cls       the detector
 #   on        args -> whether the option asks for it
 #   options   args -> the keyword arguments of cls
-#   fit       (detector, the `features`, `logits`, `gt` of the training split as a mapping)
+#   fit       (detector, the `features`, `logits`, `gt` of the training split as a mapping; with the shaping row on, `pooled` and
+#             `head` too, here and in the arrays of a split)
 #   score     (detector, arrays of a split) -> numpy `scores` [M, C] and, where the method has one, `unknown` [M]
 #   summary   (detector, args) -> the line printed after the fit, up to "; saved in: ..."
 DETECTORS = (
@@ -94,6 +101,13 @@ DETECTORS = (
                                    unknown=vim.unknown_score(a["features"], a["logits"]).cpu().numpy()),
          summary=lambda vim, args: f"ViM (dim {vim.dim} of {vim.components.shape[0]}) fitted on {vim.count} training samples in "
          f"{vim.sweeps} Jacobi sweeps, alpha {vim.alpha:.6f}"),
+    dict(name="shaping", tag="Shaping ", cls=ActivationShaping, on=lambda args: args.shaping is not None,
+         options=lambda args: dict(method=args.shaping, percentile=args.shaping_percentile),
+         fit=lambda sh, t: sh.fit(t["pooled"], t["gt"], head=t["head"]),
+         score=lambda sh, a: dict(scores=sh.predict(a["pooled"]).cpu().numpy(), unknown=sh.unknown_score(a["pooled"]).cpu().numpy()),
+         summary=lambda sh, args: f"Activation shaping ({sh.method}, percentile {sh.percentile}) " +
+         (f"clips at {sh.clip:.6f}, fitted on {sh.count} training samples" if sh.method == "react" else
+          f"keeps {sh.keep(sh.fc_weight.shape[1])} of {sh.fc_weight.shape[1]} columns")),
 )
 
 
@@ -139,12 +153,19 @@ def get_args(command_line_options=None):
                    "logit_bias=False, so ViM's origin is zero")
     p.add_argument("--vim-dim", type=int, default=None, metavar="D", help="ViM: the dimension of the principal subspace (default: the "
                    "paper's rule, 1000 for 2048 or more feature columns, 512 for 768 or more, else half of them)")
+    p.add_argument("--shaping", choices=sorted(SHAPING_METHODS), default=None, metavar="METHOD", help="also score with activation shaping "
+                   "on the pooled layer (react, ash_p, ash_b, ash_s or scale; softmax and entropic losses): the energy of the logits "
+                   "re-computed from the shaped activation; writes {loss}_{split}_arr{suffix}_shaping.npz")
+    p.add_argument("--shaping-percentile", type=float, default=None, metavar="P", help="shaping: the percentile, 0 < P < 100 (default: "
+                   "the method's own)")
     p.add_argument("--proser", action="store_true", help="also evaluate the PROSER stage saved as {loss}_proser{suffix}.pth (softmax and "
                    "entropic losses) and write {loss}_{split}_arr{suffix}_proser.npz with its scores and the probability of the unknown class")
     args = p.parse_args(command_line_options)
     post_hoc = ["proser"] * args.proser + [row["name"] for row in DETECTORS if row["on"](args)]
     if post_hoc and args.loss == "garbage":
         p.error(f"--{post_hoc[0]} needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
+    if args.shaping_percentile is not None and not 0.0 < args.shaping_percentile < 100.0:
+        p.error(f"--shaping-percentile must satisfy 0 < P < 100, got {args.shaping_percentile}")
     if args.vim_dim is not None and args.vim_dim < 1:
         p.error(f"--vim-dim must be positive, got {args.vim_dim}")
     if not 0.0 <= args.mahalanobis_shrinkage <= 1.0:
@@ -281,6 +302,15 @@ def vim_arrays(train_arrays, split_arrays, dim=None):
     return _detector_arrays("vim", train_arrays, split_arrays, dim=dim)
 
 
+def shaping_arrays(train_arrays, split_arrays, head, method, percentile=None):
+    """`--shaping` on arrays: ActivationShaping over `head` (shaping.head_of(model)), fitted on the training split's `pooled` and `gt`
+    (react; the other methods read no data) and run on the split's `pooled`. Returns (shaping, arrays) with `scores` = the [M, C]
+    softmax of the logits re-computed from the shaped activation and `unknown` = the [M] values -logsumexp of them."""
+    if not isinstance(train_arrays, ActivationShaping):
+        train_arrays = dict(train_arrays, head=head)
+    return _detector_arrays("shaping", train_arrays, split_arrays, method=method, percentile=percentile)
+
+
 def proser_arrays(proser, split_arrays):
     """`--proser` on arrays: `gt`, `logits`, `features` of one split as the fine-tuned network of `proser` (proser.PROSER) gave them
     (mappings as get_arrays' .npz holds them). Returns the numpy `gt`, `logits`, `features`, `scores` = probs[:, :C] and `unknown` =
@@ -341,13 +371,18 @@ def main(command_line_options=None):
         proser = load_proser(proser_path, n_classes)
         print(f"PROSER stage loaded from: {proser_path} (dummy {proser.dummy_count}, mix at {proser.mix_at}, bias {float(proser.bias):.6f})")
     fitted = [(row, row["cls"](**row["options"](args))) for row in DETECTORS if row["on"](args)]      # refuses bad options first
+    shaping = any(row["name"] == "shaping" for row, _ in fitted)     # the one row that reads the pooled activation and the head:
+    extra = {}                                                       # with it on, `pooled` and `head` join the mappings below
     if fitted:
         train_ds = _image_loader(args.protocol_directory / f"p{args.protocol}_train.csv", args.imagenet_directory, False, "eval")
         print(f"train dataset len:{len(train_ds)}, labels:{train_ds.table.label_count}")
         loader = torch.utils.data.DataLoader(train_ds, batch_size=args.batch_size, num_workers=args.workers)
-        t_gt, t_logits, t_features, _ = get_arrays(model=model, loader=loader)
+        arrays = get_arrays(model=model, loader=loader, pooled=shaping)
+        t_gt, t_logits, t_features = arrays[:3]
+        if shaping:
+            extra = dict(pooled=arrays[4], head=head_of(model))
     for row, detector in fitted:
-        row["fit"](detector, dict(gt=t_gt, logits=t_logits, features=t_features))
+        row["fit"](detector, dict(gt=t_gt, logits=t_logits, features=t_features, **extra))
         path = args.output_directory / f"{args.loss}_{row['name']}{suffix}.pth"
         torch.save(detector.state_dict(), path)
         print(f"{row['summary'](detector, args)}; saved in: {path}")
@@ -364,7 +399,10 @@ def main(command_line_options=None):
 
     for split, ds in splits.items():
         loader = torch.utils.data.DataLoader(ds, batch_size=args.batch_size, num_workers=args.workers)
-        gt, logits, features, scores = get_arrays(model=model, loader=loader)
+        arrays = get_arrays(model=model, loader=loader, pooled=shaping)
+        gt, logits, features, scores = arrays[:4]
+        if shaping:
+            extra = dict(extra, pooled=arrays[4])
         file_path = args.output_directory / f"{args.loss}_{split}_arr{suffix}.npz"
         np.savez(file_path, gt=gt, logits=logits, features=features, scores=scores)
         print(f"Target labels, logits, features and scores saved in: {file_path}")
@@ -374,7 +412,8 @@ def main(command_line_options=None):
             for line in oscr_lines(split, gt, s):
                 print(line)
         for row, detector in fitted:
-            write(split, row["name"], row["tag"], gt, scored_arrays(row["score"], detector, dict(gt=gt, logits=logits, features=features)))
+            write(split, row["name"], row["tag"], gt,
+                  scored_arrays(row["score"], detector, dict(gt=gt, logits=logits, features=features, **extra)))
         if proser is not None:
             p_gt, p_logits, p_features, _ = get_arrays(model=proser.model, loader=loader)
             write(split, "proser", "PROSER ", p_gt, proser_arrays(proser, dict(gt=p_gt, logits=p_logits, features=p_features)))

@@ -432,12 +432,13 @@ def validate(model, data_loader, loss_fn, n_classes, trackers, cfg, shard=None):
             trackers["conf_unk" + suffix].update(neg_sum / neg_count, int(neg_count))
 
 
-def get_arrays(model, loader):
+def get_arrays(model, loader, pooled=False):
     """Targets, logits, deep features and softmax scores of a whole dataset as numpy arrays (reference train.py:200-234);
-    everything is gathered on the device and copied to the host once."""
+    everything is gathered on the device and copied to the host once. `pooled=True` (this build's addition, for shaping.py) returns
+    a fifth array [N, 2048]: the average-pooled activation under the features (ResNet50.pooled)."""
     from .pipeline import device_batch
     model.eval()
-    t, lg, ft, sc = [], [], [], []
+    t, lg, ft, sc, pl = [], [], [], [], []
     with torch.no_grad():
         for batch in loader:
             images, labels = device_batch(batch)
@@ -446,8 +447,11 @@ def get_arrays(model, loader):
             lg.append(logit)
             ft.append(feature)
             sc.append(_losses.softmax(logit))
+            if pooled:
+                pl.append(_unwrap(model).pooled())
     cat = lambda xs: torch.cat(xs).cpu().numpy()
-    return cat(t).astype(np.float32), cat(lg), cat(ft), cat(sc)
+    arrays = cat(t).astype(np.float32), cat(lg), cat(ft), cat(sc)
+    return arrays + (cat(pl),) if pooled else arrays
 
 
 def _image_loader(csv_file, imagenet_path, train, loss_type, uint8=True):
