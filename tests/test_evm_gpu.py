@@ -14,11 +14,10 @@ import pytest
 import torch
 
 import evm_oracle as E
+from gpu_harness import Out, call, on, poisoned, same_bytes
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256                                  # bytes = 64 floats, before and after every output
-CANARY = 0xA5
 METRICS = (E.EUCLIDEAN, E.COSINE)
 NAMES = {E.EUCLIDEAN: "euclidean", E.COSINE: "cosine"}
 TAILS = (2, 20, 4096)
@@ -27,43 +26,16 @@ MULT = 0.5
 
 
 # --------------------------------------------------------------------------------------------------------------- helpers
-class Out:
-    """A device output with guard bands: `t` is the tensor the kernel writes, check() says whether the bands kept their canary."""
-
-    def __init__(self, shape, dtype, dev):
-        n = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
-        self.raw = torch.full((GUARD + (n + 7) // 8 * 8 + GUARD,), CANARY, dtype=torch.uint8, device=dev)
-        self.n = n
-        self.t = self.raw[GUARD:GUARD + n].view(dtype).view(*shape)
-
-    def check(self):
-        return bool((self.raw[:GUARD] == CANARY).all()) and bool((self.raw[GUARD + self.n:] == CANARY).all())
-
-    def np(self):
-        return self.t.cpu().numpy()
-
-
-def dev_of(cuda, *arrays):
-    return [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(cuda) for a in arrays]
-
-
-def workspace(R, N, F, cuda, fill=0xFF):
+def workspace(R, N, F, cuda, fill=None):
     from openset_imagenet import _native as NL
     nb = NL.lib().osi_evm_workspace(R, N, F)
-    return torch.full((nb,), fill, dtype=torch.uint8, device=cuda), nb
+    return poisoned(nb, cuda, fill), nb
 
 
-def call(fn, *args):
-    from openset_imagenet import _native as NL
-    conv = [a.data_ptr() if isinstance(a, torch.Tensor) else (a.t.data_ptr() if isinstance(a, Out) else a) for a in args]
-    NL.check(fn(*conv, torch.cuda.current_stream().cuda_stream), fn.__name__)
-    torch.cuda.synchronize()
-
-
-def run_distances(cuda, a, b, metric, fill=0xFF, da=None):
+def run_distances(cuda, a, b, metric, fill=None, da=None):
     from openset_imagenet import _native as NL
     (R, F), N = a.shape, b.shape[0]
-    ta, tb = dev_of(cuda, a, b)
+    ta, tb = on(cuda, a, b)
     ws, nb = workspace(R, N, F, cuda, fill)
     dist = Out((R, N), torch.float32, cuda)
     call(NL.lib().osi_evm_distances, ta if da is None else da, R, tb, N, F, metric, dist, ws, nb)
@@ -71,10 +43,10 @@ def run_distances(cuda, a, b, metric, fill=0xFF, da=None):
     return dist.np()
 
 
-def run_fit_rows(cuda, dist, N, gt, cls, T, fill=0xFF):
+def run_fit_rows(cuda, dist, N, gt, cls, T, fill=None):
     from openset_imagenet import _native as NL
     R, ld = dist.shape
-    dd, dg = dev_of(cuda, dist, gt)
+    dd, dg = on(cuda, dist, gt)
     ws, nb = workspace(R, N, 1, cuda, fill)
     outs = dict(shape=Out((R,), torch.float64, cuda), scale=Out((R,), torch.float64, cuda), shift=Out((R,), torch.float64, cuda),
                 fitted=Out((R,), torch.uint8, cuda), tail_count=Out((R,), torch.int64, cuda), flags2=Out((2,), torch.int64, cuda))
@@ -83,12 +55,12 @@ def run_fit_rows(cuda, dist, N, gt, cls, T, fill=0xFF):
     return {k: o.np() for k, o in outs.items()}
 
 
-def run_set_cover(cuda, dpp, shape, scale, shift, fitted, threshold, fill=0xFF):
+def run_set_cover(cuda, dpp, shape, scale, shift, fitted, threshold, fill=None):
     from openset_imagenet import _native as NL
     R = len(fitted)
     ws, nb = workspace(R, 1, 1, cuda, fill)
     order, n_ev = Out((R,), torch.int64, cuda), Out((1,), torch.int64, cuda)
-    call(NL.lib().osi_evm_set_cover, dev_of(cuda, dpp)[0], R, *dev_of(cuda, shape, scale, shift, fitted), MULT, threshold, order, n_ev, ws, nb)
+    call(NL.lib().osi_evm_set_cover, *on(cuda, dpp), R, *on(cuda, shape, scale, shift, fitted), MULT, threshold, order, n_ev, ws, nb)
     assert order.check() and n_ev.check()
     return order.np(), int(n_ev.np()[0])
 
@@ -98,13 +70,9 @@ def run_probs(cuda, dist, V, shape, scale, shift, ev_start):
     M, ld = dist.shape
     C = len(ev_start) - 1
     probs = Out((M, C), torch.float32, cuda)
-    call(NL.lib().osi_evm_probs, dev_of(cuda, dist)[0], M, V, ld, *dev_of(cuda, shape, scale, shift, ev_start), C, MULT, probs)
+    call(NL.lib().osi_evm_probs, *on(cuda, dist), M, V, ld, *on(cuda, shape, scale, shift, ev_start), C, MULT, probs)
     assert probs.check()
     return probs.np()
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 def same_values(a, b):
@@ -167,7 +135,7 @@ def test_distances_take_the_same_bits_on_both_load_paths(cuda):
     shifted = torch.zeros(a.size + 1, dtype=torch.float32, device=cuda)
     shifted[1:] = torch.from_numpy(a).to(cuda).reshape(-1)
     for metric in METRICS:
-        assert same_bits(run_distances(cuda, a, b, metric), run_distances(cuda, a, b, metric, da=shifted[1:]))
+        assert same_bytes(run_distances(cuda, a, b, metric), run_distances(cuda, a, b, metric, da=shifted[1:]))
 
 
 def test_distances_zero_nan_and_inf_rows(cuda):
@@ -235,7 +203,7 @@ def test_fit_rows_column_permutation_changes_no_bit(cuda):
             p = np.random.default_rng(seed).permutation(FIT_N)
             again = run_fit_rows(cuda, np.ascontiguousarray(dist[:, :FIT_N][:, p]), FIT_N, gt[p], FIT_CLS, T)     # ld == N here
             for k in base:
-                assert same_bits(base[k], again[k]), (T, seed, k)
+                assert same_bytes(base[k], again[k]), (T, seed, k)
 
 
 def test_fit_rows_labels_outside_the_classes_are_negatives(cuda):
@@ -251,8 +219,8 @@ def test_fit_rows_labels_outside_the_classes_are_negatives(cuda):
 
 def test_fit_rows_workspace_contents_do_not_matter(cuda):
     dist, gt = fit_case(cuda)
-    a, b = run_fit_rows(cuda, dist, FIT_N, gt, FIT_CLS, 20, fill=0xFF), run_fit_rows(cuda, dist, FIT_N, gt, FIT_CLS, 20, fill=0)
-    assert all(same_bits(a[k], b[k]) for k in a)
+    a, b = run_fit_rows(cuda, dist, FIT_N, gt, FIT_CLS, 20, fill=None), run_fit_rows(cuda, dist, FIT_N, gt, FIT_CLS, 20, fill=0)
+    assert all(same_bytes(a[k], b[k]) for k in a)
 
 
 # ------------------------------------------------------------------------------------------------------------- set cover
@@ -320,8 +288,8 @@ def test_set_cover_built_tie_and_unfitted_rows(cuda, R):
 
 def test_set_cover_workspace_contents_do_not_matter(cuda):
     args = cover_params(300, seed=300)
-    a, b = run_set_cover(cuda, *args, 0.5, fill=0xFF), run_set_cover(cuda, *args, 0.5, fill=0)
-    assert same_bits(a[0], b[0]) and a[1] == b[1]
+    a, b = run_set_cover(cuda, *args, 0.5, fill=None), run_set_cover(cuda, *args, 0.5, fill=0)
+    assert same_bytes(a[0], b[0]) and a[1] == b[1]
 
 
 # ----------------------------------------------------------------------------------------------------------------- probs
@@ -368,7 +336,7 @@ def fit_device(shape, integer, metric, cover, **kw):
 def check_model(evm, want, where):
     host = {k: getattr(evm, k).cpu().numpy() for k in ("ev_features", "ev_shape", "ev_scale", "ev_shift", "ev_start", "flags")}
     assert np.array_equal(host["ev_start"], want["ev_start"]), (where, host["ev_start"], want["ev_start"])
-    assert same_bits(host["ev_features"], want["ev_features"]), where       # the same rows in the same order
+    assert same_bytes(host["ev_features"], want["ev_features"]), where       # the same rows in the same order
     assert np.array_equal(host["ev_shift"], want["ev_shift"]) and np.array_equal(host["flags"], want["flags"]), where
     for k in ("ev_shape", "ev_scale"):
         if len(want[k]):
@@ -399,7 +367,7 @@ def test_end_to_end_real_features_on_the_device_s_distances(cuda, metric, cover)
     f, gt = e2e_case(shape, False)
 
     def device_distances(a, b):
-        ta, tb = dev_of(cuda, a, b)
+        ta, tb = on(cuda, a, b)
         ws, _ = workspace(len(a), len(b), a.shape[1], cuda)
         return NL.ops().evm_distances(ta, tb, metric, ws).cpu().numpy()
 
@@ -422,7 +390,7 @@ def test_use_negatives_false_drops_the_negative_rows(cuda):
     evm = fit_device(shape, True, E.EUCLIDEAN, None, use_negatives=False)
     check_model(evm, E.fit(f, gt, E2E_TAIL, MULT, E.EUCLIDEAN, use_negatives=False), "use_negatives=False")
     both = fit_device(shape, True, E.EUCLIDEAN, None)
-    assert not same_bits(evm.ev_shift.cpu().numpy(), both.ev_shift.cpu().numpy())      # the negatives were among the nearest
+    assert not same_bytes(evm.ev_shift.cpu().numpy(), both.ev_shift.cpu().numpy())      # the negatives were among the nearest
 
 
 # ------------------------------------------------------------------------------------------------------------ properties
@@ -432,8 +400,8 @@ def test_two_runs_give_identical_bits(cuda):
     for metric in METRICS:
         a, b = fit_device(shape, False, metric, 0.5), fit_device(shape, False, metric, 0.5)
         for name in ("ev_features", "ev_shape", "ev_scale", "ev_shift", "ev_start", "flags"):
-            assert same_bits(getattr(a, name).cpu().numpy(), getattr(b, name).cpu().numpy()), (metric, name)
-        assert same_bits(a.predict(q).cpu().numpy(), b.predict(q).cpu().numpy())
+            assert same_bytes(getattr(a, name).cpu().numpy(), getattr(b, name).cpu().numpy()), (metric, name)
+        assert same_bytes(a.predict(q).cpu().numpy(), b.predict(q).cpu().numpy())
 
 
 def test_chunked_predict_and_device_inputs(cuda):
@@ -442,13 +410,13 @@ def test_chunked_predict_and_device_inputs(cuda):
     evm = fit_device(shape, False, E.COSINE, None)
     whole = evm.predict(f).cpu().numpy()
     for chunk in (1, 7, 128, 299, 1000):
-        assert same_bits(evm.predict(f, chunk=chunk).cpu().numpy(), whole), chunk
-    assert same_bits(evm.predict(torch.from_numpy(f).to(cuda)).cpu().numpy(), whole)
-    assert same_bits(evm.predict(f[17:18]).cpu().numpy(), whole[17:18]) and evm.predict(f[:0]).shape == (0, 5)
+        assert same_bytes(evm.predict(f, chunk=chunk).cpu().numpy(), whole), chunk
+    assert same_bytes(evm.predict(torch.from_numpy(f).to(cuda)).cpu().numpy(), whole)
+    assert same_bytes(evm.predict(f[17:18]).cpu().numpy(), whole[17:18]) and evm.predict(f[:0]).shape == (0, 5)
     assert np.array_equal(f, e2e_case(shape, False)[0])     # inputs are never written
     dev_fit = fit_device(shape, False, E.COSINE, None)
     dev_fit.fit(torch.from_numpy(f).to(cuda), torch.from_numpy(gt).to(cuda))
-    assert same_bits(dev_fit.ev_shape.cpu().numpy(), evm.ev_shape.cpu().numpy())
+    assert same_bytes(dev_fit.ev_shape.cpu().numpy(), evm.ev_shape.cpu().numpy())
 
 
 def test_state_dict_gives_the_same_bits(cuda, tmp_path):
@@ -462,7 +430,7 @@ def test_state_dict_gives_the_same_bits(cuda, tmp_path):
     again = EVM().load_state_dict(torch.load(tmp_path / "evm.pth", weights_only=True))
     assert (again.tailsize, again.cover_threshold, again.distance, again.distance_multiplier) == (E2E_TAIL, 0.5, "euclidean", MULT)
     assert not again.ev_features.is_cuda                    # the state moves on first use
-    assert same_bits(again.predict(f).cpu().numpy(), evm.predict(f).cpu().numpy()) and again.ev_features.is_cuda
+    assert same_bytes(again.predict(f).cpu().numpy(), evm.predict(f).cpu().numpy()) and again.ev_features.is_cuda
 
 
 def test_torch_ops_match_the_abi(cuda):
@@ -470,25 +438,25 @@ def test_torch_ops_match_the_abi(cuda):
     ops = NL.ops()
     dist, gt = fit_case(cuda)
     a, b = pair((65, 129, 130), False)
-    ta, tb = dev_of(cuda, a, b)
+    ta, tb = on(cuda, a, b)
     ws, _ = workspace(65, 129, 130, cuda)
-    assert same_bits(ops.evm_distances(ta, tb, E.COSINE, ws).cpu().numpy(), run_distances(cuda, a, b, E.COSINE))
+    assert same_bytes(ops.evm_distances(ta, tb, E.COSINE, ws).cpu().numpy(), run_distances(cuda, a, b, E.COSINE))
     big_ws, _ = workspace(300, FIT_N, 1, cuda)
-    out = ops.evm_fit_rows(*dev_of(cuda, dist, gt), FIT_CLS, 20, MULT, big_ws)
+    out = ops.evm_fit_rows(*on(cuda, dist, gt), FIT_CLS, 20, MULT, big_ws)
     ref = run_fit_rows(cuda, dist, FIT_N, gt, FIT_CLS, 20)
     for got, k in zip(out, ("shape", "scale", "shift", "fitted", "tail_count", "flags2")):
-        assert same_bits(got.cpu().numpy(), ref[k]), k
+        assert same_bytes(got.cpu().numpy(), ref[k]), k
     args = cover_params(300, seed=300)
-    order, n_ev = ops.evm_set_cover(*dev_of(cuda, *args), MULT, 0.5, big_ws)
+    order, n_ev = ops.evm_set_cover(*on(cuda, *args), MULT, 0.5, big_ws)
     ref_order, ref_n = run_set_cover(cuda, *args, 0.5)
-    assert same_bits(order.cpu().numpy(), ref_order) and int(n_ev) == ref_n
+    assert same_bytes(order.cpu().numpy(), ref_order) and int(n_ev) == ref_n
     rng = np.random.default_rng(8)
     d, shape, scale, shift = (2 * rng.random((20, 6))).astype(np.float32), 1 + rng.random(6), 1 + rng.random(6), -rng.random(6)
     start = np.array([0, 2, 6], dtype=np.int64)
-    assert same_bits(ops.evm_probs(*dev_of(cuda, d, shape, scale, shift, start), MULT).cpu().numpy(),
+    assert same_bytes(ops.evm_probs(*on(cuda, d, shape, scale, shift, start), MULT).cpu().numpy(),
                      run_probs(cuda, d, 6, shape, scale, shift, start))
     with pytest.raises(RuntimeError):
-        ops.evm_fit_rows(*dev_of(cuda, dist, gt), FIT_CLS, 1, MULT, big_ws)                # tailsize 1: refused by the ABI
+        ops.evm_fit_rows(*on(cuda, dist, gt), FIT_CLS, 1, MULT, big_ws)                # tailsize 1: refused by the ABI
     with pytest.raises(RuntimeError):
         ops.evm_distances(ta, tb[:, :100].contiguous(), E.COSINE, ws)
 
@@ -504,11 +472,11 @@ def test_evm_arrays_writes_its_keys(cuda, tmp_path):
     assert sorted(arrays) == ["features", "gt", "logits", "scores"]
     assert arrays["scores"].shape == (97, 5) and arrays["scores"].dtype == np.float32
     assert all(isinstance(v, np.ndarray) for v in arrays.values())
-    assert same_bits(arrays["scores"], fit_device((300, 5, 16), True, E.COSINE, 0.5).predict(f[:97]).cpu().numpy())
+    assert same_bytes(arrays["scores"], fit_device((300, 5, 16), True, E.COSINE, 0.5).predict(f[:97]).cpu().numpy())
     np.savez(tmp_path / "x_evm.npz", **arrays)
     assert sorted(np.load(tmp_path / "x_evm.npz").files) == sorted(arrays)
     _, again = evm_arrays(evm, split, E2E_TAIL)              # a fitted object is taken as it is
-    assert same_bits(again["scores"], arrays["scores"])
+    assert same_bytes(again["scores"], arrays["scores"])
     rows = arrays["gt"] != -2                                # the scores feed the OSCR curve as they are
     ccr, fpr = util.calculate_oscr(arrays["gt"][rows], arrays["scores"][rows], unk_label=-1)
     assert len(ccr) == len(fpr) > 0

@@ -13,11 +13,10 @@ import torch
 
 import evm_oracle as E
 import knn_oracle as K
+from gpu_harness import Out, call, on, poisoned
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256                                  # bytes before and after every output
-CANARY = 0xA5
 PAD = 3                                      # padding columns behind the N used ones
 KS = (1, 2, 64, 1024)
 NS = (1, 63, 64, 65, 257, 4097)              # around the wave, more than one tile of 2048 columns (and than one wave's 2048)
@@ -26,37 +25,10 @@ TRANSFORMS = (K.RAW, K.SIM_COSINE, K.SIM_INVERSE)
 
 
 # --------------------------------------------------------------------------------------------------------------- helpers
-class Out:
-    """A device output with guard bands: `t` is the tensor the kernel writes, check() says whether the bands kept their canary."""
-
-    def __init__(self, shape, dtype, dev):
-        n = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
-        self.raw = torch.full((GUARD + (n + 7) // 8 * 8 + GUARD,), CANARY, dtype=torch.uint8, device=dev)
-        self.n = n
-        self.t = self.raw[GUARD:GUARD + n].view(dtype).view(*shape)
-
-    def check(self):
-        return bool((self.raw[:GUARD] == CANARY).all()) and bool((self.raw[GUARD + self.n:] == CANARY).all())
-
-    def np(self):
-        return self.t.cpu().numpy()
-
-
-def on(cuda, a):
-    return None if a is None else torch.tensor(np.asarray(a)).to(cuda)        # a copy: the shared matrices are read-only
-
-
-def call(fn, *args):
-    from openset_imagenet import _native as NL
-    conv = [a.data_ptr() if isinstance(a, torch.Tensor) else (a.t.data_ptr() if isinstance(a, Out) else a) for a in args]
-    NL.check(fn(*conv, torch.cuda.current_stream().cuda_stream), fn.__name__)
-    torch.cuda.synchronize()
-
-
 def workspace(M, N, k, cuda):
     from openset_imagenet import _native as NL
     nb = NL.lib().osi_knn_workspace(M, N, k)
-    return torch.full((nb,), 0xFF, dtype=torch.uint8, device=cuda), nb
+    return poisoned(nb, cuda), nb
 
 
 def run_topk(cuda, dist, N, k, skip=None):
@@ -64,7 +36,7 @@ def run_topk(cuda, dist, N, k, skip=None):
     M, ld = dist.shape
     ws, nb = workspace(M, N, k, cuda)
     d, i = Out((M, k), torch.float32, cuda), Out((M, k), torch.int64, cuda)
-    call(NL.lib().osi_knn_topk, on(cuda, dist), M, N, ld, k, on(cuda, skip), d, i, ws, nb)
+    call(NL.lib().osi_knn_topk, *on(cuda, dist), M, N, ld, k, *on(cuda, skip), d, i, ws, nb)
     assert d.check() and i.check()
     return d.np(), i.np()
 
@@ -75,7 +47,7 @@ def run_class_kth(cuda, dist, N, start, k, skip=None, what=K.RAW):
     C = len(start) - 1
     ws, nb = workspace(M, N, k, cuda)
     out = Out((M, C), torch.float32, cuda)
-    call(NL.lib().osi_knn_class_kth, on(cuda, dist), M, N, ld, on(cuda, np.asarray(start, dtype=np.int64)), C, k, on(cuda, skip), what,
+    call(NL.lib().osi_knn_class_kth, *on(cuda, dist), M, N, ld, *on(cuda, np.asarray(start, dtype=np.int64)), C, k, *on(cuda, skip), what,
          out, ws, nb)
     assert out.check()
     return out.np()

@@ -22,48 +22,20 @@ import pytest
 import torch
 
 import mahalanobis_oracle as O
+from gpu_harness import Out, call, on, poisoned, ulp32
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256                                  # bytes before and after every output
-CANARY = 0xA5
 FS = (1, 15, 16, 17, 63, 64, 65, 130, 131)
 NS = (1, 3, 4, 5, 63, 257, 1031)
 CS = (1, 3, 7)
 
 
 # --------------------------------------------------------------------------------------------------------------- helpers
-class Out:
-    """A device output with guard bands: `t` is the tensor the kernel writes, check() says whether the bands kept their canary."""
-
-    def __init__(self, shape, dtype, dev):
-        n = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
-        self.raw = torch.full((GUARD + (n + 7) // 8 * 8 + GUARD,), CANARY, dtype=torch.uint8, device=dev)
-        self.n = n
-        self.t = self.raw[GUARD:GUARD + n].view(dtype).view(*shape)
-
-    def check(self):
-        return bool((self.raw[:GUARD] == CANARY).all()) and bool((self.raw[GUARD + self.n:] == CANARY).all())
-
-    def np(self):
-        return self.t.cpu().numpy()
-
-
-def on(cuda, a):
-    return None if a is None else torch.tensor(np.asarray(a)).to(cuda)
-
-
-def call(fn, *args):
-    from openset_imagenet import _native as NL
-    conv = [a.data_ptr() if isinstance(a, torch.Tensor) else (a.t.data_ptr() if isinstance(a, Out) else a) for a in args]
-    NL.check(fn(*conv, torch.cuda.current_stream().cuda_stream), fn.__name__)
-    torch.cuda.synchronize()
-
-
 def workspace(N, C, F, cuda):
     from openset_imagenet import _native as NL
     nb = NL.lib().osi_maha_workspace(N, C, F)
-    return torch.full((nb,), 0xFF, dtype=torch.uint8, device=cuda), nb
+    return poisoned(nb, cuda), nb
 
 
 def run_means(cuda, x, gt, C):
@@ -71,7 +43,7 @@ def run_means(cuda, x, gt, C):
     N, F = x.shape
     ws, nb = workspace(N, C, F, cuda)
     mean, count = Out((C + 1, F), torch.float64, cuda), Out((C + 1,), torch.int64, cuda)
-    call(NL.lib().osi_maha_class_means, on(cuda, x), on(cuda, gt), N, C, F, mean, count, ws, nb)
+    call(NL.lib().osi_maha_class_means, *on(cuda, x), *on(cuda, gt), N, C, F, mean, count, ws, nb)
     assert mean.check() and count.check()
     return mean.np(), count.np()
 
@@ -82,7 +54,7 @@ def run_scatter(cuda, x, gt, mean, C, mode, into=None):
     N, F = x.shape
     ws, nb = workspace(N, C, F, cuda)
     S = into if into is not None else Out((F, F), torch.float64, cuda)
-    call(NL.lib().osi_maha_scatter, on(cuda, x), on(cuda, gt), on(cuda, mean), N, C, F, mode, int(into is not None), S, ws, nb)
+    call(NL.lib().osi_maha_scatter, *on(cuda, x), *on(cuda, gt), *on(cuda, mean), N, C, F, mode, int(into is not None), S, ws, nb)
     assert S.check()
     return S
 
@@ -93,7 +65,7 @@ def run_factor(cuda, S, scale, shrinkage):
     ws, nb = workspace(1, 1, F, cuda)
     L, W = Out((F, F), torch.float64, cuda), Out((F, F), torch.float64, cuda)
     logdet, info = Out((1,), torch.float64, cuda), Out((1,), torch.int32, cuda)
-    call(NL.lib().osi_maha_factor, on(cuda, S), F, float(scale), float(shrinkage), L, W, logdet, info, ws, nb)
+    call(NL.lib().osi_maha_factor, *on(cuda, S), F, float(scale), float(shrinkage), L, W, logdet, info, ws, nb)
     assert L.check() and W.check() and logdet.check() and info.check()
     return L.np(), W.np(), float(logdet.np()[0]), int(info.np()[0])
 
@@ -104,7 +76,7 @@ def run_whiten(cuda, x, W):
     ws, nb = workspace(1, 1, F, cuda)
     z = Out((M, F), torch.float64, cuda)
     fn = NL.lib().osi_maha_whiten_f32 if x.dtype == np.float32 else NL.lib().osi_maha_whiten_f64
-    call(fn, on(cuda, x), M, F, on(cuda, W), z, ws, nb)
+    call(fn, *on(cuda, x), M, F, *on(cuda, W), z, ws, nb)
     assert z.check()
     return z.np()
 
@@ -114,7 +86,7 @@ def run_sqdist(cuda, z, zm, minus=None, what=O.RAW, f64=False):
     (M, F), C = z.shape, len(zm)
     ws, nb = workspace(1, 1, F, cuda)
     out = Out((M, C), torch.float64 if f64 else torch.float32, cuda)
-    call(NL.lib().osi_maha_sqdist, on(cuda, z), M, on(cuda, zm), C, F, on(cuda, minus), what, None if f64 else out, out if f64 else None,
+    call(NL.lib().osi_maha_sqdist, *on(cuda, z), M, *on(cuda, zm), C, F, *on(cuda, minus), what, None if f64 else out, out if f64 else None,
          ws, nb)
     assert out.check()
     return out.np()
@@ -148,10 +120,6 @@ def mean_bound(x, gt, C):
 def cond_sym(a):
     ev = np.linalg.eigvalsh(a)
     return ev[-1] / ev[0] if ev[0] > 0 else np.inf
-
-
-def ulp32(ref):
-    return np.spacing(np.abs(ref).astype(np.float32)).astype(np.float64)
 
 
 # ------------------------------------------------------------------------------------------------- means, scatter: exact

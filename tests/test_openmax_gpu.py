@@ -11,11 +11,10 @@ import pytest
 import torch
 
 import openmax_oracle as O
+from gpu_harness import Out, call, on, poisoned, same_bytes, ulps
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256                                  # bytes = 64 floats, before and after every output
-CANARY = 0xA5
 METRICS = (O.EUCLIDEAN, O.COSINE)
 TAILS = (2, 20, 4096)
 
@@ -29,43 +28,16 @@ E2E_CASES = [(shape, metric) for shape in O.SHAPES for metric in METRICS]
 
 
 # --------------------------------------------------------------------------------------------------------------- helpers
-class Out:
-    """A device output with guard bands: `t` is the tensor the kernel writes, check() says whether the bands kept their canary."""
-
-    def __init__(self, shape, dtype, dev):
-        n = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
-        self.raw = torch.full((GUARD + (n + 7) // 8 * 8 + GUARD,), CANARY, dtype=torch.uint8, device=dev)
-        self.n = n
-        self.t = self.raw[GUARD:GUARD + n].view(dtype).view(*shape)
-
-    def check(self):
-        return bool((self.raw[:GUARD] == CANARY).all()) and bool((self.raw[GUARD + self.n:] == CANARY).all())
-
-    def np(self):
-        return self.t.cpu().numpy()
-
-
-def dev_of(cuda, *arrays):
-    return [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(cuda) for a in arrays]
-
-
-def workspace(N, C, F, cuda, fill=0xFF):
+def workspace(N, C, F, cuda, fill=None):
     from openset_imagenet import _native as NL
     nb = NL.lib().osi_openmax_workspace(N, C, F)
-    return torch.full((nb,), fill, dtype=torch.uint8, device=cuda), nb
+    return poisoned(nb, cuda, fill), nb
 
 
-def call(fn, *args):
-    from openset_imagenet import _native as NL
-    conv = [a.data_ptr() if isinstance(a, torch.Tensor) else (a.t.data_ptr() if isinstance(a, Out) else a) for a in args]
-    NL.check(fn(*conv, torch.cuda.current_stream().cuda_stream), fn.__name__)
-    torch.cuda.synchronize()
-
-
-def run_class_means(cuda, f, lg, gt, fill=0xFF):
+def run_class_means(cuda, f, lg, gt, fill=None):
     from openset_imagenet import _native as NL
     (N, F), C = f.shape, lg.shape[1]
-    df, dl, dg = dev_of(cuda, f, lg, gt)
+    df, dl, dg = on(cuda, f, lg, gt)
     ws, nb = workspace(N, C, F, cuda, fill)
     mav, count, correct = Out((C, F), torch.float32, cuda), Out((C,), torch.int64, cuda), Out((N,), torch.uint8, cuda)
     call(NL.lib().osi_openmax_class_means, df, dl, dg, N, C, F, mav, count, correct, ws, nb)
@@ -76,17 +48,17 @@ def run_class_means(cuda, f, lg, gt, fill=0xFF):
 def run_distances(cuda, f, mav, cls, metric):
     from openset_imagenet import _native as NL
     (N, F), C = f.shape, mav.shape[0]
-    df, dm, dc = dev_of(cuda, f, mav, cls)
+    df, dm, dc = on(cuda, f, mav, cls)
     dist = Out((N,) if cls is not None else (N, C), torch.float32, cuda)
     call(NL.lib().osi_openmax_distances, df, dm, dc, N, C, F, metric, dist)
     assert dist.check()
     return dist.np()
 
 
-def run_fit_tails(cuda, dist, gt, correct, C, T, fill=0xFF):
+def run_fit_tails(cuda, dist, gt, correct, C, T, fill=None):
     from openset_imagenet import _native as NL
     N = len(dist)
-    dd, dg, dc = dev_of(cuda, dist, gt, correct)
+    dd, dg, dc = on(cuda, dist, gt, correct)
     ws, nb = workspace(N, C, 1, cuda, fill)
     outs = dict(shape=Out((C,), torch.float64, cuda), scale=Out((C,), torch.float64, cuda), shift=Out((C,), torch.float64, cuda),
                 fitted=Out((C,), torch.uint8, cuda), tail_count=Out((C,), torch.int64, cuda), flags2=Out((2,), torch.int64, cuda))
@@ -99,7 +71,7 @@ def run_wscores(cuda, dist, shape, scale, shift, fitted):
     from openset_imagenet import _native as NL
     N, C = dist.shape
     w = Out((N, C), torch.float32, cuda)
-    call(NL.lib().osi_openmax_wscores, *dev_of(cuda, dist), N, C, *dev_of(cuda, shape, scale, shift, fitted), w)
+    call(NL.lib().osi_openmax_wscores, *on(cuda, dist), N, C, *on(cuda, shape, scale, shift, fitted), w)
     assert w.check()
     return w.np()
 
@@ -108,22 +80,9 @@ def run_recalibrate(cuda, lg, w, alpha):
     from openset_imagenet import _native as NL
     N, C = lg.shape
     probs = Out((N, C + 1), torch.float32, cuda)
-    call(NL.lib().osi_openmax_recalibrate, *dev_of(cuda, lg, w), N, C, alpha, probs)
+    call(NL.lib().osi_openmax_recalibrate, *on(cuda, lg, w), N, C, alpha, probs)
     assert probs.check()
     return probs.np()
-
-
-def ulps(a, b):
-    """Distance in fp32 ulps between two finite fp32 arrays (NaN must sit in the same places)."""
-    a, b = np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)
-    assert np.array_equal(np.isnan(a), np.isnan(b))
-    ok = ~np.isnan(a)
-    key = lambda x: np.where(x.view(np.int32) < 0, np.int64(-2 ** 31) - x.view(np.int32).astype(np.int64), x.view(np.int32).astype(np.int64))
-    return int(np.abs(key(a[ok]) - key(b[ok])).max()) if ok.any() else 0
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 def check_fit(got, want, where):
@@ -166,7 +125,7 @@ def test_class_means_without_a_correct_row_is_zero(cuda):
     mav, count, correct = run_class_means(cuda, f, lg, gt)
     mav_w, count_w, correct_w = O.class_means(f, lg, gt)
     assert count[1] == 0 and np.array_equal(count, count_w) and np.array_equal(correct.astype(bool), correct_w)
-    assert same_bits(mav, mav_w) and not mav[1].any()
+    assert same_bytes(mav, mav_w) and not mav[1].any()
 
 
 @pytest.mark.parametrize("shape", O.SHAPES)
@@ -262,7 +221,7 @@ def test_recalibrate(cuda, shape):
         print(f"recalibrate {shape} alpha={alpha}: max abs error {err:.3e}, rows sum to 1 within {total:.3e}")
         assert err <= 1.2e-7 and total <= 4e-7
         if alpha == C + 5:
-            assert same_bits(got, run_recalibrate(cuda, lg, w, C))
+            assert same_bytes(got, run_recalibrate(cuda, lg, w, C))
 
 
 def test_recalibrate_tie_ranks_the_lower_index_first(cuda):
@@ -338,7 +297,7 @@ def test_end_to_end_integer_features(cuda, shape, metric):
     om, probs = fit_predict(shape, metric, True)
     want = O.fit(f, lg, gt, E2E_TAIL, metric)
     assert probs.dtype == torch.float32 and probs.shape == (shape[0], shape[1] + 1) and probs.is_cuda
-    assert same_bits(om.mav.cpu().numpy(), want["mav"]) and np.array_equal(om.count.cpu().numpy(), want["count"])
+    assert same_bytes(om.mav.cpu().numpy(), want["mav"]) and np.array_equal(om.count.cpu().numpy(), want["count"])
     check_fit(dict(shape=om.shape.cpu().numpy(), scale=om.scale.cpu().numpy(), shift=om.shift.cpu().numpy(),
                    fitted=om.fitted.cpu().numpy(), tail_count=om.tail_count.cpu().numpy(), flags2=om.flags.cpu().numpy()),
               want, f"e2e integer {shape} metric={metric}")
@@ -373,9 +332,9 @@ def test_two_runs_give_identical_bits(cuda):
         a, pa = fit_predict(shape, metric, False)
         b, pb = fit_predict(shape, metric, False)
         for name in ("mav", "shape", "scale", "shift", "fitted", "count", "tail_count", "flags"):
-            assert same_bits(getattr(a, name).cpu().numpy(), getattr(b, name).cpu().numpy()), (metric, name)
-        assert same_bits(pa.cpu().numpy(), pb.cpu().numpy())
-        assert same_bits(a.w_scores(case(shape, False)[0]).cpu().numpy(), b.w_scores(case(shape, False)[0]).cpu().numpy())
+            assert same_bytes(getattr(a, name).cpu().numpy(), getattr(b, name).cpu().numpy()), (metric, name)
+        assert same_bytes(pa.cpu().numpy(), pb.cpu().numpy())
+        assert same_bytes(a.w_scores(case(shape, False)[0]).cpu().numpy(), b.w_scores(case(shape, False)[0]).cpu().numpy())
 
 
 def test_row_permutation_leaves_the_fit_bit_identical(cuda):
@@ -387,22 +346,22 @@ def test_row_permutation_leaves_the_fit_bit_identical(cuda):
             p = np.random.default_rng(seed).permutation(N)
             again = run_fit_tails(cuda, dist[p], gt[p], correct[p], C, T)
             for k in ("shape", "scale", "shift", "fitted", "tail_count", "flags2"):
-                assert same_bits(base[k], again[k]), (T, seed, k)
+                assert same_bytes(base[k], again[k]), (T, seed, k)
     # through the class: integer-valued features, so the means (exact sums) and with them every distance keep their bits too
     shape = (300, 5, 130)
     a, _ = fit_predict(shape, O.EUCLIDEAN, True)
     b, _ = fit_predict(shape, O.EUCLIDEAN, True, rows=np.random.default_rng(5).permutation(shape[0]))
     for name in ("mav", "count", "shape", "scale", "shift", "fitted", "tail_count", "flags"):
-        assert same_bits(getattr(a, name).cpu().numpy(), getattr(b, name).cpu().numpy()), name
+        assert same_bytes(getattr(a, name).cpu().numpy(), getattr(b, name).cpu().numpy()), name
 
 
 def test_workspace_contents_do_not_matter(cuda):
     f, lg, gt, _ = case((600, 7, 33), False)
-    a, b = run_class_means(cuda, f, lg, gt, fill=0xFF), run_class_means(cuda, f, lg, gt, fill=0)
-    assert all(same_bits(x, y) for x, y in zip(a, b))
+    a, b = run_class_means(cuda, f, lg, gt, fill=None), run_class_means(cuda, f, lg, gt, fill=0)
+    assert all(same_bytes(x, y) for x, y in zip(a, b))
     dist, gt2, correct = O.make_tail_case(600, 7, seed=600)
-    a, b = run_fit_tails(cuda, dist, gt2, correct, 7, 20, fill=0xFF), run_fit_tails(cuda, dist, gt2, correct, 7, 20, fill=0)
-    assert all(same_bits(a[k], b[k]) for k in a)
+    a, b = run_fit_tails(cuda, dist, gt2, correct, 7, 20, fill=None), run_fit_tails(cuda, dist, gt2, correct, 7, 20, fill=0)
+    assert all(same_bytes(a[k], b[k]) for k in a)
 
 
 def test_predict_on_one_row_and_device_inputs(cuda):
@@ -411,9 +370,9 @@ def test_predict_on_one_row_and_device_inputs(cuda):
     om, probs = fit_predict(shape, O.EUCLIDEAN, False)
     for i in (0, 17, 599):
         one = om.predict(lg[i:i + 1], f[i:i + 1])
-        assert one.shape == (1, 8) and same_bits(one.cpu().numpy(), probs[i:i + 1].cpu().numpy())
+        assert one.shape == (1, 8) and same_bytes(one.cpu().numpy(), probs[i:i + 1].cpu().numpy())
     dev = om.predict(torch.from_numpy(lg).to(cuda), torch.from_numpy(f).to(cuda))
-    assert same_bits(dev.cpu().numpy(), probs.cpu().numpy())
+    assert same_bytes(dev.cpu().numpy(), probs.cpu().numpy())
     assert om.predict(lg[:0], f[:0]).shape == (0, 8)
     assert np.array_equal(f, case(shape, False)[0])     # inputs are never written
 
@@ -428,20 +387,20 @@ def test_state_dict_gives_the_same_bits(cuda, tmp_path):
     torch.save(sd, tmp_path / "om.pth")
     again = OpenMax().load_state_dict(torch.load(tmp_path / "om.pth", weights_only=True))
     assert (again.tailsize, again.distance, again.alpha) == (E2E_TAIL, "cosine", E2E_ALPHA)
-    assert same_bits(again.predict(lg, f).cpu().numpy(), probs.cpu().numpy())
+    assert same_bytes(again.predict(lg, f).cpu().numpy(), probs.cpu().numpy())
 
 
 def test_torch_ops_match_the_abi(cuda):
     from openset_imagenet import _native as NL
     ops = NL.ops()
     f, lg, gt, _ = case((600, 7, 33), False)
-    df, dl, dg = dev_of(cuda, f, lg, gt)
+    df, dl, dg = on(cuda, f, lg, gt)
     ws, _ = workspace(600, 7, 33, cuda)
     mav, count, correct = ops.openmax_class_means(df, dl, dg, ws)
     a = run_class_means(cuda, f, lg, gt)
-    assert same_bits(mav.cpu().numpy(), a[0]) and same_bits(count.cpu().numpy(), a[1]) and same_bits(correct.cpu().numpy(), a[2])
+    assert same_bytes(mav.cpu().numpy(), a[0]) and same_bytes(count.cpu().numpy(), a[1]) and same_bytes(correct.cpu().numpy(), a[2])
     dist = ops.openmax_distances(df, mav, dg, O.COSINE)
-    assert same_bits(dist.cpu().numpy(), run_distances(cuda, f, a[0], gt, O.COSINE))
+    assert same_bytes(dist.cpu().numpy(), run_distances(cuda, f, a[0], gt, O.COSINE))
     assert ops.openmax_distances(df, mav, None, O.EUCLIDEAN).shape == (600, 7)
     with pytest.raises(RuntimeError):
         ops.openmax_fit_tails(dist, dg, correct, 7, 1, ws)               # tailsize 1: refused by the ABI
@@ -466,7 +425,7 @@ def test_openmax_arrays_writes_the_five_keys(cuda, tmp_path):
     np.savez(tmp_path / "x_openmax.npz", **arrays)
     assert sorted(np.load(tmp_path / "x_openmax.npz").files) == sorted(arrays)
     _, again = openmax_arrays(om, split, 20, 3, "euclidean")             # a fitted object is taken as it is
-    assert same_bits(again["scores"], arrays["scores"])
+    assert same_bytes(again["scores"], arrays["scores"])
     rows = arrays["gt"] < 7                                                # probs[:, :C] feeds the OSCR curve as it is
     ccr, fpr = util.calculate_oscr(arrays["gt"][rows], arrays["scores"][rows], unk_label=-1)
     assert len(ccr) == len(fpr) > 0

@@ -20,60 +20,17 @@ import pytest
 import torch
 
 import shaping_oracle as O
+from gpu_harness import Out, call, poisoned, same_bits_nan, twice
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256                                  # bytes before and after every output
-CANARY = 0xA5
-
 
 # --------------------------------------------------------------------------------------------------------------- helpers
-class Out:
-    """A device output with guard bands: `t` is the tensor the kernel writes, check() says whether the bands kept their canary."""
-
-    def __init__(self, shape, dev):
-        n = int(np.prod(shape)) * 4
-        self.raw = torch.full((GUARD + (n + 7) // 8 * 8 + GUARD,), CANARY, dtype=torch.uint8, device=dev)
-        self.n = n
-        self.t = self.raw[GUARD:GUARD + n].view(torch.float32).view(*shape)
-
-    def check(self):
-        return bool((self.raw[:GUARD] == CANARY).all()) and bool((self.raw[GUARD + self.n:] == CANARY).all())
-
-    def np(self):
-        return self.t.cpu().numpy()
-
-
-def call(fn, *args):
-    from openset_imagenet import _native as NL
-    conv = [a.data_ptr() if isinstance(a, torch.Tensor) else (a.t.data_ptr() if isinstance(a, Out) else a) for a in args]
-    NL.check(fn(*conv, torch.cuda.current_stream().cuda_stream), fn.__name__)
-    torch.cuda.synchronize()
-
-
-def poisoned(nb, cuda):
-    return torch.full((nb,), 0xFF, dtype=torch.uint8, device=cuda)
-
-
-def same_bits(a, b):
-    """Equal bit patterns, a NaN compared as a NaN."""
-    a, b = np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)
-    nan = np.isnan(a)
-    return a.shape == b.shape and np.array_equal(nan, np.isnan(b)) and np.array_equal(a.view(np.int32)[~nan], b.view(np.int32)[~nan])
-
-
-def twice(run):
-    """The call's output, after a second call (fresh output, fresh workspace) gave the same bits."""
-    first, second = run(), run()
-    assert same_bits(first, second), "two runs differ"
-    return first
-
-
 def run_order_stats(cuda, v_dev, n, ranks):
     from openset_imagenet import _native as NL
     lib = NL.lib()
     nb = lib.osi_order_stats_workspace(n, len(ranks))
-    out = Out((len(ranks),), cuda)
+    out = Out((len(ranks),), torch.float32, cuda)
     call(lib.osi_order_stats_f32, v_dev, n, (ctypes.c_longlong * len(ranks))(*ranks), len(ranks), out, poisoned(nb, cuda), nb)
     assert out.check()
     return out.np()
@@ -84,7 +41,7 @@ def run_shape_rows(cuda, x_dev, mode, keep, clip=0.0):
     lib = NL.lib()
     m, f = x_dev.shape
     nb = lib.osi_shape_rows_workspace(m, f)
-    out = Out((m, f), cuda)
+    out = Out((m, f), torch.float32, cuda)
     call(lib.osi_shape_rows, x_dev, m, f, mode, keep, float(clip), out, poisoned(nb, cuda), nb)
     assert out.check()
     return out.np()
@@ -93,7 +50,7 @@ def run_shape_rows(cuda, x_dev, mode, keep, clip=0.0):
 def run_logit_scores(cuda, lg_dev, mode):
     from openset_imagenet import _native as NL
     m, c = lg_dev.shape
-    out = Out((m,), cuda)
+    out = Out((m,), torch.float32, cuda)
     call(NL.lib().osi_logit_scores, lg_dev, m, c, mode, out)
     assert out.check()
     return out.np()
@@ -108,16 +65,16 @@ def test_order_stats_against_the_stable_sort(cuda, n, name):
     buf = torch.zeros(n + 8, dtype=torch.float32, device=cuda)
     v_dev = buf[lead:lead + n]
     v_dev.copy_(torch.from_numpy(v))
-    assert v_dev.data_ptr() % 16 == 4 * lead and same_bits(v_dev.cpu().numpy(), v)
+    assert v_dev.data_ptr() % 16 == 4 * lead and same_bits_nan(v_dev.cpu().numpy(), v)
     mid = (n - 1) // 2
     ranks = [0, n - 1, mid, min(mid + 1, n - 1), mid]       # the ends, an adjacent pair in the middle, a duplicate
     got = twice(lambda: run_order_stats(cuda, v_dev, n, ranks))
     want = O.order_stats(v, ranks)
-    assert same_bits(got, want), (got, want)
+    assert same_bits_nan(got, want), (got, want)
     assert not np.signbit(got[got == 0]).any()              # a zero comes back as +0
     if n >= 8:                                              # eight ranks in no order, one launch
         ranks = [n - 1, 0, n // 3, n // 3 + 1, n - 2, 1, n // 2, n // 7]
-        assert same_bits(twice(lambda: run_order_stats(cuda, v_dev, n, ranks)), O.order_stats(v, ranks))
+        assert same_bits_nan(twice(lambda: run_order_stats(cuda, v_dev, n, ranks)), O.order_stats(v, ranks))
 
 
 def test_order_stats_returns_canonical_zero(cuda):
@@ -138,17 +95,17 @@ def test_shape_rows_against_the_oracle(cuda, m, f):
     x_dev = torch.from_numpy(x).to(cuda)
     clip = float(np.float32(0.75))                          # a value the rows hold: x > clip is false on the duplicates
     got = twice(lambda: run_shape_rows(cuda, x_dev, O.REACT, 0, clip))
-    assert same_bits(got, O.shape_rows(x, O.REACT, 0, clip)[0])
+    assert same_bits_nan(got, O.shape_rows(x, O.REACT, 0, clip)[0])
     shifted = torch.zeros(m * f + 1, dtype=torch.float32, device=cuda)[1:].view(m, f)        # 4-byte aligned only: the scalar form
     shifted.copy_(x_dev)
-    assert shifted.data_ptr() % 16 == 4 and same_bits(run_shape_rows(cuda, shifted, O.REACT, 0, clip), got)
+    assert shifted.data_ptr() % 16 == 4 and same_bits_nan(run_shape_rows(cuda, shifted, O.REACT, 0, clip), got)
     filled = 0
     for keep in keeps_of(f):
         kept = O.kept_masks(x, keep)
         want, mask = O.shape_rows(x, O.ASH_P, keep, kept=kept)
         assert mask.sum(axis=1).tolist() == [keep] * m
         got = twice(lambda: run_shape_rows(cuda, x_dev, O.ASH_P, keep))
-        assert same_bits(got, want), (keep, "ash_p")
+        assert same_bits_nan(got, want), (keep, "ash_p")
         want, mask = O.shape_rows(x, O.ASH_B, keep, kept=kept)
         got = twice(lambda: run_shape_rows(cuda, x_dev, O.ASH_B, keep))
         assert np.array_equal(got != 0, want != 0), (keep, "ash_b support")          # the oracle's kept set wherever the fill is not 0
@@ -174,7 +131,7 @@ def test_shape_rows_orders_nan_and_inf(cuda):
     for keep in (1, 7, 16, 40, 150, 299, 300):              # inside the NaNs, inside the Infs, among the zeros of both signs
         want, mask = O.shape_rows(x, O.ASH_P, keep)
         got = twice(lambda: run_shape_rows(cuda, x_dev, O.ASH_P, keep))
-        assert same_bits(got, want), keep
+        assert same_bits_nan(got, want), keep
         assert np.isnan(got[4, :keep]).all() and (got[4, keep:] == 0).all()
 
 
@@ -196,7 +153,7 @@ def test_logit_scores_against_the_oracle(cuda, m, c):
         assert O.ulps(got, want).max() <= 1, (mode, got, want)
         shifted = torch.zeros(m * c + 1, dtype=torch.float32, device=cuda)[1:].view(m, c)    # 4-byte aligned rows: the same order, the same bits
         shifted.copy_(lg_dev)
-        assert shifted.data_ptr() % 16 == 4 and same_bits(run_logit_scores(cuda, shifted, mode), got)
+        assert shifted.data_ptr() % 16 == 4 and same_bits_nan(run_logit_scores(cuda, shifted, mode), got)
     if m > 1:
         e, mx, p = (run_logit_scores(cuda, lg_dev, mode)[1] for mode in (O.ENERGY, O.MAXLOGIT, O.MSP))
         assert e == -np.inf and mx == -np.inf and np.isnan(p)
@@ -207,7 +164,7 @@ def test_logit_scores_propagate_nan_and_plus_inf(cuda):
     lg_dev = torch.from_numpy(lg).to(cuda)
     for mode in (O.ENERGY, O.MAXLOGIT, O.MSP):
         got = run_logit_scores(cuda, lg_dev, mode)
-        assert same_bits(np.isnan(got).astype(np.float32), np.isnan(O.logit_scores(lg, mode)).astype(np.float32)), mode
+        assert same_bits_nan(np.isnan(got).astype(np.float32), np.isnan(O.logit_scores(lg, mode)).astype(np.float32)), mode
         assert np.isnan(got[0]) and np.isnan(got[2])
     assert run_logit_scores(cuda, lg_dev, O.ENERGY)[1] == np.inf and run_logit_scores(cuda, lg_dev, O.MAXLOGIT)[1] == np.inf
 
@@ -288,7 +245,7 @@ def test_end_to_end(cuda, method):
     want, mask = O.shape_rows(test, O.MODES[method], keep, 0.0 if s.clip is None else s.clip)
     got = shaped.cpu().numpy()
     if method in ("react", "ash_p"):
-        assert same_bits(got, want)
+        assert same_bits_nan(got, want)
     elif method == "ash_b":
         assert np.array_equal(got != 0, mask) and O.ulps(got, want).max() <= 1
     else:

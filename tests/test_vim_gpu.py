@@ -23,46 +23,18 @@ import pytest
 import torch
 
 import vim_oracle as O
+from gpu_harness import Out, call, on, poisoned, ulp32
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256                                  # bytes before and after every output
-CANARY = 0xA5
 MS, KS, CS = (1, 5, 63, 257), (1, 16, 65), (1, 7)
 
 
 # --------------------------------------------------------------------------------------------------------------- helpers
-class Out:
-    """A device output with guard bands: `t` is the tensor the kernel writes, check() says whether the bands kept their canary."""
-
-    def __init__(self, shape, dtype, dev):
-        n = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
-        self.raw = torch.full((GUARD + (n + 7) // 8 * 8 + GUARD,), CANARY, dtype=torch.uint8, device=dev)
-        self.n = n
-        self.t = self.raw[GUARD:GUARD + n].view(dtype).view(*shape)
-
-    def check(self):
-        return bool((self.raw[:GUARD] == CANARY).all()) and bool((self.raw[GUARD + self.n:] == CANARY).all())
-
-    def np(self):
-        return self.t.cpu().numpy()
-
-
-def on(cuda, a):
-    return None if a is None else torch.tensor(np.asarray(a)).to(cuda)
-
-
-def call(fn, *args):
-    from openset_imagenet import _native as NL
-    conv = [a.data_ptr() if isinstance(a, torch.Tensor) else (a.t.data_ptr() if isinstance(a, Out) else a) for a in args]
-    NL.check(fn(*conv, torch.cuda.current_stream().cuda_stream), fn.__name__)
-    torch.cuda.synchronize()
-
-
 def workspace(M, K, F, cuda):
     from openset_imagenet import _native as NL
     nb = NL.lib().osi_vim_workspace(M, K, F)
-    return torch.full((nb,), 0xFF, dtype=torch.uint8, device=cuda), nb
+    return poisoned(nb, cuda), nb
 
 
 def run_eigh(cuda, S, max_sweeps=O.MAX_SWEEPS):
@@ -72,7 +44,7 @@ def run_eigh(cuda, S, max_sweeps=O.MAX_SWEEPS):
     A, Vt = Out((F, F), torch.float64, cuda), Out((F, F), torch.float64, cuda)
     head, info, rot = Out((2,), torch.float64, cuda), Out((1,), torch.int32, cuda), Out((1,), torch.int64, cuda)
     ws, nb = workspace(1, 1, F, cuda)
-    call(lib.osi_eigh_begin, on(cuda, S), F, A, Vt, head, info, ws, nb)
+    call(lib.osi_eigh_begin, *on(cuda, S), F, A, Vt, head, info, ws, nb)
     rotations = []
     for _ in range(max_sweeps):
         ws, nb = workspace(1, 1, F, cuda)
@@ -93,7 +65,7 @@ def run_project(cuda, x, origin, R):
     (M, F), K = x.shape, len(R)
     ws, nb = workspace(M, K, F, cuda)
     z = Out((M, K), torch.float64, cuda)
-    call(NL.lib().osi_vim_project_f32, on(cuda, x), on(cuda, origin), M, F, on(cuda, R), K, z, ws, nb)
+    call(NL.lib().osi_vim_project_f32, *on(cuda, x), *on(cuda, origin), M, F, *on(cuda, R), K, z, ws, nb)
     assert z.check()
     return z.np()
 
@@ -104,14 +76,10 @@ def run_scores(cuda, z, logits, alpha, mode, f64=False):
     C = 1 if logits is None else logits.shape[1]
     ws, nb = workspace(M, K, K, cuda)
     out = Out((M, C + 1) if mode == O.PROBS else (M,), torch.float64 if f64 else torch.float32, cuda)
-    call(NL.lib().osi_vim_scores, on(cuda, z), M, K, on(cuda, logits), C, float(alpha), mode, None if f64 else out, out if f64 else None,
+    call(NL.lib().osi_vim_scores, *on(cuda, z), M, K, *on(cuda, logits), C, float(alpha), mode, None if f64 else out, out if f64 else None,
          ws, nb)
     assert out.check()
     return out.np()
-
-
-def ulp32(ref):
-    return np.spacing(np.abs(ref).astype(np.float32)).astype(np.float64)
 
 
 def check_decomposition(S, w, v, sweeps):
