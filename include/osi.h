@@ -466,6 +466,45 @@ int osi_auc_ovr_f32(const float* scores, const long long* gt, int N, int C, void
 int osi_auc_ovr_f64(const double* scores, const long long* gt, int N, int C, void* ws, size_t ws_bytes, long long* gt_c,
                     long long* eq_c, long long* pos_c, long long* flags3, osi_stream_t stream);
 
+/* ABI 28. Detection metrics and the OSCR curve by rejection score (metrics.detection_metrics, util.oscr_by_rejection; csrc/
+ * detection.hip) for the one-value-per-sample output of the post-hoc detectors: u[N] (f32 or f64), higher = more unknown, int64 labels
+ * gt[N], a negative unk_label and, optionally, correct[N] (unsigned char, non-zero = the closed-set prediction of the row is right;
+ * NULL = no row is). Populations: known = {gt >= 0}, unk = {gt == unk_label}, correct = {known, correct[i] != 0}. A row whose u is NaN
+ * belongs to no population and is counted in nan_rows; so does no row with another negative label. +-Inf are ordinary values;
+ * comparison is IEEE (-0 == +0). Everything counted is an integer, merged with integer atomics where at all: results do not depend on
+ * the grid or on the run. Every output is written or zeroed by the call; nothing allocates or synchronises. OSI_ERR_ARG before any
+ * launch on a null required pointer, N <= 0, unk_label >= 0, Q outside [1, 8] or ws_bytes < osi_det_workspace(N) (one size for the
+ * three calls, 0 for an N they refuse; the workspace is 16-byte aligned and its contents are never assumed).
+ *   osi_det_ranks_*: ranks is int32[6][N], rows kn_lt, kn_le, unk_lt, unk_le, cor_lt, cor_le: for row i and each population the
+ *     numbers #{j in population: u_j < u_i} and #{j in population: u_j <= u_i}; zeros for a NaN row. counts4 = {K, U, Kc, nan_rows},
+ *     the sizes of known, unk and correct. The one O(N^2) pass (all pairs, LDS-staged tiles, 32-bit partial counts).
+ *   osi_det_summary: from ranks, gt and a DEVICE array q[Q] of TPR levels in (0, 1] (K and U are re-counted from ranks: a member
+ *     counts itself in its own kn_le / unk_le):
+ *     ints[0] = gt_pairs = sum over unk of kn_lt; ints[1] = eq_pairs = sum over unk of (kn_le - kn_lt): with them the ROC-AUC of known
+ *       against unk is the Mann-Whitney quotient (2 gt_pairs + eq_pairs) / (2 K U);
+ *     ints[2 + t] = fpr_count[t] = min{unk_le[i] : i known, (double)kn_le[i] / (double)K >= q[t]}, the comparison in fp64 exactly as
+ *       written (U when there is no known row): fpr[argmax(tpr >= q)] * U of the ROC curve with known as the positive class, -u as score;
+ *     sums[0] = ap_in_sum = sum over known of kn_le / (kn_le + unk_le); sums[1] = ap_out_sum = sum over unk of
+ *       (U - unk_lt) / ((U - unk_lt) + (K - kn_lt)); each quotient one fp64 division of exact integers, each sum in fp64 in an order
+ *       fixed by N alone. ap_in_sum / K and ap_out_sum / U are the average precisions of known (score -u) and of unk (score u).
+ *   osi_det_curve_*: the OSCR curve with u as the rejector, osi_oscr_* with confidence -u: taus[0 .. totals[0]) = the distinct u of
+ *     the known rows in DESCENDING order (of equal values the one of the lowest row, so -0 or +0 as that row holds it); for position p
+ *     ccr_count[p] = #{correct: u < taus[p]} and fpr_count[p] = #{unk: u < taus[p]}, read from ranks (cor_lt, unk_lt) of that row;
+ *     totals = {#distinct, K, U}. The curve is the first totals[0] - 1 positions (the smallest value is dropped), ccr_count / K and
+ *     fpr_count / U in fp64. taus / ccr_count / fpr_count hold N entries each, zero past totals[0]. ranks must come from
+ *     osi_det_ranks_* on the same u, gt, unk_label. */
+size_t osi_det_workspace(int N);
+int osi_det_ranks_f32(const float* u, const long long* gt, const unsigned char* correct, int N, long long unk_label, void* ws,
+                      size_t ws_bytes, int* ranks, long long* counts4, osi_stream_t stream);
+int osi_det_ranks_f64(const double* u, const long long* gt, const unsigned char* correct, int N, long long unk_label, void* ws,
+                      size_t ws_bytes, int* ranks, long long* counts4, osi_stream_t stream);
+int osi_det_summary(const int* ranks, const long long* gt, int N, long long unk_label, const double* q, int Q, void* ws,
+                    size_t ws_bytes, long long* ints, double* sums, osi_stream_t stream);
+int osi_det_curve_f32(const float* u, const long long* gt, const int* ranks, int N, long long unk_label, void* ws, size_t ws_bytes,
+                      float* taus, long long* ccr_count, long long* fpr_count, long long* totals, osi_stream_t stream);
+int osi_det_curve_f64(const double* u, const long long* gt, const int* ranks, int N, long long unk_label, void* ws, size_t ws_bytes,
+                      double* taus, long long* ccr_count, long long* fpr_count, long long* totals, osi_stream_t stream);
+
 /* ABI 18. Evaluation histograms for util.get_histogram (util.py:202-228): the softmax-score and feature-norm histograms of known
  * against negative / unknown samples, on device-resident scores[N][C], features[N][F] (f32 or f64, type T) and int64 labels. All
  * results are integer counts or min / max of stored values: order-free. Every output is zeroed or written by the call; no

@@ -110,6 +110,7 @@ SHAPE_REACT, SHAPE_ASH_P, SHAPE_ASH_B, SHAPE_ASH_S, SHAPE_SCALE = 0, 1, 2, 3, 4
 SCORE_ENERGY, SCORE_MAXLOGIT, SCORE_MSP = 0, 1, 2
 ORDER_STATS_MAX_R = 8
 SHAPE_MAX_F = 4096
+DET_MAX_Q = 8
 
 P = c_void_p
 _PD = POINTER(ConvDesc)
@@ -197,6 +198,12 @@ _SIGS = {
     "osi_auc_binary_f64": (c_int, [P, P, c_int, c_int, c_longlong, P, c_size_t, P, P]),
     "osi_auc_ovr_f32": (c_int, [P, P, c_int, c_int, P, c_size_t, P, P, P, P, P]),
     "osi_auc_ovr_f64": (c_int, [P, P, c_int, c_int, P, c_size_t, P, P, P, P, P]),
+    "osi_det_workspace": (c_size_t, [c_int]),
+    "osi_det_ranks_f32": (c_int, [P, P, P, c_int, c_longlong, P, c_size_t, P, P, P]),
+    "osi_det_ranks_f64": (c_int, [P, P, P, c_int, c_longlong, P, c_size_t, P, P, P]),
+    "osi_det_summary": (c_int, [P, P, c_int, c_longlong, P, c_int, P, c_size_t, P, P, P]),
+    "osi_det_curve_f32": (c_int, [P, P, P, c_int, c_longlong, P, c_size_t, P, P, P, P, P]),
+    "osi_det_curve_f64": (c_int, [P, P, P, c_int, c_longlong, P, c_size_t, P, P, P, P, P]),
     "osi_eval_values_workspace": (c_size_t, [c_int]),
     "osi_eval_values_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_longlong, c_int, P, P, P, P, P, P, c_size_t, P]),
     "osi_eval_values_f64": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_longlong, c_int, P, P, P, P, P, P, c_size_t, P]),

@@ -11,6 +11,9 @@
         -> float: the ROC-AUC that sklearn.metrics.roc_auc_score gives the reference, as the Mann-Whitney quotient of exact pair
            counts made on the device (osi_auc_binary_* / osi_auc_ovr_*, csrc/auc.hip). No sklearn at run time, the [N, C] score
            matrix stays on the device, and the caller's labels are never written (the reference overwrites them with +-1).
+  detection_metrics(gt, unknown, unk_label=-2, tpr=(0.95,), correct=None)                   this build's addition
+        -> dict: AUROC, AUPR-in, AUPR-out and FPR at TPR of a rejection score (the `unknown` vector of the post-hoc detectors), from
+           six rank counts per row made on the device (osi_det_ranks_* / osi_det_summary, csrc/detection.hip).
 """
 import numpy as np
 import torch
@@ -126,3 +129,103 @@ def auc_score_multiclass(target_labels, pred_scores):
         raise ValueError("Number of classes in y_true not equal to the number of columns in 'y_score'")
     a = [_mann_whitney(gt[k], eq[k], pos[k], n - pos[k]) for k in range(len(pos))]
     return float(np.mean(np.asarray(a, dtype=np.float64)))
+
+
+def _detection_inputs(gt, unknown, correct, what):
+    """Labels (int64), the rejection score u[N] (fp32 / fp64 kept, anything else cast to fp64) and the optional `correct` flags
+    (uint8) on the current device, under the conventions of _auc_inputs. Copies only: the caller's arrays are never written."""
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"openset_imagenet (MI355X build) has no CPU path: {what} needs the GPU")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    u = torch.as_tensor(unknown).detach()
+    if u.dtype not in (torch.float32, torch.float64):
+        u = u.double()
+    if u.dim() != 1:
+        raise ValueError("unknown must be a vector [N_samples]")
+    u = u.to(dev).contiguous()
+    y = gt.detach() if isinstance(gt, torch.Tensor) else torch.as_tensor(np.asarray(gt).astype(int))
+    y = y.to(torch.int64).to(dev).contiguous()
+    if y.dim() != 1 or y.numel() != u.numel():
+        raise ValueError("gt and unknown disagree on the number of samples")
+    c = None
+    if correct is not None:
+        c = (torch.as_tensor(correct).detach().to(dev) != 0).to(torch.uint8).contiguous()
+        if c.dim() != 1 or c.numel() != u.numel():
+            raise ValueError("correct and unknown disagree on the number of samples")
+    return y, u, c
+
+
+def _det_ranks_device(y, u, c, unk_label):
+    """osi_det_ranks_* on device tensors: the int32 [6, N] ranks and the int64 counts {K, U, Kc, NaN rows}, both on the device, and the
+    workspace (of osi_det_workspace(N) bytes) for the calls that follow."""
+    if int(unk_label) >= 0:
+        raise ValueError("unk_label must be negative: labels >= 0 are the known classes")
+    n = u.numel()
+    lib = N.lib()
+    nb = lib.osi_det_workspace(n)
+    ws = torch.empty(nb, dtype=torch.uint8, device=u.device)
+    ranks = torch.empty((6, n), dtype=torch.int32, device=u.device)
+    counts = torch.empty(4, dtype=torch.int64, device=u.device)
+    fn = lib.osi_det_ranks_f32 if u.dtype == torch.float32 else lib.osi_det_ranks_f64
+    N.check(fn(N.ptr(u), N.ptr(y), N.ptr(c), n, int(unk_label), N.ptr(ws), nb, N.ptr(ranks), N.ptr(counts), N.stream_of(u)), "osi_det_ranks")
+    return ranks, counts, ws
+
+
+def _tpr_levels(tpr):
+    levels = [float(t) for t in tpr]
+    if not 1 <= len(levels) <= N.DET_MAX_Q or not all(0.0 < t <= 1.0 for t in levels):
+        raise ValueError(f"tpr must hold 1 to {N.DET_MAX_Q} levels in (0, 1]")
+    return levels
+
+
+def _detection_ranks(gt, unknown, unk_label=-2, tpr=(0.95,), correct=None):
+    """The device's integers behind detection_metrics: a dict with `ranks` (numpy int32 [6, N]: kn_lt, kn_le, unk_lt, unk_le, cor_lt,
+    cor_le), `counts` = (K, U, Kc, NaN rows), `gt_pairs`, `eq_pairs`, `fpr_count` (one per tpr level) as Python ints and the two fp64
+    sums `ap_in_sum`, `ap_out_sum` (definitions: include/osi.h, ABI 28)."""
+    levels = _tpr_levels(tpr)
+    y, u, c = _detection_inputs(gt, unknown, correct, "detection_metrics")
+    n = u.numel()
+    if n == 0:
+        return dict(ranks=np.zeros((6, 0), dtype=np.int32), counts=(0, 0, 0, 0), gt_pairs=0, eq_pairs=0, fpr_count=[0] * len(levels),
+                    ap_in_sum=0.0, ap_out_sum=0.0)
+    ranks, counts, ws = _det_ranks_device(y, u, c, unk_label)
+    q = torch.tensor(levels, dtype=torch.float64, device=u.device)
+    out = torch.empty(6 + len(levels) + 2, dtype=torch.int64, device=u.device)    # counts4, ints[2 + Q], then the two sums as fp64 bits
+    out[:4] = counts
+    ints, sums = out[4:6 + len(levels)], out[6 + len(levels):]
+    N.check(N.lib().osi_det_summary(N.ptr(ranks), N.ptr(y), n, int(unk_label), N.ptr(q), len(levels), N.ptr(ws), ws.numel(), N.ptr(ints),
+                                    N.ptr(sums), N.stream_of(u)), "osi_det_summary")
+    host = out.cpu()
+    vals = host[:-2].tolist()
+    ap_in, ap_out = host[-2:].view(torch.float64).tolist()
+    return dict(ranks=ranks.cpu().numpy(), counts=tuple(vals[:4]), gt_pairs=vals[4], eq_pairs=vals[5], fpr_count=vals[6:],
+                ap_in_sum=ap_in, ap_out_sum=ap_out)
+
+
+def detection_metrics(gt, unknown, unk_label=-2, tpr=(0.95,), correct=None):
+    """The figures the out-of-distribution literature reports for a rejection score `unknown` [N] (higher = more unknown; the `unknown`
+    vector every detector of this package writes), known rows (gt >= 0) against the rows labelled `unk_label`; rows of any other
+    negative label take no part. A dict of plain Python values:
+
+      auroc        area under the ROC curve, the Mann-Whitney quotient of exact pair counts (one division)
+      aupr_in      average precision with the known rows as the positive class (score -unknown)
+      aupr_out     average precision with the unknown rows as the positive class (score unknown)
+      fpr_at_tpr   per level of `tpr`: the share of unknown rows accepted at the first threshold that accepts that share of known rows
+                   (sklearn's fpr[argmax(tpr >= level)] of roc_curve with known as the positive class)
+      known, unknown   the sizes of the two sides
+
+    Everything is counted on the device (csrc/detection.hip; definitions in include/osi.h, ABI 28) and agrees with sklearn's
+    roc_auc_score, average_precision_score and roc_curve(drop_intermediate=False) up to fp64 rounding. Inputs as _auc_inputs takes
+    them: numpy arrays or torch tensors, host or device, fp32 / fp64 kept, never written. `correct` only adds to the raw counts
+    (_detection_ranks). ValueError("Input contains NaN.") when a value is NaN; nan figures when a side is empty."""
+    r = _detection_ranks(gt, unknown, unk_label=unk_label, tpr=tpr, correct=correct)
+    k, u, _, nan_rows = r["counts"]
+    if nan_rows:
+        raise ValueError("Input contains NaN.")
+    both = k > 0 and u > 0
+    nan = float("nan")
+    return dict(auroc=_mann_whitney(r["gt_pairs"], r["eq_pairs"], k, u),
+                aupr_in=r["ap_in_sum"] / k if both else nan,
+                aupr_out=r["ap_out_sum"] / u if both else nan,
+                fpr_at_tpr=[f / u if both else nan for f in r["fpr_count"]],
+                known=k, unknown=u)

@@ -32,7 +32,16 @@ logsumexp).
 `--proser` (likewise; softmax and entropic losses) loads the fine-tuned network, dummy classifier and calibrated bias that
 `python -m openset_imagenet.script.proser` saved as `{loss}_proser{suffix}.pth` (proser.PROSER) and writes
 `{loss}_{split}_arr{suffix}_proser.npz` with `gt`, `logits`, `features` of THAT network, `scores` = probs[:, :C] and `unknown` =
-probs[:, C]; with `--oscr` the same OSCR line is printed for those scores."""
+probs[:, C]; with `--oscr` the same OSCR line is printed for those scores.
+`--detection` (likewise) scores every REJECTION score of the run, one value per sample where higher means more unknown: the baselines
+read off the logits (MSP, MaxLogit, Energy: the negated osi_logit_scores values; for the garbage loss without the background column),
+the `unknown` vector of every detector fitted in the same run and of `--proser`, and for a detector without one (the EVM) minus its
+largest class score, tagged "(-max score)". For every split, each negative label present (-1, -2) and each scorer it prints one line
+with AUROC, AUPR-in, AUPR-out, FPR at 95 % TPR (metrics.detection_metrics: known rows against the rows of that label) and the trapezoid
+area of the OSCR curve by rejection (util.oscr_by_rejection / util.oscr_area: the scorer's `scores` decide the closed-set prediction,
+its rejection score rejects), all counted on the GPU (csrc/detection.hip), and collects the same numbers in
+`{loss}_{split}_detection{suffix}.json` (`rows`: scorer, unk_label, auroc, aupr_in, aupr_out, fpr_at_tpr95, known, unknown, oscr_area,
+oscr_points; `error` instead of figures where a score holds a NaN)."""
 import argparse
 import json
 import pathlib
@@ -126,6 +135,9 @@ def get_args(command_line_options=None):
     p.add_argument("--auc", action="store_true", help="also compute the binary ROC-AUC of each split (known vs -1, known vs -2) on the GPU")
     p.add_argument("--report", action="store_true", help="also write {loss}_{split}_report{suffix}.json (confidences, CCR at FPR, score and "
                    "norm histograms, all counted on the GPU) next to the .npz and print the row of the reference's table")
+    p.add_argument("--detection", action="store_true", help="also score every rejection score of the run (MSP, max-logit and energy of the "
+                   "logits, the `unknown` vector of every fitted detector and of PROSER) with AUROC, AUPR-in, AUPR-out, FPR at 95%% TPR "
+                   "and the area of the OSCR curve by that score, counted on the GPU; writes {loss}_{split}_detection{suffix}.json")
     p.add_argument("--averaged", action="store_true", help="evaluate the averaged weights (EMA / SWA) the checkpoint carries under "
                    "avg_state_dict (config block avg) instead of the trained ones; the output files get the suffix _avg")
     p.add_argument("--openmax", type=int, default=None, metavar="TAILSIZE", help="also fit OpenMax with this tail size on the training "
@@ -248,6 +260,59 @@ def oscr_lines(split, gt, scores, tag=""):
             at = ccr[np.searchsorted(-fpr, -0.1)] if len(ccr) and np.isfinite(fpr).all() and (fpr <= 0.1).any() else float("nan")
             lines.append(f"{split}: {tag}OSCR vs label {unk}: {len(ccr)} points, CCR@FPR<=0.1 = {at:.4f}")
     return lines
+
+
+DETECTION_TPR = (0.95,)                   # the FPR@TPR95 column of the out-of-distribution literature
+LOGIT_BASELINES = (("MSP", "SCORE_MSP"), ("MaxLogit", "SCORE_MAXLOGIT"), ("Energy", "SCORE_ENERGY"))
+
+
+def logit_baselines(logits):
+    """The three rejection scores read off the logits alone, each the NEGATED osi_logit_scores value so that higher means more
+    unknown: {"MSP": -max softmax probability, "MaxLogit": -max logit, "Energy": -logsumexp}, numpy fp32 [N]."""
+    from .. import _native as N
+    dev = util._need_gpu("logit_baselines")
+    z = torch.as_tensor(logits).detach().to(dev).float().contiguous()
+    return {name: (-N.ops().logit_scores(z, getattr(N, mode))).cpu().numpy() for name, mode in LOGIT_BASELINES}
+
+
+def detection_scorer(tag, arrays):
+    """(tag, scores, unknown) of one detector's arrays for detection_rows: its `unknown` vector, or - for a detector without one (the
+    EVM) - minus its largest class score, and then the tag says so."""
+    if "unknown" in arrays:
+        return tag.strip(), arrays["scores"], arrays["unknown"]
+    return f"{tag.strip()} (-max score)", arrays["scores"], -np.asarray(arrays["scores"]).max(1)
+
+
+def detection_rows(gt, scorers):
+    """`--detection` on arrays: for each negative label present in gt (-1, -2) and each scorer (tag, scores [N, C], unknown [N]) one
+    dict of plain values: metrics.detection_metrics of `unknown` at DETECTION_TPR, and the area (util.oscr_area) and number of points
+    of util.oscr_by_rejection, where `scores` decides the closed-set prediction and `unknown` rejects. A scorer whose `unknown` holds
+    a NaN gets a row with `error` set instead of figures."""
+    gt = np.asarray(gt)
+    rows = []
+    for unk in (-1, -2):
+        if not (gt == unk).any():
+            continue
+        for tag, scores, unknown in scorers:
+            row = {"scorer": tag, "unk_label": unk}
+            try:
+                m = metrics.detection_metrics(gt, unknown, unk_label=unk, tpr=DETECTION_TPR)
+                ccr, fpr = util.oscr_by_rejection(gt, scores, unknown, unk_label=unk)
+                row.update(auroc=m["auroc"], aupr_in=m["aupr_in"], aupr_out=m["aupr_out"], fpr_at_tpr95=m["fpr_at_tpr"][0],
+                           known=m["known"], unknown=m["unknown"], oscr_area=util.oscr_area(ccr, fpr), oscr_points=len(ccr))
+            except ValueError as refusal:
+                row["error"] = str(refusal)
+            rows.append(row)
+    return rows
+
+
+def detection_line(split, row):
+    """The line `--detection` prints for one row of detection_rows."""
+    head = f"{split}: detection {row['scorer']} vs label {row['unk_label']}: "
+    if "error" in row:
+        return head + f"refused ({row['error']})"
+    return head + (f"AUROC {row['auroc']:.4f} AUPR-in {row['aupr_in']:.4f} AUPR-out {row['aupr_out']:.4f} FPR@TPR95 {row['fpr_at_tpr95']:.4f} "
+                   f"OSCR-by-rejection area {row['oscr_area']:.4f} ({row['oscr_points']} points)")
 
 
 def scored_arrays(score, detector, split_arrays):
@@ -393,6 +458,8 @@ def main(command_line_options=None):
         np.savez(file_path, **arrays)
         print(f"{tag}scores saved in: {file_path}")
         written[f"{split}_{name}"] = file_path
+        if args.detection:
+            scorers.append(detection_scorer(tag, arrays))
         if args.oscr:
             for line in oscr_lines(split, gt, arrays["scores"], tag=tag):
                 print(line)
@@ -407,6 +474,10 @@ def main(command_line_options=None):
         np.savez(file_path, gt=gt, logits=logits, features=features, scores=scores)
         print(f"Target labels, logits, features and scores saved in: {file_path}")
         written[split] = file_path
+        scorers = []                                      # what `--detection` scores: write() adds the detectors' rows
+        if args.detection:                                # the background column is neither a known class nor a logit of one
+            class_scores, class_logits = (scores[:, :-1], logits[:, :-1]) if args.loss == "garbage" else (scores, logits)
+            scorers += [(name, class_scores, unknown) for name, unknown in logit_baselines(class_logits).items()]
         if args.oscr:
             s = scores[:, :-1] if args.loss == "garbage" else scores           # the background column is not a known class
             for line in oscr_lines(split, gt, s):
@@ -417,6 +488,16 @@ def main(command_line_options=None):
         if proser is not None:
             p_gt, p_logits, p_features, _ = get_arrays(model=proser.model, loader=loader)
             write(split, "proser", "PROSER ", p_gt, proser_arrays(proser, dict(gt=p_gt, logits=p_logits, features=p_features)))
+        if args.detection:
+            rows = detection_rows(gt, scorers)
+            for row in rows:
+                print(detection_line(split, row))
+            detection_path = args.output_directory / f"{args.loss}_{split}_detection{suffix}.json"
+            with open(detection_path, "w") as handle:
+                json.dump({"split": split, "protocol": args.protocol, "loss": args.loss, "epoch": start_epoch, "tpr": list(DETECTION_TPR),
+                           "rows": rows}, handle, default=str)
+            print(f"Detection metrics saved in: {detection_path}")
+            written[f"{split}_detection"] = detection_path
         if args.auc:
             for unk in (-1, -2):
                 sel = auc_rows(gt, scores, unk, args.loss)

@@ -4,6 +4,8 @@
 feature-norm histograms of known against negative / unknown samples): values, ranges and counts come from the GPU
 (osi_eval_values_*, osi_hist_*), the bin edges from numpy on the host, and the four returned arrays carry the reference's values
 and dtypes. `nearest_fpr` / `ccr_at_fpr` are the "CCR at FPR" rule of the reference's table (script/plot_all.py:344-385).
+`oscr_by_rejection` (this build's addition) is the OSCR curve with a detector's `unknown` vector as the rejector (osi_det_*), `oscr_area`
+the trapezoid area of either curve.
 Drawing (matplotlib, PDF pages, TensorBoard event files) stays out of scope.
 """
 import operator
@@ -76,6 +78,67 @@ def calculate_oscr(gt, scores, unk_label=-1):
         ccr = ccr_c[:pts].cpu().numpy() / np.int64(total_kn)
         fpr = fpr_c[:pts].cpu().numpy() / np.int64(total_unk)
     return np.asarray(ccr, dtype=np.float64), np.asarray(fpr, dtype=np.float64)
+
+
+def oscr_by_rejection(gt, scores, unknown, unk_label=-1):
+    """OSCR curve with a separate rejection score: (ccr, fpr) as calculate_oscr returns them (two float64 arrays, same order), where a
+    sample is rejected by `unknown` [N] (higher = more unknown, the vector the post-hoc detectors write) instead of by its class score,
+    and `scores` [N, C] only decides the closed-set prediction: a known row is correct when the first maximum of its scores is its
+    label (a row holding a NaN score is not). One point per distinct `unknown` value of the known rows except the smallest, from the
+    largest down: ccr = #{correct, unknown < t} / #known, fpr = #{gt == unk_label, unknown < t} / #{gt == unk_label}. With
+    unknown = -scores.max(1) and every known row correct this is calculate_oscr(gt, scores) bit for bit.
+
+    Counted on the MI355X (osi_det_ranks_* / osi_det_curve_*, csrc/detection.hip); inputs as calculate_oscr takes them.
+    ValueError("Input contains NaN.") when `unknown` holds a NaN."""
+    import numpy as np
+    import torch
+    from . import _native as N
+    from . import metrics
+    dev = _need_gpu("oscr_by_rejection")
+    s = _matrix_on_device(scores, dev, "scores")
+    y, u, _ = metrics._detection_inputs(gt, unknown, None, "oscr_by_rejection")
+    n = u.numel()
+    if s.shape[0] != n:
+        raise ValueError("scores and unknown disagree on the number of samples")
+    if n == 0:
+        return np.zeros(0), np.zeros(0)
+    if s.shape[1] == 0:
+        correct = torch.zeros(n, dtype=torch.uint8, device=dev)
+    else:
+        cols = torch.arange(s.shape[1], device=dev).expand_as(s)
+        first_max = torch.where(s == s.max(1, keepdim=True).values, cols, s.shape[1]).min(1).values     # C on a row holding a NaN
+        correct = (first_max == y).to(torch.uint8)
+    ranks, counts, ws = metrics._det_ranks_device(y, u, correct, unk_label)
+    taus = torch.empty(n, dtype=u.dtype, device=dev)
+    out = torch.empty(2 * n + 3 + 4, dtype=torch.int64, device=dev)          # ccr_count[N], fpr_count[N], totals[3], counts4
+    out[2 * n + 3:] = counts
+    fn = N.lib().osi_det_curve_f32 if u.dtype == torch.float32 else N.lib().osi_det_curve_f64
+    N.check(fn(N.ptr(u), N.ptr(y), N.ptr(ranks), n, int(unk_label), N.ptr(ws), ws.numel(), N.ptr(taus), N.ptr(out), N.ptr(out[n:]),
+               N.ptr(out[2 * n:]), N.stream_of(u)), "osi_det_curve")
+    host = out.cpu().numpy()
+    n_unique, total_kn, total_unk = (int(v) for v in host[2 * n:2 * n + 3])
+    if host[2 * n + 6]:
+        raise ValueError("Input contains NaN.")
+    pts = max(0, n_unique - 1)
+    with np.errstate(divide="ignore", invalid="ignore"):   # 0/0 -> nan as in calculate_oscr when a class of samples is absent
+        ccr = host[:pts] / np.int64(total_kn)
+        fpr = host[n:n + pts] / np.int64(total_unk)
+    return np.asarray(ccr, dtype=np.float64), np.asarray(fpr, dtype=np.float64)
+
+
+def oscr_area(ccr, fpr):
+    """Area under an OSCR curve as calculate_oscr / oscr_by_rejection return it (fpr falls along the curve): the trapezoid sum of ccr
+    over fpr between the curve's own end points, no extrapolation to fpr 0 or 1, on the host in fp64. 0.0 for fewer than two points,
+    nan when a point is not finite (a split without known or without unknown rows)."""
+    import numpy as np
+    ccr, fpr = np.asarray(ccr, dtype=np.float64), np.asarray(fpr, dtype=np.float64)
+    if ccr.shape != fpr.shape or ccr.ndim != 1:
+        raise ValueError("ccr and fpr must be vectors of one length")
+    if not (np.isfinite(ccr).all() and np.isfinite(fpr).all()):
+        return float("nan")
+    if len(ccr) < 2:
+        return 0.0
+    return float(np.sum((fpr[:-1] - fpr[1:]) * (ccr[:-1] + ccr[1:]) * 0.5))
 
 
 def _need_gpu(what):
