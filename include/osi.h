@@ -864,6 +864,37 @@ int osi_shape_rows(const float* x, int M, int F, int mode, int keep, float clip,
                    osi_stream_t stream);
 int osi_logit_scores(const float* logits, int M, int C, int mode, float* out, osi_stream_t stream);
 
+/* ABI 29. Gradient-based open-set scores: the head of ODIN (Liang, Li, Srikant, "Enhancing The Reliability of Out-of-distribution Image
+ * Detection in Neural Networks", ICLR 2018) and GradNorm's closed form for the last linear layer (Huang, Geng, Li, "On the Importance of
+ * Gradients for Detecting Distributional Shifts in the Wild", NeurIPS 2021; openset_imagenet/odin.py). Neither is part of the reference
+ * snapshot; this block is their definition, tests/odin_oracle.py its numpy restatement. One wave per row, everything in fp64 and
+ * rounded once to fp32, row sums in an order fixed by C (respectively F) alone, the order of osi_logit_scores. No atomics, no workspace;
+ * nothing is allocated or synchronised; every output element is written by the call; results are bit-identical from run to run and do
+ * not depend on the alignment of the buffers. OSI_ERR_ARG before any launch on a null required pointer, a non-positive size, a
+ * misaligned pointer (4 bytes; pred 8), T not finite or <= 0, dlogits overlapping logits.
+ *
+ * osi_odin_head: from logits[M][C] and the temperature T, per row
+ *     y   = the index torch.argmax returns: a NaN counts as the largest value, the lowest index wins among equal maxima (and among NaNs)
+ *     m   = the row's maximum (a NaN skipped), m' = m when it is finite, else 0 (the convention of osi_logit_scores)
+ *     e_c = exp((l_c - m') / T)
+ *     r   = sum over c != y of e_c: the predicted column is left out of the sum, not subtracted afterwards
+ *     s   = sum over all c of e_c, in the order of osi_logit_scores (e_y + r up to the rounding of fp64 sums)
+ *   score[M]      = e_y / s, the largest temperature-softmax probability S_y(x; T); at T = 1 the bits of OSI_SCORE_MSP
+ *   pred[M]       = y (int64; may be NULL)
+ *   dlogits[M][C] = e_c / s for c != y and -r / s for c = y (may be NULL). This is d(T J) / dlogits for J = -log S_y(x; T): T times the
+ *     textbook gradient of one row, without the 1 / B of a batch mean. Only the sign of dJ/dx is used by ODIN, and this scaling keeps the
+ *     seed's magnitude independent of T. -r / s rather than p_y - 1: no cancellation when one logit dominates.
+ *   A NaN in a row gives NaN in score and in every dlogits element of the row; pred is the first NaN's column. A +Inf maximum is not
+ *   subtracted, as under OSI_SCORE_MSP: score is Inf / Inf = NaN, dlogits is 0 in every finite column and -r / s = -0 or NaN in
+ *   column y (NaN in every +Inf column when there are several). A row of -Inf gives score NaN, dlogits NaN and pred 0. C = 1 gives
+ *   score 1 and dlogits -0 for a finite logit.
+ * osi_gradnorm_scores: out[M] = ||f||_1 * (sum_c |C p_c - 1|) / T from features[M][F] and logits[M][C], with p_c = e_c / s as above: the
+ *   L1 norm of d/dW sum_c -log p_c for the last linear layer logits = W features (the paper's loss with the all-ones target; a bias
+ *   does not enter). Higher means more known. Features of either sign. A NaN in either row, or an infinite maximum, gives NaN. */
+int osi_odin_head(const float* logits, int M, int C, float T, float* dlogits /* [M][C] or NULL */, long long* pred /* [M] or NULL */,
+                  float* score /* [M] */, osi_stream_t stream);
+int osi_gradnorm_scores(const float* features, const float* logits, int M, int F, int C, float T, float* out, osi_stream_t stream);
+
 /* ---- optimizer + arena utilities (train.py:356-359 construction, train.py:127,139 zero_grad/step) --- */
 int osi_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,
                   double beta2, double eps, long long step, float grad_scale, osi_stream_t stream);

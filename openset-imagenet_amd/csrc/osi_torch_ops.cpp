@@ -20,6 +20,7 @@
 //   torch.ops.osi.maha_class_means / _scatter / _factor / _whiten / _sqdist                  Mahalanobis scores (openset_imagenet/mahalanobis.py)
 //   torch.ops.osi.eigh_begin / eigh_sweep / eigh_finish / vim_project / vim_scores           ViM scores, symmetric eigensolver (openset_imagenet/vim.py)
 //   torch.ops.osi.resnet50_pooled / order_stats / shape_rows / logit_scores                  activation shaping: ReAct, ASH, SCALE (openset_imagenet/shaping.py)
+//   torch.ops.osi.odin_head / gradnorm_scores                                                ODIN's head and GradNorm (openset_imagenet/odin.py)
 //   torch.ops.osi.mix_rows_pairs / resnet50_set_mix / proser_loss_fwd_bwd / proser_scores / linear_fwd / linear_bwd    PROSER (openset_imagenet/proser.py)
 //
 // This file contains no arithmetic: every op validates its arguments, takes the CURRENT HIP stream of its tensors' device inside the
@@ -898,6 +899,30 @@ Tensor logit_scores(const Tensor& logits, int64_t mode) {
     return out;
 }
 
+// ---- gradient-based scores (include/osi.h, ABI 29): returns (dlogits [M,C] or empty, pred [M] int64, score [M])
+std::tuple<Tensor, Tensor, Tensor> odin_head(const Tensor& logits, double temperature, bool need_grad) {
+    Op op("odin_head", logits, at::kFloat, "logits", NATURAL);
+    OP_CHECK(logits.dim() == 2, "logits [M,C]");
+    const int M = op.dim(logits.size(0)), C = op.dim(logits.size(1));
+    Tensor dlogits = need_grad ? at::empty_like(logits) : at::empty({0}, logits.options());
+    Tensor pred = at::empty({(int64_t)M}, logits.options().dtype(at::kLong)), score = at::empty({(int64_t)M}, logits.options());
+    ok(osi_odin_head(logits.data_ptr<float>(), M, C, (float)temperature, need_grad ? dlogits.data_ptr<float>() : nullptr, i64(pred),
+                     score.data_ptr<float>(), op.stream()), "osi_odin_head");
+    return {dlogits, pred, score};
+}
+
+Tensor gradnorm_scores(const Tensor& features, const Tensor& logits, double temperature) {
+    Op op("gradnorm_scores", features, at::kFloat, "features", NATURAL);
+    op.need(logits, at::kFloat, "logits", NATURAL);
+    OP_CHECK(features.dim() == 2 && logits.dim() == 2, "features [M,F] and logits [M,C]");
+    op.rows(features, logits);
+    const int M = op.dim(features.size(0)), F = op.dim(features.size(1)), C = op.dim(logits.size(1));
+    Tensor out = at::empty({(int64_t)M}, features.options());
+    ok(osi_gradnorm_scores(features.data_ptr<float>(), logits.data_ptr<float>(), M, F, C, (float)temperature, out.data_ptr<float>(),
+                           op.stream()), "osi_gradnorm_scores");
+    return out;
+}
+
 // ---- PROSER (include/osi.h, ABI 23)
 void need_pairs(const Op& op, const Tensor& partner, const Tensor& weight, int64_t B) {
     op.need(partner, at::kInt, "partner", NATURAL); op.need(weight, at::kFloat, "weight", NATURAL);
@@ -1020,6 +1045,8 @@ TORCH_LIBRARY(osi, m) {
     m.def("order_stats(Tensor v, int[] ranks, Tensor(a!) workspace) -> Tensor");
     m.def("shape_rows(Tensor x, int mode, int keep, float clip, Tensor(a!) workspace) -> Tensor");
     m.def("logit_scores(Tensor logits, int mode) -> Tensor");
+    m.def("odin_head(Tensor logits, float temperature, bool need_grad) -> (Tensor, Tensor, Tensor)");
+    m.def("gradnorm_scores(Tensor features, Tensor logits, float temperature) -> Tensor");
     m.def("openmax_class_means(Tensor features, Tensor logits, Tensor gt, Tensor(a!) workspace) -> (Tensor, Tensor, Tensor)");
     m.def("openmax_distances(Tensor features, Tensor mav, Tensor? cls, int metric) -> Tensor");
     m.def("openmax_fit_tails(Tensor dist, Tensor gt, Tensor correct, int C, int tailsize, Tensor(a!) workspace) -> "
@@ -1110,6 +1137,8 @@ TORCH_LIBRARY_IMPL(osi, CUDA, m) {
     m.impl("order_stats", &order_stats);
     m.impl("shape_rows", &shape_rows);
     m.impl("logit_scores", &logit_scores);
+    m.impl("odin_head", &odin_head);
+    m.impl("gradnorm_scores", &gradnorm_scores);
     m.impl("mix_rows_pairs", &mix_rows_pairs);
     m.impl("proser_loss_fwd_bwd", &proser_loss_fwd_bwd);
     m.impl("proser_scores", &proser_scores);

@@ -21,6 +21,8 @@ from . import vim
 from .vim import ViM
 from . import shaping
 from .shaping import ActivationShaping
+from . import odin
+from .odin import ODIN
 from . import proser
 from .proser import PROSER
 from .losses import (AverageMeter, EarlyStopping, EntropicOpensetLoss, GarbageLoss, ObjectosphereLoss, SoftmaxLoss)
@@ -29,4 +31,4 @@ from .dataset import ImagenetDataset
 from .pipeline import CanvasDataset
 
 __all__ = ["ResNet50", "ImagenetDataset", "CanvasDataset", "EntropicOpensetLoss", "SoftmaxLoss", "GarbageLoss", "ObjectosphereLoss", "AverageMeter",
-           "EarlyStopping", "OpenMax", "EVM", "KNN", "Mahalanobis", "ViM", "ActivationShaping", "PROSER", "tools", "util", "train", "metrics", "losses", "dataset"]
+           "EarlyStopping", "OpenMax", "EVM", "KNN", "Mahalanobis", "ViM", "ActivationShaping", "ODIN", "PROSER", "tools", "util", "train", "metrics", "losses", "dataset"]

@@ -1,5 +1,5 @@
-"""What the post-hoc open-set detectors (openmax.OpenMax, evm.EVM, knn.KNN, mahalanobis.Mahalanobis, vim.ViM, shaping.ActivationShaping)
-share on the host: the
+"""What the post-hoc open-set detectors (openmax.OpenMax, evm.EVM, knn.KNN, mahalanobis.Mahalanobis, vim.ViM, shaping.ActivationShaping;
+odin.ODIN takes the base class alone) share on the host: the
 argument checks of their `fit` and scoring calls, the sizes of the row chunks their kernels take, and `Detector`, the base class that
 holds the fitted tensors, the workspace and the state dict. None of it computes: every check here runs before `_need_gpu`, so a host
 without a GPU still gets the ValueError of a bad argument."""

@@ -241,6 +241,8 @@ _SIGS = {
     "osi_shape_rows_workspace": (c_size_t, [c_int, c_int]),
     "osi_shape_rows": (c_int, [P, c_int, c_int, c_int, c_int, c_float, P, P, c_size_t, P]),
     "osi_logit_scores": (c_int, [P, c_int, c_int, c_int, P, P]),
+    "osi_odin_head": (c_int, [P, c_int, c_int, c_float, P, P, P, P]),
+    "osi_gradnorm_scores": (c_int, [P, P, c_int, c_int, c_int, c_float, P, P]),
     "osi_resnet50_pooled": (c_int, [c_void_p, P, P, POINTER(c_size_t), P]),
     "osi_mix_rows_pairs": (c_int, [P, P, P, c_int, c_size_t, P]),
     "osi_proser_loss_fwd_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, P, P, P, P]),

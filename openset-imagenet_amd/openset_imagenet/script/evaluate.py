@@ -33,6 +33,14 @@ logsumexp).
 `python -m openset_imagenet.script.proser` saved as `{loss}_proser{suffix}.pth` (proser.PROSER) and writes
 `{loss}_{split}_arr{suffix}_proser.npz` with `gt`, `logits`, `features` of THAT network, `scores` = probs[:, :C] and `unknown` =
 probs[:, C]; with `--oscr` the same OSCR line is printed for those scores.
+`--odin` (likewise; softmax and entropic losses) scores with ODIN (odin.ODIN: the temperature-scaled largest softmax probability after
+one signed-gradient step on the image; `--odin-temperature`, `--odin-epsilon`, in this network's [0, 1] pixel units). It needs a pass of
+its own over the images: one differentiable forward, one input-only backward and one inference forward per batch. `--odin-tune` first
+selects both settings on the `val` split against label -1 over the paper's grid (ODIN_TEMPERATURES x ODIN_EPSILONS). The detector is saved
+as `{loss}_odin{suffix}.pth`, and `{loss}_{split}_arr{suffix}_odin.npz` holds `gt`, `logits`, `features`, `scores` (the clean forward's),
+`logits_odin` (the logits of the perturbed batch) and `unknown` (minus the score).
+`--gradnorm` (likewise; `--gradnorm-temperature`; needs `--detection`) adds the scorer GradNorm (odin.gradnorm_scores, negated) beside the
+logit baselines; it has no fit and writes no file of its own.
 `--detection` (likewise) scores every REJECTION score of the run, one value per sample where higher means more unknown: the baselines
 read off the logits (MSP, MaxLogit, Energy: the negated osi_logit_scores values; for the garbage loss without the background column),
 the `unknown` vector of every detector fitted in the same run and of `--proser`, and for a detector without one (the EVM) minus its
@@ -54,6 +62,7 @@ from ..evm import EVM
 from ..knn import KNN
 from ..mahalanobis import Mahalanobis
 from ..model import ResNet50
+from ..odin import ODIN, gradnorm_scores
 from ..openmax import OpenMax
 from ..shaping import METHODS as SHAPING_METHODS, ActivationShaping, head_of
 from ..train import _image_loader, get_arrays, load_checkpoint
@@ -120,6 +129,10 @@ DETECTORS = (
 )
 
 
+ODIN_TEMPERATURES = (1, 2, 5, 10, 20, 50, 100, 200, 500, 1000)      # the grid of the ODIN paper
+ODIN_EPSILONS = tuple(float(e) for e in np.linspace(0.0, 0.004, 21))
+
+
 def get_args(command_line_options=None):
     p = argparse.ArgumentParser("Get parameters for evaluation", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument("loss", choices=["entropic", "softmax", "garbage"], help="Which loss function to evaluate")
@@ -172,10 +185,28 @@ def get_args(command_line_options=None):
                    "the method's own)")
     p.add_argument("--proser", action="store_true", help="also evaluate the PROSER stage saved as {loss}_proser{suffix}.pth (softmax and "
                    "entropic losses) and write {loss}_{split}_arr{suffix}_proser.npz with its scores and the probability of the unknown class")
+    p.add_argument("--odin", action="store_true", help="also score with ODIN (softmax and entropic losses): a pass of its own over the "
+                   "images, one input-only backward per batch; writes {loss}_{split}_arr{suffix}_odin.npz")
+    p.add_argument("--odin-temperature", type=float, default=1000.0, metavar="T", help="ODIN: the temperature of the softmax")
+    p.add_argument("--odin-epsilon", type=float, default=0.0014, metavar="E", help="ODIN: the size of the signed-gradient step, in the "
+                   "network's [0, 1] pixel units")
+    p.add_argument("--odin-tune", action="store_true", help="ODIN: select temperature and epsilon on the val split against label -1 over "
+                   "the paper's grid (lowest FPR at 95%% TPR)")
+    p.add_argument("--gradnorm", action="store_true", help="--detection also scores GradNorm for the last linear layer (softmax and "
+                   "entropic losses)")
+    p.add_argument("--gradnorm-temperature", type=float, default=1.0, metavar="T", help="GradNorm: the temperature of the softmax")
     args = p.parse_args(command_line_options)
-    post_hoc = ["proser"] * args.proser + [row["name"] for row in DETECTORS if row["on"](args)]
+    post_hoc = ["proser"] * args.proser + [row["name"] for row in DETECTORS if row["on"](args)] + ["odin"] * args.odin + ["gradnorm"] * args.gradnorm
     if post_hoc and args.loss == "garbage":
         p.error(f"--{post_hoc[0]} needs a network without a background class: use it with the softmax or entropic loss, not with garbage")
+    if args.odin_tune and not args.odin:
+        p.error("--odin-tune goes with --odin")
+    if not (np.isfinite(args.odin_temperature) and args.odin_temperature > 0.0) or not (np.isfinite(args.odin_epsilon) and args.odin_epsilon >= 0.0):
+        p.error(f"--odin-temperature must be finite and > 0 and --odin-epsilon finite and >= 0, got {args.odin_temperature}, {args.odin_epsilon}")
+    if not (np.isfinite(args.gradnorm_temperature) and args.gradnorm_temperature > 0.0):
+        p.error(f"--gradnorm-temperature must be finite and > 0, got {args.gradnorm_temperature}")
+    if args.gradnorm and not args.detection:
+        p.error("--gradnorm adds a scorer to --detection and writes nothing of its own: pass --detection as well")
     if args.shaping_percentile is not None and not 0.0 < args.shaping_percentile < 100.0:
         p.error(f"--shaping-percentile must satisfy 0 < P < 100, got {args.shaping_percentile}")
     if args.vim_dim is not None and args.vim_dim < 1:
@@ -383,6 +414,17 @@ def proser_arrays(proser, split_arrays):
     return scored_arrays(lambda p, a: _known_and_unknown(p.predict(a["logits"], p.dummy_logits(a["features"]))), proser, split_arrays)
 
 
+def odin_arrays(odin, model, loader):
+    """`--odin` on a loader: ODIN.arrays - numpy `gt`, `logits`, `features`, `scores` (the clean forward's), `logits_odin` and `unknown`."""
+    return odin.arrays(model, loader)
+
+
+def gradnorm_scorer(scores, features, logits, temperature=1.0):
+    """The `--detection` scorer of `--gradnorm`: ("GradNorm", scores, -gradnorm_scores(features, logits, temperature)) - higher means
+    more unknown -, numpy fp32 [N]."""
+    return "GradNorm", scores, (-gradnorm_scores(features, logits, temperature)).cpu().numpy()
+
+
 def load_proser(path, n_classes):
     """The PROSER module of a file written by script/proser.py, on the device, with a network of its own."""
     from ..proser import PROSER
@@ -436,6 +478,7 @@ def main(command_line_options=None):
         proser = load_proser(proser_path, n_classes)
         print(f"PROSER stage loaded from: {proser_path} (dummy {proser.dummy_count}, mix at {proser.mix_at}, bias {float(proser.bias):.6f})")
     fitted = [(row, row["cls"](**row["options"](args))) for row in DETECTORS if row["on"](args)]      # refuses bad options first
+    odin = ODIN(args.odin_temperature, args.odin_epsilon) if args.odin else None
     shaping = any(row["name"] == "shaping" for row, _ in fitted)     # the one row that reads the pooled activation and the head:
     extra = {}                                                       # with it on, `pooled` and `head` join the mappings below
     if fitted:
@@ -451,6 +494,15 @@ def main(command_line_options=None):
         path = args.output_directory / f"{args.loss}_{row['name']}{suffix}.pth"
         torch.save(detector.state_dict(), path)
         print(f"{row['summary'](detector, args)}; saved in: {path}")
+
+    if odin is not None:
+        if args.odin_tune:
+            loader = torch.utils.data.DataLoader(splits["val"], batch_size=args.batch_size, num_workers=args.workers)
+            odin.tune(model, loader, ODIN_TEMPERATURES, ODIN_EPSILONS, unk_label=-1)
+        path = args.output_directory / f"{args.loss}_odin{suffix}.pth"
+        torch.save(odin.state_dict(), path)
+        print(f"ODIN (temperature {odin.temperature:g}, epsilon {odin.epsilon:g}" +
+              (f", selected on val among {odin.grid.shape[0]} grid points" if args.odin_tune else "") + f"); saved in: {path}")
 
     def write(split, name, tag, gt, arrays):
         """One detector's arrays of a split next to the split's .npz, and its OSCR line."""
@@ -478,6 +530,8 @@ def main(command_line_options=None):
         if args.detection:                                # the background column is neither a known class nor a logit of one
             class_scores, class_logits = (scores[:, :-1], logits[:, :-1]) if args.loss == "garbage" else (scores, logits)
             scorers += [(name, class_scores, unknown) for name, unknown in logit_baselines(class_logits).items()]
+            if args.gradnorm:
+                scorers.append(gradnorm_scorer(class_scores, features, class_logits, args.gradnorm_temperature))
         if args.oscr:
             s = scores[:, :-1] if args.loss == "garbage" else scores           # the background column is not a known class
             for line in oscr_lines(split, gt, s):
@@ -488,6 +542,8 @@ def main(command_line_options=None):
         if proser is not None:
             p_gt, p_logits, p_features, _ = get_arrays(model=proser.model, loader=loader)
             write(split, "proser", "PROSER ", p_gt, proser_arrays(proser, dict(gt=p_gt, logits=p_logits, features=p_features)))
+        if odin is not None:
+            write(split, "odin", "ODIN ", gt, odin_arrays(odin, model, loader))
         if args.detection:
             rows = detection_rows(gt, scorers)
             for row in rows:
