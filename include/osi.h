@@ -102,7 +102,10 @@ enum { OSI_TILE_AUTO = 0, OSI_TILE_128x128 = 1, OSI_TILE_128x64 = 2, OSI_TILE_64
  * weights packed by osi_stem_weight_pack ([Cout][56 taps][4]). Otherwise Cin % 32 == 0, Cout % 64 == 0. */
 int osi_conv_fwd(const osi_conv_desc* d, const float* x, const float* w, float* y, int tile, osi_stream_t stream);
 /* Same convolution, and the epilogue also emits per-row-tile BatchNorm partials (mean, M2 per channel, *P tiles of
- * *rows_per_block rows) into pstats, to be finished by osi_bn_finalize_stats — the statistics never re-read y from HBM. */
+ * *rows_per_block rows) into pstats, to be finished by osi_bn_finalize_stats — the statistics never re-read y from HBM.
+ * pstats: osi_conv_fwd_bnstats_workspace(d) bytes = the partials, the scratch of osi_bn_finalize_stats and the slab of a K-split tail
+ * (a caller that offers less gets the un-split launch); workspace contents are never assumed. The same holds for pstats of
+ * osi_conv_fwd_act / osi_conv_fwd_act2. */
 size_t osi_conv_fwd_bnstats_workspace(const osi_conv_desc* d);
 int osi_conv_fwd_bnstats(const osi_conv_desc* d, const float* x, const float* w, float* y, int tile, float* pstats,
                          size_t pstats_bytes, int* P, int* rows_per_block, osi_stream_t stream);
@@ -123,7 +126,8 @@ int osi_conv_fwd_act2(const osi_conv_desc* d, const float* x, const float* in_sc
 /* Winograd F(2x2, 3x3) forms of the two calls above for 3x3 / stride 1 / pad 1 convolutions (conv2 of the bottlenecks without a stride;
  * csrc/conv_wino.hip): 2.25x fewer multiplies, every product and sum still fp32 (exact-f32 MFMA), error against fp64 below the direct
  * kernels' on the network's shapes. `ws` = osi_conv_wino_workspace(d) bytes for the transformed weights (rebuilt by every call: the
- * weights change every step). osi_conv_wino_eligible: 1 when the shape is taken (Cin % 16 == 0 and Cout % 64 == 0 forward, swapped for the
+ * weights change every step) and the stream-K slab; workspace contents are never assumed (ws, the slab of the `_pre` calls, pstats,
+ * f->partials). osi_conv_wino_eligible: 1 when the shape is taken (Cin % 16 == 0 and Cout % 64 == 0 forward, swapped for the
  * input gradient; forward: every 16-tile statistics group must hold the same number of pixels — H, W even and B * H/2 * W/2 % 16 == 0, or
  * whole images per group as at 7 x 7).
  * osi_conv_fwd_wino = osi_conv_fwd_act (in_scale / in_shift given) or osi_conv_fwd_bnstats (NULL): *P = ceil(tiles / 16) partials of
@@ -150,7 +154,7 @@ int osi_conv_fwd_wino(const osi_conv_desc* d, const float* x, const float* in_sc
  *     out = [relu](conv2d(x, w) * scale[n] + shift[n] [+ residual])          one fma, one add, one max per element
  * (the roundings of osi_bn_apply: bit-identical to osi_conv_fwd followed by osi_bn_apply on the same accumulators). residual: same
  * shape as out, may be NULL, must not alias out. ws: osi_conv_fwd_epilogue_workspace(d) bytes (slab of a K-split tail; may be 0 / NULL:
- * the launch is then single-pass). Not for the stem (its tail is osi_bn_relu_maxpool_fwd). Cin % 32 == 0, Cout % 64 == 0. */
+ * the launch is then single-pass); workspace contents are never assumed. Not for the stem (its tail is osi_bn_relu_maxpool_fwd). Cin % 32 == 0, Cout % 64 == 0. */
 typedef struct {
     const float* scale;     /* [Cout], e.g. from osi_bn_eval_coeffs */
     const float* shift;     /* [Cout] */
@@ -174,7 +178,8 @@ int osi_conv_dgrad(const osi_conv_desc* d, const float* dy, const float* w, floa
  * through the ReLU that produced this conv's input (bitmask written by osi_bn_apply_relu_mask); when `partials` is set the
  * epilogue also emits, per row tile, the column sums of g, g*xhat0 and (y1 != NULL) g*xhat1 (xhat = (y - mean)*invstd) — the
  * BatchNorm-backward reductions of the layer(s) that produced that input — as partials[3][*P][Cin], to be finished by
- * osi_bn_backward_fused. addend may be dx. */
+ * osi_bn_backward_fused. addend may be dx. f->partials: osi_conv_dgrad_fused_workspace(d) bytes (the partial sums, then the slab of a
+ * K-split tail); workspace contents are never assumed (also for osi_conv_dgrad_fused_frozen). */
 typedef struct {
     const void* relu_mask;  /* may be NULL: no mask */
     const float* y0;        /* pre-BN tensor of the consumer BatchNorm, same shape as dx */
@@ -216,8 +221,9 @@ int osi_conv_dgrad_fused_wino(const osi_conv_desc* d, const float* dy, const flo
                               size_t ws_bytes, int* P, osi_stream_t stream);
 int osi_conv_dgrad_fused_wino_pre(const osi_conv_desc* d, const float* dy, const float* u, float* dx, const osi_dgrad_fusion* f, void* slab,
                                   size_t slab_bytes, int* P, osi_stream_t stream);
-/* dw = conv2d_weight_grad(dy, x), deterministic split-K through `ws` (size from osi_conv_wgrad_workspace). The stem writes
- * the packed [Cout][224] form; osi_stem_grad_unpack converts to [Cout][7][7][3]. */
+/* dw = conv2d_weight_grad(dy, x), deterministic split-K through `ws` (size from osi_conv_wgrad_workspace; 0 / NULL when the plan has
+ * one split); workspace contents are never assumed. The stem writes the packed [Cout][224] form; osi_stem_grad_unpack converts to
+ * [Cout][7][7][3]. */
 size_t osi_conv_wgrad_workspace(const osi_conv_desc* d);
 int osi_conv_wgrad(const osi_conv_desc* d, const float* dy, const float* x, float* dw, void* ws, size_t ws_bytes,
                    osi_stream_t stream);
@@ -227,7 +233,7 @@ int osi_conv_wgrad_act(const osi_conv_desc* d, const float* dy, const float* x, 
 /* Winograd F(3x3, 2x2) form of the two calls above for 3x3 / stride 1 / pad 1 convolutions with Cin % 64 == 0 and Cout % 64 == 0
  * (csrc/conv_wino.hip): the sum over output tiles is taken in the transformed domain (16 multiplies per tile and (cout, cin) pair
  * instead of 36), deterministic (split-K over the tile axis into partial slabs, fixed-order reduce). in_scale / in_shift may be NULL.
- * ws: osi_conv_wgrad_wino_workspace(d) bytes; 0 = the shape is not taken. */
+ * ws: osi_conv_wgrad_wino_workspace(d) bytes; 0 = the shape is not taken; workspace contents are never assumed. */
 size_t osi_conv_wgrad_wino_workspace(const osi_conv_desc* d);
 int osi_conv_wgrad_wino(const osi_conv_desc* d, const float* dy, const float* x, const float* in_scale, const float* in_shift, float* dw,
                         void* ws, size_t ws_bytes, osi_stream_t stream);
@@ -236,14 +242,15 @@ int osi_stem_weight_pack(const float* w_krsc3, float* w_packed, int Cout, osi_st
  * torchvision's resnet50 under model.py:17 at any image size that is a multiple of 16 x 32): writes the gradient in the PARAMETER
  * layout [64][7][7][3] directly (no packed form, no unpack pass), deterministic (one partial per workgroup, fixed-order reduce).
  * osi_stem_wgrad_direct_workspace returns 0 for a geometry it does not take (use osi_conv_wgrad + osi_stem_grad_unpack then);
- * osi_stem_wgrad_direct returns OSI_ERR_ARG for it. x4 = the NHWC4 image the forward read. */
+ * osi_stem_wgrad_direct returns OSI_ERR_ARG for it. x4 = the NHWC4 image the forward read. workspace contents are never assumed. */
 size_t osi_stem_wgrad_direct_workspace(const osi_conv_desc* d);
 int osi_stem_wgrad_direct(const osi_conv_desc* d, const float* dy, const float* x4, float* dw_krsc3, void* ws, size_t ws_bytes,
                           osi_stream_t stream);
 /* The same gradient with the whole stem tail fused into the operand loader: dY = BatchNorm backward of the ReLU-gated max-pool
  * scatter of gpool (the gradient w.r.t. the pooled activation) is built per tile in LDS from gpool, the arg-max bytes of
  * osi_bn_relu_maxpool_fwd and the stem's conv output y, and never written to memory. dgamma / dbeta: the stem BatchNorm's reductions
- * (osi_bn_relu_maxpool_bwd with dy = NULL computes exactly those). ws: osi_stem_wgrad_fused_workspace(d) bytes. */
+ * (osi_bn_relu_maxpool_bwd with dy = NULL computes exactly those). ws: osi_stem_wgrad_fused_workspace(d) bytes; workspace contents are
+ * never assumed. */
 size_t osi_stem_wgrad_fused_workspace(const osi_conv_desc* d);
 int osi_stem_wgrad_fused(const osi_conv_desc* d, const float* gpool, const void* pool_idx, const float* y, const float* x4,
                          const float* gamma, const float* mean, const float* invstd, const float* dgamma, const float* dbeta,
@@ -281,11 +288,14 @@ int osi_stem_dgrad_pgd(const float* dy, const float* w_krsc3, const float* x_cur
 /* ---- BatchNorm2d in training mode + ReLU + residual (torchvision Bottleneck under model.py:37; train() at train.py:125) --- */
 size_t osi_bn_workspace(int M, int C);
 /* batch statistics of y[M][C]: mean, invstd = 1/sqrt(biased var + eps), scale = gamma*invstd, shift = beta - mean*scale;
- * running stats updated with the unbiased variance when running_mean/var are non-NULL. */
+ * running stats updated with the unbiased variance when running_mean/var are non-NULL. ws: osi_bn_workspace(M, C) bytes; workspace
+ * contents are never assumed. */
 int osi_bn_train_stats(const float* y, int M, int C, const float* gamma, const float* beta, float eps, float momentum,
                        float* running_mean, float* running_var, float* mean, float* invstd, float* scale, float* shift,
                        void* ws, size_t ws_bytes, osi_stream_t stream);
-/* second half of osi_bn_train_stats for partials produced elsewhere (osi_conv_fwd_bnstats): pstats = [P][C] means then [P][C] M2 */
+/* second half of osi_bn_train_stats for partials produced elsewhere (osi_conv_fwd_bnstats): pstats = [P][C] means then [P][C] M2 (only
+ * read), then the scratch of the two-level merge, 64 * C floats: pstats_bytes >= (2 * P + 64) * C * 4 (OSI_ERR_ARG below that), and
+ * what the scratch holds is never assumed. */
 int osi_bn_finalize_stats(float* pstats, size_t pstats_bytes, int P, int rows_per_block, int M, int C, const float* gamma,
                           const float* beta, float eps, float momentum, float* running_mean, float* running_var, float* mean,
                           float* invstd, float* scale, float* shift, osi_stream_t stream);
@@ -314,7 +324,9 @@ int osi_bn_frozen_coeffs_multi(const osi_bn_frozen_layer* layers, int n, float e
 int osi_bn_apply(const float* y, const float* residual, const float* scale, const float* shift, float* out, int M, int C,
                  int relu, osi_stream_t stream);
 /* g = dout * (act > 0) (act NULL: g = dout); dgamma, dbeta; dy = gamma*invstd*(g - mean(g) - xhat*mean(g*xhat)).
- * gmasked (optional) receives g, the gradient that continues along the skip connection. dy may alias dout. */
+ * gmasked (optional) receives g, the gradient that continues along the skip connection. dy may alias dout. ws:
+ * osi_bn_backward_workspace(M, C) bytes, here and for every BatchNorm backward below that names this query (osi_bn_backward_relu_mask,
+ * osi_bn_backward_fused, osi_bn_backward_frozen, osi_bn_backward_reduce); workspace contents are never assumed by any of them. */
 size_t osi_bn_backward_workspace(int M, int C);
 int osi_bn_backward(const float* dout, const float* act, const float* y, const float* mean, const float* invstd,
                     const float* gamma, float* dy, float* gmasked, float* dgamma, float* dbeta, int M, int C, void* ws,
@@ -345,7 +357,7 @@ int osi_bn_backward_fused(const float* g, const float* y, const float* mean, con
  * BatchNorm): g is streamed once, both sets of sums are finished in one launch (two for P beyond the one-launch limit), and every
  * consumer's dy, dgamma and dbeta are bit for bit those of its own osi_bn_backward_fused call. psum_g [P][C] is shared (dbeta = sum g for
  * both), psum_gx [P][C] is per consumer. consumers[0].dy may alias g; consumers[1].dy is a third buffer.
- * ws: osi_bn_backward_fused2_workspace(C) bytes (any P). */
+ * ws: osi_bn_backward_fused2_workspace(C) bytes (any P); workspace contents are never assumed. */
 typedef struct {
     const float *y, *mean, *invstd, *gamma;   /* pre-BN tensor, batch statistics, scale parameter */
     const float* psum_gx;                     /* [P][C] row-tile partials of sum g * xhat */
@@ -391,7 +403,8 @@ int osi_maxpool3x3s2_bwd(const float* dy, const void* idx, float* dx, int B, int
  *   fwd: pooled = maxpool3x3s2(relu(y*scale + shift)); the post-ReLU activation is never stored. idx bytes as above with bit 7 =
  *        "window maximum > 0" (the ReLU gate of the pixel the gradient will return to).
  *   bwd: gpool = dJ/dpooled -> dgamma, dbeta and dy = BatchNorm backward of the pool-scattered, ReLU-gated gradient, gathered on
- *        the fly (no [B][H][W][C] gradient tensor). ws: osi_bn_backward_workspace(B*H*W, C) bytes. */
+ *        the fly (no [B][H][W][C] gradient tensor). ws: osi_bn_backward_workspace(B*H*W, C) bytes; workspace contents are never
+ *        assumed (osi_bn_relu_maxpool_bwd and osi_bn_relu_maxpool_bwd_frozen). */
 /* The reduction half of osi_bn_backward_fused alone: merges per-row-tile partials (psum_g, psum_gx: [P][C], e.g. from a pool-mode
  * osi_conv_dgrad_fused) into dgamma / dbeta. M = elements per channel of the BatchNorm (c1 = dbeta / M, c2 = dgamma / M are left in ws
  * for callers that want them). ws: osi_bn_backward_workspace(M, C) bytes. */
@@ -949,7 +962,8 @@ int osi_sgd_step_groups(float* param, const float* grad, float* momentum_buf, si
  * 2048, as the grouped steps cut it); per lane in index order, then wave, workgroup, one 8-byte partial in ws per workgroup; a second
  * launch of one workgroup adds the partials, eight consecutive ones per lane in index order, then the same tree, and writes out2. Two
  * calls on the same data give the same bits. Two launches, nothing allocated, nothing synchronised (graph-capturable).
- * ws: osi_grad_norm_workspace(n) bytes (0 for an n the call would refuse), 8-byte aligned, overwritten. grad 16-byte aligned.
+ * ws: osi_grad_norm_workspace(n) bytes (0 for an n the call would refuse), 8-byte aligned, overwritten (workspace contents are never
+ * assumed). grad 16-byte aligned.
  * OSI_ERR_ARG before any launch on: a null or misaligned grad, ws or out2; n == 0, n % 4 != 0 or n/4 > 2^32 - 512; ws_bytes too
  * small; a malformed span table (begin % 4 != 0, numel == 0, unsorted, overlapping, past n, n_spans outside 1..OSI_OPT_MAX_SEGMENTS,
  * or NULL with n_spans != 0); a norm_type other than the two constants; max_norm negative or NaN; a non-finite grad_scale.

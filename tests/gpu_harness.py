@@ -1,5 +1,5 @@
 """What the GPU parity tests of the detectors share when they call the C ABI directly: guard-banded outputs, a poisoned workspace,
-bit-preserving uploads, and the bit / ulp comparisons. A plain module, imported like the oracles."""
+bit-preserving uploads, 0xFF-banded inputs, and the bit / ulp comparisons. A plain module, imported like the oracles."""
 import numpy as np
 import torch
 
@@ -7,20 +7,73 @@ GUARD = 256                                  # bytes = 64 floats, before and aft
 CANARY = 0xA5
 
 
-class Out:
-    """A device output with guard bands: `t` is the tensor the kernel writes, check() says whether the bands kept their canary."""
+def _band(band):
+    assert band >= 0 and band % 256 == 0, "a band is a multiple of 256 bytes: the payload keeps the alignment torch gives"
+    return int(band)
 
-    def __init__(self, shape, dtype, dev):
+
+def _banded(n, lead, trail, band_byte, dev):
+    """(raw, payload) bytes: `lead` and `trail` bytes of `band_byte` around n payload bytes (padded to 8, the padding is band)."""
+    raw = torch.full((lead + (n + 7) // 8 * 8 + trail,), band_byte, dtype=torch.uint8, device=dev)
+    return raw, raw[lead:lead + n]
+
+
+def _bands_hold(raw, lead, n, band_byte):
+    return bool((raw[:lead] == band_byte).all()) and bool((raw[lead + n:] == band_byte).all())
+
+
+class Out:
+    """A device output with guard bands: `t` is the tensor the kernel writes, check() says whether the bands kept their canary.
+    band: bytes before and after (a multiple of 256), or a pair (before, after). fill: the payload's pre-fill (NaN shows an unwritten
+    float element in any comparison); None leaves the canary in it."""
+
+    def __init__(self, shape, dtype, dev, band=GUARD, fill=None):
+        self.lead, self.trail = (_band(b) for b in (band if isinstance(band, tuple) else (band, band)))
         n = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
-        self.raw = torch.full((GUARD + (n + 7) // 8 * 8 + GUARD,), CANARY, dtype=torch.uint8, device=dev)
+        self.raw, payload = _banded(n, self.lead, self.trail, CANARY, dev)
         self.n = n
-        self.t = self.raw[GUARD:GUARD + n].view(dtype).view(*shape)
+        self.t = payload.view(dtype).view(*shape)
+        if fill is not None:
+            self.t.fill_(fill)
 
     def check(self):
-        return bool((self.raw[:GUARD] == CANARY).all()) and bool((self.raw[GUARD + self.n:] == CANARY).all())
+        return bool((self.raw[:self.lead] == CANARY).all()) and bool((self.raw[self.lead + self.n:] == CANARY).all())
 
     def np(self):
         return self.t.cpu().numpy()
+
+
+class In:
+    """A device copy of a CPU tensor (same bits) between bands of 0xFF bytes: a NaN in fp32 / fp64, -1 in an integer, 255 in a byte, so
+    a load outside the tensor that reaches an accumulator shows as NaN in the output. `t` is the tensor to pass; unchanged() says
+    that the payload still holds the uploaded bits and both bands are whole: the kernel wrote nothing into its input."""
+
+    def __init__(self, tensor, dev, band=GUARD):
+        self.lead = self.trail = _band(band)
+        src = tensor.detach().cpu().contiguous()
+        self.bits = src.reshape(-1).view(torch.uint8).clone()
+        self.n = self.bits.numel()
+        self.raw, payload = _banded(self.n, self.lead, self.trail, 0xFF, dev)
+        payload.copy_(self.bits)
+        self.t = payload.view(src.dtype).view(*src.shape)
+
+    def unchanged(self):
+        return _bands_hold(self.raw, self.lead, self.n, 0xFF) and torch.equal(self.raw[self.lead:self.lead + self.n].cpu(), self.bits)
+
+
+class Ws:
+    """A workspace of exactly nbytes between canary bands, every byte of it set to `fill`. nbytes = 0: ptr is None (a null pointer
+    and size 0, as the header allows). check() as for Out."""
+
+    def __init__(self, nbytes, dev, fill=0xFF, band=GUARD):
+        self.lead = self.trail = _band(band)
+        self.nbytes = self.n = int(nbytes)
+        self.raw, self.t = _banded(self.n, self.lead, self.trail, CANARY, dev)
+        self.t.fill_(fill)
+        self.ptr = self.t.data_ptr() if self.n else None
+
+    def check(self):
+        return _bands_hold(self.raw, self.lead, self.n, CANARY)
 
 
 def call(fn, *args):

@@ -52,35 +52,44 @@ def oihw(w):
     return w.permute(0, 3, 1, 2)
 
 
-def conv_fwd(x_nhwc, w_krsc, k, stride, pad, tile=0):
+def conv_fwd(x_nhwc, w_krsc, k, stride, pad, tile=0, y=None):
+    """y: the caller's output buffer (default: a fresh one)."""
     B, H, W, Cin = x_nhwc.shape
     Cout = w_krsc.shape[0]
     d = N.ConvDesc.make(B, H, W, Cin, Cout, k, stride, pad)
-    y = torch.empty(B, d.Ho, d.Wo, Cout, device=x_nhwc.device)
+    if y is None:
+        y = torch.empty(B, d.Ho, d.Wo, Cout, device=x_nhwc.device)
     N.check(N.lib().osi_conv_fwd(ctypes.byref(d), N.ptr(x_nhwc), N.ptr(w_krsc), N.ptr(y), tile, S()), "conv_fwd")
     return y
 
 
-def conv_dgrad(dy_nhwc, w_krsc, H, W, k, stride, pad, accumulate_into=None, tile=0):
+def conv_dgrad(dy_nhwc, w_krsc, H, W, k, stride, pad, accumulate_into=None, tile=0, accumulate=None):
+    """accumulate_into: the caller's buffer; accumulate: the mode it is passed with (default: 1 when a buffer is given, else 0)."""
     B, Ho, Wo, Cout = dy_nhwc.shape
     Cin = w_krsc.shape[3]
     d = N.ConvDesc.make(B, H, W, Cin, Cout, k, stride, pad)
     assert (d.Ho, d.Wo) == (Ho, Wo)
     dx = accumulate_into if accumulate_into is not None else torch.full((B, H, W, Cin), float("nan"), device=dy_nhwc.device)
-    N.check(N.lib().osi_conv_dgrad(ctypes.byref(d), N.ptr(dy_nhwc), N.ptr(w_krsc), N.ptr(dx), int(accumulate_into is not None), tile, S()), "conv_dgrad")
+    N.check(N.lib().osi_conv_dgrad(ctypes.byref(d), N.ptr(dy_nhwc), N.ptr(w_krsc), N.ptr(dx), int(accumulate_into is not None) if accumulate is None else accumulate, tile, S()),
+            "conv_dgrad")
     return dx
 
 
-def conv_wgrad(dy_nhwc, x_nhwc, k, stride, pad):
+def conv_wgrad(dy_nhwc, x_nhwc, k, stride, pad, dw=None, ws=None):
+    """dw / ws: the caller's output and workspace (ws: uint8, exactly osi_conv_wgrad_workspace(d) bytes; default: fresh ones)."""
     B, H, W, Cin = x_nhwc.shape
     Cout = dy_nhwc.shape[3]
     d = N.ConvDesc.make(B, H, W, Cin, Cout, k, stride, pad)
     stem = Cin == 4 and k == 7
     ktot = 224 if stem else k * k * Cin
-    dw = torch.full((Cout, ktot), float("nan"), device=x_nhwc.device)
+    if dw is None:
+        dw = torch.full((Cout, ktot), float("nan"), device=x_nhwc.device)
     nbytes = N.lib().osi_conv_wgrad_workspace(ctypes.byref(d))
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x_nhwc.device)
-    N.check(N.lib().osi_conv_wgrad(ctypes.byref(d), N.ptr(dy_nhwc), N.ptr(x_nhwc), N.ptr(dw), N.ptr(ws), nbytes, S()), "conv_wgrad")
+    if ws is None:
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x_nhwc.device)
+    else:
+        assert ws.numel() == nbytes
+    N.check(N.lib().osi_conv_wgrad(ctypes.byref(d), N.ptr(dy_nhwc), N.ptr(x_nhwc), N.ptr(dw), N.ptr(ws) if nbytes else None, nbytes, S()), "conv_wgrad")
     return dw if stem else dw.view(Cout, k, k, Cin)
 
 
